@@ -17,6 +17,12 @@ Launch forms (both give one process per GPU over torch.distributed, backend nccl
 The JSON line carries what was actually observed: `n_gpus` = the torch.distributed world size, `ranks` = per-rank device,
 evals/s and wall time, `backend`.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything else it can measure -- the blocking-call
+stepping, the roofline leg, the CPU baseline, the aux legs (other configurations and entry points), --extras, --eps-stream and the
+strong-scaling leg of --gpus N -- runs after the timed steps only with --full.  --dump-outputs DIR writes what the last timed step
+returned to the caller (F and dF of rank 0, float64) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
 """
 from __future__ import annotations
@@ -239,29 +245,54 @@ def entropy_kernel_label(D, K):
                                                      "" if hv.value == 1 else ",HV=%d" % hv.value)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the (F, dF) a caller of the timed path received in the last step, as float64 .npy files.  Above 64 MB in all,
+    dF keeps a fixed, seeded choice of its restart columns, whose indices go to dF_columns.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    F = np.array(out["F"], dtype=np.float64)
+    dF = np.array(out["dF"], dtype=np.float64)
+    if F.nbytes + dF.nbytes > DUMP_BYTES_MAX:
+        ncol = max(1, (DUMP_BYTES_MAX - F.nbytes) // (8 * dF.shape[0]) - 1)
+        cols = np.sort(np.random.default_rng(0).choice(dF.shape[1], ncol, replace=False))
+        dF = dF[:, cols]
+        np.save(os.path.join(dirname, "dF_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(dirname, "F.npy"), F)
+    np.save(os.path.join(dirname, "dF.npy"), dF)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--restarts", type=int, default=64, help="R: ELBO+grad evaluations batched per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--D", type=int, default=10)
     ap.add_argument("--N", type=int, default=400)
     ap.add_argument("--K", type=int, default=50)
     ap.add_argument("--Ns", type=int, default=10000)
     ap.add_argument("--S", type=int, default=20)
-    ap.add_argument("--eps-stream", action="store_true", help="(kept for compatibility: the parity-mode leg now runs by default, see --no-aux)")
-    ap.add_argument("--extras", action="store_true", help="also report the host-loop single-chain rate and block-sparse mode")
+    ap.add_argument("--eps-stream", action="store_true", help="(kept for compatibility: the parity-mode leg runs with --full, see --no-aux)")
+    ap.add_argument("--extras", action="store_true", help="with --full: also report the host-loop single-chain rate and block-sparse mode")
     ap.add_argument("--no-aux", action="store_true",
-                    help="skip the auxiliary legs (parity-mode eps stream, single-chain device Adam, GP-side entry points) reported under 'aux'")
+                    help="with --full: skip the auxiliary legs (parity-mode eps stream, single-chain device Adam, GP-side entry points) reported under 'aux'")
     ap.add_argument("--shard-s", action="store_true",
                     help="fewer restarts than GPUs (SURVEY 8e): every step is ONE batch of --restarts evaluations sharded over the ranks "
                          "along the GP hyper-sample axis and the entropy sample chunks (strong scaling, bit-identical to 1 GPU)")
     ap.add_argument("--sync-steps", action="store_true", help="one blocking vbmc_elbo_batch call per step instead of the pipelined submit / collect")
     ap.add_argument("--check-launch", action="store_true",
                     help="rendezvous only: every rank reports (rank, pid, device) through an all-gather and rank 0 prints them; no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: blocking-call stepping, roofline, CPU baseline, aux legs, "
+                         "--extras / --eps-stream, the strong-scaling leg of --gpus N (--no-aux / --no-cpu-baseline trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the (F, dF) the last timed step returned (rank 0) as DIR/F.npy and DIR/dF.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -468,9 +499,11 @@ def main():
     if multi:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)    # before any later call can reuse the buffers the last step returned
     # ---- strong scaling (BASELINE configs[3]: the SAME 64 restarts over the GPUs): R restarts in total, R / world per rank
     strong = None
-    if comm is not None and Rr >= world:
+    if args.full and comm is not None and Rr >= world:
         batch = np.ascontiguousarray(thetas_all[:, :Rr], dtype=np.float64)
         batch = np.asfortranarray(batch)
         po_strong = comm.prepare(T, Rr, 0, vp, gps_all, Ns)
@@ -497,8 +530,8 @@ def main():
         elapsed = max(r[2] for r in rank_rows)   # MAX over ranks
     assert np.all(np.isfinite(out["F"])) and np.all(np.isfinite(out["dF"]))
 
-    # ---- everything below runs AFTER the timed region.  Each leg is guarded: a failing side measurement is recorded as
-    # {"error": ...} in its place and never suppresses the headline line.
+    # ---- everything below runs AFTER the timed region, and only with --full.  Each leg is guarded: a failing side measurement is
+    # recorded as {"error": ...} in its place and never suppresses the headline line.
     roof = None
     extra = {}
     leg_errors = {}
@@ -515,7 +548,7 @@ def main():
             return None
 
     M = Ns + (Ns % 2)
-    aux_on = rank == 0 and world == 1 and not args.no_aux
+    aux_on = args.full and rank == 0 and world == 1 and not args.no_aux
 
     def roofline_leg():
         """HIP-event duration of the dominant kernel (rank 0): the kernel ALONE on the device (vbmc_ctx_set_profiling(ctx, 2): the
@@ -810,12 +843,12 @@ def main():
             step(1000 + i)
         return 1e3 * (time.perf_counter() - t1) / n
 
-    if rank == 0 and pipelined and world == 1:
+    if args.full and rank == 0 and pipelined and world == 1:
         v = leg("sync_steps", sync_leg)
         if v is not None:
             extra["blocking_call_ms_per_step"] = v
             extra["blocking_call_evals_per_s"] = Rr / (v * 1e-3)
-    if rank == 0:
+    if args.full and rank == 0:
         roof = leg("roofline", roofline_leg)
         if args.extras:
             extra.update(leg("extras", extras_leg) or {})
@@ -853,11 +886,11 @@ def main():
                 except Exception as e_:  # noqa: BLE001
                     v["fp32_exponent"] = {"error": str(e_)[:200]}
         extra["aux"] = aux
-    elif rank == 0 and args.eps_stream:
+    elif args.full and rank == 0 and args.eps_stream:
         extra["eps_streamed"] = leg("eps_streamed", eps_leg)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = leg("cpu_baseline", lambda: cpu_baseline(inp, gp, D, K, Ns))
         if cpu is not None:
             cpu["interpreted"] = leg("cpu_baseline.interpreted", lambda: interpreted_baseline(D, K, Ns))
@@ -871,7 +904,7 @@ def main():
         line = {
             "metric": "ELBO+grad evals/sec (Ns=1e4, K=50, D=10, N=400)" if (D, N, K, Ns) == (10, 400, 50, 10000)
             else "ELBO+grad evals/sec (Ns=%d, K=%d, D=%d, N=%d)" % (Ns, K, D, N),
-            "value": evals / elapsed, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": evals / elapsed, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "warmup_untimed_extra": WARM_EXTRA,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong" if shard_ex is not None else "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic (seeded lumpy 12-component target, SURVEY 8d); device Philox MC draws",

@@ -320,7 +320,7 @@ def test_bench_multi_gpu_code_path_with_one_rank(va):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VBMC_BENCH_FORCE_COMM="1", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-aux",
+                        "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--no-aux",
                         "--no-cpu-baseline", "--restarts", "8"], capture_output=True, text=True, cwd=root, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

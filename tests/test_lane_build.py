@@ -45,7 +45,7 @@ def test_fused_prediction_kernel_does_not_spill(tmp_path):
     with open(src, "w") as f:
         f.write('#include "%s/common.h"\n#include "%s/device_math.h"\n#include "%s/trsm_mfma.h"\n#include "%s/gp_kernels.h"\n' % ((CSRC,) * 4))
         for q, p in combos:
-            f.write("template __global__ void k_pred_fused<%d, %d>(PredArgs, const double*, const double*, const double*, double*, double*);\n" % (q, p))
+            f.write("template __global__ void k_pred_fused<%d, %d>(PredArgs, const double*, const double*, const double*, double*, double*, int);\n" % (q, p))
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-I" + os.path.join(ROOT, "include"),
                         "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "pf.o")], capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]

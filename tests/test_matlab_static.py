@@ -1,12 +1,29 @@
 """CPU: static sanity of the MATLAB side (there is no MATLAB / Octave here to run it): every .m file under matlab/ and tools/ has
 balanced block keywords, a leading function line whose name matches the file, and calls into the MEX gateway only with commands
-the gateway implements."""
+the gateway implements.  What the checks need to know of the reference's MATLAB files (the function lines of the files the shims
+replace, hashes of the code lines of the two callers the shims wrap, the random draws of three files) is stored in
+tests/golden/reference_matlab.json; `python tests/test_matlab_static.py <reference root>` regenerates it."""
 import glob
+import hashlib
+import json
 import os
 import re
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MFILES = sorted(glob.glob(os.path.join(ROOT, "matlab", "*.m")) + glob.glob(os.path.join(ROOT, "tools", "*.m")))
+REF_FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_matlab.json")
+REF_SIEVE_CALLERS = ("misc/vpsieve_vbmc.m", "misc/vpoptimize_vbmc.m")
+REF_DRAWS = ("ent/entmc_vbmc.m", "misc/vpoptimize_vbmc.m", "misc/negelcbo_vbmc.m")
+
+
+def _reference():
+    with open(REF_FIXTURE) as f:
+        return json.load(f)
+
+
+def _line_hash(line):
+    return hashlib.sha256(line.encode()).hexdigest()[:16]
 
 
 def strip(txt):
@@ -45,6 +62,11 @@ def test_mex_commands_exist_in_the_gateway():
     assert used and used <= implemented, sorted(used - implemented)
 
 
+def calls(txt):
+    """the random-stream draws a MATLAB text makes, in order"""
+    return re.findall(r"\b(randn|randi|rand|randperm)\s*\(", strip(txt))
+
+
 def _signature(path):
     txt = open(path, errors="replace").read()
     m = re.search(r"^\s*function\s+(?:\[([^\]]*)\]|(\w+))?\s*=?\s*(\w+)\s*\(([^)]*)\)", txt, re.M)
@@ -56,18 +78,9 @@ def _signature(path):
 
 def test_shim_signatures_match_the_reference():
     """Drop-in by path lookup only works if a same-named shim takes and returns what the reference function does: compare the
-    function lines (names and ORDER of inputs and outputs) with the reference's files where the reference is available (this
-    container; skipped on a box without /root/reference)."""
-    import pytest
-
-    ref_root = "/root/reference"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference not present")
-    index = {}
-    for dp, _, fn in os.walk(ref_root):
-        for f in fn:
-            if f.endswith(".m"):
-                index.setdefault(f, []).append(os.path.join(dp, f))
+    function lines (names and ORDER of inputs and outputs) with the reference's files (their function lines as recorded in
+    tests/golden/reference_matlab.json)."""
+    index = _reference()["signatures"]
     checked = 0
     for f in sorted(glob.glob(os.path.join(ROOT, "matlab", "*.m"))):
         base = os.path.basename(f)
@@ -75,7 +88,7 @@ def test_shim_signatures_match_the_reference():
             continue                      # helpers of the shim layer itself
         # gplite/private/sq_dist.m and utils/sq_dist.m are the same function; any one of the candidates must match
         name, outs, args = _signature(f)
-        cands = [_signature(p) for p in index[base]]
+        cands = index[base]
         assert any(name == n and len(outs) == len(o) and [a.lower() for a in args] == [b.lower() for b in a_]
                    for n, o, a_ in cands), (base, outs, args, cands)
         checked += 1
@@ -103,17 +116,14 @@ def test_caller_shims_do_not_restate_the_reference():
     """matlab/vpsieve_vbmc.m (record and replay around the reference's own sieve) and matlab/vpoptimize_vbmc.m (+ its pruning
     helper) must not carry the reference's text: fewer than 15 % of their code lines, whitespace-stripped, occur in the
     same-named reference file -- block keywords (end / else / try) included in the count; the function line is left out (it is
-    the interface: test_shim_signatures_match_the_reference REQUIRES it to be the reference's)."""
-    import pytest
-
-    ref_root = "/root/reference/misc"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference not present")
-    for mine, ref in (("vpsieve_vbmc.m", "vpsieve_vbmc.m"), ("vpoptimize_vbmc.m", "vpoptimize_vbmc.m"),
-                      ("vbmc_hip_prune.m", "vpoptimize_vbmc.m"), ("vbmc_hip_sieve.m", "vpsieve_vbmc.m")):
+    the interface: test_shim_signatures_match_the_reference REQUIRES it to be the reference's).  The reference's lines are known by
+    their hashes (tests/golden/reference_matlab.json)."""
+    hashes = _reference()["code_line_sha256_16"]
+    for mine, ref in (("vpsieve_vbmc.m", "misc/vpsieve_vbmc.m"), ("vpoptimize_vbmc.m", "misc/vpoptimize_vbmc.m"),
+                      ("vbmc_hip_prune.m", "misc/vpoptimize_vbmc.m"), ("vbmc_hip_sieve.m", "misc/vpsieve_vbmc.m")):
         a = [ln for ln in _code_lines(os.path.join(ROOT, "matlab", mine)) if not ln.startswith("function[")]
-        b = set(_code_lines(os.path.join(ref_root, ref)))
-        same = [ln for ln in a if ln in b]
+        b = set(hashes[ref])
+        same = [ln for ln in a if _line_hash(ln) in b]
         assert len(same) < 0.15 * len(a), (mine, len(same), len(a), [ln for ln in same if ln not in ("end", "else", "try")])
 
 
@@ -139,7 +149,6 @@ def test_random_draws_per_branch_match_the_reference():
     Ns == 0 (entlb_vbmc), one randi per pruning attempt (misc/vpoptimize_vbmc.m:204), nothing else.  The seed of the device
     stream (a randi) may only be drawn where the device stream is used.  Static: no MATLAB here to run the shims."""
     rd = lambda f: open(os.path.join(ROOT, "matlab", f)).read()  # noqa: E731
-    calls = lambda txt: re.findall(r"\b(randn|randi|rand|randperm)\s*\(", strip(txt))  # noqa: E731
     # negelcbo_vbmc: every draw sits inside `if Ns > 0`; there, randn in the parity branch and the seed in the other
     src = rd("negelcbo_vbmc.m")
     blk = _block(src, "if Ns > 0")
@@ -167,12 +176,11 @@ def test_random_draws_per_branch_match_the_reference():
     assert calls(head) == [] and "inside_path" in head
     assert "vbmc_hip_state('parity')" in _block(src, "function ok = inside_path")
     assert set(calls(src)) == {"randi"} and "randi(2^31-1)" in src and len(calls(src)) == 2
-    if os.path.isdir("/root/reference"):
-        # the reference's own counts, so that drift upstream is noticed
-        assert len(calls(open("/root/reference/ent/entmc_vbmc.m").read())) == 1
-        ref = open("/root/reference/misc/vpoptimize_vbmc.m").read()
-        assert calls(ref) == ["randi"] and "idx(randi(numel(idx)))" in ref
-        assert calls(open("/root/reference/misc/negelcbo_vbmc.m").read()) == []
+    # the reference's own counts (as recorded in tests/golden/reference_matlab.json), so that drift upstream is noticed
+    ref = _reference()["random_draws"]
+    assert len(ref["ent/entmc_vbmc.m"]) == 1
+    assert ref["misc/vpoptimize_vbmc.m"] == ["randi"] and _reference()["vpoptimize_draws_idx_randi_numel_idx"]
+    assert ref["misc/negelcbo_vbmc.m"] == []
 
 
 def test_gplite_post_keeps_the_device_posterior_and_gplogjoint_falls_through():
@@ -187,3 +195,27 @@ def test_gplite_post_keeps_the_device_posterior_and_gplogjoint_falls_through():
     lj = strip(open(os.path.join(ROOT, "matlab", "gplogjoint.m")).read())
     assert "try" in lj and "catch err" in lj and "vbmc_hip_supported(gp,vp" in lj
     assert re.search(r"strcmp\(err\.identifier,\s*''\)", lj) and "vbmc_hip_reference(''" in lj
+
+
+def write_reference_fixture(ref_root):
+    """tests/golden/reference_matlab.json from a checkout of the reference: no source text, only what the checks above compare."""
+    index = {}
+    for dp, _, fn in os.walk(ref_root):
+        for f in sorted(fn):
+            if f.endswith(".m"):
+                index.setdefault(f, []).append(os.path.join(dp, f))
+    shims = sorted(os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "matlab", "*.m")))
+    rd = lambda rel: open(os.path.join(ref_root, rel), errors="replace").read()  # noqa: E731
+    fixture = {
+        "signatures": {b: [list(_signature(p)) for p in sorted(index[b])] for b in shims if not b.startswith("vbmc_hip_") and b in index},
+        "code_line_sha256_16": {rel: sorted({_line_hash(ln) for ln in _code_lines(os.path.join(ref_root, rel))}) for rel in REF_SIEVE_CALLERS},
+        "random_draws": {rel: calls(rd(rel)) for rel in REF_DRAWS},
+        "vpoptimize_draws_idx_randi_numel_idx": "idx(randi(numel(idx)))" in rd("misc/vpoptimize_vbmc.m"),
+    }
+    with open(REF_FIXTURE, "w") as f:
+        json.dump(fixture, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    write_reference_fixture(sys.argv[1])

@@ -75,7 +75,7 @@ for name, label in (("c1", "BASELINE configs[1]: D=6 N=200 K=10 Ns=1000 S=8, R=6
     if os.path.exists(o + "kernel_trace_%s.md" % name):
         bl = last_json(rd("bench_%s.json" % name))
         cfg_txt += f"""
-## {label}: `rocprofv3 --kernel-trace --stats` and one `--pmc` pass of `python bench.py <shape flags> --no-cpu-baseline --no-aux`
+## {label}: `rocprofv3 --kernel-trace --stats` and one `--pmc` pass of `python bench.py --full <shape flags> --no-cpu-baseline --no-aux`
 
 ```
 {bl[:1500]}
@@ -88,16 +88,16 @@ for name, label in (("c1", "BASELINE configs[1]: D=6 N=200 K=10 Ns=1000 S=8, R=6
 txt = f"""# Round {int(RND[1:])}, profile {tag[1:]}
 
 Produced by `bash tools/profile_round.sh {tag}` on the MI355X box (`cd /tmp && export TMPDIR=/tmp` first): full GPU
-test suite, `python bench.py --extras`, `tools/bench_aux.py`, `tools/microbench.hip`, then
+test suite, `python bench.py --full --extras`, `tools/bench_aux.py`, `tools/microbench.hip`, then
 `rocprofv3 --kernel-trace --stats` and two separate `--pmc` passes of
-`python bench.py [--steps 3 --warmup 1] --no-cpu-baseline --no-aux` (the timed region of the default command; the auxiliary legs and the CPU baseline run after it); assembled by `tools/compose_profile.py`.  {changes}
+`python bench.py --full [--steps 3 --warmup 1] --no-cpu-baseline --no-aux` (the timed region of the default command; the side legs of --full run after it); assembled by `tools/compose_profile.py`.  {changes}
 In a blocking call `k_logjoint_mfma` runs on the context's second, lower-priority stream beside the entropy kernel: its traced duration there
 is the span over which its workgroups were fitted into the entropy kernel's idle slots (alone it takes 0.12 ms); in the pipelined steps it runs
 at the head of its pass on the slot stream, beside the other pass's entropy kernel.
 
 `pytest tests -m gpu`: **{rd('pytest_gpu.txt').splitlines()[-1]}**.
 
-## Bench line (`python bench.py --extras`, un-profiled)
+## Bench line (`python bench.py --full --extras`, un-profiled)
 
 ```
 {rd('bench.json')}
