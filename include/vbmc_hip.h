@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VBMC_ABI_VERSION 5
+#define VBMC_ABI_VERSION 6
 
 typedef int vbmc_status;
 enum {
@@ -457,6 +457,26 @@ int vbmc_entropy_plan(int D, int K, int* qs, int* kt, int* hv, int* tail);
 /* Test hook: y = exp(x) evaluated by the hot-loop device implementations (0: polynomial, 1 / 2: 256-entry table with the two- /
  * one-constant reduction, 3: the Monte-Carlo entropy kernel's exponential as built, 4 / 5: its cubic / quadratic form). */
 vbmc_status vbmc_test_exp(vbmc_ctx* ctx, int n, int variant, const double* x, double* y);
+
+/* Test hook (ABI version 6): which kernels the last ELBO pass enqueued on ctx (vbmc_elbo_batch, vbmc_elbo_submit, vbmc_adam_batch's
+ * last iteration, a shard's vbmc_elbo_shard_begin) used for the entropy and for the expected log joint; 0 where none ran.  The
+ * launch forms are chosen by shape and by the VBMC_*_KERNEL / VBMC_LJ_CO switches, and some requests fall back silently (a forced
+ * matrix-core log joint whose moment exchange exceeds 64 KB runs the VALU kernel): tests that force a form check it here. */
+enum {
+  VBMC_ENTFORM_LB = 1,          /* k_entlb: the deterministic bound (Ns = 0)                                                     */
+  VBMC_ENTFORM_VALU = 2,        /* k_entropy<DT>                                                                                  */
+  VBMC_ENTFORM_MFMA = 3,        /* k_entropy_mfma                                                                                 */
+  VBMC_ENTFORM_LANE = 4         /* k_entropy_lane                                                                                 */
+};
+enum {
+  VBMC_LJFORM_VALU_WAVE = 1,    /* separate k_logjoint<DT>, one wave per cell                                                     */
+  VBMC_LJFORM_VALU_SPLIT = 2,   /* separate k_logjoint<DT>, the training set split over four waves per cell                       */
+  VBMC_LJFORM_MFMA_GRAD = 3,    /* k_logjoint_mfma<DT, true>                                                                      */
+  VBMC_LJFORM_MFMA_VALUE = 4,   /* k_logjoint_mfma<DT, false> (value-only passes)                                                 */
+  VBMC_LJFORM_ROLE_MFMA = 5,    /* a role inside the k_entropy_mfma launch                                                        */
+  VBMC_LJFORM_ROLE_LANE = 6     /* a role inside the k_entropy_lane launch                                                        */
+};
+vbmc_status vbmc_ctx_last_launch(vbmc_ctx* ctx, int* ent_form, int* lj_form);
 
 /* Device-memory helpers for callers without their own allocator (MEX). */
 vbmc_status vbmc_device_alloc(vbmc_ctx* ctx, size_t bytes, void** dptr);

@@ -127,8 +127,9 @@ static double scalar_field(const mxArray* s, const char* name, double dflt) {
   return (f && !mxIsEmpty(f)) ? mxGetScalar(f) : dflt;
 }
 
-// vp struct + thetabnd -> the parameter-layout part of vbmc_elbo_args (shared by 'elbo', 'elbo_batch', 'adam')
-static void fill_vp_args(vbmc_elbo_args& a, const mxArray* vp, const mxArray* tb, std::vector<double>& delta) {
+// vp struct + thetabnd -> the parameter-layout part of vbmc_elbo_args (shared by 'elbo', 'elbo_batch', 'adam').  Returns nonzero with a
+// pending 'vbmc_hip:unsupported' error for a vp.delta that is neither a scalar nor a D-vector (the reference cannot evaluate it either)
+static int fill_vp_args(vbmc_elbo_args& a, const mxArray* vp, const mxArray* tb, std::vector<double>& delta) {
   memset(&a, 0, sizeof a);
   a.struct_size = sizeof a;
   a.D = (int)scalar_field(vp, "D", 0); a.K = (int)scalar_field(vp, "K", 0); a.R = 1;
@@ -137,8 +138,10 @@ static void fill_vp_args(vbmc_elbo_args& a, const mxArray* vp, const mxArray* tb
   a.vp_mu = dbl(field(vp, "mu")); a.vp_sigma = dbl(field(vp, "sigma")); a.vp_lambda = dbl(field(vp, "lambda")); a.vp_w = dbl(field(vp, "w"));
   const mxArray* dl = field(vp, "delta");
   if (dl && !mxIsEmpty(dl)) {  // scalar or D-vector (gplogjoint.m:85-89)
+    const size_t nd = mxGetNumberOfElements(dl);
+    if (nd != 1 && nd != (size_t)a.D) return raise("vbmc_hip:unsupported", "vp.delta has neither one entry nor D");
     delta.assign(a.D, mxGetDoubles(dl)[0]);
-    if ((int)mxGetNumberOfElements(dl) == a.D) memcpy(delta.data(), mxGetDoubles(dl), a.D * sizeof(double));
+    if (nd == (size_t)a.D) memcpy(delta.data(), mxGetDoubles(dl), a.D * sizeof(double));
     a.vp_delta = delta.data();
   }
   if (tb && !mxIsEmpty(tb)) {
@@ -146,6 +149,7 @@ static void fill_vp_args(vbmc_elbo_args& a, const mxArray* vp, const mxArray* tb
     a.WeightThreshold = scalar_field(tb, "WeightThreshold", 0); a.WeightPenalty = scalar_field(tb, "WeightPenalty", 0);
   }
   { const char* sc = getenv("VBMC_HIP_SPARSE_CUTOFF"); a.sparse_cutoff = sc ? atof(sc) : 0.0; }
+  return 0;
 }
 
 // gp struct (gplite_post.m:94-157) -> the flat arrays of vbmc_gp_upload; returns the sizes
@@ -274,7 +278,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     const mxArray* vp = prhs[3];
     vbmc_elbo_args a;
     std::vector<double> delta;
-    fill_vp_args(a, vp, nrhs > 9 ? prhs[9] : nullptr, delta);
+    if (fill_vp_args(a, vp, nrhs > 9 ? prhs[9] : nullptr, delta)) return 1;
     a.theta = mxGetDoubles(theta);
     a.Ns = (int)mxGetScalar(prhs[4]);
     a.compute_grad = (int)mxGetScalar(prhs[5]); a.compute_var = (int)mxGetScalar(prhs[6]); a.separate_K = (int)mxGetScalar(prhs[7]);
@@ -341,7 +345,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     const mxArray* Theta = prhs[2];
     vbmc_elbo_args a;
     std::vector<double> delta;
-    fill_vp_args(a, prhs[3], nrhs > 8 ? prhs[8] : nullptr, delta);
+    if (fill_vp_args(a, prhs[3], nrhs > 8 ? prhs[8] : nullptr, delta)) return 1;
     const size_t T = mxGetM(Theta);
     a.R = (int)mxGetN(Theta);
     a.theta = mxGetDoubles(Theta);
@@ -383,7 +387,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     const mxArray* Theta = prhs[2];
     vbmc_elbo_args a;
     std::vector<double> delta;
-    fill_vp_args(a, prhs[3], nrhs > 7 ? prhs[7] : nullptr, delta);
+    if (fill_vp_args(a, prhs[3], nrhs > 7 ? prhs[7] : nullptr, delta)) return 1;
     const size_t T = mxGetM(Theta);
     a.R = (int)mxGetN(Theta);
     a.theta = mxGetDoubles(Theta);

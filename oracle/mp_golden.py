@@ -14,6 +14,8 @@ Formulas follow (reference paths, acerbilab/vbmc v1.0.12):
   pred     gplite/gplite_noisefun.m:176-210 + gplite_core.m:33-102 + gplite_pred.m:60-127 with the general noise models,
            ystar / s2star and the log predictive density lp (mp_pred_case*.json)
   pen      misc/vpbndloss.m:1-73, utils/softbndloss.m:1-30, misc/negelcbo_vbmc.m:146-162 (mp_pen_case*.json)
+  delta    misc/gplogjoint.m:164,171-172,274,313 with a per-dimension vp.delta (mp_delta_case*.json; the gradient of the
+           diagonal variance by 50-digit central differences of the value)
   nlZ      gplite/private/gplite_core.m:205 (value); its gradient (:236-275) is pinned by 50-digit central
            differences of the value, i.e. independently of the reference's analytic Q-matrix formulas
 
@@ -194,10 +196,12 @@ def mp_gp_pred(hyp, X, alpha, L, sn2, Xs, meanfun):
 
 
 # ------------------------------------------------------------------ gplogjoint
-def mp_logjoint(mu, sigma, lam, w, eta, X, posts, meanfun, compute_var):
+def mp_logjoint(mu, sigma, lam, w, eta, X, posts, meanfun, compute_var, delta=None):
     """posts: list of dict(hyp, alpha, L, sn2).  Returns per-sample F[s], dF[s][t],
-    I_sk, J_sjk (full), varF[s] for compute_var in {1,2}; averaging done by caller tests."""
+    I_sk, J_sjk (full), varF[s] for compute_var in {1,2}; averaging done by caller tests.
+    delta: vp.delta per dimension (None: zero), gplogjoint.m:164,171-172,274,313."""
     D, K, N = len(mu), len(sigma), len(X)
+    dl2 = [mp.mpf(0)] * D if delta is None else [delta[d] ** 2 for d in range(D)]
     S = len(posts)
     eps = mp.mpf(2) ** -52
     Fs, dFs, I_sk, J_all, varFs = [], [], [], [], []
@@ -223,14 +227,15 @@ def mp_logjoint(mu, sigma, lam, w, eta, X, posts, meanfun, compute_var):
         Ik = []
         zs = []
         for k in range(K):
-            tau = [mp.sqrt(sigma[k] ** 2 * lam[d] ** 2 + ell[d] ** 2) for d in range(D)]
+            tau = [mp.sqrt(sigma[k] ** 2 * lam[d] ** 2 + ell[d] ** 2 + dl2[d]) for d in range(D)]
             lnnf = ln_sf2 + sum_lnell - mp.fsum(mp.log(t) for t in tau)
             delt = [[(mu[d][k] - X[n][d]) / tau[d] for n in range(N)] for d in range(D)]
             z = [mp.e ** (lnnf - mp.fsum(delt[d][n] ** 2 for d in range(D)) / 2) for n in range(N)]
             zs.append(z)
             I = mp.fsum(z[n] * alpha[n] for n in range(N)) + m0
             if meanfun == 4:
-                I += -mp.fsum((mu[d][k] ** 2 + sigma[k] ** 2 * lam[d] ** 2 - 2 * mu[d][k] * xm[d] + xm[d] ** 2) / om[d] ** 2 for d in range(D)) / 2
+                I += -mp.fsum((mu[d][k] ** 2 + sigma[k] ** 2 * lam[d] ** 2 - 2 * mu[d][k] * xm[d] + xm[d] ** 2 + dl2[d]) / om[d] ** 2
+                              for d in range(D)) / 2
             Ik.append(I)
             F += w[k] * I
             for d in range(D):
@@ -259,7 +264,7 @@ def mp_logjoint(mu, sigma, lam, w, eta, X, posts, meanfun, compute_var):
             J = [[mp.mpf(0)] * K for _ in range(K)]
             for k in range(K):
                 for j in range(K):
-                    tau_jk = [mp.sqrt((sigma[j] ** 2 + sigma[k] ** 2) * lam[d] ** 2 + ell[d] ** 2) for d in range(D)]
+                    tau_jk = [mp.sqrt((sigma[j] ** 2 + sigma[k] ** 2) * lam[d] ** 2 + ell[d] ** 2 + 2 * dl2[d]) for d in range(D)]
                     lnnf_jk = ln_sf2 + sum_lnell - mp.fsum(mp.log(t) for t in tau_jk)
                     d_jk = mp.fsum(((mu[d][j] - mu[d][k]) / tau_jk[d]) ** 2 for d in range(D))
                     J[j][k] = mp.e ** (lnnf_jk - d_jk / 2) - mp.fsum(zs[k][n] * Kinvz[j][n] for n in range(N))
@@ -845,6 +850,110 @@ def main_nlz():
         print("wrote", path, os.path.getsize(path), "bytes", file=sys.stderr)
 
 
+# ------------------------------------------------------------------ vp.delta (gplogjoint.m:164,171-172,274,313)
+def mp_vardiag_theta(th, D, K, X, posts, delta):
+    """varG_s_diag (compute_var = 2, gplogjoint.m:273-283) as a function of theta = [mu (D K) | log sigma | log lambda | eta]:
+    a second scalar restatement of the self-variance alone, differentiated numerically below (its closed-form gradient,
+    :286-304, is what the fixtures pin)."""
+    N = len(X)
+    mu = [[th[k * D + d] for k in range(K)] for d in range(D)]
+    sigma = [mp.e ** th[D * K + k] for k in range(K)]
+    lam = [mp.e ** th[D * K + K + d] for d in range(D)]
+    ee = [mp.e ** t for t in th[D * K + K + D :]]
+    w = [t / mp.fsum(ee) for t in ee]
+    dl2 = [delta[d] ** 2 for d in range(D)]
+    eps = mp.mpf(2) ** -52
+    out = []
+    for p in posts:
+        hyp, L, sn2 = p["hyp"], p["L"], p["sn2"]
+        ell2 = [mp.e ** (2 * hyp[d]) for d in range(D)]
+        lnsf2_lnell = 2 * hyp[D] + mp.fsum(hyp[:D])
+        v = mp.mpf(0)
+        for k in range(K):
+            tau2 = [sigma[k] ** 2 * lam[d] ** 2 + ell2[d] + dl2[d] for d in range(D)]
+            lnnf = lnsf2_lnell - mp.fsum(mp.log(t) for t in tau2) / 2
+            z = [mp.e ** (lnnf - mp.fsum((mu[d][k] - X[n][d]) ** 2 / tau2[d] for d in range(D)) / 2) for n in range(N)]
+            Kinvz = [t / sn2 for t in mp_solve_ut(L, mp_solve_ut_t(L, z))]
+            tau2_kk = [2 * sigma[k] ** 2 * lam[d] ** 2 + ell2[d] + 2 * dl2[d] for d in range(D)]
+            J_kk = mp.e ** (lnsf2_lnell - mp.fsum(mp.log(t) for t in tau2_kk) / 2) - mp.fsum(z[n] * Kinvz[n] for n in range(N))
+            v += w[k] ** 2 * max(eps, J_kk)
+        out.append(max(v, eps))
+    return out
+
+
+DELTA_CASES = [
+    # delta: a vector whose entries differ per dimension, of the order of ell_d (~0.8) and sigma_k lambda_d (~0.4): z moves by O(1);
+    # "scalar": one value for every dimension (vpsieve_vbmc.m:16 with a scalar options.Bandwidth)
+    dict(seed=51, D=2, K=3, N=8, S=1, meanfun=4, delta="vector"),
+    dict(seed=52, D=3, K=4, N=10, S=3, meanfun=4, delta="vector"),
+    dict(seed=53, D=1, K=3, N=8, S=2, meanfun=1, delta="vector"),
+    dict(seed=54, D=3, K=3, N=9, S=2, meanfun=0, delta="vector"),
+    dict(seed=55, D=2, K=2, N=7, S=2, meanfun=4, delta="scalar"),
+]
+
+
+def make_delta_case(seed, D, K, N, S, meanfun, delta):
+    c = make_case(seed, D, K, N, S, 1, meanfun)
+    for k in ("Mh", "eps", "Xstar"):     # the entropy / prediction inputs of the mp_case family are not used here
+        del c[k]
+    rng = np.random.default_rng(2000 + seed)
+    c["delta"] = float(0.3 + 0.5 * rng.random()) if delta == "scalar" else 0.3 + 0.6 * rng.random(D)
+    return c
+
+
+def run_delta_case(c):
+    """G_s, dG_s, I_sk, J_sjk, varG_s_full, varG_s_diag with vp.delta, and dvarG_s_diag: 50-digit central differences of varG_s_diag
+    over theta (independent of the closed form, gplogjoint.m:286-304)."""
+    D, K, N, S = c["D"], c["K"], c["N"], c["S"]
+    mu = [[M(c["mu"][d, k]) for k in range(K)] for d in range(D)]
+    sigma = [M(t) for t in c["sigma"]]
+    lam = [M(t) for t in c["lam"]]
+    eta = [M(t) for t in c["eta"]]
+    ee = [mp.e ** t for t in eta]
+    w = [t / mp.fsum(ee) for t in ee]
+    X = [[M(c["X"][n, d]) for d in range(D)] for n in range(N)]
+    y = [M(t) for t in c["y"]]
+    delta = [M(c["delta"])] * D if np.ndim(c["delta"]) == 0 else [M(t) for t in c["delta"]]
+    out = {"alpha": [], "L": []}
+    posts = []
+    for s in range(S):
+        hyp = [M(t) for t in c["hyp"][:, s]]
+        alpha, L, sn2 = mp_gp_post(hyp, X, y, c["meanfun"])
+        posts.append(dict(hyp=hyp, alpha=alpha, L=L, sn2=sn2))
+        out["alpha"].append(fl(alpha))
+        out["L"].append(fl(L))
+    Fs, dFs, I_sk, J, varF1 = mp_logjoint(mu, sigma, lam, w, eta, X, posts, c["meanfun"], 1, delta=delta)
+    _, _, _, _, varF2 = mp_logjoint(mu, sigma, lam, w, eta, X, posts, c["meanfun"], 2, delta=delta)
+    out["G_s"], out["dG_s"], out["I_sk"], out["J_sjk"] = fl(Fs), fl(dFs), fl(I_sk), fl(J)
+    out["varG_s_full"], out["varG_s_diag"] = fl(varF1), fl(varF2)
+    th0 = [mu[d][k] for k in range(K) for d in range(D)] + [mp.log(t) for t in sigma] + [mp.log(t) for t in lam] + eta
+    v0 = mp_vardiag_theta(th0, D, K, X, posts, delta)
+    assert all(abs(a - b) <= mp.mpf(10) ** -40 * abs(b) for a, b in zip(v0, varF2)), "the two restatements of varG_s_diag disagree"
+    h = mp.mpf(10) ** -18
+    g = [[None] * len(th0) for _ in range(S)]
+    for i in range(len(th0)):
+        vp_ = mp_vardiag_theta(th0[:i] + [th0[i] + h] + th0[i + 1 :], D, K, X, posts, delta)
+        vm_ = mp_vardiag_theta(th0[:i] + [th0[i] - h] + th0[i + 1 :], D, K, X, posts, delta)
+        for s in range(S):
+            g[s][i] = (vp_[s] - vm_[s]) / (2 * h)
+    out["dvarG_s_diag"] = fl(g)
+    return out
+
+
+def main_delta():
+    outdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+    for i, spec in enumerate(DELTA_CASES):
+        c = make_delta_case(**spec)
+        out = run_delta_case(c)
+        rec = {"generator": "oracle/mp_golden.py delta (mpmath %s, dps=%d)" % (mp.__version__, mp.mp.dps),
+               "inputs": {k: (tolist(v) if isinstance(v, np.ndarray) else v) for k, v in c.items()},
+               "expected": out}
+        path = os.path.join(outdir, "mp_delta_case%d.json" % i)
+        with open(path, "w") as f:
+            json.dump(rec, f)
+        print("wrote", path, os.path.getsize(path), "bytes", file=sys.stderr)
+
+
 if __name__ == "__main__":
     if "rosenbrock" in sys.argv[1:]:
         main(only=[i for i, c in enumerate(CASES) if c.get("target") == "rosenbrock"])   # only mp_case4.json (BASELINE configs[0])
@@ -856,9 +965,12 @@ if __name__ == "__main__":
         main_pen()
     elif "acq" in sys.argv[1:]:
         main_acq()      # only the acquisition-function fixtures
+    elif "delta" in sys.argv[1:]:
+        main_delta()    # only the vp.delta fixtures (mp_delta_case*.json)
     else:
         main()
         main_nlz()
         main_acq()
         main_pred()
         main_pen()
+        main_delta()

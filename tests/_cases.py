@@ -14,6 +14,23 @@ def golden_cases():
     return sorted(glob.glob(os.path.join(GOLDEN, "mp_case*.json")))
 
 
+def delta_golden_cases():
+    """tests/golden/mp_delta_case*.json: gplogjoint with a nonzero vp.delta (oracle/mp_golden.py delta)."""
+    return sorted(glob.glob(os.path.join(GOLDEN, "mp_delta_case*.json")))
+
+
+def load_delta_golden(path):
+    """-> (inputs dict, vp with its delta, gp with the 50-digit alpha / L plugged in, expected dict of arrays)."""
+    inp, exp = load_golden(path)
+    vp = vp_from_inputs(inp)
+    vp["delta"] = inp["delta"]      # a float (scalar case) or a D-vector
+    gp = R.gplite_post(inp["hyp"], inp["X"], inp["y"], meanfun=inp["meanfun"])
+    for s, post in enumerate(gp["post"]):
+        post["alpha"] = np.array(exp["alpha"][s])
+        post["L"] = np.array(exp["L"][s])
+    return inp, vp, gp, {k: np.array(v, dtype=np.float64) for k, v in exp.items()}
+
+
 def nlz_golden_cases():
     return sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "mp_nlz_case*.json")))
 

@@ -85,6 +85,9 @@ SHAPES = [
 
 @pytest.mark.parametrize("D,N,K,S,Ns", SHAPES)
 def test_lane_kernel_matches_oracle_and_matrix_core_kernel(va, monkeypatch, D, N, K, S, Ns):
+    from tests.test_gpu_delta import lane_role_fits
+    from vbmc_amd import _lib
+
     monkeypatch.setenv("VBMC_ENT_KERNEL", "lane")    # (a single evaluation is below the width the policy gives the lane kernel: ask for it)
     p, gp, vp, theta = problem(100 + D + K, D, N, K, S)
     Mh = (Ns + 1) // 2
@@ -99,6 +102,13 @@ def test_lane_kernel_matches_oracle_and_matrix_core_kernel(va, monkeypatch, D, N
         m = va.negelcbo_batch(theta, 0, vp, gp, Ns, True, 0, eps=eps)
         md = va.negelcbo_batch(theta, 0, vp, gp, Ns, True, 0, seed=11)
     ld = va.negelcbo_batch(theta, 0, vp, gp, Ns, True, 0, seed=11)
+    ctx = va.default_engine().ctx
+    # the lane launch carries the log joint as a role wherever the role's staged inputs fit its LDS block; the corner the lane kernels
+    # are not built for (DT = 12 with KP >= 10, DT = 10 with KP >= 12) stays on the matrix-core kernel and its role
+    dt, kp = 2 * ((D + 1) // 2), 2 * ((K + 1) // 2)
+    lane = not ((dt >= 12 and kp >= 10) or (dt >= 10 and kp >= 12))
+    ent = _lib.ENTFORM_LANE if lane else _lib.ENTFORM_MFMA
+    assert ctx.last_launch() == (ent, (_lib.LJFORM_ROLE_LANE if lane_role_fits(D, K, N, S) else _lib.LJFORM_VALU_SPLIT) if lane else _lib.LJFORM_ROLE_MFMA)
     for a, b in ((r, m), (ld, md)):
         assert relerr(a["H"][0], b["H"][0]) < 1e-12 and relerr(a["dH"][:, 0], b["dH"][:, 0]) < 1e-11
         # (the expected log joint is a sum of terms z_n alpha_n that cancel: both are compared with the oracle at 1e-10 above; against
@@ -109,6 +119,7 @@ def test_lane_kernel_matches_oracle_and_matrix_core_kernel(va, monkeypatch, D, N
     assert relerr(v["H"][0], ld["H"][0]) < 1e-13 and relerr(v["G"][0], ld["G"][0]) < RT_VAL
     with env(VBMC_LJ_CO="0"):
         o = va.negelcbo_batch(theta, 0, vp, gp, Ns, True, 0, seed=11)
+        assert ctx.last_launch() == (ent, _lib.LJFORM_VALU_SPLIT if N > 64 else _lib.LJFORM_VALU_WAVE), ctx.last_launch()
     assert np.array_equal(o["H"], ld["H"]) and np.array_equal(o["dH"], ld["dH"])
     assert relerr(o["G"][0], ld["G"][0]) < RT_VAL and relerr(o["dG"][:, 0], ld["dG"][:, 0]) < RT_GRAD
 

@@ -307,6 +307,33 @@ def test_acquisition_commands(mex, va):
     mex.call(0, "gp_free", hh)
 
 
+def test_vp_delta_column_and_scalar(mex, va):
+    """vp.delta as VBMC sets it (a D x 1 column, vpsieve_vbmc.m:16) and as a scalar: bit-identical to the ctypes path; a length that is
+    neither 1 nor D is refused as unsupported (the shim falls through), not broadcast from its first entry"""
+    from tests._mex import MexError
+
+    p, gp, vp, theta = make(seed=6)
+    D = vp["D"]
+    rng = np.random.default_rng(2)
+    Th = np.asfortranarray(theta[:, None] + 0.05 * rng.standard_normal((theta.size, 3)))
+    hh = np.uint64(mex.call(1, "gp_upload", gp_struct(gp))[0][0, 0])
+    plain = va.negelcbo_batch(Th, 0, vp, gp, 40, True, 0, None, seed=5)
+    for delta in (0.4 + 0.5 * rng.random((D, 1)), np.full((1, 1), 0.6)):
+        F, dF = mex.call(2, "elbo_batch", hh, Th, dict(vp_struct(vp), delta=delta), 40, 1, 0, 0, None, 5)
+        ref = va.negelcbo_batch(Th, 0, dict(vp, delta=delta.reshape(-1) if delta.size > 1 else float(delta[0, 0])), gp, 40, True, 0, None, seed=5)
+        same(F[0], ref["F"]); same(dF, ref["dF"])
+        assert np.max(np.abs(ref["F"] - plain["F"])) > 1e-6 * np.max(np.abs(plain["F"]))      # the delta reached the device
+        out = mex.call(5, "elbo", hh, theta.reshape(-1, 1), dict(vp_struct(vp), delta=delta), 0, 0, 2, 0, 1.0, None, None, 1, 3)
+        r1 = va.negelcbo_batch(theta, 1.0, dict(vp, delta=delta.reshape(-1)), gp, 0, False, 2, None)
+        same(out[0][0, 0], r1["F"][0]); same(out[4][0, 0], r1["varG"][0])
+    for bad in (np.full((D + 1, 1), 0.5), np.full((2, 1), 0.5)):
+        with pytest.raises(MexError) as e:
+            mex.call(2, "elbo_batch", hh, Th, dict(vp_struct(vp), delta=bad), 40, 1, 0, 0, None, 5)
+        assert e.value.identifier == "vbmc_hip:unsupported" and "delta" in e.value.message
+    mex.call(0, "gp_free", hh)
+    assert mex.live_arrays() == 0
+
+
 def test_errors_cross_the_boundary_as_matlab_ids(mex):
     """VBMC_ERR_UNSUPPORTED -> 'vbmc_hip:unsupported' (what every shim catches to fall through); INVALID messages that start
     with a reference error id keep it (negelcbo_vbmc.m:22-23); everything the failed call created is released."""

@@ -3,8 +3,8 @@ import numpy as np
 import pytest
 
 from oracle import vbmc_ref as R
-from tests._cases import (acq_golden_cases, golden_cases, load_acq_golden, load_golden, load_nlz_golden, load_pen_golden, load_pred_golden,
-                          nlz_golden_cases, pen_golden_cases, pred_golden_cases, synth_problem, vp_from_inputs)
+from tests._cases import (acq_golden_cases, delta_golden_cases, golden_cases, load_acq_golden, load_delta_golden, load_golden, load_nlz_golden,
+                          load_pen_golden, load_pred_golden, nlz_golden_cases, pen_golden_cases, pred_golden_cases, synth_problem, vp_from_inputs)
 
 RTOL = 1e-11  # fp64 restatement vs 50-digit evaluation; sums of <= ~100 terms
 
@@ -67,6 +67,32 @@ def test_gplogjoint_matches_mpmath(path):
     close(np.atleast_1d(r["varF"]), exp["varG_s_full"], rtol=1e-8)
     r2 = R.gplogjoint(vp, gp, (0, 0, 0, 0), avg_flag=False, compute_var=2, separate_K=True)
     close(np.atleast_1d(r2["varF"]), exp["varG_s_diag"], rtol=1e-8)
+
+
+def test_delta_golden_family_present():
+    assert len(delta_golden_cases()) >= 5
+    assert not set(delta_golden_cases()) & set(golden_cases())
+
+
+@pytest.mark.parametrize("path", delta_golden_cases())
+def test_gplogjoint_delta_matches_mpmath(path):
+    """vp.delta != 0 (gplogjoint.m:164,171-172,274,313): every output of the full and the diagonal variance forms, and the
+    closed-form gradient of the diagonal variance (:286-304) against 50-digit central differences of its value."""
+    inp, vp, gp, exp = load_delta_golden(path)
+    S, D, K = inp["S"], inp["D"], inp["K"]
+    r = R.gplogjoint(vp, gp, (1, 1, 1, 1), avg_flag=False, jacobian_flag=True, compute_var=1, separate_K=True)
+    close(np.atleast_1d(r["F"]), exp["G_s"])
+    close(np.asarray(r["dF"]).reshape(D * K + 2 * K + D, S).T, exp["dG_s"])
+    close(r["I_sk"], exp["I_sk"])
+    close(r["J_sjk"], exp["J_sjk"], rtol=1e-8)  # z' K^-1 z cancels against nf_jk
+    close(np.atleast_1d(r["varF"]), exp["varG_s_full"], rtol=1e-8)
+    r2 = R.gplogjoint(vp, gp, (1, 1, 1, 1), avg_flag=False, compute_var=2, separate_K=True, compute_vargrad=True)
+    close(np.atleast_1d(r2["varF"]), exp["varG_s_diag"], rtol=1e-8)
+    close(np.asarray(r2["dvarF"]).reshape(D * K + 2 * K + D, S).T, exp["dvarG_s_diag"], rtol=1e-8)
+    # the case's delta matters: without it the outputs are far outside these tolerances
+    r0 = R.gplogjoint(dict(vp, delta=None), gp, (1, 1, 1, 1), avg_flag=False, compute_var=2, compute_vargrad=True)
+    assert np.max(np.abs(np.atleast_1d(r0["F"]) - exp["G_s"])) > 1e-6 * max(1.0, np.max(np.abs(exp["G_s"])))
+    assert np.max(np.abs(np.atleast_1d(r0["varF"]) - exp["varG_s_diag"])) > 1e-5 * np.max(np.abs(exp["varG_s_diag"]))
 
 
 def test_averaging_over_hyper_samples():

@@ -78,6 +78,47 @@ def test_diag_variance_gradient_is_exact_derivative():
     assert np.max(np.abs(g - r["dF"])) < 5e-8 * max(1, np.max(np.abs(g)))
 
 
+def delta_vector(D, seed=7):
+    """a per-dimension vp.delta of the order of ell_d and sigma_k lambda_d (entries differ per dimension)"""
+    return 0.3 + 0.6 * np.random.default_rng(seed).random(D)
+
+
+@pytest.mark.parametrize("meanfun", [0, 1, 4])
+def test_gplogjoint_gradient_with_delta_is_exact_derivative(meanfun):
+    """dG with a vector vp.delta (tau_k, gplogjoint.m:164; nu_k :171-172)"""
+    p, gp, vp, theta = build(seed=3, meanfun=meanfun)
+    vp["delta"] = delta_vector(p["D"])
+    r = R.negelcbo_vbmc(theta, 0, vp, gp, 0, True, 0)
+    g = fd(lambda t: R.negelcbo_vbmc(t, 0, vp, gp, 0, False, 0)["G"], theta)
+    assert np.max(np.abs(g - r["dG"])) < 2e-8 * max(1, np.max(np.abs(g)))
+    r0 = R.negelcbo_vbmc(theta, 0, dict(vp, delta=None), gp, 0, True, 0)
+    assert np.max(np.abs(r0["dG"] - r["dG"])) > 1e-3 * max(1, np.max(np.abs(g)))
+
+
+@pytest.mark.parametrize("meanfun", [0, 1, 4])
+def test_diag_variance_gradient_with_delta_is_exact_derivative(meanfun):
+    """dF of the diagonal variance (compute_var = 2) with a vector vp.delta (tau_kk, gplogjoint.m:274)"""
+    p, gp, vp, theta = build(seed=4, meanfun=meanfun)
+    vp["delta"] = delta_vector(p["D"], seed=8)
+    r = R.negelcbo_vbmc(theta, 1.5, vp, gp, 0, True, 2)
+    g = fd(lambda t: R.negelcbo_vbmc(t, 1.5, vp, gp, 0, False, 2)["F"], theta)
+    assert np.max(np.abs(g - r["dF"])) < 5e-8 * max(1, np.max(np.abs(g)))
+
+
+@pytest.mark.parametrize("cv", [1, 2])
+def test_delta_zero_and_scalar_delta_identities(cv):
+    """delta = zeros(D) gives the bits of no delta; a scalar delta the bits of that value broadcast to D"""
+    p, gp, vp, _ = build(seed=5)
+    D = p["D"]
+    kw = dict(grad_flags=(1, 1, 1, 1), avg_flag=False, compute_var=cv, separate_K=True, compute_vargrad=cv == 2)
+    outs = [R.gplogjoint(dict(vp, delta=d), gp, **kw) for d in (None, np.zeros(D), 0.45, np.full(D, 0.45))]
+    for a, b in ((outs[0], outs[1]), (outs[2], outs[3])):
+        for key in ("F", "dF", "varF", "dvarF", "I_sk", "J_sjk"):
+            if a[key] is not None:
+                assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), key
+    assert not np.array_equal(outs[0]["F"], outs[2]["F"])
+
+
 def test_entmc_eta_block_is_exact_derivative_other_blocks_are_not():
     # SURVEY 0.5: only the weight block differentiates the MC value itself
     p, gp, vp, theta = build(seed=5)

@@ -18,7 +18,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VBMC_HIP_LIB: an alternative build of the SAME library (kernel A/B experiments, tools/ent_experiments.py)
 LIB_PATH = os.environ.get("VBMC_HIP_LIB") or os.path.join(_HERE, "lib", "libvbmc_hip.so")
 
-ABI_VERSION = 5   # include/vbmc_hip.h: VBMC_ABI_VERSION
+ABI_VERSION = 6   # include/vbmc_hip.h: VBMC_ABI_VERSION
+# the launch forms vbmc_ctx_last_launch reports (include/vbmc_hip.h: VBMC_ENTFORM_* / VBMC_LJFORM_*; 0: none ran)
+ENTFORM_LB, ENTFORM_VALU, ENTFORM_MFMA, ENTFORM_LANE = 1, 2, 3, 4
+LJFORM_VALU_WAVE, LJFORM_VALU_SPLIT, LJFORM_MFMA_GRAD, LJFORM_MFMA_VALUE, LJFORM_ROLE_MFMA, LJFORM_ROLE_LANE = 1, 2, 3, 4, 5, 6
 VBMC_OK, VBMC_ERR_INVALID, VBMC_ERR_NO_DEVICE, VBMC_ERR_HIP, VBMC_ERR_UNSUPPORTED, VBMC_ERR_NOT_POSDEF = range(6)
 _STATUS_NAMES = {0: "OK", 1: "INVALID", 2: "NO_DEVICE", 3: "HIP", 4: "UNSUPPORTED", 5: "NOT_POSDEF"}
 
@@ -91,6 +94,7 @@ def load():
     lib.vbmc_ctx_synchronize.argtypes = [vp]
     lib.vbmc_ctx_set_profiling.argtypes = [vp, C.c_int]
     lib.vbmc_ctx_last_kernel_ms.argtypes = [vp, _dp, _dp]
+    lib.vbmc_ctx_last_launch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.vbmc_gp_upload.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.POINTER(vp)]
     lib.vbmc_gp_free.argtypes = [vp, vp]
@@ -203,6 +207,12 @@ class Context:
     def last_kernel_ms(self):
         a, b = C.c_double(), C.c_double()
         self.check(self.lib.vbmc_ctx_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_launch(self):
+        """(ent_form, lj_form) of the last ELBO pass enqueued on this context (test hook: ENTFORM_* / LJFORM_*, 0 where none ran)"""
+        a, b = C.c_int(), C.c_int()
+        self.check(self.lib.vbmc_ctx_last_launch(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def rng_dump(self, D, K, R, Ns, seed):

@@ -131,6 +131,13 @@ extern "C" vbmc_status vbmc_ctx_last_kernel_ms(vbmc_ctx* ctx, double* ent_ms, do
   return VBMC_OK;
 }
 
+extern "C" vbmc_status vbmc_ctx_last_launch(vbmc_ctx* ctx, int* ent_form, int* lj_form) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  if (ent_form) *ent_form = ctx->last_ent_form;
+  if (lj_form) *lj_form = ctx->last_lj_form;
+  return VBMC_OK;
+}
+
 extern "C" vbmc_status vbmc_device_alloc(vbmc_ctx* ctx, size_t bytes, void** dptr) {
   if (!ctx || !dptr) return VBMC_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -590,7 +597,8 @@ static int lj_co_nsplit(const vbmc_ctx* ctx, const ElboPlan& P) {
 // Does the expected log joint run as a role of the MFMA entropy launch (entropy_mfma.h CO = true; see elbo_enqueue)?  The part of the
 // answer that elbo_plan needs too (the chunk model asks for the occupancy of the kernel that will run).
 static bool lj_co_shape(const vbmc_ctx* ctx, const ElboPlan& P) {
-  static const bool co_off = [] { const char* e = getenv("VBMC_LJ_CO"); return e && !strcmp(e, "0"); }();
+  const char* coe = getenv("VBMC_LJ_CO");       // read per call, as VBMC_LJ_KERNEL is: an in-process toggle takes effect on the next pass
+  const bool co_off = coe && !strcmp(coe, "0");
   const char* ljf = getenv("VBMC_LJ_KERNEL");
   const int Rp = P.Rp > 0 ? P.Rp : P.dm.R;        // (plan_restarts: the undivided batch decides)
   const long long SR = (long long)P.dm.S * Rp;
@@ -981,6 +989,7 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
   const int perC = shard_per(P.C, sh.world), c0 = sh.mode == 1 ? std::min(P.C, sh.rank * perC) : 0;
   const int nc = sh.mode == 1 ? std::min(P.C, c0 + perC) - c0 : P.C;
   double* const lj_out = sh.mode == 1 ? sh.send : P.d_lj;
+  if (sh.mode != 2) ctx->last_ent_form = ctx->last_lj_form = 0;   // vbmc_ctx_last_launch: set below as the kernels are enqueued
   const size_t prep_lds = ((size_t)D * K + 3 * K + D + 8) * sizeof(double);
   if (prep_lds > 64 * 1024)
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds));
@@ -1003,7 +1012,8 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
   // (round 4: from S R = one workgroup per compute unit on -- below, the finer-grained VALU kernel is the faster one: R = 8 at the headline
   // shape, 160 (hyper-sample, restart) workgroups: 56 us against 34 alone, the step 0.394 -> 0.360 ms; equal at R = 16, 142 against 174 us at R = 64)
   // (round 6) the lane-per-sample kernel of small mixtures carries the role at every batch width: a pass of that class is ONE chip-wide launch
-  static const bool co_off_env = [] { const char* e = getenv("VBMC_LJ_CO"); return e && !strcmp(e, "0"); }();
+  const char* coe = getenv("VBMC_LJ_CO");
+  const bool co_off_env = coe && !strcmp(coe, "0");
   const bool co_lane = lane_role_possible && sh.mode == 0 && !lj_force && !co_off_env && !(ljf && !strcmp(ljf, "valu"));
   const bool co_shape = co_lane || (sh.mode == 0 && !fork && !lj_force && lj_co_shape(ctx, P));      // (the role takes precedence over the matrix-core kernel where its limits admit the batch)
   // (round 5) ... and enough WAVES in each: with K <= 16 a workgroup of the matrix-core kernel is a single wave walking the whole training
@@ -1043,7 +1053,9 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
             hipLaunchKernelGGL((k_logjoint_mfma<DT, false>), dim3(ns, R), dim3(WAVE * nw), mom_lds, ls, dml, P.d_vpd,
                                gp->X, gp->d_meanX, al, gc, P.d_delta2, lj_out);
           LAUNCH_CHECK(ctx, "k_logjoint_mfma");
+          ctx->last_lj_form = P.compute_grad ? VBMC_LJFORM_MFMA_GRAD : VBMC_LJFORM_MFMA_VALUE;
         } else {
+          ctx->last_lj_form = lj_split ? VBMC_LJFORM_VALU_SPLIT : VBMC_LJFORM_VALU_WAVE;
           hipLaunchKernelGGL((k_logjoint<DT>), dim3((K + 3) / 4, ns, R), dim3(lj_split ? WAVE * LJ_MAXW : WAVE), 0, ls, dml, P.d_vpd, gp->X, al, gc,
                              P.d_delta2, lj_out, P.compute_grad);
           LAUNCH_CHECK(ctx, "k_logjoint");
@@ -1104,6 +1116,10 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
       lc.dm = dm; lc.X = gp->X; lc.alpha = gp->alpha; lc.gpc = gp->gpc; lc.delta2 = P.d_delta2; lc.lj = P.d_lj;
     }
     if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
+    if (sh.mode != 2 && nc > 0) {
+      ctx->last_ent_form = P.use_lane ? VBMC_ENTFORM_LANE : (P.use_mfma ? VBMC_ENTFORM_MFMA : VBMC_ENTFORM_VALU);
+      if (co) ctx->last_lj_form = P.use_lane ? VBMC_LJFORM_ROLE_LANE : VBMC_LJFORM_ROLE_MFMA;
+    }
     if (sh.mode == 2 || nc <= 0) {
     } else if (P.use_lane) {
       ea.nc_launch = nc;
@@ -1142,6 +1158,7 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
       HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_entlb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_entlb, dim3(R), dim3(256), lds, st, dm, P.d_vpd, P.d_part, P.compute_grad, P.d_gamma);
     LAUNCH_CHECK(ctx, "k_entlb");
+    ctx->last_ent_form = VBMC_ENTFORM_LB;
     fa.entpart = nullptr; fa.entlb = P.d_part;
   }
 
@@ -1593,6 +1610,7 @@ extern "C" vbmc_status vbmc_elbo_submit(vbmc_ctx* ctx, const vbmc_gp* gp, const 
   { vbmc_status s_ = slot_ctx(ctx, a, slot, &sc, &inner); if (s_) return s_; }
   { vbmc_status s_ = elbo_submit_core(sc, gp, a, inner, "vbmc_elbo_submit", true); if (s_) return slot_err(ctx, sc, s_); }
   ctx->slot_where[slot] = sc; ctx->slot_inner[slot] = inner;
+  ctx->last_ent_form = sc->last_ent_form; ctx->last_lj_form = sc->last_lj_form;    // (a child context's pass: vbmc_ctx_last_launch asks this one)
   return slot_err(ctx, sc, elbo_submit_mark(sc, inner, "vbmc_elbo_submit"));
 }
 

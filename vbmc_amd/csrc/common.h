@@ -55,6 +55,7 @@ struct vbmc_ctx {
   bool profiling = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double last_ent_ms = 0.0, last_lj_ms = 0.0;
+  int last_ent_form = 0, last_lj_form = 0;     // the kernels of the last ELBO pass enqueued here (VBMC_ENTFORM_* / VBMC_LJFORM_*, vbmc_ctx_last_launch)
   std::vector<PoolBlk> pool;
   size_t pool_bytes = 0;
   // pipelined evaluations (vbmc_elbo_submit / vbmc_elbo_collect, abi_elbo.hip): each of the two slots has its own pinned
