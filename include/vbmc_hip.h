@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VBMC_ABI_VERSION 6
+#define VBMC_ABI_VERSION 7
 
 typedef int vbmc_status;
 enum {
@@ -176,6 +176,76 @@ vbmc_status vbmc_acq_iqr_eval(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_i
 vbmc_status vbmc_gp_nlz(vbmc_ctx* ctx, int N, int D, int B, int Nhyp, int meanfun, const int32_t noisefun[3],
                         const double* X, const double* y, const double* s2, const double* hyp, int compute_grad,
                         double* nlZ, double* dnlZ);
+
+/*
+ * [samples,fvals,exitflag,output] = slicesamplebnd(@(hyp) gp_objfun(hyp(:),gp,hprior,0,1), hyp_start', Ns, widths, LB, UB, opts)
+ * (ABI version 7; utils/slicesamplebnd.m:229-358 with StepOut = false, its default; call site gplite/gplite_train.m:318-330) with the
+ * WHOLE chain on the device: the training set is uploaded once, candidates never leave the device, every evaluation of the target
+ * -gplite_nlZ(hyp) + gplite_hypprior(hyp) runs on the batched kernels of vbmc_gp_nlz, and the host only polls a progress word.
+ * Model: as vbmc_gp_nlz (SE-ARD, mean functions 0/1/4, the noise models of gplite_noisefun.m:176-210; anything else is
+ * VBMC_ERR_UNSUPPORTED).  logpdfbound (:415-449): a proposal outside [LB, UB] is -Inf without an evaluation, a NaN target (a matrix
+ * still not positive definite after the jitter retries, gplite_train.m:542-546) a rejected proposal that counts as an evaluation.
+ *
+ * SPECULATION.  Without step-out the k-th shrink proposal of a coordinate, GIVEN that proposals 1 .. k-1 were rejected, is a function
+ * of the current point, the interval and the uniforms alone (:283-304), so W of them are evaluated in one batched pass and the first
+ * accepted one is taken.  Candidates are consumed in order: samples, logp, widths and funccount are BIT-IDENTICAL for every W; only
+ * `performed` changes.  W = 0 asks for the library's default, 1: the table of repeated runs that a wider default has to rest on has not
+ * been measured yet (profiles/gp_slice_sample.md holds what has: one run per width); a caller who wants speculation passes W itself.
+ *
+ * `performed` counts every evaluation launched: the speculative ones, and -- once more -- the candidates of a round that had to be
+ * repeated with the jitter retries because a consumed candidate's first factorisation failed.  At large N the library lowers W until
+ * the W work matrices (W N^2 doubles) stay below 2 GiB; the results do not change, `performed` follows the W actually used.
+ *
+ * RANDOM NUMBERS, sweeps = Burnin + Ns + (Ns - 1) * (Thin - 1) (:205,229):
+ *   perms     sweeps x Nhyp int32, row `sweep` = the 0-BASED permutation randperm(D) - 1 of that sweep (:239), stored sweep after sweep;
+ *   uniforms  U[sweep][idd][slot], slot = 0 .. 1 + Kmax fastest, idd (the position in the sweep's permutation, fixed coordinates keep
+ *             their unused rows) next: slot 0 is the slice level's rand (:245), slot 1 the interval placement's (:252), slot 2 + k the
+ *             k-th shrink proposal's, k = 0, 1, ... (:286).  A coordinate that needs more than Kmax proposals ends the call with
+ *             VBMC_ERR_INVALID ("uniform block exhausted").
+ *   rng_mode 1 (parity): the caller supplies both.  rng_mode 0 (device): the library's counter-based generator (Philox4x32-10 keyed by
+ *   seed, counter (sweep, idd, slot)), no limit on the shrink count; vbmc_slice_rng_dump writes exactly the perms and the uniform block
+ *   (for a Kmax of the caller's choosing) that seed stands for -- a pure host function -- so that a replay in parity mode is bit-identical.
+ *
+ * widths: positive and finite (the caller resolves the reference's defaults, :173-174); basewidths: the user-supplied widths of :166
+ * for the end-of-burn-in update (:350-356), NULL = none were supplied.  LB / UB may be infinite; LB == UB fixes a coordinate (:243).
+ * prior_mu NULL: no hyper-prior; prior_df NULL: 7 for every coordinate (gplite_hypprior.m:26).
+ * Outputs (any may be NULL): samples Ns x Nhyp (column-major), logp Ns (fvals), widths_out Nhyp (output.widths), funccount
+ * (output.funccount: evaluations of the sequential algorithm), performed (evaluations launched), max_shrink (largest number of
+ * proposals a coordinate took).  The reference's own failure -- the interval shrunk onto the current point with the proposal still
+ * rejected (:298-301) -- returns VBMC_ERR_INVALID with the reference's message; the context stays usable after any error.
+ */
+typedef struct vbmc_slice_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_slice_args) */
+  int32_t N, D, Nhyp, meanfun;
+  int32_t noisefun[3];
+  const double* X;           /* N x D */
+  const double* y;           /* N */
+  const double* s2;          /* N or NULL */
+  const double* prior_mu;    /* Nhyp or NULL */
+  const double* prior_sigma; /* Nhyp */
+  const double* prior_df;    /* Nhyp or NULL */
+  const double* LB;          /* Nhyp */
+  const double* UB;          /* Nhyp */
+  const double* hyp_start;   /* Nhyp, inside the bounds */
+  const double* widths;      /* Nhyp */
+  const double* basewidths;  /* Nhyp or NULL */
+  int32_t Ns, Thin, Burnin, Adaptive;
+  int32_t W;                 /* speculation width, 0 .. 16 (0: default) */
+  int32_t rng_mode;          /* 0 device generator, 1 parity */
+  uint64_t seed;             /* rng_mode 0 */
+  int32_t Kmax;              /* rng_mode 1: shrink slots per coordinate in `uniforms` */
+  const int32_t* perms;      /* rng_mode 1 */
+  const double* uniforms;    /* rng_mode 1 */
+  double* samples;
+  double* logp;
+  double* widths_out;
+  int64_t* funccount;
+  int64_t* performed;
+  int32_t* max_shrink;
+  int64_t* rounds;           /* 2 or NULL: rounds that did work, rounds enqueued (the difference ran behind the chain's end or a stall) */
+} vbmc_slice_args;
+vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args* args);
+vbmc_status vbmc_slice_rng_dump(uint64_t seed, int sweeps, int Nhyp, int Kmax, int32_t* perms, double* uniforms);
 
 /*
  * [ymu,ys2,fmu,fs2] = gplite_pred(gp, Xstar, ystar, s2star, ssflag)   (gplite/gplite_pred.m:1-165).

@@ -28,6 +28,11 @@
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
+//     [samples,logp,widths,counts] = vbmc_hip_mex('slice_sample', X, y, s2, meanfun, noisefun, prior /*struct mu, sigma, df or []*/, LB, UB,
+//                                hyp_start, widths, basewidths_or_empty, [Ns Thin Burnin Adaptive W], seed, perms_or_empty, U_or_empty)
+//                                (slicesamplebnd on -gplite_nlZ + log prior, the chain on the device: vbmc_gp_slice_sample.  perms:
+//                                 Nhyp x sweeps, column s = randperm(Nhyp)' of sweep s, 1-based; U: (2+Kmax) x Nhyp x sweeps; both
+//                                 empty: the device generator keyed by seed.  counts = [funccount performed max_shrink])
 //     C = vbmc_hip_mex('sq_dist', a, b)
 //     lim = vbmc_hip_mex('limits')                          -> struct max_D, max_K, max_N, max_Na, max_T_vargrad, delta_ok, meanfun: the shapes the
 //                                                             library accepts (vbmc_get_limits; no device needed) -- matlab/vbmc_hip_supported.m
@@ -518,6 +523,62 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
                                  mxGetDoubles(hyp), g ? 1 : 0, mxGetDoubles(plhs[0]), g ? mxGetDoubles(g) : nullptr);
     if (st != VBMC_OK) return fail(st);
     if (g) plhs[1] = g;
+    return 0;
+  }
+
+  if (!strcmp(cmd, "slice_sample")) {
+    if (nrhs < 16) return raise("vbmc_hip:usage", "slice_sample: X, y, s2, meanfun, noisefun, prior, LB, UB, hyp_start, widths, basewidths, options, seed, perms, U");
+    const mxArray *X = prhs[1], *pr = prhs[6], *opt = prhs[12], *pm = prhs[14], *U = prhs[15];
+    if (mxGetNumberOfElements(opt) < 5) return raise("vbmc_hip:usage", "slice_sample: options are [Ns Thin Burnin Adaptive W]");
+    vbmc_slice_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.N = (int)mxGetM(X); a.D = (int)mxGetN(X); a.Nhyp = (int)mxGetNumberOfElements(prhs[9]); a.meanfun = (int)mxGetScalar(prhs[4]);
+    a.noisefun[0] = 1;
+    for (int i = 0; i < 3 && i < (int)mxGetNumberOfElements(prhs[5]); ++i) a.noisefun[i] = (int32_t)mxGetDoubles(prhs[5])[i];
+    a.X = mxGetDoubles(X); a.y = dbl(prhs[2]); a.s2 = dbl(prhs[3]);
+    if (pr && !mxIsEmpty(pr) && mxIsStruct(pr)) { a.prior_mu = dbl(field(pr, "mu")); a.prior_sigma = dbl(field(pr, "sigma")); a.prior_df = dbl(field(pr, "df")); }
+    a.LB = dbl(prhs[7]); a.UB = dbl(prhs[8]); a.hyp_start = dbl(prhs[9]); a.widths = dbl(prhs[10]); a.basewidths = dbl(prhs[11]);
+    const double* o = mxGetDoubles(opt);
+    a.Ns = (int)o[0]; a.Thin = (int)o[1]; a.Burnin = (int)o[2]; a.Adaptive = (int)o[3]; a.W = (int)o[4];
+    const double seed = mxGetScalar(prhs[13]);
+    if (!(seed >= 0.0 && seed <= 9007199254740992.0)) return raise("vbmc_hip:usage", "slice_sample: the seed must be an integer in 0 .. 2^53");
+    a.seed = (uint64_t)seed;
+    const size_t nh = (size_t)a.Nhyp;
+    for (int i : {7, 8, 10})
+      if (mxGetNumberOfElements(prhs[i]) != nh) return raise("vbmc_hip:usage", "slice_sample: LB, UB and widths need numel(hyp_start) entries");
+    if (!mxIsEmpty(prhs[11]) && mxGetNumberOfElements(prhs[11]) != nh) return raise("vbmc_hip:usage", "slice_sample: basewidths needs numel(hyp_start) entries");
+    if (pr && !mxIsEmpty(pr) && mxIsStruct(pr))
+      for (const char* fn : {"mu", "sigma", "df"})
+        if (field(pr, fn) && !mxIsEmpty(field(pr, fn)) && mxGetNumberOfElements(field(pr, fn)) != nh)
+          return raise("vbmc_hip:usage", "slice_sample: prior.mu / sigma / df need numel(hyp_start) entries");
+    std::vector<int32_t> perms;
+    if (!mxIsEmpty(pm) && !mxIsEmpty(U)) {
+      const size_t np = mxGetNumberOfElements(pm);
+      const double sweeps = o[2] + o[0] + (o[0] - 1.0) * (o[1] - 1.0);
+      if (o[0] < 1.0 || o[1] < 1.0 || o[2] < 0.0 || (double)np != sweeps * (double)nh || mxGetDimensions(U)[0] < 3 ||
+          (double)mxGetNumberOfElements(U) != sweeps * (double)nh * (double)mxGetDimensions(U)[0])
+        return raise("vbmc_hip:usage", "slice_sample: perms must be Nhyp x sweeps and U (2+Kmax) x Nhyp x sweeps, sweeps = Burnin + Ns + (Ns-1)*(Thin-1)");
+      perms.resize(np);
+      for (size_t i = 0; i < np; ++i) perms[i] = (int32_t)mxGetDoubles(pm)[i] - 1;
+      a.rng_mode = 1; a.perms = perms.data(); a.uniforms = mxGetDoubles(U);
+      a.Kmax = (int)mxGetDimensions(U)[0] - 2;
+    }
+    if (a.Ns < 1 || a.Nhyp < 1) return raise("vbmc_hip:usage", "slice_sample: Ns and numel(hyp_start) must be positive");
+    plhs[0] = mxCreateDoubleMatrix(a.Ns, a.Nhyp, mxREAL);
+    mxArray* lp = mxCreateDoubleMatrix(a.Ns, 1, mxREAL);
+    mxArray* wo = mxCreateDoubleMatrix(1, a.Nhyp, mxREAL);
+    mxArray* cn = mxCreateDoubleMatrix(1, 3, mxREAL);
+    int64_t fc = 0, pf = 0;
+    int32_t ms = 0;
+    a.samples = mxGetDoubles(plhs[0]); a.logp = mxGetDoubles(lp); a.widths_out = mxGetDoubles(wo);
+    a.funccount = &fc; a.performed = &pf; a.max_shrink = &ms;
+    vbmc_status st = vbmc_gp_slice_sample(g_ctx, &a);
+    if (st != VBMC_OK) { mxDestroyArray(lp); mxDestroyArray(wo); mxDestroyArray(cn); return fail(st); }
+    mxGetDoubles(cn)[0] = (double)fc; mxGetDoubles(cn)[1] = (double)pf; mxGetDoubles(cn)[2] = (double)ms;
+    if (nlhs > 1) plhs[1] = lp; else mxDestroyArray(lp);
+    if (nlhs > 2) plhs[2] = wo; else mxDestroyArray(wo);
+    if (nlhs > 3) plhs[3] = cn; else mxDestroyArray(cn);
     return 0;
   }
 

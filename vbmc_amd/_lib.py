@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VBMC_HIP_LIB: an alternative build of the SAME library (kernel A/B experiments, tools/ent_experiments.py)
 LIB_PATH = os.environ.get("VBMC_HIP_LIB") or os.path.join(_HERE, "lib", "libvbmc_hip.so")
 
-ABI_VERSION = 6   # include/vbmc_hip.h: VBMC_ABI_VERSION
+ABI_VERSION = 7   # include/vbmc_hip.h: VBMC_ABI_VERSION
 # the launch forms vbmc_ctx_last_launch reports (include/vbmc_hip.h: VBMC_ENTFORM_* / VBMC_LJFORM_*; 0: none ran)
 ENTFORM_LB, ENTFORM_VALU, ENTFORM_MFMA, ENTFORM_LANE = 1, 2, 3, 4
 LJFORM_VALU_WAVE, LJFORM_VALU_SPLIT, LJFORM_MFMA_GRAD, LJFORM_MFMA_VALUE, LJFORM_ROLE_MFMA, LJFORM_ROLE_LANE = 1, 2, 3, 4, 5, 6
@@ -67,6 +67,28 @@ class ElboArgs(C.Structure):
         ("dG_s", _dp),
         ("dvarG_s", _dp),
         ("plan_restarts", C.c_int32),
+    ]
+
+
+class SliceArgs(C.Structure):
+    """vbmc_slice_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("N", C.c_int32), ("D", C.c_int32), ("Nhyp", C.c_int32), ("meanfun", C.c_int32),
+        ("noisefun", C.c_int32 * 3),
+        ("X", _dp), ("y", _dp), ("s2", _dp),
+        ("prior_mu", _dp), ("prior_sigma", _dp), ("prior_df", _dp),
+        ("LB", _dp), ("UB", _dp), ("hyp_start", _dp), ("widths", _dp), ("basewidths", _dp),
+        ("Ns", C.c_int32), ("Thin", C.c_int32), ("Burnin", C.c_int32), ("Adaptive", C.c_int32),
+        ("W", C.c_int32), ("rng_mode", C.c_int32),
+        ("seed", C.c_uint64),
+        ("Kmax", C.c_int32),
+        ("perms", C.POINTER(C.c_int32)),
+        ("uniforms", _dp),
+        ("samples", _dp), ("logp", _dp), ("widths_out", _dp),
+        ("funccount", C.POINTER(C.c_int64)), ("performed", C.POINTER(C.c_int64)),
+        ("max_shrink", C.POINTER(C.c_int32)),
+        ("rounds", C.POINTER(C.c_int64)),
     ]
 
 
@@ -130,6 +152,8 @@ def load():
     lib.vbmc_acq_is_free.restype = None
     lib.vbmc_acq_iqr_eval.argtypes = [vp, vp, vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp]
     lib.vbmc_gp_nlz.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]
+    lib.vbmc_gp_slice_sample.argtypes = [vp, C.POINTER(SliceArgs)]
+    lib.vbmc_slice_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)

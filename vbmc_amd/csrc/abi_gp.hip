@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "gp_kernels.h"
+#include "slice_kernels.h"
 
 namespace {
 
@@ -107,6 +108,37 @@ struct GpFactor {
   TmpBuf dIn, dX, dy, dhyp, dXc, daa, dsn2, dscal, dact, dA, dpf, dr, dz, dones, dninv, dlch, dal, dfinv, dExtra;   // dIn: the packed inputs (dX .. dninv, dExtra are windows)
 };
 
+// The launches of the factorisation path, shared by gp_factorize (hyper-parameters uploaded by the call) and the device-resident
+// slice sampler (vbmc_gp_slice_sample: hyper-parameters written by a kernel): every argument is a device pointer.
+inline void gp_launch_scale(hipStream_t st, int N, int D, int S, int Nhyp, int moff, int meanfun, const double* X, const double* hyp,
+                            double* Xc, double* aa, const double* y, double* r) {
+  hipLaunchKernelGGL(k_gp_scale, dim3(4, S), dim3(256), 0, st, N, D, Nhyp, X, hyp, Xc, aa, moff, meanfun, y, r);
+}
+// one try of the jittered Cholesky: kernel matrices of the active vectors, factorisation, block inverses, z = R' \ r
+inline hipError_t gp_launch_try(hipStream_t st, int N, int D, int S, int Nhyp, const double* hyp, const double* Xc, const double* aa,
+                                const double* sn2, const double* scal, const unsigned char* act, double* A, int* pf, double* Pg,
+                                double* finv, double* pfd, const double* r, double* z) {
+  DISPATCH_GPDT(D, hipLaunchKernelGGL((k_gp_build<DT>), dim3((N + GPB_T - 1) / GPB_T, (N + GPB_T - 1) / GPB_T, S), dim3(256), 0, st, N, D,
+                                      Nhyp, hyp, Xc, aa, sn2, scal, act, A));
+  return chol2_launch(N, S, A, pf, act, Pg, st, finv, pfd, r, z);
+}
+// alpha = R \ z / sl: the backward half of the two-sided solve
+inline void gp_launch_alpha(hipStream_t sa, int N, int S, const double* A, const double* finv, const unsigned char* on, const double* z,
+                            double* al, const double* scal) {
+  if (N <= ASOLVE1_THREADS)
+    hipLaunchKernelGGL(k_alpha_solve1, dim3(S), dim3(ASOLVE1_THREADS), 0, sa, N, A, finv, on, z, al, 1, scal);
+  else
+    hipLaunchKernelGGL(k_alpha_solve, dim3(S), dim3(ASOLVE_THREADS), (size_t)((TRSM_NBLK(N) << 4) + 16) * sizeof(double), sa, N, A, finv, on, z,
+                       al, 1, scal);
+}
+// the closing kernel of gplite_nlZ: out = [nlZ B | failure indices B | dnlZ B x Nhyp]
+inline void gp_launch_nlz_final(hipStream_t st, int N, int D, int B, int Nhyp, int Nnoise, int Nmean, int meanfun, int ntile, int grad,
+                                const double* X, const double* y, const double* hyp, const double* A, const double* al, const double* scal,
+                                const double* part, const double* pfd, double* out) {
+  DISPATCH_GPDT(D, hipLaunchKernelGGL((k_nlz_final<DT>), dim3(B), dim3(256), 0, st, N, D, Nhyp, Nnoise, Nmean, meanfun, ntile, grad, X, y, hyp, A, al,
+                                      scal, part, pfd, out));
+}
+
 // fail_is_error: vbmc_gp_post refuses a matrix that is still not positive definite after the retries;
 // vbmc_gp_nlz marks that hyper-parameter vector as failed (NaN result, gplite_train.m:542-546) and goes on.
 //
@@ -200,8 +232,8 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, const char* who, int N, int D, int S, in
                        dIn.as<double>());
   else
     HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin, in_doubles * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_gp_scale, dim3(4, S), dim3(256), 0, st, N, D, Nhyp, dX.as<double>(), dhyp.as<double>(), dXc.as<double>(), daa.as<double>(),
-                     moff, meanfun, dy.as<double>(), dr.as<double>());
+  gp_launch_scale(st, N, D, S, Nhyp, moff, meanfun, dX.as<double>(), dhyp.as<double>(), dXc.as<double>(), daa.as<double>(), dy.as<double>(),
+                  dr.as<double>());
 
   // jittered Cholesky: up to 10 tries, noise multiplier x10 per failure (gplite_core.m:77-80,91-94)
   // the 16 x N panel of the Cholesky lives in LDS up to N = 1120, in a global scratch block beyond (chol_mfma.h)
@@ -214,11 +246,9 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, const char* who, int N, int D, int S, in
       HIP_TRY(ctx, hipMemcpyAsync(dscal.p, scal.data(), (size_t)S * 4 * 8, hipMemcpyHostToDevice, st));
       HIP_TRY(ctx, hipMemcpyAsync(dact.p, active.data(), S, hipMemcpyHostToDevice, st));
     }
-    DISPATCH_GPDT(D, hipLaunchKernelGGL((k_gp_build<DT>), dim3((N + GPB_T - 1) / GPB_T, (N + GPB_T - 1) / GPB_T, S), dim3(256), 0, st, N, D,
-                                        Nhyp, dhyp.as<double>(), dXc.as<double>(), daa.as<double>(), dsn2.as<double>(), dscal.as<double>(),
-                                        dact.as<unsigned char>(), dA.as<double>()));
-    HIP_TRY(ctx, chol2_launch(N, S, dA.as<double>(), dpf.as<int>(), dact.as<unsigned char>(), dPg.p ? dPg.as<double>() : nullptr, st,
-                              dfinv.as<double>(), f.d_pfd, dr.as<double>(), dz.as<double>()));
+    HIP_TRY(ctx, gp_launch_try(st, N, D, S, Nhyp, dhyp.as<double>(), dXc.as<double>(), daa.as<double>(), dsn2.as<double>(), dscal.as<double>(),
+                               dact.as<unsigned char>(), dA.as<double>(), dpf.as<int>(), dPg.p ? dPg.as<double>() : nullptr, dfinv.as<double>(),
+                               f.d_pfd, dr.as<double>(), dz.as<double>()));
     if (optimistic) {
       // Almost every factorisation succeeds at the first try (the retries exist for hyper-parameter vectors at the edge of the
       // prior).  The flags are NOT waited for: everything downstream is enqueued as if the try had succeeded, they travel with
@@ -264,12 +294,7 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, const char* who, int N, int D, int S, in
     sa = ctx->aux;
     f.alpha_event = true;
   }
-  if (N <= ASOLVE1_THREADS)
-    hipLaunchKernelGGL(k_alpha_solve1, dim3(S), dim3(ASOLVE1_THREADS), 0, sa, N, dA.as<double>(), dfinv.as<double>(), dones.as<unsigned char>(),
-                       dz.as<double>(), dal.as<double>(), 1, dscal.as<double>());
-  else
-    hipLaunchKernelGGL(k_alpha_solve, dim3(S), dim3(ASOLVE_THREADS), (size_t)((TRSM_NBLK(N) << 4) + 16) * sizeof(double), sa, N, dA.as<double>(),
-                       dfinv.as<double>(), dones.as<unsigned char>(), dz.as<double>(), dal.as<double>(), 1, dscal.as<double>());
+  gp_launch_alpha(sa, N, S, dA.as<double>(), dfinv.as<double>(), dones.as<unsigned char>(), dz.as<double>(), dal.as<double>(), dscal.as<double>());
   if (f.alpha_event) HIP_TRY(ctx, hipEventRecord(ctx->ev_join, sa));
   HIP_TRY(ctx, hipGetLastError());
   return VBMC_OK;
@@ -520,10 +545,9 @@ static vbmc_status gp_nlz_impl(vbmc_ctx* ctx, int N, int D, int B, int Nhyp, int
                                         f.dXc.as<double>(), f.daa.as<double>(), dKi.as<double>(), f.dal.as<double>(), f.dscal.as<double>(),
                                         f.dExtra.as<double>(), dpart.as<double>()));
   }
-  DISPATCH_GPDT(D, hipLaunchKernelGGL((k_nlz_final<DT>), dim3(B), dim3(256), 0, st, N, D, Nhyp, Nnoise, Nmean, meanfun, ntile, compute_grad ? 1 : 0,
-                                      f.dX.as<double>(), f.dy.as<double>(), f.dhyp.as<double>(), f.dA.as<double>(), f.dal.as<double>(),
-                                      f.dscal.as<double>(), compute_grad ? dpart.as<double>() : (const double*)nullptr,
-                                      (const double*)f.d_pfd, dnlz));
+  gp_launch_nlz_final(st, N, D, B, Nhyp, Nnoise, Nmean, meanfun, ntile, compute_grad ? 1 : 0, f.dX.as<double>(), f.dy.as<double>(), f.dhyp.as<double>(),
+                      f.dA.as<double>(), f.dal.as<double>(), f.dscal.as<double>(), compute_grad ? dpart.as<double>() : (const double*)nullptr,
+                      (const double*)f.d_pfd, dnlz);
   HIP_TRY(ctx, hipGetLastError());
   if (!out_direct) HIP_TRY(ctx, hipMemcpyAsync(f.pin_out, dnlz, nout * 8, hipMemcpyDeviceToHost, st));   // pinned: asynchronous
   f.h_pfd = f.pin_out + B;
@@ -1178,3 +1202,255 @@ extern "C" vbmc_status vbmc_gp_rank1_update(vbmc_ctx* ctx, const vbmc_gp* gp, co
   return VBMC_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// vbmc_gp_slice_sample: slicesamplebnd on the GP hyper-parameter posterior, the chain resident on the device (slice_kernels.h).
+// The host enqueues ROUNDS (propose, the value path of gplite_nlZ for the W candidates, decide) in chunks on the context's stream and
+// reads the chain's state word once per chunk, one chunk behind the one being enqueued: no round trip per evaluation.  A candidate
+// whose first factorisation fails stalls the chain (rounds already enqueued become no-ops); the host then enqueues ONE checked round
+// with the nine x10 noise-inflation retries of gplite_core.m:77-80,91-94 between the tries, all on the device, and goes on.
+namespace {
+double host_eps(double x) {   // MATLAB's eps(x): NaN for an infinite x
+  const double ax = std::fabs(x);
+  return std::nextafter(ax, std::numeric_limits<double>::infinity()) - ax;
+}
+#define SLICE_DEFAULT_W 1   // the five-run table that a wider default has to rest on has not been measured (profiles/gp_slice_sample.md)
+#define SLICE_CHUNK 32
+}  // namespace
+
+extern "C" vbmc_status vbmc_slice_rng_dump(uint64_t seed, int sweeps, int Nhyp, int Kmax, int32_t* perms, double* uniforms) {
+  if (sweeps <= 0 || Nhyp <= 0 || Kmax < 0) return VBMC_ERR_INVALID;
+  for (int sw = 0; sw < sweeps; ++sw) {
+    if (perms) {   // Fisher-Yates driven by the generator's permutation stream
+      int32_t* p = perms + (size_t)sw * Nhyp;
+      for (int i = 0; i < Nhyp; ++i) p[i] = i;
+      for (int i = Nhyp - 1; i > 0; --i) {
+        const unsigned j = slice_perm_word(seed, (unsigned)sw, (unsigned)i) % (unsigned)(i + 1);
+        std::swap(p[i], p[j]);
+      }
+    }
+    if (uniforms)
+      for (int i = 0; i < Nhyp; ++i)
+        for (int k = 0; k < 2 + Kmax; ++k)
+          uniforms[((size_t)sw * Nhyp + i) * (size_t)(2 + Kmax) + k] = slice_uniform(seed, (unsigned)sw, (unsigned)i, (unsigned)k);
+  }
+  return VBMC_OK;
+}
+
+extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  if (!args || args->struct_size != sizeof(vbmc_slice_args)) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: struct_size mismatch");
+  const vbmc_slice_args& g = *args;
+  const int N = g.N, D = g.D, Nhyp = g.Nhyp, meanfun = g.meanfun;
+  if (N <= 0 || D <= 0 || !g.X || !g.y || !g.LB || !g.UB || !g.hyp_start || !g.widths)
+    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: bad arguments");
+  if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
+  if (!(meanfun == 0 || meanfun == 1 || meanfun == 4))
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "gplite mean function %d not accelerated (0,1,4 are)", meanfun);
+  for (int i = 0; i < 3; ++i)
+    if (g.noisefun[i] < 0 || g.noisefun[i] > (i == 1 ? 2 : 1))
+      return set_err(ctx, VBMC_ERR_UNSUPPORTED, "gplite noise function [%d %d %d] not accelerated", g.noisefun[0], g.noisefun[1], g.noisefun[2]);
+  const int Ncov = D + 1, Nnoise = noise_nhyp(g.noisefun), Nmean = meanfun == 0 ? 0 : (meanfun == 1 ? 1 : 2 * D + 1);
+  if (Nhyp != Ncov + Nnoise + Nmean)
+    return set_err(ctx, VBMC_ERR_INVALID, "gplite_nlZ:dimmismatch Number of hyperparameters mismatched with GP model specification.");
+  if (trsm_cw_for(N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d > %d not accelerated", N, trsm_max_n());
+  if (Nhyp > SLICE_MAXHYP) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Nhyp = %d > %d not accelerated", Nhyp, SLICE_MAXHYP);
+  if (g.Ns < 1 || g.Thin < 1 || g.Burnin < 0)
+    return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:options Ns and the thinning factor need to be positive integers, the burn-in non-negative.");
+  if (g.W < 0 || g.W > SLICE_MAXW) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: speculation width W = %d outside 0 .. %d", g.W, SLICE_MAXW);
+  if (g.rng_mode != 0 && g.rng_mode != 1) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: rng_mode %d (0 device, 1 parity)", g.rng_mode);
+  if (g.rng_mode == 1 && (!g.perms || !g.uniforms || g.Kmax < 1))
+    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: parity mode needs perms, uniforms and Kmax >= 1");
+  if (g.prior_mu && !g.prior_sigma) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: prior_mu without prior_sigma");
+  const long long total_ll = (long long)g.Burnin + g.Ns + (long long)(g.Ns - 1) * (g.Thin - 1);   // effN + burn (:205,229)
+  if (total_ll > (1ll << 30) / Nhyp) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: %lld sweeps are too many", total_ll);
+  const int total = (int)total_ll;
+  std::vector<double> wd(g.widths, g.widths + Nhyp), xx0(g.hyp_start, g.hyp_start + Nhyp), LBo(Nhyp), UBo(Nhyp);
+  for (int i = 0; i < Nhyp; ++i) {
+    const double lb = g.LB[i], ub = g.UB[i];
+    if (lb != lb || ub != ub || !(ub >= lb))
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:bounds All upper bounds UB need to be equal or greater than lower bounds LB.");
+    if (lb == ub) wd[i] = 1.0;                                            // (:185)
+    if (!(wd[i] > 0.0) || !std::isfinite(wd[i]))
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:widths The vector WIDTHS need to be all positive real numbers.");
+    if (!(xx0[i] >= lb && xx0[i] <= ub))
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:start The initial starting point X0 is outside the bounds.");
+    if (g.basewidths && !(g.basewidths[i] >= 0.0))
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:widths The vector WIDTHS need to be all positive real numbers.");
+    LBo[i] = lb - host_eps(lb);                                           // (:164-165)
+    UBo[i] = ub + host_eps(ub);
+  }
+  if (g.rng_mode == 1)
+    for (size_t e = 0; e < (size_t)total * Nhyp; ++e)
+      if (g.perms[e] < 0 || g.perms[e] >= Nhyp) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: perms holds an index outside 0 .. Nhyp - 1");
+  // hyper-prior classes and normalising terms (gplite_hypprior.m:34-36,49-58)
+  std::vector<double> pmu(Nhyp, 0.0), psig(Nhyp, 1.0), pdf(Nhyp, 7.0), pc(Nhyp, 0.0);
+  std::vector<int> ptype(Nhyp, 0);
+  if (g.prior_mu)
+    for (int i = 0; i < Nhyp; ++i) {
+      const double mu = g.prior_mu[i], sg = std::fabs(g.prior_sigma[i]), df = g.prior_df ? g.prior_df[i] : 7.0;
+      if (!std::isfinite(mu) || !std::isfinite(sg)) continue;
+      pmu[i] = mu; psig[i] = sg; pdf[i] = df;
+      if (df == 0.0 || !std::isfinite(df)) { ptype[i] = 1; pc[i] = std::log(2.0 * 3.14159265358979323846 * sg * sg); }
+      else if (df > 0.0) { ptype[i] = 2; pc[i] = std::lgamma(0.5 * (df + 1.0)) - std::lgamma(0.5 * df) - 0.5 * std::log(3.14159265358979323846 * df) - std::log(sg); }
+    }
+  int W = g.W == 0 ? SLICE_DEFAULT_W : g.W;
+  while (W > 1 && (size_t)W * N * N * 8 > ((size_t)2 << 30)) --W;        // the W factorisations' work matrices stay below 2 GiB (include/vbmc_hip.h says so)
+  std::vector<int32_t> perm_own;
+  const int32_t* perms = g.perms;
+  if (g.rng_mode == 0) {
+    perm_own.resize((size_t)total * Nhyp);
+    vbmc_slice_rng_dump(g.seed, total, Nhyp, 0, perm_own.data(), nullptr);
+    perms = perm_own.data();
+  }
+
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t nU = g.rng_mode == 1 ? (size_t)total * Nhyp * (size_t)(2 + g.Kmax) : 0;
+  // one block of fp64 inputs / chain vectors, one of work space
+  //   X | y | s2 | LB UB LBo UBo | pmu psig pdf pc | basew | xx widths xsum xsq | U
+  const size_t nX = (size_t)N * D;
+  const size_t in_doubles = nX + 2 * (size_t)N + 13 * (size_t)Nhyp + nU;
+  TmpBuf dIn, dInt, dState, dHyp, dSn2, dScal, dLp, dFlags, dXc, daa, dA, dpf, dr, dz, dal, dfinv, dPg, dOut, dSmp;
+  HIP_TRY(ctx, dIn.alloc(ctx, in_doubles * 8));
+  HIP_TRY(ctx, dInt.alloc(ctx, ((size_t)total * Nhyp + Nhyp) * sizeof(int)));
+  HIP_TRY(ctx, dState.alloc(ctx, sizeof(SliceChainState)));
+  HIP_TRY(ctx, dHyp.alloc(ctx, (size_t)W * Nhyp * 8));
+  HIP_TRY(ctx, dSn2.alloc(ctx, (size_t)W * N * 8));
+  HIP_TRY(ctx, dScal.alloc(ctx, (size_t)W * 4 * 8));
+  HIP_TRY(ctx, dLp.alloc(ctx, (size_t)W * 8));
+  HIP_TRY(ctx, dFlags.alloc(ctx, 2 * (size_t)SLICE_MAXW));
+  HIP_TRY(ctx, dXc.alloc(ctx, (size_t)W * N * D * 8));
+  HIP_TRY(ctx, daa.alloc(ctx, (size_t)W * N * 8));
+  HIP_TRY(ctx, dA.alloc(ctx, (size_t)W * N * N * 8));
+  HIP_TRY(ctx, dpf.alloc(ctx, (size_t)W * sizeof(int)));
+  HIP_TRY(ctx, dr.alloc(ctx, (size_t)W * N * 8));
+  HIP_TRY(ctx, dz.alloc(ctx, (size_t)W * N * 8));
+  HIP_TRY(ctx, dal.alloc(ctx, ((size_t)W * N + W) * 8));
+  HIP_TRY(ctx, dfinv.alloc(ctx, (size_t)W * TRSM_NBLK(N) * 256 * 8));
+  if (chol2_needs_gpanel(N, true)) HIP_TRY(ctx, dPg.alloc(ctx, (size_t)W * 16 * (size_t)(((N + 15) >> 4) << 4) * 8));
+  HIP_TRY(ctx, dOut.alloc(ctx, (size_t)W * 2 * 8));
+  HIP_TRY(ctx, dSmp.alloc(ctx, ((size_t)g.Ns * Nhyp + g.Ns) * 8));
+  { vbmc_status s_ = ensure_pin(ctx, 2 * sizeof(SliceChainState) + 64); if (s_) return s_; }
+  SliceChainState* hst = (SliceChainState*)ctx->pin;                                // two landing slots of the progress word
+
+  std::vector<double> hin(in_doubles, 0.0);
+  {
+    double* q = hin.data();
+    memcpy(q, g.X, nX * 8); q += nX;
+    memcpy(q, g.y, (size_t)N * 8); q += N;
+    if (g.s2) memcpy(q, g.s2, (size_t)N * 8);
+    q += N;
+    const double* blocks[9] = {g.LB, g.UB, LBo.data(), UBo.data(), pmu.data(), psig.data(), pdf.data(), pc.data(), g.basewidths};
+    for (int b = 0; b < 9; ++b, q += Nhyp) if (blocks[b]) memcpy(q, blocks[b], (size_t)Nhyp * 8);
+    memcpy(q, xx0.data(), (size_t)Nhyp * 8); q += Nhyp;
+    memcpy(q, wd.data(), (size_t)Nhyp * 8); q += 3 * (size_t)Nhyp;      // xsum, xsq start at zero
+    if (nU) memcpy(q, g.uniforms, nU * 8);
+  }
+  std::vector<int> hint((size_t)total * Nhyp + Nhyp);
+  for (size_t e = 0; e < (size_t)total * Nhyp; ++e) hint[e] = perms[e];
+  for (int i = 0; i < Nhyp; ++i) hint[(size_t)total * Nhyp + i] = ptype[i];
+  HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin.data(), in_doubles * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(dInt.p, hint.data(), hint.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(dState.p, 0, sizeof(SliceChainState), st));
+  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, 2 * (size_t)SLICE_MAXW, st));
+  HIP_TRY(ctx, hipMemsetAsync(dHyp.p, 0, (size_t)W * Nhyp * 8, st));     // k_gp_scale / k_nlz_final are not gated: they read every row
+  HIP_TRY(ctx, hipMemsetAsync(dScal.p, 0, (size_t)W * 4 * 8, st));
+
+  SliceKernelArgs a{};
+  a.N = N; a.D = D; a.Nhyp = Nhyp; a.Ncov = Ncov; a.W = W; a.Kmax = g.Kmax; a.Ns = g.Ns; a.thin = g.Thin; a.burn = g.Burnin;
+  a.adaptive = g.Adaptive ? 1 : 0; a.total = total; a.parity = g.rng_mode; a.nf0 = g.noisefun[0]; a.nf1 = g.noisefun[1]; a.nf2 = g.noisefun[2];
+  a.has_base = g.basewidths ? 1 : 0; a.has_prior = g.prior_mu ? 1 : 0; a.seed = g.seed;
+  {
+    double* q = dIn.as<double>();
+    double* dX = q; q += nX;
+    a.y = q; q += N;
+    a.s2 = g.s2 ? q : nullptr; q += N;
+    a.LB = q; a.UB = q + Nhyp; a.LBo = q + 2 * Nhyp; a.UBo = q + 3 * Nhyp; a.pmu = q + 4 * Nhyp; a.psig = q + 5 * Nhyp; a.pdf = q + 6 * Nhyp;
+    a.pc = q + 7 * Nhyp; a.basew = q + 8 * Nhyp; a.xx = q + 9 * Nhyp; a.widths = q + 10 * Nhyp; a.xsum = q + 11 * Nhyp; a.xsq = q + 12 * Nhyp;
+    a.U = nU ? q + 13 * Nhyp : nullptr;
+    a.perms = dInt.as<int>(); a.ptype = dInt.as<int>() + (size_t)total * Nhyp;
+    a.st = dState.as<SliceChainState>();
+    a.hyp = dHyp.as<double>(); a.sn2 = dSn2.as<double>(); a.scal = dScal.as<double>(); a.lp = dLp.as<double>();
+    a.act = dFlags.as<unsigned char>(); a.on = a.act + SLICE_MAXW; a.out = dOut.as<double>();
+    a.samples = dSmp.as<double>(); a.logp = a.samples + (size_t)g.Ns * Nhyp;
+    const int moff = Ncov + Nnoise;
+    double* pfd = dal.as<double>() + (size_t)W * N;
+    long long enqueued = 0;
+    auto round = [&](int checked) -> vbmc_status {
+      ++enqueued;
+      hipLaunchKernelGGL(k_slice_propose, dim3(W), dim3(256), 0, st, a, checked);
+      gp_launch_scale(st, N, D, W, Nhyp, moff, meanfun, dX, a.hyp, dXc.as<double>(), daa.as<double>(), a.y, dr.as<double>());
+      for (int t = 0; t < (checked ? 10 : 1); ++t) {
+        if (t > 0) hipLaunchKernelGGL(k_slice_retry, dim3(1), dim3(64), 0, st, W, dpf.as<int>(), a.scal, a.act);
+        HIP_TRY(ctx, gp_launch_try(st, N, D, W, Nhyp, a.hyp, dXc.as<double>(), daa.as<double>(), a.sn2, a.scal, a.act, dA.as<double>(),
+                                   dpf.as<int>(), dPg.p ? dPg.as<double>() : nullptr, dfinv.as<double>(), pfd, dr.as<double>(), dz.as<double>()));
+      }
+      gp_launch_alpha(st, N, W, dA.as<double>(), dfinv.as<double>(), a.on, dz.as<double>(), dal.as<double>(), a.scal);
+      gp_launch_nlz_final(st, N, D, W, Nhyp, Nnoise, Nmean, meanfun, 0, 0, dX, a.y, a.hyp, dA.as<double>(), dal.as<double>(), a.scal, nullptr, pfd,
+                          dOut.as<double>());
+      hipLaunchKernelGGL(k_slice_decide, dim3(1), dim3(64), 0, st, a, checked);
+      HIP_TRY(ctx, hipGetLastError());
+      return VBMC_OK;
+    };
+    // chunks of rounds, the state word read one chunk behind (ev_fork / ev_join: this call forks nothing onto the second stream)
+    hipEvent_t ev[2] = {ctx->ev_fork, ctx->ev_join};
+    if (!ev[0] || !ev[1]) return set_err(ctx, VBMC_ERR_HIP, "vbmc_gp_slice_sample: the context has no events");
+    // (rounds enqueued behind the end of the chain, or behind a stall, launch nothing in propose / build / factorise / solve / decide,
+    // but k_gp_scale and k_nlz_final still run their W workgroups: the chunks start at 4 rounds and double up to SLICE_CHUNK, so that
+    // a short chain wastes a handful of such rounds and a long one at most two chunks of them)
+    int k = 0, chunk = 4;
+    bool have_prev = false, finished = false;
+    vbmc_status rs = VBMC_OK;
+    while (!finished && rs == VBMC_OK) {
+      for (int r = 0; r < chunk && rs == VBMC_OK; ++r) rs = round(0);
+      chunk = std::min(2 * chunk, SLICE_CHUNK);
+      if (rs != VBMC_OK) break;
+      HIP_TRY(ctx, hipMemcpyAsync(&hst[k], dState.p, sizeof(SliceChainState), hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipEventRecord(ev[k], st));
+      if (have_prev) {
+        HIP_TRY(ctx, hipEventSynchronize(ev[k ^ 1]));
+        const SliceChainState& h = hst[k ^ 1];
+        if (h.phase >= 2) finished = true;
+        else if (h.stall) {
+          HIP_TRY(ctx, hipStreamSynchronize(st));     // the rounds behind a stall are no-ops: nothing to wait for but the queue
+          rs = round(1);
+          have_prev = false;
+          k ^= 1;
+          continue;
+        }
+      }
+      have_prev = true;
+      k ^= 1;
+    }
+    (void)hipStreamSynchronize(st);                    // whatever is still enqueued finds the chain finished and does nothing
+    if (rs != VBMC_OK) return rs;
+    if (g.rounds) g.rounds[1] = enqueued;
+  }
+  SliceChainState fin;
+  HIP_TRY(ctx, hipMemcpy(&fin, dState.p, sizeof(SliceChainState), hipMemcpyDeviceToHost));
+  if (fin.phase == 3) {
+    if (fin.err == SLICE_ERR_COLLAPSE) {
+      std::vector<double> xx(Nhyp);
+      HIP_TRY(ctx, hipMemcpy(xx.data(), a.xx, (size_t)Nhyp * 8, hipMemcpyDeviceToHost));
+      std::string pos;
+      char b[64];
+      for (int i = 0; i < Nhyp && pos.size() < 300; ++i) { snprintf(b, sizeof b, " %g", xx[i]); pos += b; }
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:collapse Shrunk to current position and proposal still not acceptable. Current position:%s. "
+                     "Log f: (new value) %g, (target value) %g.", pos.c_str(), fin.err_newval, fin.log_uprime);
+    }
+    if (fin.err == SLICE_ERR_X0)
+      return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:start The initial starting point X0 needs to evaluate to a real number (not Inf or NaN).");
+    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: uniform block exhausted: a coordinate of sweep %d needed more than Kmax = %d shrink proposals",
+                   fin.sweep, g.Kmax);
+  }
+  if (fin.phase != 2) return set_err(ctx, VBMC_ERR_HIP, "vbmc_gp_slice_sample: the chain did not finish (phase %d)", fin.phase);
+  if (g.samples) HIP_TRY(ctx, hipMemcpy(g.samples, a.samples, (size_t)g.Ns * Nhyp * 8, hipMemcpyDeviceToHost));
+  if (g.logp) HIP_TRY(ctx, hipMemcpy(g.logp, a.logp, (size_t)g.Ns * 8, hipMemcpyDeviceToHost));
+  if (g.widths_out) HIP_TRY(ctx, hipMemcpy(g.widths_out, a.widths, (size_t)Nhyp * 8, hipMemcpyDeviceToHost));
+  if (g.funccount) *g.funccount = fin.funccount;
+  if (g.performed) *g.performed = fin.performed;
+  if (g.max_shrink) *g.max_shrink = fin.maxshrink;
+  if (g.rounds) g.rounds[0] = fin.rounds;
+  return VBMC_OK;
+}

@@ -266,3 +266,144 @@ def gplite_nlZ(hyp, gp, hprior=None, nargout=2, *, engine=None):
     if single:
         return (float(nlZ[0]), dnlZ[:, 0].copy()) if grad else float(nlZ[0])
     return (nlZ, dnlZ) if grad else nlZ
+
+
+def slice_rng_dump(seed, sweeps, Nhyp, Kmax):
+    """(perms, U): the 0-based permutations (sweeps x Nhyp, int32) and the indexed uniform block U[sweep, idd, slot]
+    (sweeps x Nhyp x (2 + Kmax)) that ``seed`` stands for in the device-RNG mode of slicesamplebnd_gp (vbmc_slice_rng_dump: a
+    host function).  Feeding them back as ``perms=`` / ``uniforms=`` replays the chain bit for bit."""
+    from ._lib import load
+
+    perms = np.zeros((int(sweeps), int(Nhyp)), dtype=np.int32)
+    U = np.zeros((int(sweeps), int(Nhyp), 2 + int(Kmax)))
+    st = load().vbmc_slice_rng_dump(C.c_uint64(int(seed)), int(sweeps), int(Nhyp), int(Kmax), perms.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    U.ctypes.data_as(C.POINTER(C.c_double)))
+    if st != 0:
+        raise ValueError("vbmc_slice_rng_dump: bad arguments")
+    return perms, U
+
+
+class SliceOutput(dict):
+    """The reference's fourth output (output.widths, output.funccount) plus the device chain's own counters."""
+    __getattr__ = dict.__getitem__
+
+
+def slicesamplebnd_gp(gp, hprior, x0, N, widths=None, LB=None, UB=None, options=None, *, seed=0, uniforms=None, perms=None, W=None,
+                      engine=None):
+    """[samples,fvals,exitflag,output] = slicesamplebnd(@(hyp) gp_objfun(hyp(:),gp,hprior,0,1), x0, N, widths, LB, UB, options)
+    (utils/slicesamplebnd.m:1, the call of gplite/gplite_train.m:318-330) with the whole chain on the device.
+
+    ``options``: Thin (1), Burnin (round(N/3)), Adaptive (True) as in the reference (:143-147); StepOut must stay false, Display and
+    Diagnostics are not offered (exitflag is 0, as with Diagnostics = false, :395).  Random numbers: the library's generator keyed by
+    ``seed``, or -- parity mode -- the caller's ``perms`` (sweeps x Nhyp, 0-based) and ``uniforms`` (sweeps x Nhyp x (2 + Kmax), see
+    include/vbmc_hip.h).  ``W``: speculation width (None: the library's default); every W returns the same bits.
+    ``output``: widths, funccount (evaluations of the sequential algorithm), performed (evaluations launched), maxshrink,
+    rounds_done / rounds_enqueued (rounds of the device chain that did work / that the host enqueued)."""
+    from ._lib import SliceArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    options = dict(options or {})
+    if options.get("StepOut"):
+        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "slicesamplebnd_gp: the step-out procedure is not accelerated")
+    X = f64(gp["X"])
+    Np, D = X.shape
+    y = f64(np.asarray(gp["y"], dtype=np.float64).reshape(-1))
+    s2 = gp.get("s2")
+    s2 = None if s2 is None or np.size(s2) == 0 else f64(np.asarray(s2, dtype=np.float64).reshape(-1))
+    x0 = f64(np.asarray(x0, dtype=np.float64).reshape(-1))
+    Nhyp = x0.size
+    if gp.get("intmeanfun", 0) or gp.get("outwarpfun") is not None or int(np.atleast_1d(gp.get("covfun", 1))[0]) != 1:
+        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "slicesamplebnd_gp: integrated mean / output warping / non-SE covariance are not accelerated")
+    lb = f64(np.broadcast_to(np.asarray(-np.inf if LB is None or np.size(LB) == 0 else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    ub = f64(np.broadcast_to(np.asarray(np.inf if UB is None or np.size(UB) == 0 else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    base = None
+    if widths is None or np.size(widths) == 0:
+        wd = (ub - lb) / 2                                                       # :173-174
+        wd[np.isinf(wd)] = 10.0
+    else:
+        wd = np.broadcast_to(np.asarray(widths, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+        base = f64(wd.copy())                                                    # :166
+    wd = f64(wd)
+    N = int(N)
+    thin = int(np.floor(options.get("Thin", 1)))
+    burn = int(np.floor(options.get("Burnin", round(N / 3))))
+    a = SliceArgs()
+    a.struct_size = C.sizeof(SliceArgs)
+    a.N, a.D, a.Nhyp, a.meanfun = Np, D, Nhyp, int(gp["meanfun"])
+    nf = [int(v) for v in (list(gp["noisefun"]) + [0, 0, 0])[:3]]
+    for i in range(3):
+        a.noisefun[i] = nf[i]
+    a.X, a.y, a.s2 = ptr(X), ptr(y), ptr(s2)
+    keep = []
+    if hprior is not None:
+        mu = f64(np.asarray(hprior["mu"], dtype=np.float64).reshape(-1))
+        sg = f64(np.asarray(hprior["sigma"], dtype=np.float64).reshape(-1))
+        df = hprior.get("df")
+        df = None if df is None or np.size(df) == 0 else f64(np.asarray(df, dtype=np.float64).reshape(-1))
+        if mu.size != Nhyp or sg.size != Nhyp or (df is not None and df.size != Nhyp):
+            raise ValueError("slicesamplebnd_gp: hprior.mu / sigma / df need one entry per hyper-parameter")
+        keep += [mu, sg, df]
+        a.prior_mu, a.prior_sigma, a.prior_df = ptr(mu), ptr(sg), ptr(df)
+    a.LB, a.UB, a.hyp_start, a.widths, a.basewidths = ptr(lb), ptr(ub), ptr(x0), ptr(wd), ptr(base)
+    a.Ns, a.Thin, a.Burnin, a.Adaptive = N, thin, burn, int(bool(options.get("Adaptive", True)))
+    a.W = 0 if W is None else int(W)
+    if uniforms is not None or perms is not None:
+        if uniforms is None or perms is None:
+            raise ValueError("slicesamplebnd_gp: parity mode needs both perms and uniforms")
+        sweeps = burn + N + (N - 1) * (thin - 1)
+        U = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
+        P = np.ascontiguousarray(np.asarray(perms, dtype=np.int32))
+        if U.ndim != 3 or U.shape[0] < sweeps or U.shape[1] != Nhyp or U.shape[2] < 3 or P.shape[0] < sweeps or P.shape[1:] != (Nhyp,):
+            raise ValueError("slicesamplebnd_gp: uniforms must be sweeps x Nhyp x (2 + Kmax) and perms sweeps x Nhyp for %d sweeps" % sweeps)
+        keep += [U, P]
+        a.rng_mode, a.Kmax = 1, U.shape[2] - 2
+        a.perms, a.uniforms = P.ctypes.data_as(C.POINTER(C.c_int32)), U.ctypes.data_as(C.POINTER(C.c_double))
+    else:
+        a.rng_mode, a.seed = 0, int(seed)
+    samples = np.zeros((N, Nhyp), order="F")
+    logp = np.zeros(N)
+    wout = np.zeros(Nhyp)
+    fc, pf, ms = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    a.samples, a.logp, a.widths_out = ptr(samples), ptr(logp), ptr(wout)
+    a.funccount, a.performed, a.max_shrink = C.pointer(fc), C.pointer(pf), C.pointer(ms)
+    rd = (C.c_int64 * 2)()
+    a.rounds = C.cast(rd, C.POINTER(C.c_int64))
+    ctx.check(ctx.lib.vbmc_gp_slice_sample(ctx.h, C.byref(a)))
+    out = SliceOutput(widths=wout, funccount=int(fc.value), performed=int(pf.value), maxshrink=int(ms.value), logpriors=None, rounds_done=int(rd[0]),
+                      rounds_enqueued=int(rd[1]))
+    return samples, logp, 0, out
+
+
+def gplite_train_sample(gp, hyp_start, Ns, hprior=None, LB=None, UB=None, widths=None, *, Thin=1, Burnin=None, seed=0, uniforms=None,
+                        perms=None, W=None, need_L=True, engine=None):
+    """The sampling half of gplite_train (gplite/gplite_train.m:303-340, sampler 'slicesample'), the thinning that follows it
+    (:459-461) and the closing gplite_post of the thinned samples (:474): ``Ns * Thin`` sweeps are recorded after ``Burnin``
+    (default: Thin * Ns, :51), every Thin-th is kept, and the returned ``gp`` holds the Ns hyper-samples with its posterior on the
+    device (``need_L`` as in gplite_post).  The optimisation half (:200-306) is not part of this package: ``hyp_start`` is the caller's.
+    Returns (gp, hyp, output): hyp Nhyp x Ns, output = {hyp_prethin, logp, logp_prethin, widths, funccount, performed, maxshrink}."""
+    hyp_start = np.asarray(hyp_start, dtype=np.float64).reshape(-1)
+    Nhyp = hyp_start.size
+    Ns, Thin = int(Ns), int(Thin)
+    if Ns < 1 or Thin < 1:
+        raise ValueError("gplite_train_sample: Ns and Thin must be positive")
+    Burnin = Thin * Ns if Burnin is None else int(Burnin)
+    lb = np.broadcast_to(np.asarray(-np.inf if LB is None else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+    ub = np.broadcast_to(np.asarray(np.inf if UB is None else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+    # the starting point inside the bounds, fixed coordinates at their value (:304-306)
+    with np.errstate(invalid="ignore"):
+        elb = np.where(np.isfinite(lb), np.spacing(np.abs(lb)), 0.0)
+        eub = np.where(np.isfinite(ub), np.spacing(np.abs(ub)), 0.0)
+    x0 = np.minimum(np.maximum(hyp_start, lb + elb), ub - eub)
+    fixed = lb == ub
+    x0[fixed] = lb[fixed]
+    samples, fvals, _, out = slicesamplebnd_gp(gp, hprior, x0, Ns * Thin, widths, lb, ub, {"Thin": 1, "Burnin": Burnin}, seed=seed,
+                                               uniforms=uniforms, perms=perms, W=W, engine=engine)
+    hyp_prethin = np.ascontiguousarray(samples.T)
+    hyp = hyp_prethin[:, Thin - 1::Thin].copy()
+    new = gplite_post(hyp, gp["X"], gp["y"], 1, gp["meanfun"], gp["noisefun"], gp.get("s2"), need_L=need_L, engine=engine)
+    output = {"hyp_prethin": hyp_prethin, "logp": fvals[Thin - 1::Thin].copy(), "logp_prethin": fvals, "widths": out["widths"],
+              "funccount": out["funccount"], "performed": out["performed"], "maxshrink": out["maxshrink"]}
+    return new, hyp, output
