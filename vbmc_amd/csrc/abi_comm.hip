@@ -260,7 +260,7 @@ static vbmc_status comm_allgather_enqueue(vbmc_comm* c, const double* const* d_s
 extern "C" vbmc_status vbmc_allgather_f64(vbmc_comm* c, const double* const* d_send, double* const* d_recv, size_t count) {
   if (!c) return VBMC_ERR_INVALID;
   if (!d_send || !d_recv || count == 0) return comm_err(c, VBMC_ERR_INVALID, "vbmc_allgather_f64: null blocks / zero count");
-  { vbmc_status s_ = comm_allgather_enqueue(c, d_send, d_recv, count); if (s_) return s_; }
+  VB_TRY(comm_allgather_enqueue(c, d_send, d_recv, count));
   for (int i = 0; i < c->n; ++i) {
     COMM_HIP(c, hipSetDevice(c->ctx[i]->device));
     COMM_HIP(c, hipStreamSynchronize(c->ctx[i]->stream));
@@ -271,12 +271,12 @@ extern "C" vbmc_status vbmc_allgather_f64(vbmc_comm* c, const double* const* d_s
 extern "C" vbmc_status vbmc_allgather_host_f64(vbmc_comm* c, const double* send, double* recv, size_t count) {
   if (!c) return VBMC_ERR_INVALID;
   if (!send || !recv || count == 0) return comm_err(c, VBMC_ERR_INVALID, "vbmc_allgather_host_f64: null blocks / zero count");
-  { vbmc_status s_ = comm_reserve(c, count); if (s_) return s_; }
+  VB_TRY(comm_reserve(c, count));
   for (int i = 0; i < c->n; ++i) {
     COMM_HIP(c, hipSetDevice(c->ctx[i]->device));
     COMM_HIP(c, hipMemcpyAsync(c->d_send[i], send + (size_t)i * count, count * sizeof(double), hipMemcpyHostToDevice, c->ctx[i]->stream));
   }
-  { vbmc_status s_ = comm_allgather_enqueue(c, c->d_send.data(), c->d_recv.data(), count); if (s_) return s_; }
+  VB_TRY(comm_allgather_enqueue(c, c->d_send.data(), c->d_recv.data(), count));
   COMM_HIP(c, hipSetDevice(c->ctx[0]->device));
   COMM_HIP(c, hipMemcpyAsync(recv, c->d_recv[0], count * c->world * sizeof(double), hipMemcpyDeviceToHost, c->ctx[0]->stream));
   for (int i = 0; i < c->n; ++i) {
@@ -338,7 +338,7 @@ extern "C" vbmc_status vbmc_elbo_batch_multi(vbmc_comm* c, const vbmc_gp* const*
   { const int n[4] = {D * K, K, D, K}; for (int g = 0; g < 4; ++g) if (a->optimize[g]) T += n[g]; }
   if (T > 0 && !a->theta) return comm_err(c, VBMC_ERR_INVALID, "vbmc_elbo_batch_multi: theta is null");
   const int P = (R + G - 1) / G;                    // restarts per rank, padded
-  { vbmc_status s_ = comm_reserve(c, 2 * (size_t)P); if (s_) return s_; }
+  VB_TRY(comm_reserve(c, 2 * (size_t)P));
   // A failure that is local to one rank (a resource error, a missing surrogate) must not leave the other ranks waiting in the
   // collective: the rank still enters it, contributing an all-NaN block, and reports its error after the exchange.
   vbmc_status local_fail = VBMC_OK;
@@ -398,7 +398,7 @@ extern "C" vbmc_status vbmc_elbo_batch_multi(vbmc_comm* c, const vbmc_gp* const*
     COMM_HIP(c, hipGetLastError());
   }
   // ---- the exchange: [F | varG] of every rank to every rank, on the streams the passes run on
-  { vbmc_status s_ = comm_allgather_enqueue(c, c->d_send.data(), c->d_recv.data(), 2 * (size_t)P); if (s_) return s_; }
+  VB_TRY(comm_allgather_enqueue(c, c->d_send.data(), c->d_recv.data(), 2 * (size_t)P));
   if (local_fail) {
     const std::string keep = c->err;
     for (int i = 0; i < c->n; ++i) { (void)hipSetDevice(c->ctx[i]->device); (void)hipStreamSynchronize(c->ctx[i]->stream); }
@@ -507,7 +507,7 @@ static vbmc_status multi_submit_impl(vbmc_comm* c, const vbmc_gp* const* gps, co
   { const int n[4] = {D * K, K, D, K}; for (int g = 0; g < 4; ++g) if (a->optimize[g]) T += n[g]; }
   if (T > 0 && !a->theta) return comm_err(c, VBMC_ERR_INVALID, "vbmc_elbo_multi_submit: theta is null");
   const int P = (R + G - 1) / G;
-  { vbmc_status s_ = comm_slot_reserve(c, sl, 2 * (size_t)P); if (s_) return s_; }
+  VB_TRY(comm_slot_reserve(c, sl, 2 * (size_t)P));
   sl.R = R; sl.T = T; sl.P = P;
   sl.n.assign(c->n, 0); sl.st.assign(c->n, VBMC_OK);
   if ((int)sl.theta.size() != c->n) { sl.theta.resize(c->n); sl.sub.resize(c->n); }
@@ -571,7 +571,7 @@ static vbmc_status multi_submit_impl(vbmc_comm* c, const vbmc_gp* const* gps, co
     }
   }
   const std::string keep = c->err;
-  { vbmc_status s_ = comm_allgather_enqueue(c, sl.d_send.data(), sl.d_recv.data(), 2 * (size_t)P, sl.xst.data()); if (s_) return s_; }
+  VB_TRY(comm_allgather_enqueue(c, sl.d_send.data(), sl.d_recv.data(), 2 * (size_t)P, sl.xst.data()));
   COMM_HIP(c, hipSetDevice(c->ctx[0]->device));
   COMM_HIP(c, hipMemcpyAsync(sl.h_gather, sl.d_recv[0], 2 * (size_t)P * G * sizeof(double), hipMemcpyDeviceToHost, sl.xst[0]));
   for (int i = 0; i < c->n; ++i) {

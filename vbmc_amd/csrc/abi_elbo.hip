@@ -7,6 +7,7 @@
 #include "elbo_kernels.h"
 #include "var_kernels.h"
 #include "gp_kernels.h"
+#include "elbo_launch_plan.h"
 #include <cstdlib>
 
 // ------------------------------------------------------------------------------------------
@@ -306,35 +307,23 @@ extern "C" void vbmc_gp_free(vbmc_ctx* ctx, vbmc_gp* gp) {
 // ------------------------------------------------------------------------------------------
 // template dispatch on the padded dimension DT
 // ------------------------------------------------------------------------------------------
+// the padded dimensions DT the DT-templated kernels are instantiated for: one list for pick_dt and DISPATCH_DT (X(n, what the caller passes on))
+#define VBMC_DT_LIST(X, ...) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(5, __VA_ARGS__) X(6, __VA_ARGS__) X(7, __VA_ARGS__) X(8, __VA_ARGS__) X(9, __VA_ARGS__) X(10, __VA_ARGS__) \
+  X(11, __VA_ARGS__) X(12, __VA_ARGS__) X(14, __VA_ARGS__) X(16, __VA_ARGS__) X(18, __VA_ARGS__) X(20, __VA_ARGS__) X(24, __VA_ARGS__) X(28, __VA_ARGS__) X(32, __VA_ARGS__)
 static int pick_dt(int D) {
-  static const int dts[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 18, 20, 24, 28, 32};
+#define X(n, ...) n,
+  static const int dts[] = {VBMC_DT_LIST(X, 0)};
+#undef X
   for (int t : dts)
     if (t >= D) return t;
   return -1;
 }
 
-#define DISPATCH_DT(DTV, ...)                                                                      \
-  switch (DTV) {                                                                                   \
-    case 1: { constexpr int DT = 1; __VA_ARGS__; } break;                                                 \
-    case 2: { constexpr int DT = 2; __VA_ARGS__; } break;                                                 \
-    case 3: { constexpr int DT = 3; __VA_ARGS__; } break;                                                 \
-    case 4: { constexpr int DT = 4; __VA_ARGS__; } break;                                                 \
-    case 5: { constexpr int DT = 5; __VA_ARGS__; } break;                                                 \
-    case 6: { constexpr int DT = 6; __VA_ARGS__; } break;                                                 \
-    case 7: { constexpr int DT = 7; __VA_ARGS__; } break;                                                 \
-    case 8: { constexpr int DT = 8; __VA_ARGS__; } break;                                                 \
-    case 9: { constexpr int DT = 9; __VA_ARGS__; } break;                                                 \
-    case 10: { constexpr int DT = 10; __VA_ARGS__; } break;                                               \
-    case 11: { constexpr int DT = 11; __VA_ARGS__; } break;                                               \
-    case 12: { constexpr int DT = 12; __VA_ARGS__; } break;                                               \
-    case 14: { constexpr int DT = 14; __VA_ARGS__; } break;                                               \
-    case 16: { constexpr int DT = 16; __VA_ARGS__; } break;                                               \
-    case 18: { constexpr int DT = 18; __VA_ARGS__; } break;                                               \
-    case 20: { constexpr int DT = 20; __VA_ARGS__; } break;                                               \
-    case 24: { constexpr int DT = 24; __VA_ARGS__; } break;                                               \
-    case 28: { constexpr int DT = 28; __VA_ARGS__; } break;                                               \
-    case 32: { constexpr int DT = 32; __VA_ARGS__; } break;                                               \
-    default: return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", dm.D);            \
+#define DISPATCH_DT_CASE(n, ...) case n: { constexpr int DT = n; __VA_ARGS__; } break;
+#define DISPATCH_DT(DTV, ...)                                                            \
+  switch (DTV) {                                                                         \
+    VBMC_DT_LIST(DISPATCH_DT_CASE, __VA_ARGS__)                                          \
+    default: return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", dm.D);  \
   }
 
 template <int DT>
@@ -350,101 +339,37 @@ static hipError_t set_entropy_lds(bool grad, size_t lds) {
   return hipFuncSetAttribute((const void*)k_entropy<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
+// ---- MFMA entropy kernel dispatch: QS = ceil((D+2)/4) in 1..9 (one translation unit each, ent_mfma_inst.hip), KT = ceil(K/16) in 1..8
+// (1..4 for QS > 6: register budget) -- and the lane-per-sample entropy kernel (entropy_lane.h; round 6): small mixtures, K <= 16 and D <= 12,
+// one translation unit per padded dimension DT = 2, 4, .., 12 (ent_lane_inst.hip), KP = K rounded up to even.
+// The per-instantiation launchers and occupancy queries, and the tables over them, from one list each (vbmc_amd/build.py: QS_RANGE, LANE_DT).
+#define VBMC_QS_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define VBMC_LANE_DT_LIST(X) X(2) X(4) X(6) X(8) X(10) X(12)
+extern "C" {
+#define X(n) int vbmc_launch_ent_mfma_qs##n(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*); int vbmc_occupancy_ent_mfma_qs##n(int, int, int, const EntArgs*);
+VBMC_QS_LIST(X)
+#undef X
+#define X(n) int vbmc_launch_ent_lane_dt##n(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*); int vbmc_occupancy_ent_lane_dt##n(int, int, const EntArgs*);
+VBMC_LANE_DT_LIST(X)
+#undef X
+}
+#define X(n) {vbmc_launch_ent_mfma_qs##n, vbmc_occupancy_ent_mfma_qs##n},
+static const struct { decltype(&vbmc_launch_ent_mfma_qs1) launch; decltype(&vbmc_occupancy_ent_mfma_qs1) occupancy; } ent_mfma_inst[9] = {VBMC_QS_LIST(X)};
+#undef X
+#define X(n) {vbmc_launch_ent_lane_dt##n, vbmc_occupancy_ent_lane_dt##n},
+static const struct { decltype(&vbmc_launch_ent_lane_dt2) launch; decltype(&vbmc_occupancy_ent_lane_dt2) occupancy; } ent_lane_inst[6] = {VBMC_LANE_DT_LIST(X)};
+#undef X
 
-// ---- MFMA entropy kernel dispatch: QS = ceil((D+2)/4) in 1..9 (one translation unit each,
-// ent_mfma_inst.hip), KT = ceil(K/16) in 1..8 (1..4 for QS > 6: register budget)
-extern "C" {
-int vbmc_launch_ent_mfma_qs1(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs2(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs3(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs4(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs5(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs6(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs7(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs8(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_mfma_qs9(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs1(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs2(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs3(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs4(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs5(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs6(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs7(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs8(int, int, int, const EntArgs*);
-int vbmc_occupancy_ent_mfma_qs9(int, int, int, const EntArgs*);
-}
-// ---- lane-per-sample entropy kernel (entropy_lane.h; round 6): small mixtures, K <= 16 and D <= 12.  One translation unit per padded
-// dimension DT = 2, 4, .., 12 (ent_lane_inst.hip), KP = K rounded up to even.
-extern "C" {
-int vbmc_launch_ent_lane_dt2(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_lane_dt4(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_lane_dt6(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_lane_dt8(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_lane_dt10(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_launch_ent_lane_dt12(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt2(int, int, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt4(int, int, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt6(int, int, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt8(int, int, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt10(int, int, const EntArgs*);
-int vbmc_occupancy_ent_lane_dt12(int, int, const EntArgs*);
-}
-#define ENT_LANE_WAVES_HOST 4     // = ENT_LANE_WAVES (entropy_lane.h)
-// the role's staged inputs (entropy_lane.h: ent_lane_role_lds) must fit the launch's dynamic LDS; larger training sets keep the separate log-joint kernel
-static bool lane_role_fits(int D, int K, int N, int S) {
-  return ((size_t)((N + 63) & ~63) * (D + ENT_LANE_WAVES_HOST) + (size_t)S * GPC_STRIDE(D) + (size_t)VpLayout{D, K}.stride() + D) * sizeof(double) <= 48 * 1024;
-}
-// The class: K <= 16, D <= 12, dense -- minus the corner where the two signs' densities and the gradient accumulators of a lane do not
-// fit 256 registers (DT = 12 with KP >= 10, DT = 10 with KP >= 12: built for one wave per SIMD those kernels take 2-3x the matrix-core
-// kernel's time, tools/run_lane_sweep.sh; they are not instantiated).
-static bool lane_entropy_fits(int D, int K, double cutoff) {
-  const int dt = 2 * ((D + 1) / 2), kp = 2 * ((K + 1) / 2);
-  return D >= 1 && D <= 12 && K >= 1 && K <= 16 && !(cutoff > 0.0) && !((dt >= 12 && kp >= 10) || (dt >= 10 && kp >= 12));
-}
-// ... and a batch wide enough to fill the chip with 64-sample tiles: a single chain (K R tiles < ~100) is bound by the launch's own
-// latencies, where the matrix-core kernel's role splits the training set over more waves (6 % to 10 % faster there)
-#define ENT_LANE_MIN_TILES 96
-static bool launch_entropy_lane(int D, int K, bool grad, dim3 g, hipStream_t st, const EntArgs& ea) {
-  typedef int (*fn_t)(int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-  static const fn_t fns[6] = {vbmc_launch_ent_lane_dt2, vbmc_launch_ent_lane_dt4, vbmc_launch_ent_lane_dt6,
-                              vbmc_launch_ent_lane_dt8, vbmc_launch_ent_lane_dt10, vbmc_launch_ent_lane_dt12};
-  return fns[(D + 1) / 2 - 1](2 * ((K + 1) / 2), grad ? 1 : 0, g.x, g.y, g.z, (void*)st, &ea) == 0;
-}
 static int entropy_lane_occupancy(int D, int K, bool grad) {
-  typedef int (*fn_t)(int, int, const EntArgs*);
-  static const fn_t fns[6] = {vbmc_occupancy_ent_lane_dt2, vbmc_occupancy_ent_lane_dt4, vbmc_occupancy_ent_lane_dt6,
-                              vbmc_occupancy_ent_lane_dt8, vbmc_occupancy_ent_lane_dt10, vbmc_occupancy_ent_lane_dt12};
   static int cache[6][9][2];      // 0: not asked yet
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   int& c = cache[(D + 1) / 2 - 1][(K + 1) / 2][grad ? 1 : 0];
-  if (c == 0) { EntArgs q{}; const int nb = fns[(D + 1) / 2 - 1](2 * ((K + 1) / 2), grad ? 1 : 0, &q); c = nb > 0 ? nb : -1; }
+  if (c == 0) { EntArgs q{}; const int nb = ent_lane_inst[(D + 1) / 2 - 1].occupancy(2 * ((K + 1) / 2), grad ? 1 : 0, &q); c = nb > 0 ? nb : -1; }
   return c;
-}
-
-// Waves per workgroup for 64 < K <= 128 (tools/tune_sweep.py, round 2): two -- four are 10-30 % slower (more exchange and barrier
-// coupling) -- EXCEPT where the two-wave kernel with four k-tiles per wave and a wide operand (D >= 15) spills its way down:
-// there four waves with two k-tiles each fit their registers (D = 24, K = 128: 3.4 vs 5.7 ms; D = 20, K = 128: 3.9 vs 5.0;
-// D = 20, K = 100 the other way: 50 vs 57 ms at configs[4]).
-// K <= 64: one wave per workgroup.  Round 3 (tools/hv_small_sweep.py -> profiles/r03_hv_small.md) tried two waves with two k-tiles
-// each where the one-wave kernel with four k-tiles spills: once those kernels were rebuilt for ONE wave per SIMD (512 registers,
-// VBMC_ENT_ONE_WAVE in entropy_mfma.h: 11-23 % faster) the split only wins at K = 57..64 for D >= 31 (6 %) and costs 6-85 % everywhere else.
-static int ent_hv_small(int qs, int K) { return (qs >= 9 && K > 52) ? 2 : 1; }   // (round 4, with the shared even part in the two-wave kernels: K = 53..56 at D >= 31 too, 0.77 of the one-wave time)
-static int ent_hv_mid(int qs, int K) { return (K > 96 && (qs >= 7 || (qs >= 5 && K > 112))) ? 4 : 2; }
-static bool launch_entropy_mfma(int qs, int kt, int hv, bool grad, dim3 g, hipStream_t st, const EntArgs& ea) {
-  typedef int (*fn_t)(int, int, int, unsigned, unsigned, unsigned, void*, const EntArgs*);
-  static const fn_t fns[9] = {vbmc_launch_ent_mfma_qs1, vbmc_launch_ent_mfma_qs2, vbmc_launch_ent_mfma_qs3,
-                              vbmc_launch_ent_mfma_qs4, vbmc_launch_ent_mfma_qs5, vbmc_launch_ent_mfma_qs6,
-                              vbmc_launch_ent_mfma_qs7, vbmc_launch_ent_mfma_qs8, vbmc_launch_ent_mfma_qs9};
-  if (qs < 1 || qs > 9) return false;
-  return fns[qs - 1](kt, grad ? 1 : 0, hv, g.x, g.y, g.z, (void*)st, &ea) == 0;
 }
 // workgroups of the chosen instantiation per compute unit (registers and LDS: hipOccupancyMaxActiveBlocksPerMultiprocessor), cached
 static int entropy_mfma_occupancy(int qs, int kt, int hv, bool grad, const EntArgs& ea) {
-  typedef int (*fn_t)(int, int, int, const EntArgs*);
-  static const fn_t fns[9] = {vbmc_occupancy_ent_mfma_qs1, vbmc_occupancy_ent_mfma_qs2, vbmc_occupancy_ent_mfma_qs3,
-                              vbmc_occupancy_ent_mfma_qs4, vbmc_occupancy_ent_mfma_qs5, vbmc_occupancy_ent_mfma_qs6,
-                              vbmc_occupancy_ent_mfma_qs7, vbmc_occupancy_ent_mfma_qs8, vbmc_occupancy_ent_mfma_qs9};
   if (qs < 1 || qs > 9) return -1;
   struct Key { int qs, kt, hv, grad, co, sparse, ldsk; };
   static std::vector<std::pair<Key, int>> cache;
@@ -452,44 +377,10 @@ static int entropy_mfma_occupancy(int qs, int kt, int hv, bool grad, const EntAr
   std::lock_guard<std::mutex> lock(mu);
   const Key k{qs, kt, hv, grad ? 1 : 0, ea.lj.rows > 0 ? 1 : 0, ea.cutoff > 0.0 ? 1 : 0, ea.K * (ea.D + ENTP_EXTRA)};
   for (const auto& c : cache)
-    if (c.first.qs == k.qs && c.first.kt == k.kt && c.first.hv == k.hv && c.first.grad == k.grad && c.first.co == k.co &&
-        c.first.sparse == k.sparse && c.first.ldsk == k.ldsk) return c.second;
-  const int nb = fns[qs - 1](kt, grad ? 1 : 0, hv, &ea);
+    if (!memcmp(&c.first, &k, sizeof(Key))) return c.second;
+  const int nb = ent_mfma_inst[qs - 1].occupancy(kt, grad ? 1 : 0, hv, &ea);
   cache.push_back({k, nb});
   return nb;
-}
-// K <= 64: one wave per (chunk, component, restart) with kt = ceil(K/16) k-tiles; larger mixtures split their components
-// over the hv = 2 or 4 waves of a workgroup, kt = ceil(ceil(K/hv)/16) <= 4: two waves up to K = 128, four up to K = 256.
-// VBMC_ENT_HV = 2 / 4 forces the split where both fit (A/B runs).  D <= 34 (qs <= 9).
-// hv + 16: every wave runs kt = Kh / 16 full k-tiles and its Kh mod 16 <= 4 remaining components (Kh = components per wave) as a
-// lane-layout TAIL instead of a k-tile of their own (entropy_mfma.h, TL = values per lane): one value for up to 4 components
-// (K = 17..20, 33..36, 49..52 on one wave, 66..72 and 98..104 on two, 130..144 and 194..208 on four), two for 5..8 where that
-// kernel keeps its registers (tail8_ok below).  VBMC_ENT_TAIL=0 keeps the padded k-tile (A/B runs);
-// the block-sparse mode (cutoff > 0) always does.
-static bool mfma_entropy_fits(int D, int K, double cutoff, int* qs_out, int* kt_out, int* hv_out) {
-  const int qs = (D + 2 + 3) / 4;
-  int hv = K <= 64 ? ent_hv_small(qs, K) : (K <= 128 ? ent_hv_mid(qs, K) : (K <= 256 ? 4 : 8));   // (round 5: eight waves for 256 < K <= 512, full k-tiles only)
-  if (K > 64 && K <= 128)
-    if (const char* f = getenv("VBMC_ENT_HV")) { const int v = atoi(f); if (v == 2 || v == 4) hv = v; }
-  if (K > 32 && K <= 64)
-    if (const char* f = getenv("VBMC_ENT_HV")) { const int v = atoi(f); if (v == 1 || v == 2) hv = v; }
-  int kt = (((K + hv - 1) / hv) + 15) / 16;
-  static const bool tail_on = [] { const char* e = getenv("VBMC_ENT_TAIL"); return !(e && !strcmp(e, "0")); }();
-  {
-    const int Kh = (K + hv - 1) / hv;      // components of the first waves (the last one may hold fewer: its tail lanes idle)
-    static const int tail_max = [] { const char* e = getenv("VBMC_ENT_TAIL"); return e ? atoi(e) : 2; }();   // 0 / 1 / 2 values per lane at most (A/B runs)
-    const int tl = (Kh % 16 + 3) / 4;         // tail values per lane that would be needed: 1 for 1..4 components, 2 for 5..8
-    // two values per lane pay except where that kernel runs out of registers (tools/tail_sweep.py: 57 shapes x tail limit 0 / 1 / 2)
-    const int ktf = Kh / 16, rem = Kh % 16;
-    const bool tail8_ok = ktf == 1 || (hv == 1 && ktf == 2 && (qs >= 5 || rem <= 6)) || (hv == 1 && ktf == 3 && qs <= 4) ||
-                          (hv > 1 && ktf == 2) || (hv > 1 && ktf == 3 && qs >= 5);
-    if (tail_on && hv != 8 && Kh > 16 && tl >= 1 && tl <= tail_max && (tl == 1 || (tl == 2 && tail8_ok)) && !(cutoff > 0.0) && !(hv > 1 && ktf < 2)) {
-      kt = ktf;
-      hv += 16 * tl;
-    }
-  }
-  *qs_out = qs; *kt_out = kt; *hv_out = hv;
-  return qs >= 1 && qs <= 9 && K >= 1 && K <= 512 && kt >= 1 && kt <= 4 && !(hv == 2 && kt < 2) && !(hv == 4 && kt < 2) && !(hv == 8 && kt < 3) && !(hv > 16 && kt > 3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -554,20 +445,14 @@ static vbmc_status ensure_tinv(vbmc_ctx* ctx, const vbmc_gp* gp, bool* have) {
   return VBMC_OK;
 }
 
-struct ElboPlan {
-  ElboDims dm{};
-  int compute_grad = 0, compute_var = 0, dt = 0;
+// Its LaunchShape part is what the launch decisions are made from, its LaunchChoice part their outcome (elbo_launch_plan.h).
+struct ElboPlan : LaunchShape, LaunchChoice {
+  int compute_var = 0, var_stride = 0, ncol = 1, no_jacobian = 0;
   double beta = 0.0;
-  bool mc = false, has_bnd = false, use_mfma = false, use_lane = false, vgrad = false, any_nochol = false, needX = false, fin_big = false, tri_gemm = false;
+  bool mc = false, has_bnd = false, vgrad = false, any_nochol = false, needX = false, fin_big = false, tri_gemm = false;
   double *d_finbig = nullptr, *d_gamma = nullptr;
-  int Mh = 0, C = 1, tpc = 1, ncol = 1, qs = 0, kt = 0, hv = 1, var_stride = 0;
-  int no_jacobian = 0;
-  int Rp = 0;                // the restarts the launch shapes are chosen for: R, or the undivided batch's (vbmc_elbo_args.plan_restarts)
-  int walk_tpw = 0, walk_nw = 0;   // > 0: the matrix-core entropy kernel WALKS (entropy_mfma.h): tiles per wave, waves of the launch
-  int co_c1 = 0, co_c2 = 0, co_tpc2 = 0;   // co_c2 > 0: two chunk classes (EntArgs: the role's workgroups take the second, shorter one)
   double* d_dvs = nullptr;   // per-hyper-sample variance gradient block (dvarG_s), pooled for the call
-  bool lj_records = false;   // the caller reads per-hyper-sample log-joint records (separate_K, G_s / varG_s, the variance kernels)
-  int r0 = 0, rstride = 1;   // device-RNG key of restart r: r0 + r * rstride (vbmc_elbo_args.restart_offset / restart_stride)
+  int r0 = 0;                // device-RNG key of restart r: r0 + r * rstride (vbmc_elbo_args.restart_offset / restart_stride)
   size_t n_theta = 0, n_up = 0, out_n = 0, ent_lds = 0, tlds = 0, n_sepk = 0;
   double *d_theta = nullptr, *d_fix = nullptr, *d_delta2 = nullptr, *d_bnd = nullptr;
   double *d_ljbar = nullptr;
@@ -576,47 +461,8 @@ struct ElboPlan {
   const double* d_eps = nullptr;
   double* out_direct = nullptr;   // the pinned result block itself: the finalize kernel writes the records there (small pipelined passes)
   long long eps_stride_r = 0;
-  double TolCon = 0.0, WeightThreshold = 0.0, WeightPenalty = 0.0, cutoff = 0.0;
+  double TolCon = 0.0, WeightThreshold = 0.0, WeightPenalty = 0.0;
 };
-
-// Splits of the training set per cell group of the log-joint role: per-workgroup set-up (exp table, tau / log tau) against the length of the
-// dependent loop over the training set.  Single chain at the headline shape (260 cell groups, 25 slabs of 16 points), us per Adam
-// iteration: 1 split 46.6, 2: 41.1, 3: 41.2, 4: 43.0, 6: 45.4, 8: 52.2 (more workgroups than wave slots) -> about 640 role workgroups per restart
-static int lj_co_nsplit(const vbmc_ctx* ctx, const ElboPlan& P) {
-  const int K = P.dm.K, S = P.dm.S, R = P.dm.R;
-  const long long cells = (long long)((K + 3) / 4) * S;   // per restart: a restart's bits do not depend on the batch it is in
-  const int slabs = (P.dm.N + 15) / 16;
-  int ns = (int)std::max<long long>(1, std::min<long long>(std::min(LJ_CO_SPLIT, slabs), (640 + cells / 2) / cells));
-  // (round 5) a BATCH wide enough that the record buffer holds one record per hyper-sample (elbo_plan: ljrec): one role workgroup per
-  // cell group -- the restarts supply the parallelism the splits supply to a single chain
-  if ((long long)S * std::min(R, P.Rp) >= ctx->num_cu / 2) ns = 1;
-  if (P.use_lane) ns = 1;      // (the lane kernel's role walks the LDS-staged training set whole)
-  return ns;
-}
-
-// Does the expected log joint run as a role of the MFMA entropy launch (entropy_mfma.h CO = true; see elbo_enqueue)?  The part of the
-// answer that elbo_plan needs too (the chunk model asks for the occupancy of the kernel that will run).
-static bool lj_co_shape(const vbmc_ctx* ctx, const ElboPlan& P) {
-  const char* coe = getenv("VBMC_LJ_CO");       // read per call, as VBMC_LJ_KERNEL is: an in-process toggle takes effect on the next pass
-  const bool co_off = coe && !strcmp(coe, "0");
-  const char* ljf = getenv("VBMC_LJ_KERNEL");
-  const int Rp = P.Rp > 0 ? P.Rp : P.dm.R;        // (plan_restarts: the undivided batch decides)
-  const long long SR = (long long)P.dm.S * Rp;
-  const bool lj_force_mfma = ljf && !strcmp(ljf, "mfma");
-  // ... and only where the ENTROPY launch is small too (K R waves per sample chunk: a single chain has 50, a batch of restarts over one
-  // hyper-sample -- or an entropy-only evaluation, whose surrogate is a one-point stand-in -- can fill the chip by itself and wants the
-  // kernels built for occupancy, not these)
-  const long long KR = (long long)P.dm.K * (P.Rp > P.dm.R ? P.Rp : (long long)P.dm.R * P.rstride);
-  const double lim_sr = 0.5, lim_kr = 2.0;     // the two width limits in units of the chip's compute units (other values measured in round 5: profiles/r05_experiments.md section 8)
-  return !co_off && !lj_force_mfma && P.mc && P.use_mfma && (P.hv & 15) == 1 && P.qs <= 8 && !(P.cutoff > 0.0) && P.compute_grad &&
-         !P.lj_records && SR < lim_sr * ctx->num_cu && (P.Rp > P.dm.R || SR * P.rstride < lim_sr * ctx->num_cu) &&   // (the undivided batch's choice when the restarts are dealt over devices)
-         KR < lim_kr * ctx->num_cu && P.dm.N > 1 &&
-         // (round 4) ... and small in WORK, not only in width: with many sample tiles per wave (Ns = 1e4 per component: 313 tiles per
-         // (component, restart)) the role's workgroups delay an entropy launch that fills the chip by itself -- R = 4 at the headline
-         // shape: 0.242 ms with the role, 0.221 without; equal at R = 2 -- while at the optimiser's own sample counts (Ns = 28..400)
-         // the role wins by 13-24 % for R <= 4.  The bound: sixteen sample tiles per resident wave slot.
-         KR * ((P.Mh + 15) / 16) <= 16LL * 8 * ctx->num_cu;
-}
 
 // dynamic LDS of k_var_final: reduction scratch, two S-vectors, five T-vectors (only with a gradient), two K-vectors
 #define VAR_FINAL_LDS(S_, K_, Tg_) ((VARFIN_THREADS + 2 * (size_t)(S_) + 5 * (size_t)(Tg_) + 2 * (size_t)(K_) + 8) * sizeof(double))
@@ -706,8 +552,8 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
   // to be packed by a kernel (k_pack_sepk)
   P.n_sepk = (a->separate_K && (a->I_sk || a->J_sjk)) ? (size_t)S * K * R * (1 + (size_t)K) : 0;
   if (P.n_sepk * sizeof(double) > COPY_KERNEL_MAX_BYTES * 4) P.n_sepk = 0;
-  { vbmc_status s_ = ensure_pin(ctx, (n_up + P.out_n + (size_t)S * K * R + P.n_sepk) * sizeof(double)); if (s_) return s_; }
-  { vbmc_status s_ = ensure(ctx, ctx->theta, n_up * sizeof(double)); if (s_) return s_; }
+  VB_TRY(ensure_pin(ctx, (n_up + P.out_n + (size_t)S * K * R + P.n_sepk) * sizeof(double)));
+  VB_TRY(ensure(ctx, ctx->theta, n_up * sizeof(double)));
   double* hp = (double*)ctx->pin;
   if (n_theta) memcpy(hp, a->theta, n_theta * sizeof(double));
   double* hfix = hp + n_theta;
@@ -742,21 +588,21 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
   P.cutoff = a->sparse_cutoff > 0.0 ? a->sparse_cutoff : 0.0;
 
   // ---- scratch
-  { vbmc_status s_ = ensure(ctx, ctx->prep, (size_t)R * VL.stride() * sizeof(double)); if (s_) return s_; }
-  { vbmc_status s_ = ensure(ctx, ctx->entp, (size_t)R * K * (D + ENTP_EXTRA) * sizeof(double)); if (s_) return s_; }
+  VB_TRY(ensure(ctx, ctx->prep, (size_t)R * VL.stride() * sizeof(double)));
+  VB_TRY(ensure(ctx, ctx->entp, (size_t)R * K * (D + ENTP_EXTRA) * sizeof(double)));
   const int LJS = 2 * D + 2;
-  // (LJ_CO_SPLIT records per hyper-sample where the log joint may run as a role of the entropy launch: small grids only, see elbo_enqueue)
   // (also set when the caller asks for the numbers a SHARDED evaluation gives -- chunk_world: the sharded path adds the log-joint
   // records per hyper-sample, so the unsharded evaluation it is compared with bit for bit must too)
   P.lj_records = a->separate_K || a->G_s || a->varG_s || a->dG_s || compute_var != 0 || chunk_world > 0 || a->chunk_world > 1;
-  const size_t ljrec = (size_t)R * S * K * LJS * (((long long)S * std::min(R, P.Rp) < ctx->num_cu / 2 && !P.lj_records) ? LJ_CO_SPLIT : 1);
-  { vbmc_status s_ = ensure(ctx, ctx->ljpart, (ljrec + (size_t)R * K * LJS) * sizeof(double)); if (s_) return s_; }
-  { vbmc_status s_ = ensure(ctx, ctx->out, P.out_n * sizeof(double)); if (s_) return s_; }
+  // (LJ_CO_SPLIT records per hyper-sample where the log joint may run as a role of the entropy launch: small grids only)
+  const size_t ljrec = (size_t)R * S * K * LJS * ((lj_records_split(S, R, P.Rp, ctx->num_cu) && !P.lj_records) ? LJ_CO_SPLIT : 1);
+  VB_TRY(ensure(ctx, ctx->ljpart, (ljrec + (size_t)R * K * LJS) * sizeof(double)));
+  VB_TRY(ensure(ctx, ctx->out, P.out_n * sizeof(double)));
   {
     const size_t nbig = P.fin_big ? (size_t)R * (3 * (size_t)T + (size_t)D * K) : 0;
     const size_t ngam = (!(a->Ns > 0) && K > 128) ? (size_t)R * K * K : 0;      // entlb's K x K table beyond the LDS
     if (nbig + ngam) {
-      vbmc_status s_ = ensure(ctx, ctx->bnd, (nbig + ngam) * sizeof(double)); if (s_) return s_;
+      VB_TRY(ensure(ctx, ctx->bnd, (nbig + ngam) * sizeof(double)));
       P.d_finbig = nbig ? (double*)ctx->bnd.p : nullptr;
       P.d_gamma = ngam ? (double*)ctx->bnd.p + nbig : nullptr;
     }
@@ -767,109 +613,22 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
   P.d_ljbar = P.d_lj + ljrec;
   P.d_out = (double*)ctx->out.p;
 
+  // ---- every launch decision of the pass (elbo_launch_plan.h); `sharded`: chunk_world > 0, the calls enqueued with ShardSpec.mode != 0
+  // (NOT a->chunk_world > 1: that call gives a sharded evaluation's numbers from one unsharded pass)
+  P.plan_restarts = a->plan_restarts; P.eps_mode = a->eps_mode; P.pipelined = pipelined;
+  P.cw = chunk_world > 0 ? chunk_world : (a->chunk_world > 1 ? a->chunk_world : 1);   // sharded over cw devices
+  const LaunchDevice dev{ctx->num_cu, ctx->prof_alone, ctx, entropy_mfma_occupancy, entropy_lane_occupancy};
+  if (!plan_launch(P, dev, chunk_world > 0, read_launch_switches(), P))
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "K = %d, D = %d: the eight-wave entropy kernel needs more than the 160 KiB of LDS", K, D);
   if (P.mc) {
-    const char* force = getenv("VBMC_ENT_KERNEL");  // "valu" (A/B testing); default: the MFMA kernel when it fits
-    P.use_mfma = mfma_entropy_fits(D, K, P.cutoff, &P.qs, &P.kt, &P.hv);
-    if (force && !strcmp(force, "valu")) P.use_mfma = false;
-    // small mixtures: the lane-per-sample kernel (entropy_lane.h).  VBMC_ENT_KERNEL=mfma keeps the matrix-core kernel there (A/B runs, tests)
-    P.use_lane = lane_entropy_fits(D, K, P.cutoff) && !(force && (!strcmp(force, "valu") || !strcmp(force, "mfma"))) &&
-                 ((long long)K * P.Rp * ((Mh + 63) / 64) >= ENT_LANE_MIN_TILES || (force && !strcmp(force, "lane")));
-    if (P.use_lane) P.use_mfma = false;
-    const int tile_sz = P.use_lane ? 64 : (P.use_mfma ? 16 : 32);          // base samples per tile
-    const int ntile = (Mh + tile_sz - 1) / tile_sz;
-    // chunks per (component, restart): minimise  ceil(waves / resident slots) * (setup + tiles per wave),
-    // i.e. whole rounds of resident waves, with the per-wave setup worth ~1.5 tiles
-    {
-      const int cw = chunk_world > 0 ? chunk_world : (a->chunk_world > 1 ? a->chunk_world : 1);   // sharded over cw devices
-      // resident waves: what the chosen instantiation really holds per compute unit (registers AND LDS; round 3 -- rounds 1-2 assumed two
-      // waves per SIMD for every MFMA kernel, which under-filled the chip for the small kernels that hold three or four)
-      int waves_per_cu = P.use_mfma ? 8 : 5;
-      if (P.use_mfma) {
-        EntArgs q{};
-        q.D = D; q.K = K; q.cutoff = P.cutoff; q.lj.rows = lj_co_shape(ctx, P) ? 1 : 0;
-        const int nb = entropy_mfma_occupancy(P.qs, P.kt, P.hv, compute_grad != 0, q);
-        if (nb > 0) waves_per_cu = nb * (P.hv & 15);
-        // eight-wave workgroups (K > 256): the parameter block, the parked exponents of eight waves and the PV exchange can exceed the
-        // 160 KB of a compute unit at large D -- then no workgroup fits and the shape is refused below (the VALU kernel's LDS does not
-        // hold K > 256 either)
-        if (nb <= 0 && (P.hv & 15) == 8) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "K = %d, D = %d: the eight-wave entropy kernel needs more than the 160 KiB of LDS", K, D);
-        // wide operands (D >= 15): the kernels that COULD hold more than eight waves (one k-tile) do not gain from shorter chunks -- their
-        // per-wave set-up grows with D (D = 20, K = 8: 0.27 -> 0.37 ms with twelve assumed) -- while the ones that hold fewer (LDS: seven)
-        // are where the correction pays (D = 28, K = 40: 1.36 -> 1.10 ms): profiles/r03_shape_sweep.md
-        if (P.qs >= 5 && waves_per_cu > 8) waves_per_cu = 8;
-      }
-      if (P.use_lane) {
-        const int nb = entropy_lane_occupancy(D, K, compute_grad != 0);
-        waves_per_cu = ENT_LANE_WAVES_HOST * (nb > 0 ? nb : 2);
-      }
-      const long long slots = (long long)ctx->num_cu * waves_per_cu * cw;
-      const long long kr = (long long)K * P.Rp * (P.use_mfma ? (P.hv & 15) : 1);   // waves per chunk index (hv + 16 TL: with a component tail); Rp: R, or the undivided batch's (plan_restarts)
-      const double setup = P.use_lane ? 1.0 : 1.5;   // (lane kernel: a tile of 64 samples is ~1.5 us, the set-up about that)  measured: C = 7 (45 tiles per wave) beats C = 5 (63) by 1 % at the headline shape once the setup loads are batched
-      double best = 1e300;
-      int bestC = 1;
-      for (int c = 1; c <= ntile; ++c) {
-        const int tpc = (ntile + c - 1) / c;
-        const int ceff = (ntile + tpc - 1) / tpc;
-        const long long rounds = (kr * ceff + slots - 1) / slots;
-        const double cost = (double)rounds * (setup + tpc);
-        if (cost < best - 1e-9) { best = cost; bestC = ceff; }
-        if (tpc == 1) break;
-      }
-      if (const char* fc = getenv("VBMC_ENT_CHUNKS")) {   // A/B testing of the chunk model
-        const int c = atoi(fc);
-        if (c >= 1 && c <= ntile) bestC = c;
-      }
-      if (getenv("VBMC_DEBUG_OCC")) fprintf(stderr, "chunks: D %d K %d R %d qs %d kt %d hv %d waves/CU %d slots %lld kr %lld ntile %d -> C %d\n", D, K, R, P.qs, P.kt, P.hv, waves_per_cu, slots, kr, ntile, bestC);
-      P.tpc = (ntile + bestC - 1) / bestC;
-      P.C = (ntile + P.tpc - 1) / P.tpc;
-      // Two chunk classes where the launch carries the log-joint role (one or two restarts at Ns = 1e4: ~2000 entropy waves + 500-1000 role
-      // waves on 2048 slots -- the role's waves went first and a quarter of the entropy waves entered a role late): the role's workgroups go
-      // on to a chunk of the entropy that is a role's length (~4 tiles: 18 us) shorter, every wave of the launch is resident from the
-      // start and all leave together.  Not where the chunking must be another launch's (sharded, plan_restarts) or is forced.
-      if (P.use_mfma && (P.hv & 15) == 1 && cw == 1 && chunk_world == 0 && a->plan_restarts == 0 && !getenv("VBMC_ENT_CHUNKS") && compute_grad &&
-          lj_co_shape(ctx, P)) {
-        const int role_per_r = ((K + 3) / 4) * S * lj_co_nsplit(ctx, P);
-        const long long waves0 = slots - (long long)role_per_r * R;
-        const int TROLE = 4;                                   // a role in tiles (role + its later set-up against 4.5 us per tile of a wave that shares its SIMD)
-        const int c1 = (int)(waves0 / ((long long)K * R)), c2max = role_per_r / K;
-        if (c1 >= 1 && c2max >= 1 && ntile > TROLE * c1 + c1 + c2max) {
-          const int tpc2 = (ntile - TROLE * c1 + c1 + c2max - 1) / (c1 + c2max);
-          const int tpc1 = (ntile - c2max * tpc2 + c1 - 1) / c1;
-          const int rest = ntile - c1 * tpc1;
-          if (tpc2 >= 1 && tpc1 > tpc2 && rest > 0) {
-            P.co_c1 = c1; P.co_tpc2 = tpc2; P.co_c2 = (rest + tpc2 - 1) / tpc2;
-            P.tpc = tpc1; P.C = P.co_c1 + P.co_c2;
-            if (getenv("VBMC_DEBUG_OCC")) fprintf(stderr, "two chunk classes: %d x %d tiles + %d x %d tiles (role workgroups per restart %d)\n", c1, tpc1, P.co_c2, tpc2, role_per_r);
-          }
-        }
-      }
-      // The walk (entropy_mfma.h): once the chunk grid would hand every wave slot two or more waves, ONE wave per slot walks its share of
-      // all the (restart, component) pairs' tiles instead -- a set-up per (wave, pair) instead of per chunk.  The device-RNG gradient kernels of
-      // single-wave workgroups at D <= 14, K <= 56 (the instantiations that take the loop without spilling); not where
-      // the bits must be those of another launch shape (sharded evaluation, plan_restarts) or the launch carries the log-joint role.
-      // Not for the passes of a pipeline either (vbmc_elbo_submit): there the short kernels of the NEXT pass take the slots the chunk grid's
-      // waves free as they finish, and the step is the sum of its kernels' work with no gap at all (2.19 ms at the headline shape) -- a launch
-      // whose waves all end together leaves them nothing until it is over (2.24); a blocking call or an optimiser iteration has no next pass
-      // to interleave (2.29 -> 2.25 ms).  VBMC_ENT_WALK=0: the chunk grid (A/B runs, tests).
-      const char* walk_env = getenv("VBMC_ENT_WALK");
-      const bool walk_off = walk_env && !strcmp(walk_env, "0");
-      const long long total = (long long)K * R * ntile;
-      if (P.use_mfma && (P.hv & 15) == 1 && P.qs <= 4 && P.kt <= 3 && a->eps_mode == 0 && compute_grad && !(P.cutoff > 0.0) && cw == 1 && chunk_world == 0 && !pipelined && a->plan_restarts == 0 && !walk_off && !getenv("VBMC_ENT_CHUNKS") &&
-          kr * P.C >= 2 * slots && total < (1LL << 31) && !lj_co_shape(ctx, P)) {
-        P.walk_tpw = (int)((total + slots - 1) / slots);
-        P.walk_nw = (int)((total + P.walk_tpw - 1) / P.walk_tpw);
-        P.C = ent_walk_max_slots(ntile, P.walk_tpw);
-        if (getenv("VBMC_DEBUG_OCC")) fprintf(stderr, "walk: %d waves x %d tiles, %d record slots per pair\n", P.walk_nw, P.walk_tpw, P.C);
-      }
-    }
     P.ncol = compute_grad ? (2 + 2 * D + K) : 1;
-    { vbmc_status s_ = ensure(ctx, ctx->entpart, ((size_t)R * K * P.C * P.ncol + (size_t)R * K * P.ncol) * sizeof(double)); if (s_) return s_; }
+    VB_TRY(ensure(ctx, ctx->entpart, ((size_t)R * K * P.C * P.ncol + (size_t)R * K * P.ncol) * sizeof(double)));
     P.d_part = (double*)ctx->entpart.p;
     P.d_red = P.d_part + (size_t)R * K * P.C * P.ncol;
     const size_t eps_block = (size_t)D * Mh * K;
     if (a->eps_mode == 1) {
       const size_t n_eps = eps_block * (a->eps_shared ? 1 : (size_t)R);
-      { vbmc_status s_ = ensure(ctx, ctx->eps, n_eps * sizeof(double)); if (s_) return s_; }
+      VB_TRY(ensure(ctx, ctx->eps, n_eps * sizeof(double)));
       HIP_TRY(ctx, hipMemcpyAsync(ctx->eps.p, a->eps, n_eps * sizeof(double), hipMemcpyHostToDevice, st));
       P.d_eps = (const double*)ctx->eps.p; P.eps_stride_r = a->eps_shared ? 0 : (long long)eps_block;
     } else if (a->eps_mode == 2) {
@@ -881,7 +640,7 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
     }
   } else {
     const size_t ebs = 1 + (size_t)D * K + 2 * K + D;
-    { vbmc_status s_ = ensure(ctx, ctx->entpart, (size_t)R * ebs * sizeof(double)); if (s_) return s_; }
+    VB_TRY(ensure(ctx, ctx->entpart, (size_t)R * ebs * sizeof(double)));
     P.d_part = (double*)ctx->entpart.p;
   }
   if (compute_var != 0) {
@@ -890,7 +649,7 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
     P.vgrad = compute_grad && compute_var == 2;
     for (int s = 0; s < S; ++s) P.any_nochol |= (gp->Lchol[s] == 0);
     const size_t nz = (size_t)R * S * K * N;
-    { vbmc_status s_ = ensure(ctx, ctx->zbuf, nz * sizeof(double)); if (s_) return s_; }
+    VB_TRY(ensure(ctx, ctx->zbuf, nz * sizeof(double)));
     const size_t nJ = (size_t)R * S * K * K, nvg = (size_t)R * S * K * (2 * D + 1), nvo = (size_t)R * P.var_stride;
     // full variance without its gradient (eval_fullelcbo): V = inv(L') Z as a product with the explicit inverse (k_tri_gemm, out of
     // place into the X block) instead of the substitution
@@ -899,14 +658,13 @@ static vbmc_status elbo_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_a
       for (int s = 0; s < S; ++s) any_chol |= (gp->Lchol[s] != 0);
       if (compute_var == 1 && any_chol) {
         bool have = false;
-        vbmc_status s_ = ensure_tinv(ctx, gp, &have);
-        if (s_) return s_;
+        VB_TRY(ensure_tinv(ctx, gp, &have));
         P.tri_gemm = have;
       }
     }
     P.needX = P.vgrad || P.any_nochol || P.tri_gemm;
     const size_t nvs = P.vgrad ? (size_t)R * S * 2 * (size_t)dm.T : 0;
-    { vbmc_status s_ = ensure(ctx, ctx->varbuf, ((P.needX ? nz : 0) + nJ + nvg + nvo + nvs) * sizeof(double)); if (s_) return s_; }
+    VB_TRY(ensure(ctx, ctx->varbuf, ((P.needX ? nz : 0) + nJ + nvg + nvo + nvs) * sizeof(double)));
     P.d_Z = (double*)ctx->zbuf.p;
     P.d_X = (double*)ctx->varbuf.p;
     P.d_J = P.d_X + (P.needX ? nz : 0);
@@ -999,53 +757,25 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
     LAUNCH_CHECK(ctx, "k_prep");
   }
 
-  // ---- expected log joint: enqueued on `ls` -- the context's stream, or the auxiliary one beside the entropy kernel
-  // ... and so does a pass on a slot stream: the pass on the other slot stream is what fills in around its entropy kernel, and a log
-  // joint forked off there is the last to be let onto the chip (profiles/r04_experiments.md section 11)
-  const bool lane_role_possible = P.use_lane && P.compute_grad && !P.lj_records && dm.N > 1 && lane_role_fits(D, K, dm.N, S);     // (decided below: co_lane)
-  const bool fork = sh.mode == 0 && P.mc && (long long)S * R >= ctx->num_cu / 2 && !ctx->prof_alone && !lane_role_possible && ctx_aux(ctx);   // a single chain: the fork / join events cost more than they hide
-  // value + gradient: moments on the matrix cores (k_logjoint_mfma); value only: the VALU kernel.  VBMC_LJ_KERNEL=valu / mfma forces one of them.
-  const char* ljf = getenv("VBMC_LJ_KERNEL");
-  // one workgroup per (hyper-sample, restart): needs enough of them to fill the chip, otherwise (a single chain) the finer-grained VALU
-  // kernel has the lower latency
-  const bool lj_force = ljf && !strcmp(ljf, "mfma");   // tests: exercise the MFMA kernel on small grids too
-  // (round 4: from S R = one workgroup per compute unit on -- below, the finer-grained VALU kernel is the faster one: R = 8 at the headline
-  // shape, 160 (hyper-sample, restart) workgroups: 56 us against 34 alone, the step 0.394 -> 0.360 ms; equal at R = 16, 142 against 174 us at R = 64)
-  // (round 6) the lane-per-sample kernel of small mixtures carries the role at every batch width: a pass of that class is ONE chip-wide launch
-  const char* coe = getenv("VBMC_LJ_CO");
-  const bool co_off_env = coe && !strcmp(coe, "0");
-  const bool co_lane = lane_role_possible && sh.mode == 0 && !lj_force && !co_off_env && !(ljf && !strcmp(ljf, "valu"));
-  const bool co_shape = co_lane || (sh.mode == 0 && !fork && !lj_force && lj_co_shape(ctx, P));      // (the role takes precedence over the matrix-core kernel where its limits admit the batch)
-  // (round 5) ... and enough WAVES in each: with K <= 16 a workgroup of the matrix-core kernel is a single wave walking the whole training
-  // set, and the VALU kernel's four waves per cell group are faster until the batch is several chips wide (BASELINE configs[1], K = 10,
-  // S R = 512: 28.3 us against 19.9)
-  const bool lj_wide = K > 16 || (long long)S * P.Rp >= 4LL * ctx->num_cu;
-  // (round 6: value-only passes too -- the sieve's 250 candidates -- through the kernel's GRAD = false form, once the batch is four chips wide)
-  const bool lj_mfma = !co_shape && (P.compute_grad || (long long)S * P.Rp >= 4LL * ctx->num_cu) && K <= 256 && (lj_force || ((long long)S * P.Rp >= ctx->num_cu && lj_wide)) && !(ljf && !strcmp(ljf, "valu"));
-  // Small grids (a single chain, a handful of restarts): the VALU log joint runs as a ROLE of the entropy launch (single-wave
-  // workgroups ahead of the entropy ones, entropy_mfma.h CO = true) -- two dependent-chain-bound kernels side by side instead of
-  // one after the other, one launch less.  Its records are per (hyper-sample, split of the training set); the reduction over
-  // hyper-samples adds the splits.  VBMC_LJ_CO=0 keeps the separate launch (A/B runs, tests).
-  const bool co = co_shape && !lj_mfma;
+  // ---- expected log joint: enqueued on `ls` -- the context's stream, or the auxiliary one beside the entropy kernel -- unless it runs as a
+  // role of the entropy launch.  Which of these, and which kernel, is the plan's decision (elbo_launch_plan.h: plan_launch).
+  const bool fork = P.fork, co = P.role();
   auto enqueue_logjoint = [&](hipStream_t ls) -> vbmc_status {
     if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ls));
-    if (!co) {
-      // VALU kernel: four waves per cell (training set split, lower latency) while the grid is small, one wave per cell (no
-      // replicated per-wave setup) once there are enough cells to fill the chip several times over
-      const bool lj_split = dm.N > 64 && (long long)((K + 3) / 4) * S * P.Rp < 8LL * ctx->num_cu;
+    if (!co && ns > 0) {
+      const bool lj_mfma = P.lj_form == VBMC_LJFORM_MFMA_GRAD || P.lj_form == VBMC_LJFORM_MFMA_VALUE;
+      ctx->last_lj_form = P.lj_form;
       DISPATCH_DT(dt, {
-        constexpr int NCT = (2 * DT + 1 + 15) / 16;
         const int nw = (K + 15) / 16;
-        const size_t mom_lds = LJ_MFMA_DYN_LDS(DT, nw);   // feature rows / moment exchange; large K x D falls back to the VALU kernel
         // the kernels reach hyper-sample s only through alpha + s N and gpc + s GPC_STRIDE and use dm.S as the record
-        // stride: a slice [s0, s0 + ns) is the same launch with shifted pointers (the variant choice above uses the FULL S,
+        // stride: a slice [s0, s0 + ns) is the same launch with shifted pointers (the plan chose the variant from the FULL S,
         // so a sharded evaluation runs the kernel the unsharded one would)
         ElboDims dml = dm;
         dml.S = sh.mode == 1 ? perS : S;
         const double* al = gp->alpha + (size_t)s0 * dm.N;
         const double* gc = gp->gpc + (size_t)s0 * GPC_STRIDE(D);
-        if (ns <= 0) {
-        } else if (lj_mfma && mom_lds + LJ_MFMA_STATIC_LDS <= 64 * 1024) {
+        if (lj_mfma) {
+          const size_t mom_lds = LJ_MFMA_DYN_LDS(DT, nw);   // feature rows / moment exchange
           if (P.compute_grad)
             hipLaunchKernelGGL((k_logjoint_mfma<DT, true>), dim3(ns, R), dim3(WAVE * nw), mom_lds, ls, dml, P.d_vpd,
                                gp->X, gp->d_meanX, al, gc, P.d_delta2, lj_out);
@@ -1053,10 +783,8 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
             hipLaunchKernelGGL((k_logjoint_mfma<DT, false>), dim3(ns, R), dim3(WAVE * nw), mom_lds, ls, dml, P.d_vpd,
                                gp->X, gp->d_meanX, al, gc, P.d_delta2, lj_out);
           LAUNCH_CHECK(ctx, "k_logjoint_mfma");
-          ctx->last_lj_form = P.compute_grad ? VBMC_LJFORM_MFMA_GRAD : VBMC_LJFORM_MFMA_VALUE;
         } else {
-          ctx->last_lj_form = lj_split ? VBMC_LJFORM_VALU_SPLIT : VBMC_LJFORM_VALU_WAVE;
-          hipLaunchKernelGGL((k_logjoint<DT>), dim3((K + 3) / 4, ns, R), dim3(lj_split ? WAVE * LJ_MAXW : WAVE), 0, ls, dml, P.d_vpd, gp->X, al, gc,
+          hipLaunchKernelGGL((k_logjoint<DT>), dim3((K + 3) / 4, ns, R), dim3(P.lj_split ? WAVE * LJ_MAXW : WAVE), 0, ls, dml, P.d_vpd, gp->X, al, gc,
                              P.d_delta2, lj_out, P.compute_grad);
           LAUNCH_CHECK(ctx, "k_logjoint");
         }
@@ -1073,8 +801,7 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
   } else if (sh.mode != 2) {
-    vbmc_status s_ = enqueue_logjoint(st);
-    if (s_) return s_;
+    VB_TRY(enqueue_logjoint(st));
   }
   if (sh.mode == 2) {   // the gathered records of all ranks -> the unsharded layouts
     const size_t blk = shard_doubles(P, sh.world), ljn = shard_lj_doubles(P, sh.world);
@@ -1097,28 +824,18 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
     ea.eps = P.d_eps; ea.eps_stride_r = P.eps_stride_r; ea.cutoff = P.cutoff; ea.r0 = P.r0; ea.rstride = P.rstride;
     ea.prio = 1;   // progress-ordered wave priorities (entropy_mfma.h)
     ea.co_c1 = P.co_c1; ea.co_c2 = P.co_c2; ea.co_tpc2 = P.co_tpc2;
-    const bool walk = P.walk_tpw > 0;
-    if (walk && (sh.mode != 0 || co)) return set_err(ctx, VBMC_ERR_INVALID, "internal: the walking entropy launch was planned for a sharded / role-carrying pass");
+    const bool walk = P.walk_tpw > 0;      // (never with a role or a shard: plan_launch)
     if (walk) { ea.walk_tpw = P.walk_tpw; ea.walk_R = R; }
-    int co_rows = 0;
     if (co) {
       LjCo& lc = ea.lj;
-      lc.nsplit = lj_co_nsplit(ctx, P);
-      lc.nwg = ((K + 3) / 4) * S * lc.nsplit;
-      if (P.use_lane) {      // the role is dealt over the entropy waves themselves (entropy_lane.h): no rows of its own
-        lc.rows = co_rows = 0;
-      } else {
-        // (two chunk classes: the grid's x extent is the first class, the role's workgroups -- and as many more as the second class needs -- follow in rows)
-        const int gx = P.co_c2 > 0 ? P.co_c1 : nc;
-        lc.rows = co_rows = (std::max(lc.nwg, P.co_c2 > 0 ? K * P.co_c2 : 0) + gx - 1) / gx;
-      }
+      lc.nsplit = P.co_nsplit; lc.nwg = P.co_nwg; lc.rows = P.co_rows;
       lc.want_grad = P.compute_grad;
       lc.dm = dm; lc.X = gp->X; lc.alpha = gp->alpha; lc.gpc = gp->gpc; lc.delta2 = P.d_delta2; lc.lj = P.d_lj;
     }
     if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
     if (sh.mode != 2 && nc > 0) {
-      ctx->last_ent_form = P.use_lane ? VBMC_ENTFORM_LANE : (P.use_mfma ? VBMC_ENTFORM_MFMA : VBMC_ENTFORM_VALU);
-      if (co) ctx->last_lj_form = P.use_lane ? VBMC_LJFORM_ROLE_LANE : VBMC_LJFORM_ROLE_MFMA;
+      ctx->last_ent_form = P.ent_form;
+      if (co) ctx->last_lj_form = P.lj_form;
     }
     if (sh.mode == 2 || nc <= 0) {
     } else if (P.use_lane) {
@@ -1127,16 +844,16 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
       // group (a single chain has ten entropy waves and twenty-four cell groups: two groups behind each other on a wave were most of its launch)
       int gx = (K * nc + ENT_LANE_WAVES_HOST - 1) / ENT_LANE_WAVES_HOST;
       if (co) gx = std::max(gx, (ea.lj.nwg + ENT_LANE_WAVES_HOST - 1) / ENT_LANE_WAVES_HOST);
-      bool ok = launch_entropy_lane(D, K, P.compute_grad != 0, dim3(gx, 1 + co_rows, R), st, ea);
-      if (!ok) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "no lane entropy kernel for D = %d, K = %d", D, K);
+      if (ent_lane_inst[(D + 1) / 2 - 1].launch(2 * ((K + 1) / 2), P.compute_grad, gx, 1 + P.co_rows, R, (void*)st, &ea) != 0)
+        return set_err(ctx, VBMC_ERR_UNSUPPORTED, "no lane entropy kernel for D = %d, K = %d", D, K);
     } else if (P.use_mfma) {
-      bool ok = launch_entropy_mfma(P.qs, P.kt, P.hv, P.compute_grad != 0, walk ? dim3(P.walk_nw, 1, 1) : dim3((co && P.co_c2 > 0) ? P.co_c1 : nc, K + co_rows, R), st, ea);
-      if (!ok) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "no MFMA entropy kernel for D = %d", D);
+      const dim3 g = walk ? dim3(P.walk_nw, 1, 1) : dim3((co && P.co_c2 > 0) ? P.co_c1 : nc, K + P.co_rows, R);
+      if (P.qs < 1 || P.qs > 9 || ent_mfma_inst[P.qs - 1].launch(P.kt, P.compute_grad, P.hv, g.x, g.y, g.z, (void*)st, &ea) != 0)
+        return set_err(ctx, VBMC_ERR_UNSUPPORTED, "no MFMA entropy kernel for D = %d", D);
     } else {
-      const size_t lds = P.ent_lds;
       DISPATCH_DT(dt, {
-        HIP_TRY(ctx, set_entropy_lds<DT>(P.compute_grad != 0, lds));
-        launch_entropy<DT>(P.compute_grad != 0, dim3(nc, K, R), lds, st, ea);
+        HIP_TRY(ctx, set_entropy_lds<DT>(P.compute_grad != 0, P.ent_lds));
+        launch_entropy<DT>(P.compute_grad != 0, dim3(nc, K, R), P.ent_lds, st, ea);
       });
     }
     LAUNCH_CHECK(ctx, "the entropy kernel");
@@ -1158,16 +875,13 @@ static vbmc_status elbo_enqueue(vbmc_ctx* ctx, const vbmc_gp* gp, const ElboPlan
       HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_entlb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_entlb, dim3(R), dim3(256), lds, st, dm, P.d_vpd, P.d_part, P.compute_grad, P.d_gamma);
     LAUNCH_CHECK(ctx, "k_entlb");
-    ctx->last_ent_form = VBMC_ENTFORM_LB;
+    ctx->last_ent_form = P.ent_form;
     fa.entpart = nullptr; fa.entlb = P.d_part;
   }
 
   if (fork) {   // the entropy kernel is already queued on the main stream: the log joint fills in around it
-    {
-      vbmc_status s_ = enqueue_logjoint(ctx->aux);
-      if (s_) return s_;
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-    }
+    VB_TRY(enqueue_logjoint(ctx->aux));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
     HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
   }
 
@@ -1262,9 +976,7 @@ static vbmc_status null_gp_for(vbmc_ctx* ctx, int D, const vbmc_gp** out) {
     std::vector<double> X(D, 0.0), hyp(D + 2, 0.0);
     const double alpha = 0.0, sW1 = 1.0;
     const uint8_t lchol = 1;
-    vbmc_status s_ = gp_upload_impl(ctx, 1, D, 1, D + 2, D + 1, 1, 0, X.data(), hyp.data(), &alpha, nullptr, nullptr, nullptr, &sW1,
-                                    &lchol, &ctx->null_gp[D]);
-    if (s_) return s_;
+    VB_TRY(gp_upload_impl(ctx, 1, D, 1, D + 2, D + 1, 1, 0, X.data(), hyp.data(), &alpha, nullptr, nullptr, nullptr, &sW1, &lchol, &ctx->null_gp[D]));
   }
   *out = ctx->null_gp[D];
   return VBMC_OK;
@@ -1324,7 +1036,7 @@ static vbmc_status elbo_read_results(vbmc_ctx* ctx, const ElboPlan& P, const vbm
 
   // ---- results: one packed D2H (+ I_sk / J_sjk when requested)
   double* hout = (double*)ctx->pin + P.n_up;
-  { vbmc_status s_ = elbo_enqueue_readback(ctx, P, a, hout); if (s_) return s_; }
+  VB_TRY(elbo_enqueue_readback(ctx, P, a, hout));
   std::vector<double> ljh;
   std::vector<double> Jh;
   double* hI = hout + P.out_n + (size_t)S * K * R;   // (behind the slack the block has always carried)
@@ -1407,17 +1119,15 @@ static vbmc_status elbo_read_results(vbmc_ctx* ctx, const ElboPlan& P, const vbm
   return VBMC_OK;
 }
 
-
 extern "C" vbmc_status vbmc_elbo_batch(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a) {
   if (!ctx) return VBMC_ERR_INVALID;
   if (!gp && a) {  // entropy only
     if (a->compute_var != 0 || a->separate_K)
       return set_err(ctx, VBMC_ERR_INVALID, "vbmc_elbo_batch: an entropy-only call (gp == NULL) has no variance / per-component outputs");
-    vbmc_status s_ = null_gp_for(ctx, a->D, &gp);
-    if (s_) return s_;
+    VB_TRY(null_gp_for(ctx, a->D, &gp));
   }
   ElboPlan P;
-  { vbmc_status s_ = elbo_plan(ctx, gp, a, P); if (s_) return s_; }
+  VB_TRY(elbo_plan(ctx, gp, a, P));
   const size_t ndvs = a->dvarG_s ? (size_t)P.dm.T * P.dm.S * P.dm.R : 0;    // gplogjoint's dvarF with avg_flag = 0: T x S per restart
   if (ndvs) HIP_TRY(ctx, pool_get(ctx, ndvs * sizeof(double), (void**)&P.d_dvs));
   vbmc_status st = elbo_enqueue(ctx, gp, P, a->seed);
@@ -1454,8 +1164,7 @@ static vbmc_status elbo_submit_core(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: host-resident draws (eps_mode 1) only through vbmc_elbo_batch", who);
   if (!gp) {
     if (a->compute_var != 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: an entropy-only call (gp == NULL) has no variance", who);
-    vbmc_status s_ = null_gp_for(ctx, a->D, &gp);
-    if (s_) return s_;
+    VB_TRY(null_gp_for(ctx, a->D, &gp));
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->slot_ev[slot]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->slot_ev[slot], hipEventDisableTiming));
@@ -1607,7 +1316,7 @@ extern "C" vbmc_status vbmc_elbo_submit(vbmc_ctx* ctx, const vbmc_gp* gp, const 
   if (slot_in_flight(ctx, slot)) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_elbo_submit: slot %d holds an uncollected pass", slot);
   vbmc_ctx* sc = ctx;
   int inner = slot;
-  { vbmc_status s_ = slot_ctx(ctx, a, slot, &sc, &inner); if (s_) return s_; }
+  VB_TRY(slot_ctx(ctx, a, slot, &sc, &inner));
   { vbmc_status s_ = elbo_submit_core(sc, gp, a, inner, "vbmc_elbo_submit", true); if (s_) return slot_err(ctx, sc, s_); }
   ctx->slot_where[slot] = sc; ctx->slot_inner[slot] = inner;
   ctx->last_ent_form = sc->last_ent_form; ctx->last_lj_form = sc->last_lj_form;    // (a child context's pass: vbmc_ctx_last_launch asks this one)
@@ -1658,21 +1367,20 @@ extern "C" vbmc_status vbmc_elbo_abandon(vbmc_ctx* ctx, int slot) {
 }
 
 // ---- one evaluation sharded over `world` ranks along the hyper-sample axis and the entropy sample chunks (see ShardSpec)
-static vbmc_status shard_check(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a, int rank, int world) {
+static vbmc_status shard_plan(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a, int rank, int world, ElboPlan& P) {
   if (!gp || !a) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_elbo_shard_*: null gp / args");
   if (world < 1 || rank < 0 || rank >= world) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_elbo_shard_*: rank %d of world %d", rank, world);
   if (a->compute_var != 0 || a->separate_K || a->G_s || a->varG_s || a->dG_s || a->dvarG_s)
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_elbo_shard_*: the sharded evaluation covers value + gradient without variance "
                                               "(the optimiser-loop call, misc/vpoptimize_vbmc.m:71)");
   if (a->eps_mode != 0 && a->Ns > 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_elbo_shard_*: device RNG only (eps_mode 0)");
-  return VBMC_OK;
+  return elbo_plan(ctx, gp, a, P, world);
 }
 
 extern "C" vbmc_status vbmc_elbo_shard_size(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a, int world, size_t* n_doubles) {
   if (!ctx || !n_doubles) return VBMC_ERR_INVALID;
-  { vbmc_status s_ = shard_check(ctx, gp, a, 0, world); if (s_) return s_; }
   ElboPlan P;
-  { vbmc_status s_ = elbo_plan(ctx, gp, a, P, world); if (s_) return s_; }
+  VB_TRY(shard_plan(ctx, gp, a, 0, world, P));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   *n_doubles = shard_doubles(P, world);
   return VBMC_OK;
@@ -1681,13 +1389,12 @@ extern "C" vbmc_status vbmc_elbo_shard_size(vbmc_ctx* ctx, const vbmc_gp* gp, co
 extern "C" vbmc_status vbmc_elbo_shard_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a, int rank, int world,
                                              double* d_send) {
   if (!ctx || !d_send) return VBMC_ERR_INVALID;
-  { vbmc_status s_ = shard_check(ctx, gp, a, rank, world); if (s_) return s_; }
   ElboPlan P;
-  { vbmc_status s_ = elbo_plan(ctx, gp, a, P, world); if (s_) return s_; }
+  VB_TRY(shard_plan(ctx, gp, a, rank, world, P));
   ShardSpec sh;
   sh.mode = 1; sh.rank = rank; sh.world = world; sh.send = d_send;
   HIP_TRY(ctx, hipMemsetAsync(d_send, 0, shard_doubles(P, world) * sizeof(double), ctx->stream));   // unused slots of an uneven split
-  { vbmc_status s_ = elbo_enqueue(ctx, gp, P, a->seed, nullptr, 0, &sh); if (s_) return s_; }
+  VB_TRY(elbo_enqueue(ctx, gp, P, a->seed, nullptr, 0, &sh));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the exchange runs on the caller's stream / communicator
   return VBMC_OK;
 }
@@ -1695,12 +1402,11 @@ extern "C" vbmc_status vbmc_elbo_shard_begin(vbmc_ctx* ctx, const vbmc_gp* gp, c
 extern "C" vbmc_status vbmc_elbo_shard_finish(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_elbo_args* a, int world,
                                               const double* d_gathered) {
   if (!ctx || !d_gathered) return VBMC_ERR_INVALID;
-  { vbmc_status s_ = shard_check(ctx, gp, a, 0, world); if (s_) return s_; }
   ElboPlan P;
-  { vbmc_status s_ = elbo_plan(ctx, gp, a, P, world); if (s_) return s_; }
+  VB_TRY(shard_plan(ctx, gp, a, 0, world, P));
   ShardSpec sh;
   sh.mode = 2; sh.world = world; sh.gathered = d_gathered;
-  { vbmc_status s_ = elbo_enqueue(ctx, gp, P, a->seed, nullptr, 0, &sh); if (s_) return s_; }
+  VB_TRY(elbo_enqueue(ctx, gp, P, a->seed, nullptr, 0, &sh));
   return elbo_read_results(ctx, P, a);
 }
 
@@ -1764,11 +1470,11 @@ extern "C" vbmc_status vbmc_adam_batch(vbmc_ctx* ctx, const vbmc_gp* gp, const v
   if (a->separate_K || a->I_sk || a->J_sjk || a->G_s || a->varG_s || a->dG_s || a->dvarG_s || a->dvarG)      // (accepted by elbo_plan, never served here)
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_adam_batch: per-component / per-hyper-sample outputs only through vbmc_elbo_batch");
   ElboPlan P;
-  { vbmc_status s_ = elbo_plan(ctx, gp, a, P); if (s_) return s_; }
+  VB_TRY(elbo_plan(ctx, gp, a, P));
   const int T = P.dm.T, R = P.dm.R;
   hipStream_t st = ctx->stream;
   const size_t nT = (size_t)T * R, nx = (size_t)T * MaxIter * R, nf = (size_t)MaxIter * R;
-  { vbmc_status s_ = ensure(ctx, ctx->misc, (2 * nT + nx + nf) * sizeof(double) + (size_t)R * sizeof(int)); if (s_) return s_; }
+  VB_TRY(ensure(ctx, ctx->misc, (2 * nT + nx + nf) * sizeof(double) + (size_t)R * sizeof(int)));
   AdamState A{};
   A.m = (double*)ctx->misc.p; A.v = A.m + nT; A.xtab = A.v + nT; A.ftab = A.xtab + nx; A.done = (int*)(A.ftab + nf);
   A.T = T; A.R = R; A.MaxIter = MaxIter; A.step_min = step_min; A.step_max = step_max; A.step_decay = step_decay; A.TolFun = TolFun;
@@ -1790,7 +1496,7 @@ extern "C" vbmc_status vbmc_adam_batch(vbmc_ctx* ctx, const vbmc_gp* gp, const v
     const bool last = check || iter == MaxIter;
     const bool fuse = !last;
     adam_set_iter(A, iter);
-    { vbmc_status s_ = elbo_enqueue(ctx, gp, P, a->seed + (unsigned long long)iter, nullptr, 0, nullptr, fuse ? &A : nullptr, iter, prepped); if (s_) return s_; }
+    VB_TRY(elbo_enqueue(ctx, gp, P, a->seed + (unsigned long long)iter, nullptr, 0, nullptr, fuse ? &A : nullptr, iter, prepped));
     prepped = fuse;
     // the stopping test and the final read-back need this iteration's update now; the next pass unpacks theta itself
     if (!fuse) hipLaunchKernelGGL(k_adam_step, dim3(R), dim3(256), 0, st, A, iter, P.d_theta, P.d_out);
@@ -1873,7 +1579,7 @@ extern "C" int vbmc_entropy_plan(int D, int K, int* qs, int* kt, int* hv, int* t
     return 2;
   }
   int q = 0, k = 0, h = 0;
-  const bool ok = mfma_entropy_fits(D, K, 0.0, &q, &k, &h);
+  const bool ok = mfma_entropy_fits(D, K, 0.0, read_launch_switches(), &q, &k, &h);
   if (qs) *qs = q;
   if (kt) *kt = k;
   if (hv) *hv = h & 15;
@@ -1915,7 +1621,7 @@ __global__ void k_test_exp1k(int n, int variant, const double* __restrict__ x, d
 extern "C" vbmc_status vbmc_test_exp(vbmc_ctx* ctx, int n, int variant, const double* x, double* y) {
   if (!ctx || n <= 0 || !x || !y) return VBMC_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { vbmc_status s_ = ensure(ctx, ctx->misc, 2 * (size_t)n * sizeof(double)); if (s_) return s_; }
+  VB_TRY(ensure(ctx, ctx->misc, 2 * (size_t)n * sizeof(double)));
   double* dx = (double*)ctx->misc.p;
   HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   if (variant >= 3 && variant <= 5) hipLaunchKernelGGL(k_test_exp1k, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, variant, dx, dx + n);
@@ -1932,7 +1638,7 @@ extern "C" vbmc_status vbmc_rng_dump(vbmc_ctx* ctx, int D, int K, int R, int Ns,
   const int Mh = (Ns + 1) / 2;
   const size_t n = (size_t)D * Mh * K * R;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { vbmc_status s_ = ensure(ctx, ctx->eps, n * sizeof(double)); if (s_) return s_; }
+  VB_TRY(ensure(ctx, ctx->eps, n * sizeof(double)));
   const long long total = (long long)R * K * Mh;
   hipLaunchKernelGGL(k_rng_dump, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, D, K, R, Mh,
                      (unsigned long long)seed, (double*)ctx->eps.p);

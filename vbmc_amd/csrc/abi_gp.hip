@@ -194,7 +194,7 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, const char* who, int N, int D, int S, in
   const size_t nX = (size_t)N * D, nH = (size_t)Nhyp * S, nS = (size_t)S * N, nC = (size_t)S * 4;
   const size_t nB = (4 * (size_t)S + 7) / 8;             // ones | needinv | active | lchol
   const size_t in_doubles = nX + N + nH + nS + nC + nB + f.extra_in;
-  { vbmc_status s_ = ensure_pin(ctx, (in_doubles + pin_extra_doubles) * 8 + 8); if (s_) return s_; }
+  VB_TRY(ensure_pin(ctx, (in_doubles + pin_extra_doubles) * 8 + 8));
   double* hin = (double*)ctx->pin;
   f.pin_out = hin + in_doubles;      // the caller's results come back through the same pinned block (pin_extra_doubles of it)
   memcpy(hin, X, nX * 8);
@@ -355,7 +355,7 @@ static vbmc_status gp_post_impl(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, in
       }
     };
   }
-  { vbmc_status s_ = gp_factorize(ctx, "vbmc_gp_post", N, D, S, Nhyp, meanfun, noisefun, X, y, s2, hyp, true, f, (size_t)S * N + S, optimistic); if (s_ != VBMC_OK) return s_; }
+  VB_TRY(gp_factorize(ctx, "vbmc_gp_post", N, D, S, Nhyp, meanfun, noisefun, X, y, s2, hyp, true, f, (size_t)S * N + S, optimistic));
   hipStream_t st = ctx->stream;
   const int Ncov = f.Ncov, Nnoise = f.Nnoise;
   const bool any_inv = f.any_inv;
@@ -392,13 +392,11 @@ static vbmc_status gp_post_impl(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, in
   if (L) {
     // the caller's copy of gp.post(s).L (D2H only when asked for)
     if (!any_inv || inv_in_place) {   // one contiguous block: every sample on the Cholesky branch, or the inverses already in their places
-      vbmc_status s_ = d2h_bounced(ctx, L, dA.as<double>(), (size_t)S * N * N * 8);
-      if (s_) return s_;
+      VB_TRY(d2h_bounced(ctx, L, dA.as<double>(), (size_t)S * N * N * 8));
     } else {
       for (int s = 0; s < S; ++s) {
         const double* src = lch[s] ? dA.as<double>() + (size_t)s * N * N : dXi.as<double>() + (size_t)s * N * N;
-        vbmc_status s_ = d2h_bounced(ctx, L + (size_t)s * N * N, src, (size_t)N * N * 8);
-        if (s_) return s_;
+        VB_TRY(d2h_bounced(ctx, L + (size_t)s * N * N, src, (size_t)N * N * 8));
       }
     }
   }
@@ -510,7 +508,7 @@ static vbmc_status gp_nlz_impl(vbmc_ctx* ctx, int N, int D, int B, int Nhyp, int
   // few matrices of moderate order with a gradient: the factor's inverse and alpha's backward solve share one launch
   const bool combined = compute_grad && N > 0 && N <= ASOLVE1_THREADS && (size_t)B * TRSM_NBLK(N) <= 1024 && tri_inverse2_fits(N);
   f.defer_alpha = combined;
-  { vbmc_status s_ = gp_factorize(ctx, "vbmc_gp_nlz", N, D, B, Nhyp, meanfun, noisefun, X, y, s2, hyp, false, f, nout, optimistic, compute_grad && B <= 16); if (s_ != VBMC_OK) return s_; }
+  VB_TRY(gp_factorize(ctx, "vbmc_gp_nlz", N, D, B, Nhyp, meanfun, noisefun, X, y, s2, hyp, false, f, nout, optimistic, compute_grad && B <= 16));
   hipStream_t st = ctx->stream;
   const int Nnoise = f.Nnoise, Nmean = f.Nmean;
   TmpBuf dout, dKi, dpart, dTT;
@@ -604,8 +602,7 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   hipStream_t st = ctx->stream;
   if (!slab_pred) {   // Tinv = inv(L') = L' \ I for the Lchol samples, once per GP (the kernels skip the others)
     bool have = false;
-    vbmc_status s_ = ensure_tinv(ctx, gp, &have);
-    if (s_) return s_;
+    VB_TRY(ensure_tinv(ctx, gp, &have));
   }
   // column means for sq_dist's centring (sq_dist.m:36), O((N + Nstar) D) on the host in MATLAB's order
   std::vector<double> mb(D);
@@ -777,7 +774,7 @@ extern "C" vbmc_status vbmc_gp_pred(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar,
     return VBMC_OK;
   }
   PredBufs pb;
-  { vbmc_status s_ = pred_on_device(ctx, "vbmc_gp_pred", gp, Nstar, Xstar, ystar, s2star, pb); if (s_ != VBMC_OK) return s_; }
+  VB_TRY(pred_on_device(ctx, "vbmc_gp_pred", gp, Nstar, Xstar, ystar, s2star, pb));
   hipStream_t st = ctx->stream;
   const int S = gp->S;
   TmpBuf davg;
@@ -831,7 +828,7 @@ extern "C" vbmc_status vbmc_acq_eval(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar
     return VBMC_OK;
   }
   PredBufs pb;
-  { vbmc_status s_ = pred_on_device(ctx, "vbmc_acq_eval", gp, Nstar, Xs, nullptr, nullptr, pb); if (s_ != VBMC_OK) return s_; }
+  VB_TRY(pred_on_device(ctx, "vbmc_acq_eval", gp, Nstar, Xs, nullptr, nullptr, pb));
   hipStream_t st = ctx->stream;
   const int N = gp->N, D = gp->D, S = gp->S;
   if ((size_t)(2 * K * D + K) * 8 > 64 * 1024) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_acq_eval: K*D = %d too large", K * D);
@@ -995,7 +992,7 @@ extern "C" vbmc_status vbmc_acq_iqr_eval(vbmc_ctx* ctx, const vbmc_gp* gp, const
     return VBMC_OK;
   }
   PredBufs pb;
-  { vbmc_status s_ = pred_on_device(ctx, "vbmc_acq_iqr_eval", gp, Nstar, Xs, nullptr, nullptr, pb, true); if (s_ != VBMC_OK) return s_; }
+  VB_TRY(pred_on_device(ctx, "vbmc_acq_iqr_eval", gp, Nstar, Xs, nullptr, nullptr, pb, true));
   hipStream_t st = ctx->stream;
   const int N = gp->N, D = gp->D, S = gp->S;
   TmpBuf dgl, dXr, dsn, dsx, dacqs, dres;
@@ -1090,7 +1087,7 @@ extern "C" vbmc_status vbmc_gp_rank1_solves(vbmc_ctx* ctx, const vbmc_gp* gp, co
   if (!gp->hasL) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_rank1_solves needs gp.post(s).L on the device");
   const int N = gp->N, S = gp->S;
   TmpBuf dKs, dV, dXo;
-  { vbmc_status s_ = rank1_solves_dev(ctx, gp, xstar, dKs, dV, dXo); if (s_) return s_; }
+  VB_TRY(rank1_solves_dev(ctx, gp, xstar, dKs, dV, dXo));
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipMemcpyAsync(Ks, dKs.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(v, dV.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, st));
@@ -1112,7 +1109,7 @@ extern "C" vbmc_status vbmc_gp_rank1_update(vbmc_ctx* ctx, const vbmc_gp* gp, co
   std::vector<double> xs(D);
   for (int d = 0; d < D; ++d) xs[d] = X_new[(size_t)N + (size_t)N1 * d];   // the appended row of the (N+1) x D matrix
   TmpBuf dKs, dV, dXo, dsc, dLn, dan;
-  { vbmc_status s_ = rank1_solves_dev(ctx, gp, xs.data(), dKs, dV, dXo); if (s_) return s_; }
+  VB_TRY(rank1_solves_dev(ctx, gp, xs.data(), dKs, dV, dXo));
   hipStream_t st = ctx->stream;
   // per-sample scalars: sn2_eff (:207), Kss = sf2 (:213), (mstar - ystar)/vstar (:245), vstar
   std::vector<double> sc((size_t)S * 4);
@@ -1143,7 +1140,7 @@ extern "C" vbmc_status vbmc_gp_rank1_update(vbmc_ctx* ctx, const vbmc_gp* gp, co
   const int Nhyp = gp->Nhyp;
   const size_t nXn = (size_t)N1 * D, nG = (size_t)S * GPC_STRIDE(D), nH = (size_t)Nhyp * S;
   const size_t nsmall = nXn + D + nH + nG + 2 * (size_t)S + ((size_t)S + 7) / 8;
-  { vbmc_status s_ = ensure_pin(ctx, ((nXn + D) + (size_t)S * N1) * 8 + 8); if (s_) return s_; }
+  VB_TRY(ensure_pin(ctx, ((nXn + D) + (size_t)S * N1) * 8 + 8));
   double* hin = (double*)ctx->pin;
   memcpy(hin, X_new, nXn * 8);
   for (int d = 0; d < D; ++d) {
@@ -1331,7 +1328,7 @@ extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args
   if (chol2_needs_gpanel(N, true)) HIP_TRY(ctx, dPg.alloc(ctx, (size_t)W * 16 * (size_t)(((N + 15) >> 4) << 4) * 8));
   HIP_TRY(ctx, dOut.alloc(ctx, (size_t)W * 2 * 8));
   HIP_TRY(ctx, dSmp.alloc(ctx, ((size_t)g.Ns * Nhyp + g.Ns) * 8));
-  { vbmc_status s_ = ensure_pin(ctx, 2 * sizeof(SliceChainState) + 64); if (s_) return s_; }
+  VB_TRY(ensure_pin(ctx, 2 * sizeof(SliceChainState) + 64));
   SliceChainState* hst = (SliceChainState*)ctx->pin;                                // two landing slots of the progress word
 
   std::vector<double> hin(in_doubles, 0.0);

@@ -200,6 +200,13 @@ static inline vbmc_status set_err(vbmc_ctx* ctx, vbmc_status st, const char* fmt
     }                                                                                        \
   } while (0)
 
+// ... and a vbmc_status: pass on the failure of a call that has already recorded its error
+#define VB_TRY(expr)                              \
+  do {                                            \
+    vbmc_status vs_ = (expr);                     \
+    if (vs_ != VBMC_OK) return vs_;               \
+  } while (0)
+
 static inline vbmc_status ensure(vbmc_ctx* ctx, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return VBMC_OK;
   if (b.p) HIP_TRY(ctx, hipFree(b.p));

@@ -79,6 +79,12 @@ __host__ __device__ inline int ent_walk_slots(long long p, int ntile, int tpw) {
 }
 __host__ __device__ inline int ent_walk_max_slots(int ntile, int tpw) { return (ntile - 1) / tpw + 2; }
 
+// Which k_entropy_mfma<QS, KT, .., HV, ..> exist beyond the plain forms (ent_mfma_inst.hip instantiates by these, the launch plan asks by them;
+// hv: waves per workgroup, without the tail bits).  The log-joint role rides single-wave workgroups up to QS = 8; the device-RNG gradient
+// form -- and its walking variant -- is built where the kernel takes the loop without spilling.
+constexpr bool ent_mfma_role_inst(int qs, int hv) { return hv == 1 && qs <= 8; }
+constexpr bool ent_mfma_walk_inst(int qs, int kt, int hv) { return hv == 1 && qs <= 4 && kt <= 3; }
+
 // The short kernels of a pass (copies, k_prep, the log joint, the reductions, the finalize kernel) ask for the highest issue priority: in
 // the pipelined step they share SIMDs with the other pass's entropy kernel, whose waves run at priorities 3 -> 0 (entropy_mfma.h), and
 // they are what the next pass waits for.

@@ -23,7 +23,7 @@ static int launch_kp(int mode, int grad, dim3 grid, hipStream_t st, const EntArg
   return 0;
 }
 
-// (DT = 12 with KP >= 10 and DT = 10 with KP >= 12 are outside the class: abi_elbo.hip, lane_entropy_fits)
+// (DT = 12 with KP >= 10 and DT = 10 with KP >= 12 are outside the class: elbo_launch_plan.h, lane_entropy_fits)
 static int dispatch(int mode, int kp, int grad, dim3 grid, hipStream_t st, const EntArgs* ea) {
   switch (kp) {
     case 2: return launch_kp<2>(mode, grad, grid, st, *ea);

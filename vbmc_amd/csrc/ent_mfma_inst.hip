@@ -10,7 +10,7 @@
 #define CAT(a, b) CAT2(a, b)
 
 // mode 0: launch.  mode 1: no launch -- returns the number of workgroups of this instantiation one compute unit holds at the launch's
-// dynamic LDS size (hipOccupancyMaxActiveBlocksPerMultiprocessor: registers AND LDS), for the chunk model of elbo_plan.
+// dynamic LDS size (hipOccupancyMaxActiveBlocksPerMultiprocessor: registers AND LDS), for the chunk model (elbo_launch_plan.h: plan_launch).
 template <int KT, int HV, int TL = 0>
 static int launch_kt(int mode, int grad, dim3 grid, hipStream_t st, const EntArgs& ea) {
   // dynamic LDS: the parameter block (<= 74 KB at K = 256, D = 32), reused by the exp table (8 KB) and the PV exchange of
@@ -21,15 +21,15 @@ static int launch_kt(int mode, int grad, dim3 grid, hipStream_t st, const EntArg
   if (HV > 1) after += (size_t)(VBMC_ENT_EO(HV) ? 1 : 2) * HV * NPV_ * 4 * WAVE * sizeof(double);   // PV exchange: per sign, or one for both (entropy_mfma.h: YXSB)
   if (after > lds) lds = after;
   const void* fn = nullptr;
-  if constexpr (HV == 1 && QS_VALUE <= 8) {
+  if constexpr (ent_mfma_role_inst(QS_VALUE, HV)) {
     // the launch carries the log-joint role (gradient kernels, dense): the caller checked the shape
     if (ea.lj.rows > 0) fn = (const void*)k_entropy_mfma<QS_VALUE, KT, true, false, 1, TL, true>;
   }
-  // the walking launch (entropy_mfma.h: WALK; elbo_plan decides): the device-RNG gradient kernels of single-wave workgroups, without the role
+  // the walking launch (entropy_mfma.h: WALK; elbo_launch_plan.h decides): the device-RNG gradient kernels of single-wave workgroups, without the role
   const bool walk = ea.walk_tpw > 0;
-  if (walk && !(HV == 1 && QS_VALUE <= 4 && KT <= 3 && grad && !fn && !ea.eps && !(ea.cutoff > 0.0))) return mode != 0 ? -1 : 1;
+  if (walk && !(ent_mfma_walk_inst(QS_VALUE, KT, HV) && grad && !fn && !ea.eps && !(ea.cutoff > 0.0))) return mode != 0 ? -1 : 1;
   // the device-RNG launch of a kernel that otherwise spends registers on the parity mode's prefetch (entropy_mfma.h: EM, EPF)
-  if constexpr (HV == 1 && QS_VALUE <= 4 && KT <= 3) {
+  if constexpr (ent_mfma_walk_inst(QS_VALUE, KT, HV)) {
     if (!fn && grad && !ea.eps && !(ea.cutoff > 0.0))
       fn = walk ? (const void*)k_entropy_mfma<QS_VALUE, KT, true, false, 1, TL, false, false, true> : (const void*)k_entropy_mfma<QS_VALUE, KT, true, false, 1, TL, false, false>;
   }

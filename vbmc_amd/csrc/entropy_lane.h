@@ -41,7 +41,7 @@ static inline size_t ent_lane_role_lds(const EntArgs& ea) {
 #endif
 // Two.  No lane kernel may spill: with 87 spilled registers (DT = 12, KP = 14, four role slabs per trip) a launch returned run-to-run
 // different, wrong sums -- the instantiations whose two signs' densities, weight-gradient and 4 DT gradient accumulators do not fit
-// 256 registers are outside the class (abi_elbo.hip: lane_entropy_fits), and tests/test_lane_build.py compiles every instantiation
+// 256 registers are outside the class (elbo_launch_plan.h: lane_entropy_fits), and tests/test_lane_build.py compiles every instantiation
 // and requires a zero spill count and no private segment.
 #ifndef ENT_LANE_OCC
 #define ENT_LANE_OCC(DT_, KP_) 2
