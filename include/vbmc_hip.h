@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VBMC_ABI_VERSION 7
+#define VBMC_ABI_VERSION 8
 
 typedef int vbmc_status;
 enum {
@@ -246,6 +246,83 @@ typedef struct vbmc_slice_args {
 } vbmc_slice_args;
 vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args* args);
 vbmc_status vbmc_slice_rng_dump(uint64_t seed, int sweeps, int Nhyp, int Kmax, int32_t* perms, double* uniforms);
+
+/*
+ * The optimisation half of gplite_train (ABI version 8; gplite/gplite_train.m:200-306, utils/fminfill.m:101-114) with the training
+ * set uploaded once and only a progress word crossing the host link until the result:
+ *   1. FILL (fminfill.m:101-114).  gp_objfun = gplite_nlZ - gplite_hypprior at the Ninit rows of `design` (Ninit x Nhyp, column-major;
+ *      its first rows are the caller's hyp0, the rest the space-filling design of fminfill.m:42-101, which the caller builds), in
+ *      chunks whose work matrices stay below 2 GiB.  A matrix that is still not positive definite after the ten noise-inflation
+ *      retries gives NaN (gplite_train.m:542-546).  The values are sorted as MATLAB's sort does: ascending, stable, NaN last.
+ *   2. STARTS.  The first Nopts sorted rows (:206); with a noise hyper-parameter, Nopts > 1 and Ninit > Nopts the second start is
+ *      the best of the fifth of the remaining rows with the smallest first noise parameter (:210-221); all are moved into
+ *      [LB + eps(LB), UB - eps(UB)] (:272, an infinite bound leaves the coordinate alone: MATLAB's min / max pass over the NaN of
+ *      eps(Inf)) and a fixed coordinate (LB == UB) is put on its value.  widths_default = std(design) with the zero widths repaired
+ *      (:207,258-267).  Ninit = 0 is the branch of :249-256: the N0 given columns are evaluated and sorted, they are the starts, and
+ *      widths_default (PUB - PLB there) is left to the caller.
+ *   3. OPTIMISER.  fmincon is toolbox code outside the reference tree, so its trajectory cannot be reproduced; this is the library's
+ *      OWN bound-constrained quasi-Newton method, a projected BFGS with a dense inverse-Hessian approximation H per start:
+ *        free set   F = { i : LB_i < UB_i and not (x_i <= LB_i, g_i > 0) and not (x_i >= UB_i, g_i < 0) }, recomputed every iteration;
+ *        direction  d_F = -H_FF g_F, d = 0 elsewhere; if g'd is not negative H is reset to the identity (d_F = -g_F);
+ *        line search  candidates clip(x + t0 2^-k d, LB, UB), k = 0, 1, ..., t0 = 1 (min(1, 1 / |g_F|_1) while H is the identity);
+ *                   the first with a finite value and f_c <= f + 1e-4 g'(x_c - x) is taken, NaN is a rejection that counts as an
+ *                   evaluation; a candidate equal to x ends the start with exit flag 3, thirty rejected candidates with -2;
+ *        update     s = x_c - x, y = g_c - g (zero on fixed coordinates); skipped unless s'y > 1e-10 |s| |y|; the first update after a
+ *                   reset starts from H = (s'y / y'y) I;  H <- H - rho (s (Hy)' + (Hy) s') + (rho^2 y'Hy + rho) s s', rho = 1 / s'y;
+ *        stopping   |x - clip(x - g)|_inf <= TolFun (exit flag 1), |f - f_old| <= TolFun (1 + |f|) (2), MaxIter iterations or
+ *                   MaxFunEvals evaluations (0); a start whose first value is not finite ends with -3.
+ *      All Nopts starts advance in lock-step; one ROUND is one batched value + gradient pass over Nopts x W candidates, the W
+ *      consecutive backtracking candidates of every start, consumed in order: hyp, nll, iterations, funccount and the history are
+ *      BIT-IDENTICAL for every W, only `performed` changes.  W = 0 asks for the default, 1.  A consumed candidate whose first
+ *      factorisation fails stalls the call until the host has repeated that round with the retries, as in vbmc_gp_slice_sample.
+ *   4. CLOSING (:298-306).  best = argmin of nll ignoring NaN, hyp_start = that column inside the bounds, fixed coordinates at LB.
+ * Model set and refusals as vbmc_gp_nlz; Nhyp <= 128, 1 <= Nopts <= 16, W <= 16, at most 16384 design rows, and Nopts N^2 doubles
+ * below 2 GiB (the starts are not chunked; W is lowered until Nopts W N^2 doubles are), VBMC_ERR_UNSUPPORTED beyond.  TolFun: the caller passes TolOpt or TolOptMCMC
+ * (:163-167).  MaxIter <= 0: 1000; MaxFunEvals <= 0: 3000.  prior_mu NULL: no hyper-prior; prior_df NULL: 7 (gplite_hypprior.m:26).
+ * Outputs (any may be NULL): fill_fvals Ninit (sorted), fill_order Ninit (0-based rows of the design), widths_default Nhyp, hyp
+ * Nhyp x Nopts (column-major), nll Nopts, best (0-based), hyp_start Nhyp, iterations / funccount / exitflag Nopts, performed
+ * (evaluations launched by the optimiser, the speculative and the repeated ones included), and the history of the first hist_cap
+ * iterations of every start: hist_x [start][iteration][Nhyp], hist_f and hist_k [start][iteration] (the accepted candidate's k).
+ * The context stays usable after any error.
+ */
+typedef struct vbmc_gptrain_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_gptrain_args) */
+  int32_t N, D, Nhyp, meanfun;
+  int32_t noisefun[3];
+  const double* X;           /* N x D */
+  const double* y;           /* N */
+  const double* s2;          /* N or NULL */
+  const double* prior_mu;    /* Nhyp or NULL */
+  const double* prior_sigma; /* Nhyp */
+  const double* prior_df;    /* Nhyp or NULL */
+  const double* LB;          /* Nhyp */
+  const double* UB;          /* Nhyp */
+  const double* design;      /* max(Ninit, N0) x Nhyp, column-major */
+  int32_t Ninit;             /* rows of the design; 0: the N0 given rows only (:249-256) */
+  int32_t N0;                /* rows of the design that are the caller's hyp0 (used when Ninit = 0) */
+  int32_t Nopts;
+  int32_t Ncov;              /* D + 1: the column of the first noise parameter (the low-noise pick) */
+  double TolFun;
+  int32_t MaxIter;
+  int32_t MaxFunEvals;
+  int32_t W;                 /* speculation width, 0 .. 16 (0: default) */
+  int32_t hist_cap;          /* iterations per start the history blocks hold */
+  double* fill_fvals;
+  int32_t* fill_order;
+  double* widths_default;
+  double* hyp;
+  double* nll;
+  int32_t* best;
+  double* hyp_start;
+  int32_t* iterations;
+  int64_t* funccount;
+  int32_t* exitflag;
+  int64_t* performed;
+  double* hist_x;
+  double* hist_f;
+  int32_t* hist_k;
+} vbmc_gptrain_args;
+vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_args* args);
 
 /*
  * [ymu,ys2,fmu,fs2] = gplite_pred(gp, Xstar, ystar, s2star, ssflag)   (gplite/gplite_pred.m:1-165).

@@ -33,6 +33,13 @@
 //                                (slicesamplebnd on -gplite_nlZ + log prior, the chain on the device: vbmc_gp_slice_sample.  perms:
 //                                 Nhyp x sweeps, column s = randperm(Nhyp)' of sweep s, 1-based; U: (2+Kmax) x Nhyp x sweeps; both
 //                                 empty: the device generator keyed by seed.  counts = [funccount performed max_shrink])
+//     [hyp,nll,hyp_start,best,widths_default,counts,performed,fill_fvals,fill_order] = vbmc_hip_mex('gp_train_opt', X, y, s2, meanfun,
+//                                noisefun, prior /*struct mu, sigma, df or []*/, LB, UB, design /*rows x Nhyp*/,
+//                                [Ninit Nopts TolFun MaxIter MaxFunEvals W])
+//                                (the optimisation half of gplite_train, gplite_train.m:200-306, on the device: vbmc_gp_train_optimize.
+//                                 design: the points fminfill evaluates, hyp0' in its first rows -- the caller builds it, fminfill.m:42-101;
+//                                 Ninit = 0: the rows are the caller's hyp0 alone (:249-256) and widths_default comes back NaN.
+//                                 hyp Nhyp x Nopts, counts 3 x Nopts = [iterations; funccount; exitflag], best and fill_order 1-based)
 //     C = vbmc_hip_mex('sq_dist', a, b)
 //     lim = vbmc_hip_mex('limits')                          -> struct max_D, max_K, max_N, max_Na, max_T_vargrad, delta_ok, meanfun: the shapes the
 //                                                             library accepts (vbmc_get_limits; no device needed) -- matlab/vbmc_hip_supported.m
@@ -57,6 +64,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -579,6 +587,68 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     if (nlhs > 1) plhs[1] = lp; else mxDestroyArray(lp);
     if (nlhs > 2) plhs[2] = wo; else mxDestroyArray(wo);
     if (nlhs > 3) plhs[3] = cn; else mxDestroyArray(cn);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "gp_train_opt")) {
+    if (nrhs < 11) return raise("vbmc_hip:usage", "gp_train_opt: X, y, s2, meanfun, noisefun, prior, LB, UB, design, options");
+    const mxArray *X = prhs[1], *pr = prhs[6], *des = prhs[9], *opt = prhs[10];
+    if (mxGetNumberOfElements(opt) < 6) return raise("vbmc_hip:usage", "gp_train_opt: options are [Ninit Nopts TolFun MaxIter MaxFunEvals W]");
+    const double* o = mxGetDoubles(opt);
+    vbmc_gptrain_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.N = (int)mxGetM(X); a.D = (int)mxGetN(X); a.Nhyp = (int)mxGetN(des); a.meanfun = (int)mxGetScalar(prhs[4]);
+    a.noisefun[0] = 1;
+    for (int i = 0; i < 3 && i < (int)mxGetNumberOfElements(prhs[5]); ++i) a.noisefun[i] = (int32_t)mxGetDoubles(prhs[5])[i];
+    a.X = mxGetDoubles(X); a.y = dbl(prhs[2]); a.s2 = dbl(prhs[3]);
+    if (pr && !mxIsEmpty(pr) && mxIsStruct(pr)) { a.prior_mu = dbl(field(pr, "mu")); a.prior_sigma = dbl(field(pr, "sigma")); a.prior_df = dbl(field(pr, "df")); }
+    a.LB = dbl(prhs[7]); a.UB = dbl(prhs[8]); a.design = mxGetDoubles(des);
+    const int rows = (int)mxGetM(des);
+    a.Ninit = (int)o[0]; a.N0 = rows; a.Nopts = (int)o[1]; a.Ncov = a.D + 1; a.TolFun = o[2]; a.MaxIter = (int)o[3]; a.MaxFunEvals = (int)o[4];
+    a.W = (int)o[5];
+    const size_t nh = (size_t)a.Nhyp;
+    if (a.Nhyp < 1 || rows < 1 || a.Nopts < 1 || (a.Ninit != 0 && a.Ninit != rows))
+      return raise("vbmc_hip:usage", "gp_train_opt: the design is Ninit x Nhyp (Ninit = 0: hyp0' alone), Nopts is positive");
+    for (int i : {7, 8})
+      if (mxGetNumberOfElements(prhs[i]) != nh) return raise("vbmc_hip:usage", "gp_train_opt: LB and UB need one entry per column of the design");
+    if (pr && !mxIsEmpty(pr) && mxIsStruct(pr))
+      for (const char* fn : {"mu", "sigma", "df"})
+        if (field(pr, fn) && !mxIsEmpty(field(pr, fn)) && mxGetNumberOfElements(field(pr, fn)) != nh)
+          return raise("vbmc_hip:usage", "gp_train_opt: prior.mu / sigma / df need one entry per column of the design");
+    mxArray* out[9];
+    out[0] = mxCreateDoubleMatrix(a.Nhyp, a.Nopts, mxREAL);
+    out[1] = mxCreateDoubleMatrix(1, a.Nopts, mxREAL);
+    out[2] = mxCreateDoubleMatrix(a.Nhyp, 1, mxREAL);
+    out[3] = mxCreateDoubleMatrix(1, 1, mxREAL);
+    out[4] = mxCreateDoubleMatrix(1, a.Nhyp, mxREAL);
+    out[5] = mxCreateDoubleMatrix(3, a.Nopts, mxREAL);
+    out[6] = mxCreateDoubleMatrix(1, 1, mxREAL);
+    out[7] = mxCreateDoubleMatrix(1, rows, mxREAL);
+    out[8] = mxCreateDoubleMatrix(1, rows, mxREAL);
+    vbmc_status st;
+    {
+      std::vector<int32_t> its(a.Nopts), ef(a.Nopts), ord(rows);
+      std::vector<int64_t> fc(a.Nopts);
+      int32_t best = 0;
+      int64_t perf = 0;
+      for (size_t i = 0; i < nh; ++i) mxGetDoubles(out[4])[i] = std::numeric_limits<double>::quiet_NaN();
+      a.hyp = mxGetDoubles(out[0]); a.nll = mxGetDoubles(out[1]); a.hyp_start = mxGetDoubles(out[2]); a.best = &best;
+      a.widths_default = mxGetDoubles(out[4]); a.iterations = its.data(); a.funccount = fc.data(); a.exitflag = ef.data(); a.performed = &perf;
+      a.fill_fvals = mxGetDoubles(out[7]); a.fill_order = ord.data();
+      st = vbmc_gp_train_optimize(g_ctx, &a);
+      if (st == VBMC_OK) {
+        mxGetDoubles(out[3])[0] = (double)best + 1.0;
+        mxGetDoubles(out[6])[0] = (double)perf;
+        for (int s = 0; s < a.Nopts; ++s) {
+          mxGetDoubles(out[5])[3 * s] = (double)its[s]; mxGetDoubles(out[5])[3 * s + 1] = (double)fc[s]; mxGetDoubles(out[5])[3 * s + 2] = (double)ef[s];
+        }
+        for (int r = 0; r < rows; ++r) mxGetDoubles(out[8])[r] = (double)ord[r] + 1.0;
+      }
+    }
+    if (st != VBMC_OK) { for (mxArray* m : out) mxDestroyArray(m); return fail(st); }
+    plhs[0] = out[0];
+    for (int i = 1; i < 9; ++i) { if (nlhs > i) plhs[i] = out[i]; else mxDestroyArray(out[i]); }
     return 0;
   }
 

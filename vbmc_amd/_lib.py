@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VBMC_HIP_LIB: an alternative build of the SAME library (kernel A/B experiments, tools/ent_experiments.py)
 LIB_PATH = os.environ.get("VBMC_HIP_LIB") or os.path.join(_HERE, "lib", "libvbmc_hip.so")
 
-ABI_VERSION = 7   # include/vbmc_hip.h: VBMC_ABI_VERSION
+ABI_VERSION = 8   # include/vbmc_hip.h: VBMC_ABI_VERSION
 # the launch forms vbmc_ctx_last_launch reports (include/vbmc_hip.h: VBMC_ENTFORM_* / VBMC_LJFORM_*; 0: none ran)
 ENTFORM_LB, ENTFORM_VALU, ENTFORM_MFMA, ENTFORM_LANE = 1, 2, 3, 4
 LJFORM_VALU_WAVE, LJFORM_VALU_SPLIT, LJFORM_MFMA_GRAD, LJFORM_MFMA_VALUE, LJFORM_ROLE_MFMA, LJFORM_ROLE_LANE = 1, 2, 3, 4, 5, 6
@@ -92,6 +92,26 @@ class SliceArgs(C.Structure):
     ]
 
 
+class GpTrainArgs(C.Structure):
+    """vbmc_gptrain_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("N", C.c_int32), ("D", C.c_int32), ("Nhyp", C.c_int32), ("meanfun", C.c_int32),
+        ("noisefun", C.c_int32 * 3),
+        ("X", _dp), ("y", _dp), ("s2", _dp),
+        ("prior_mu", _dp), ("prior_sigma", _dp), ("prior_df", _dp),
+        ("LB", _dp), ("UB", _dp), ("design", _dp),
+        ("Ninit", C.c_int32), ("N0", C.c_int32), ("Nopts", C.c_int32), ("Ncov", C.c_int32),
+        ("TolFun", C.c_double),
+        ("MaxIter", C.c_int32), ("MaxFunEvals", C.c_int32), ("W", C.c_int32), ("hist_cap", C.c_int32),
+        ("fill_fvals", _dp), ("fill_order", C.POINTER(C.c_int32)), ("widths_default", _dp),
+        ("hyp", _dp), ("nll", _dp), ("best", C.POINTER(C.c_int32)), ("hyp_start", _dp),
+        ("iterations", C.POINTER(C.c_int32)), ("funccount", C.POINTER(C.c_int64)), ("exitflag", C.POINTER(C.c_int32)),
+        ("performed", C.POINTER(C.c_int64)),
+        ("hist_x", _dp), ("hist_f", _dp), ("hist_k", C.POINTER(C.c_int32)),
+    ]
+
+
 _lib = None
 
 
@@ -153,6 +173,7 @@ def load():
     lib.vbmc_acq_iqr_eval.argtypes = [vp, vp, vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp]
     lib.vbmc_gp_nlz.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]
     lib.vbmc_gp_slice_sample.argtypes = [vp, C.POINTER(SliceArgs)]
+    lib.vbmc_gp_train_optimize.argtypes = [vp, C.POINTER(GpTrainArgs)]
     lib.vbmc_slice_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]

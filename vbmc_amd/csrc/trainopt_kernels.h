@@ -1,0 +1,443 @@
+// Device-resident optimisation half of gplite_train (gplite/gplite_train.m:200-306, utils/fminfill.m:101-114): the fill stage, the
+// choice of the starting points and a bound-constrained quasi-Newton optimiser of gp_objfun = gplite_nlZ - gplite_hypprior, all
+// driven from the device; include/vbmc_hip.h (vbmc_gp_train_optimize) describes the algorithm, tests/_trainopt_ref.py restates it.
+//   k_topt_propose    the candidates of one ROUND (Nopts starts x W consecutive backtracking steps) or a chunk of the design:
+//                     hyper-parameter block, noise vectors AND their derivatives (gplite_noisefun.m:176-210), Cholesky-branch
+//                     scalars, hyper-prior value and gradient (gplite_hypprior.m:17-65) -- the inputs of the batched gplite_nlZ path
+//   k_topt_decide     one wave per start: first accepted candidate in order, BFGS update, free set, direction, stopping tests
+//   k_topt_fill_sort  MATLAB's sort of the fill values (stable, NaN last), the starts (:206,210-221,272) and widths_default (:207,258-267)
+//   k_topt_close      argmin ignoring NaN, clamp, fixed coordinates (:298-306)
+// Speculation: the k-th backtracking candidate clip(x + t0 2^-k d) is a function of the iterate alone, the decide kernel consumes
+// candidates in order, so iterates, values, iterations and funccount are the sequential algorithm's for every W, bit for bit.
+// The optimiser's own arithmetic is written with plain operators in scopes with contraction off (see slice_prop in slice_kernels.h).
+#pragma once
+#include "common.h"
+#include "device_math.h"
+
+#define TOPT_MAXHYP 128
+#define TOPT_MAXOPTS 16
+#define TOPT_MAXW 16
+#define TOPT_MAXBACK 30
+static_assert(TOPT_MAXHYP >= (VBMC_LIM_D + 1) + 4 + (2 * VBMC_LIM_D + 1), "k_topt_decide keeps Nhyp doubles in LDS arrays of TOPT_MAXHYP");
+
+// what k_topt_propose says about candidate b to k_topt_decide
+enum { TOPT_VOID = 0, TOPT_EVAL = 1, TOPT_SKIP = 2, TOPT_ATX = 3, TOPT_EXHAUSTED = 4 };
+// exit flags of a start
+enum { TOPT_EXIT_LIMIT = 0, TOPT_EXIT_GRAD = 1, TOPT_EXIT_DF = 2, TOPT_EXIT_STEP = 3, TOPT_EXIT_LINESEARCH = -2, TOPT_EXIT_START = -3 };
+
+struct ToptStart {      // the progress word of one start (the host reads the Nopts of them one chunk of rounds behind)
+  int started;          // the evaluation at the starting point has been consumed
+  int done, exitflag;
+  int iterations;
+  int k;                // backtracking steps of the open iteration consumed so far
+  int fresh;            // the inverse-Hessian approximation is the identity (start, or reset): next update scales it first
+  int stall;            // a candidate that had to be consumed failed its first (unjittered) factorisation: the host runs a checked round
+  int rounds;
+  long long funccount;  // evaluations the sequential algorithm needs
+  long long performed;  // evaluations launched
+  double f, t0;
+};
+
+struct ToptArgs {
+  int N, D, Nhyp, Ncov, Nnoise, Nopts, W, Ninit, nf0, nf1, nf2, has_prior, max_iter, hist_cap, lownoise;
+  long long max_evals;
+  double tol;
+  const double *y, *s2;                       // N (s2 may be null)
+  const double *LB, *UB;                      // Nhyp
+  const double *pmu, *psig, *pdf, *pc;        // Nhyp: hyper-prior location, scale, degrees of freedom, normalising term
+  const int* ptype;                           // Nhyp: 0 flat, 1 Gaussian, 2 Student-t
+  const double* design;                       // Ninit x Nhyp, column-major
+  ToptStart* st;                              // Nopts
+  double *x, *g, *d, *H;                      // Nopts x Nhyp (x 3), Nopts x Nhyp x Nhyp
+  double *hyp, *sn2, *scal, *lp, *dlp, *dsn2; // B x Nhyp, B x N, B x 4, B, B x Nhyp, B x Nnoise x N
+  unsigned char *act, *on;                    // B: factorise / solve this candidate
+  int* code;                                  // B: TOPT_*
+  const double* out;                          // [nlZ B | failure index B | dnlZ B x Nhyp] of k_nlz_final
+  double *fvals, *fsorted;                    // Ninit
+  int* order;                                 // Ninit, 0-based
+  double* widths;                             // Nhyp
+  double *hist_x, *hist_f;                    // Nopts x hist_cap x Nhyp, Nopts x hist_cap (may be null)
+  int* hist_k;                                // Nopts x hist_cap: the backtracking index of the accepted candidate
+  double *res_nll, *hyp_start;                // Nopts, Nhyp
+  int* best;
+};
+
+// MATLAB's eps(x) for a finite x
+__device__ __forceinline__ double topt_eps(double x) {
+  const double ax = fabs(x);
+  if (ax < 2.2250738585072014e-308) return 4.9406564584124654e-324;
+  int e;
+  (void)frexp(ax, &e);
+  return ldexp(1.0, e - 53);
+}
+__device__ __forceinline__ bool topt_finite(double v) { return v > -__builtin_inf() && v < __builtin_inf(); }
+// min(UB - eps(UB), max(LB + eps(LB), v))   (:272,304): MATLAB's min / max pass over the NaN that eps(Inf) produces
+__device__ __forceinline__ double topt_clamp_in(double v, double lb, double ub) {
+#pragma clang fp contract(off)
+  if (topt_finite(lb)) v = fmax(lb + topt_eps(lb), v);
+  if (topt_finite(ub)) v = fmin(ub - topt_eps(ub), v);
+  return v;
+}
+__device__ __forceinline__ double topt_clip(double v, double lb, double ub) { return fmin(fmax(v, lb), ub); }
+__device__ __forceinline__ double topt_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// One workgroup writes everything the batched gplite_nlZ path needs for candidate b, whose hyper-parameters hv(i) returns.
+template <class HV>
+__device__ __forceinline__ void topt_emit(const ToptArgs& a, int b, HV hv) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N;
+  double* h = a.hyp + (size_t)b * a.Nhyp;
+  for (int i = tid; i < a.Nhyp; i += 256) h[i] = hv(i);
+  // noise variance per training point and its derivatives
+  int idx = a.Ncov, i0 = -1, i1 = -1, i2 = -1;
+  double base = 2.220446049250313e-16, c1 = 0.0, ythr = 0.0, w2 = 0.0;
+  if (a.nf0 == 1) { base = exp(2.0 * hv(idx)); i0 = idx - a.Ncov; idx++; }
+  if (a.nf1 == 2) { c1 = exp(hv(idx)); i1 = idx - a.Ncov; idx++; }
+  if (a.nf2 == 1) { ythr = hv(idx); w2 = exp(2.0 * hv(idx + 1)); i2 = idx - a.Ncov; }
+  double* ds = a.dsn2 + (size_t)b * a.Nnoise * N;
+  double mn = __builtin_inf();
+  for (int n = tid; n < N; n += 256) {
+    double v = base;
+    if (a.nf1 == 1 && a.s2) v += a.s2[n];
+    else if (a.nf1 == 2 && a.s2) v += c1 * a.s2[n];
+    if (i0 >= 0) ds[(size_t)i0 * N + n] = 2.0 * base;
+    if (i1 >= 0) ds[(size_t)i1 * N + n] = a.s2 ? c1 * a.s2[n] : 0.0;
+    if (i2 >= 0) {
+      const double df = ythr - a.y[n], zz = fmax(0.0, df);
+      v += w2 * zz * zz;
+      ds[(size_t)i2 * N + n] = zz > 0.0 ? 2.0 * w2 * df : 0.0;
+      ds[(size_t)(i2 + 1) * N + n] = 2.0 * w2 * zz * zz;
+    }
+    a.sn2[(size_t)b * N + n] = v;
+    mn = fmin(mn, v);
+  }
+  __shared__ double red[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
+  if (lane == 0) red[wave] = mn;
+  __syncthreads();
+  if (tid == 0) {
+    mn = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
+    const bool lch = mn >= 1e-6;
+    double* sc = a.scal + (size_t)b * 4;
+    sc[0] = lch ? mn : 1.0;      // sn2div
+    sc[1] = 1.0;                 // sn2_mult
+    sc[2] = lch ? 1.0 : 0.0;
+    sc[3] = lch ? mn : 1.0;      // sl = sn2div * sn2_mult
+  }
+  if (wave == 0) {
+    double t = 0.0;
+    for (int i = lane; i < a.Nhyp; i += 64) {
+      const int ty = a.has_prior ? a.ptype[i] : 0;
+      double dl = 0.0;
+      if (ty != 0) {
+        const double z = (hv(i) - a.pmu[i]) / a.psig[i], z2 = z * z;
+        if (ty == 1) { t += -0.5 * (a.pc[i] + z2); dl = -z / a.psig[i]; }
+        else {
+          const double nu = a.pdf[i];
+          t += a.pc[i] - 0.5 * (nu + 1.0) * log1p(z2 / nu);
+          dl = -(nu + 1.0) / nu / (1.0 + z2 / nu) * z / a.psig[i];
+        }
+      }
+      a.dlp[(size_t)b * a.Nhyp + i] = dl;
+    }
+    t = wave_sum(t);
+    if (lane == 0) a.lp[b] = t;
+  }
+}
+
+// mode 1: rows c0 + b of the design (the fill stage).  mode 0: candidate j = b % W of start s = b / W.
+__global__ void __launch_bounds__(256) k_topt_propose(ToptArgs a, int mode, int c0, int checked) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (mode == 1) {
+    if (tid == 0) { a.act[b] = 1; a.on[b] = 1; }
+    const int r = c0 + b;
+    topt_emit(a, b, [&](int i) { return a.design[(size_t)r + (size_t)a.Ninit * i]; });
+    return;
+  }
+  const int s = b / a.W, j = b - s * a.W;
+  const ToptStart* st = a.st + s;
+  bool any_stall = false;
+  for (int q = 0; q < a.Nopts; ++q) any_stall |= a.st[q].stall != 0;
+  int code = TOPT_EVAL;
+  double t = 0.0;
+  if (st->done || (any_stall && !checked)) code = TOPT_VOID;
+  else if (!st->started) code = j == 0 ? TOPT_EVAL : TOPT_SKIP;
+  else if (st->k + j >= TOPT_MAXBACK) code = TOPT_EXHAUSTED;
+  else t = ldexp(st->t0, -(st->k + j));
+  const double *x = a.x + (size_t)s * a.Nhyp, *d = a.d + (size_t)s * a.Nhyp;
+  auto cand = [&](int i) { return t == 0.0 ? x[i] : topt_clip(x[i] + t * d[i], a.LB[i], a.UB[i]); };
+  if (code == TOPT_EVAL && st->started) {
+    int neq = 0;
+    for (int i = tid; i < a.Nhyp; i += 256) neq |= cand(i) != x[i];
+    if (!__syncthreads_or(neq)) code = TOPT_ATX;
+  }
+  if (tid == 0) { a.code[b] = code; a.act[b] = code == TOPT_EVAL; a.on[b] = code == TOPT_EVAL; }
+  if (code != TOPT_EVAL) return;                           // (workgroup-uniform)
+  topt_emit(a, b, cand);
+}
+
+// The x10 noise inflation between two tries of a checked factorisation (gplite_core.m:77-80,91-94)
+__global__ void k_topt_retry(int B, const int* __restrict__ pf, double* __restrict__ scal, unsigned char* __restrict__ act) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= B || !act[w]) return;
+  if (pf[w] > 0) {
+    const double m = scal[w * 4 + 1] * 10.0;
+    scal[w * 4 + 1] = m;
+    scal[w * 4 + 3] = scal[w * 4 + 2] != 0.0 ? scal[w * 4 + 0] * m : 1.0;
+  } else act[w] = 0;
+}
+
+// fill values of a chunk: gp_objfun, NaN for a matrix that is not positive definite after the retries (gplite_train.m:542-546)
+__global__ void k_topt_fill_collect(ToptArgs a, int n, int c0) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  a.fvals[c0 + b] = a.out[n + b] > 0.0 ? __builtin_nan("") : a.out[b] - a.lp[b];
+}
+
+// a before b in MATLAB's ascending sort: NaN last, ties in index order
+__device__ __forceinline__ bool topt_before(double fa, int ia, double fb, int ib) {
+  const bool na = fa != fa, nb = fb != fb;
+  if (na != nb) return nb;
+  if (na) return ia < ib;
+  return fa < fb || (fa == fb && ia < ib);
+}
+
+__global__ void __launch_bounds__(256) k_topt_fill_sort(ToptArgs a) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, Ninit = a.Ninit, Nhyp = a.Nhyp, Nopts = a.Nopts;
+  for (int r = tid; r < Ninit; r += 256) {
+    const double fr = a.fvals[r];
+    int rank = 0;
+    for (int q = 0; q < Ninit; ++q) rank += topt_before(a.fvals[q], q, fr, r);
+    a.order[rank] = r;
+    a.fsorted[rank] = fr;
+  }
+  __syncthreads();
+  // the starts: the best Nopts rows (:206) ...
+  for (int e = tid; e < Nopts * Nhyp; e += 256) {
+    const int s = e / Nhyp, i = e - s * Nhyp;
+    a.x[e] = a.design[(size_t)a.order[s] + (size_t)Ninit * i];
+  }
+  __syncthreads();
+  // ... the second one replaced by the best of the fifth of the remaining rows with the smallest noise parameter (:210-221)
+  const int M = Ninit - Nopts;
+  if (a.lownoise && a.Nnoise > 0 && Nopts > 1 && M > 0) {
+    const int m20 = (int)ceil(0.2 * (double)M);
+    __shared__ double bf[256];
+    __shared__ int br[256], bq[256];
+    double best_f = __builtin_nan("");
+    int best_rank = 0x7fffffff, best_q = -1;
+    for (int q = tid; q < M; q += 256) {
+      const double pq = a.design[(size_t)a.order[Nopts + q] + (size_t)Ninit * a.Ncov];
+      int rank = 0;
+      for (int u = 0; u < M; ++u) {
+        const double pu = a.design[(size_t)a.order[Nopts + u] + (size_t)Ninit * a.Ncov];
+        rank += topt_before(pu, u, pq, q);
+      }
+      if (rank >= m20) continue;
+      const double fq = a.fsorted[Nopts + q];
+      // min over noise_y(1:m20): NaN ignored, the first of equal values; all NaN: the first element
+      const bool better = best_q < 0 || (fq == fq && (best_f != best_f || fq < best_f || (fq == best_f && rank < best_rank))) ||
+                          (fq != fq && best_f != best_f && rank < best_rank);
+      if (better) { best_f = fq; best_rank = rank; best_q = q; }
+    }
+    bf[tid] = best_f; br[tid] = best_rank; bq[tid] = best_q;
+    __syncthreads();
+    if (tid == 0) {
+      for (int u = 1; u < 256; ++u) {
+        if (bq[u] < 0) continue;
+        const double fq = bf[u];
+        const bool better = bq[0] < 0 || (fq == fq && (bf[0] != bf[0] || fq < bf[0] || (fq == bf[0] && br[u] < br[0]))) ||
+                            (fq != fq && bf[0] != bf[0] && br[u] < br[0]);
+        if (better) { bf[0] = fq; br[0] = br[u]; bq[0] = bq[u]; }
+      }
+    }
+    __syncthreads();
+    const int row = a.order[Nopts + bq[0]];
+    for (int i = tid; i < Nhyp; i += 256) a.x[(size_t)Nhyp + i] = a.design[(size_t)row + (size_t)Ninit * i];
+    __syncthreads();
+  }
+  // widths_default = std(output_fill.X,[],1) (:207), zero widths repaired (:258-267)
+  for (int i = tid; i < Nhyp; i += 256) {
+    if (a.lownoise) {   // (Ninit > 0 in the caller's terms; the other branch's PUB - PLB stays with the caller)
+      double m = 0.0, v = 0.0;
+      for (int r = 0; r < Ninit; ++r) m += a.design[(size_t)r + (size_t)Ninit * i];
+      m = m / (double)Ninit;
+      for (int r = 0; r < Ninit; ++r) { const double t = a.design[(size_t)r + (size_t)Ninit * i] - m; v += t * t; }
+      double w = Ninit > 1 ? __dsqrt_rn(v / (double)(Ninit - 1)) : 0.0;
+      if (w == 0.0 && Nopts > 1) {
+        m = 0.0; v = 0.0;
+        for (int s = 0; s < Nopts; ++s) m += a.x[(size_t)s * Nhyp + i];
+        m = m / (double)Nopts;
+        for (int s = 0; s < Nopts; ++s) { const double t = a.x[(size_t)s * Nhyp + i] - m; v += t * t; }
+        w = __dsqrt_rn(v / (double)(Nopts - 1));
+      }
+      if (w == 0.0) w = fmin(1.0, a.UB[i] - a.LB[i]);
+      a.widths[i] = w;
+    }
+  }
+  __syncthreads();
+  // inside the bounds (:272); a fixed coordinate sits on its bound
+  for (int e = tid; e < Nopts * Nhyp; e += 256) {
+    const int i = e % Nhyp;
+    const double lb = a.LB[i], ub = a.UB[i];
+    a.x[e] = lb == ub ? lb : topt_clamp_in(a.x[e], lb, ub);
+  }
+}
+
+// One wave per start.
+__global__ void __launch_bounds__(64) k_topt_decide(ToptArgs a, int checked) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.x, lane = threadIdx.x, W = a.W, Nhyp = a.Nhyp, B = a.Nopts * a.W, b0 = s * W;
+  ToptStart* st = a.st + s;
+  if (st->done || a.code[b0] == TOPT_VOID) return;
+  __shared__ double x[TOPT_MAXHYP], g[TOPT_MAXHYP], sv[TOPT_MAXHYP], yv[TOPT_MAXHYP], Hy[TOPT_MAXHYP];
+  double* xg = a.x + (size_t)s * Nhyp;
+  double* gg = a.g + (size_t)s * Nhyp;
+  double* H = a.H + (size_t)s * Nhyp * Nhyp;
+  for (int i = lane; i < Nhyp; i += 64) { x[i] = xg[i]; g[i] = gg[i]; }
+  __syncthreads();
+  int started = st->started, done = 0, exitflag = 0, iterations = st->iterations, k = st->k, fresh = st->fresh, stall = 0;
+  long long funccount = st->funccount, performed = st->performed;
+  double f = st->f, t0 = st->t0, fold = 0.0;
+  performed += __popcll(__ballot(lane < W && a.code[b0 + (lane < W ? lane : 0)] == TOPT_EVAL));
+  const double qnan = __builtin_nan("");
+  int acc_b = -1, acc_k = 0;
+  bool moved = false;
+  if (!started) {
+    const bool pfail = a.out[B + b0] > 0.0;
+    if (pfail && !checked) stall = 1;
+    else {
+      f = pfail ? qnan : a.out[b0] - a.lp[b0];
+      funccount = 1; started = 1; k = 0; fresh = 1; iterations = 0;
+      if (!topt_finite(f)) { done = 1; exitflag = TOPT_EXIT_START; }
+      else acc_b = b0;
+    }
+  } else {
+    for (int j = 0; j < W; ++j) {
+      const int b = b0 + j, code = a.code[b];
+      if (code == TOPT_EXHAUSTED) { done = 1; exitflag = TOPT_EXIT_LINESEARCH; break; }
+      if (code == TOPT_ATX) { done = 1; exitflag = TOPT_EXIT_STEP; break; }
+      if (funccount >= a.max_evals) { done = 1; exitflag = TOPT_EXIT_LIMIT; break; }
+      const bool pfail = a.out[B + b] > 0.0;
+      if (pfail && !checked) { stall = 1; break; }
+      ++funccount;
+      const double val = pfail ? qnan : a.out[b] - a.lp[b];
+      const double* c = a.hyp + (size_t)b * Nhyp;
+      double part = 0.0;
+      for (int i = lane; i < Nhyp; i += 64) part += g[i] * (c[i] - x[i]);
+      const double slope = wave_sum(part);
+      if (topt_finite(val) && val <= f + 1e-4 * slope) { acc_b = b; acc_k = k; fold = f; f = val; moved = true; break; }
+      ++k;
+    }
+  }
+  if (acc_b >= 0) {
+    const double* c = a.hyp + (size_t)acc_b * Nhyp;
+    const double* gn = a.out + 2 * (size_t)B + (size_t)acc_b * Nhyp;
+    const double* dl = a.dlp + (size_t)acc_b * Nhyp;
+    if (moved) {
+      double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+      for (int i = lane; i < Nhyp; i += 64) {
+        const bool fixed = a.LB[i] == a.UB[i];
+        const double si = c[i] - x[i], yi = fixed ? 0.0 : (gn[i] - dl[i]) - g[i];
+        sv[i] = si; yv[i] = yi;
+        p0 += si * yi; p1 += yi * yi; p2 += si * si;
+      }
+      const double sy = wave_sum(p0), yy = wave_sum(p1), ss = wave_sum(p2);
+      __syncthreads();
+      if (sy > 1e-10 * __dsqrt_rn(ss) * __dsqrt_rn(yy)) {           // the update is skipped unless s'y is safely positive
+        if (fresh) {
+          const double gam = sy / yy;
+          for (int e = lane; e < Nhyp * Nhyp; e += 64) H[e] = (e / Nhyp == e % Nhyp) ? gam : 0.0;
+          fresh = 0;
+          __syncthreads();
+        }
+        double p3 = 0.0;
+        for (int i = lane; i < Nhyp; i += 64) {
+          double t = 0.0;
+          for (int j = 0; j < Nhyp; ++j) t += H[(size_t)j * Nhyp + i] * yv[j];     // (H is symmetric: column i read along the lanes)
+          Hy[i] = t;
+          p3 += yv[i] * t;
+        }
+        const double yHy = wave_sum(p3), rho = 1.0 / sy, cc = rho * rho * yHy + rho;
+        __syncthreads();
+        for (int j = 0; j < Nhyp; ++j)
+          for (int i = lane; i < Nhyp; i += 64)
+            H[(size_t)j * Nhyp + i] = H[(size_t)j * Nhyp + i] - rho * (sv[i] * Hy[j] + Hy[i] * sv[j]) + cc * (sv[i] * sv[j]);
+        __syncthreads();
+      }
+      ++iterations;
+      k = 0;
+    }
+    for (int i = lane; i < Nhyp; i += 64) { x[i] = c[i]; g[i] = gn[i] - dl[i]; }
+    __syncthreads();
+    if (moved && a.hist_f && iterations <= a.hist_cap) {
+      const size_t e = (size_t)s * a.hist_cap + (iterations - 1);
+      for (int i = lane; i < Nhyp; i += 64) a.hist_x[e * Nhyp + i] = x[i];
+      if (lane == 0) { a.hist_f[e] = f; a.hist_k[e] = acc_k; }
+    }
+    // stopping tests
+    double pg = 0.0;
+    for (int i = lane; i < Nhyp; i += 64) pg = fmax(pg, fabs(x[i] - topt_clip(x[i] - g[i], a.LB[i], a.UB[i])));
+    pg = topt_wave_max(pg);
+    if (pg <= a.tol) { done = 1; exitflag = TOPT_EXIT_GRAD; }
+    else if (moved && fabs(f - fold) <= a.tol * (1.0 + fabs(f))) { done = 1; exitflag = TOPT_EXIT_DF; }
+    else if (iterations >= a.max_iter || funccount >= a.max_evals) { done = 1; exitflag = TOPT_EXIT_LIMIT; }
+    if (!done) {
+      // free set from the bounds and the gradient's sign, d = -H_FF g_F
+      double p0 = 0.0, p1 = 0.0;
+      for (int i = lane; i < Nhyp; i += 64) {
+        const double lb = a.LB[i], ub = a.UB[i];
+        const bool fr = !(lb == ub) && !(x[i] <= lb && g[i] > 0.0) && !(x[i] >= ub && g[i] < 0.0);
+        yv[i] = fr ? g[i] : 0.0;                      // g_F
+        sv[i] = fr ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      if (!fresh) {
+        for (int i = lane; i < Nhyp; i += 64) {
+          double t = 0.0;
+          for (int j = 0; j < Nhyp; ++j) t += H[(size_t)j * Nhyp + i] * yv[j];
+          Hy[i] = sv[i] != 0.0 ? -t : 0.0;
+          p0 += g[i] * Hy[i];
+        }
+        const double gtd = wave_sum(p0);
+        if (!(gtd < 0.0)) fresh = 1;                  // not a descent direction: back to the identity
+      }
+      if (fresh) {
+        for (int i = lane; i < Nhyp; i += 64) { Hy[i] = -yv[i]; p1 += fabs(yv[i]); }
+        const double g1 = wave_sum(p1);
+        t0 = fmin(1.0, 1.0 / g1);
+      } else t0 = 1.0;
+      double* dg = a.d + (size_t)s * Nhyp;
+      for (int i = lane; i < Nhyp; i += 64) dg[i] = Hy[i];
+    }
+    for (int i = lane; i < Nhyp; i += 64) { xg[i] = x[i]; gg[i] = g[i]; }
+  }
+  if (lane == 0) {
+    st->started = started; st->done = done; st->exitflag = exitflag; st->iterations = iterations; st->k = k; st->fresh = fresh;
+    st->stall = stall; st->rounds = st->rounds + 1; st->funccount = funccount; st->performed = performed; st->f = f; st->t0 = t0;
+  }
+}
+
+// [~,idx] = min(nll); hyp_start inside the bounds, fixed coordinates on their value (:298-306)
+__global__ void __launch_bounds__(64) k_topt_close(ToptArgs a) {
+  const int lane = threadIdx.x;
+  int best = 0;
+  double bv = __builtin_nan("");
+  for (int s = 0; s < a.Nopts; ++s) {
+    const double v = a.st[s].f;
+    if (lane == 0) a.res_nll[s] = v;
+    if (v == v && (bv != bv || v < bv)) { bv = v; best = s; }
+  }
+  if (lane == 0) *a.best = best;
+  for (int i = lane; i < a.Nhyp; i += 64) {
+    const double lb = a.LB[i], ub = a.UB[i];
+    a.hyp_start[i] = lb == ub ? lb : topt_clamp_in(a.x[(size_t)best * a.Nhyp + i], lb, ub);
+  }
+}

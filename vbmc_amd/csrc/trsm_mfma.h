@@ -686,10 +686,12 @@ __global__ void __launch_bounds__(256) k_syrk_tt(int N, const double* __restrict
         }
       }
 }
-// C = T'T for S matrices on stream st (fullneg: C = -T'T, both triangles)
-static inline void syrk_tt_launch(hipStream_t st, int N, int S, const double* TT, const unsigned char* on, double* C, bool fullneg = false) {
+// C = T'T for S matrices on stream st (fullneg: C = -T'T, both triangles).  form: 0 chosen from the amount of work, 1 / 2 the tile
+// form NT of k_syrk_tt (a caller whose results must not depend on its batch size fixes it)
+static inline void syrk_tt_launch(hipStream_t st, int N, int S, const double* TT, const unsigned char* on, double* C, bool fullneg = false,
+                                  int form = 0) {
   const int t64 = (N + 63) / 64, t32 = (N + 31) / 32;
-  const bool small = (size_t)S * t64 * (t64 + 1) / 2 <= 128;
+  const bool small = form ? form == 1 : (size_t)S * t64 * (t64 + 1) / 2 <= 128;
   if (fullneg) {
     if (small) hipLaunchKernelGGL((k_syrk_tt<1, true>), dim3(t32, t32, S), dim3(256), 0, st, N, TT, on, C);
     else hipLaunchKernelGGL((k_syrk_tt<2, true>), dim3(t64, t64, S), dim3(256), 0, st, N, TT, on, C);

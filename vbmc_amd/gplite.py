@@ -407,3 +407,234 @@ def gplite_train_sample(gp, hyp_start, Ns, hprior=None, LB=None, UB=None, widths
     output = {"hyp_prethin": hyp_prethin, "logp": fvals[Thin - 1::Thin].copy(), "logp_prethin": fvals, "widths": out["widths"],
               "funccount": out["funccount"], "performed": out["performed"], "maxshrink": out["maxshrink"]}
     return new, hyp, output
+
+
+def _uuinv(p, B, w):
+    """Inverse cdf of w U(B2, B3) + (1 - w)/2 (U(B1, B2) + U(B3, B4))   (utils/fminfill.m:132-171)"""
+    p = np.asarray(p, dtype=np.float64)
+    x = np.zeros_like(p)
+    L = B[3] - B[0] + B[1] - B[2]
+    if w == 1:
+        return p * (B[2] - B[1]) + B[1]
+    if L == 0:   # a delta at either end and the uniform between
+        i1 = p <= (1 - w) / 2
+        x[i1] = B[0]
+        if w != 0:
+            i2 = (p <= (1 - w) / 2 + w) & ~i1
+            x[i2] = (p[i2] - (1 - w) / 2) * (B[2] - B[1]) / w + B[1]
+        x[p > (1 - w) / 2 + w] = B[3]
+        return x
+    t1 = (1 - w) * (B[1] - B[0]) / L
+    i1 = p <= t1
+    x[i1] = B[0] + p[i1] * L / (1 - w)
+    i2 = (p <= t1 + w) & ~i1
+    if w != 0:
+        x[i2] = (p[i2] - t1) * (B[2] - B[1]) / w + B[1]
+    i3 = p > t1 + w
+    x[i3] = (p[i3] - w - t1) * L / (1 - w) + B[2]
+    x[(p < 0) | (p > 1)] = np.nan
+    return x
+
+
+def fminfill_design(hyp0, LB, UB, PLB, PUB, hprior, Ninit, S=None, *, seed=0):
+    """The points fminfill evaluates (utils/fminfill.m:42-101): the rows of ``hyp0`` (N0 x Nhyp) moved inside the bounds, then
+    Ninit - N0 points mapped from the unit-cube block ``S`` -- the mixture of uniforms over the hard and the plausible box for a
+    coordinate without a prior, the truncated Student-t quantile (df capped at 3, df = 0: normal) for one with a prior.  ``S``
+    defaults to uniform random numbers (VBMC's own design, 'rand', vbmc.m:238); a caller who wants a Sobol design passes its block.
+    Returns Ninit x Nhyp (max(Ninit, N0) rows when hyp0 holds more than Ninit)."""
+    x0 = np.atleast_2d(np.asarray(hyp0, dtype=np.float64))
+    nvars = x0.shape[1]
+    bc = lambda v, dflt: np.broadcast_to(np.asarray(dflt if v is None or np.size(v) == 0 else v, dtype=np.float64).reshape(-1), (nvars,)).copy()
+    LB, UB = bc(LB, -np.inf), bc(UB, np.inf)
+    PLB, PUB = bc(PLB, LB), bc(PUB, UB)
+    x0 = np.maximum(np.minimum(x0, UB), LB)                                      # :44
+    N0, Ninit = x0.shape[0], int(Ninit)
+    if Ninit <= N0:
+        return x0
+    hprior = hprior or {}
+    pad = lambda v: np.concatenate([np.asarray([] if v is None else v, dtype=np.float64).reshape(-1), np.full(nvars, np.nan)])[:nvars]
+    mu, sigma, dfs = pad(hprior.get("mu")), pad(hprior.get("sigma")), pad(hprior.get("df"))
+    if S is None:
+        S = np.random.default_rng(seed).random((Ninit - N0, nvars))
+    S = np.asarray(S, dtype=np.float64)
+    if S.shape != (Ninit - N0, nvars):
+        raise ValueError("fminfill_design: S must be (Ninit - N0) x Nhyp = %d x %d" % (Ninit - N0, nvars))
+    Xs = np.zeros((Ninit - N0, nvars))
+    for i in range(nvars):
+        if not np.isfinite(mu[i]) or not np.isfinite(sigma[i]):
+            if np.isfinite(LB[i]) and np.isfinite(UB[i]):
+                Xs[:, i] = _uuinv(S[:, i], [LB[i], PLB[i], PUB[i], UB[i]], 0.5 ** (1.0 / nvars))   # :77-78
+            else:
+                Xs[:, i] = S[:, i] * (PUB[i] - PLB[i]) + PLB[i]                  # :81
+        else:
+            from scipy import special as sp                                      # lazy: only a design with a prior needs it
+
+            df = dfs[i] if np.isfinite(dfs[i]) else 3.0                          # :85-88
+            df = min(df, 3.0)
+            if df == 0:
+                cdf, inv = sp.ndtr, sp.ndtri
+            else:
+                cdf, inv = (lambda z, v=df: sp.stdtr(v, z)), (lambda q, v=df: sp.stdtrit(v, q))
+            lo, hi = cdf((LB[i] - mu[i]) / sigma[i]), cdf((UB[i] - mu[i]) / sigma[i])
+            Xs[:, i] = inv(lo + (hi - lo) * S[:, i]) * sigma[i] + mu[i]          # :90-93
+    return np.vstack([x0, Xs])
+
+
+def gplite_train_optimize(gp, hyp0, LB, UB, PLB=None, PUB=None, hprior=None, options=None, *, engine=None):
+    """The optimisation half of gplite_train (gplite/gplite_train.m:200-306) in ONE device call (vbmc_gp_train_optimize): fill
+    stage over ``fminfill_design``, the starts, the library's own projected-BFGS optimiser from all Nopts starts in lock-step, the
+    closing.  ``hyp0``: Nhyp or Nhyp x N0 as in the reference.  ``options``: Ninit (1024), Nopts (3), TolFun (1e-5), MaxIter (1000),
+    MaxFunEvals (3000), W (library default), S / seed (the unit-cube block of the design or the seed of its uniform default),
+    Design (the finished Ninit x Nhyp design, instead of S), History (iterations per start to record, 0).
+    Returns a dict: hyp (Nhyp x Nopts), nll, best, hyp_start, widths_default, fill_fvals, fill_order, design, iterations,
+    funccount, exitflag, performed and, with History, hist_x (Nopts x History x Nhyp), hist_f, hist_k."""
+    from ._lib import GpTrainArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    options = dict(options or {})
+    if gp.get("intmeanfun", 0) or gp.get("outwarpfun") is not None or int(np.atleast_1d(gp.get("covfun", 1))[0]) != 1:
+        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train_optimize: integrated mean / output warping / non-SE covariance are not accelerated")
+    X = f64(gp["X"])
+    Np, D = X.shape
+    y = f64(np.asarray(gp["y"], dtype=np.float64).reshape(-1))
+    s2 = gp.get("s2")
+    s2 = None if s2 is None or np.size(s2) == 0 else f64(np.asarray(s2, dtype=np.float64).reshape(-1))
+    H0 = np.asarray(hyp0, dtype=np.float64)
+    H0 = H0.reshape(H0.shape[0], -1)
+    Nhyp, N0 = H0.shape
+    lb = f64(np.broadcast_to(np.asarray(-np.inf if LB is None or np.size(LB) == 0 else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    ub = f64(np.broadcast_to(np.asarray(np.inf if UB is None or np.size(UB) == 0 else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    Ninit, Nopts = int(options.get("Ninit", 1024)), int(options.get("Nopts", 3))
+    if options.get("Design") is not None:
+        design = np.atleast_2d(np.asarray(options["Design"], dtype=np.float64))
+        Ninit = design.shape[0]
+    elif Ninit > 0:
+        design = fminfill_design(H0.T, lb, ub, PLB, PUB, hprior, Ninit, options.get("S"), seed=int(options.get("seed", 0)))
+    else:
+        design = H0.T.copy()
+    design = f64(design)
+    rows = design.shape[0]
+    if design.ndim != 2 or design.shape[1] != Nhyp or (Ninit > 0 and rows != Ninit):
+        raise ValueError("gplite_train_optimize: the design must be Ninit x Nhyp")
+    a = GpTrainArgs()
+    a.struct_size = C.sizeof(GpTrainArgs)
+    a.N, a.D, a.Nhyp, a.meanfun = Np, D, Nhyp, int(gp["meanfun"])
+    nf = [int(v) for v in (list(gp["noisefun"]) + [0, 0, 0])[:3]]
+    for i in range(3):
+        a.noisefun[i] = nf[i]
+    a.X, a.y, a.s2 = ptr(X), ptr(y), ptr(s2)
+    keep = []
+    if hprior is not None and hprior.get("mu") is not None and np.size(hprior.get("mu")) > 0:
+        mu = f64(np.asarray(hprior["mu"], dtype=np.float64).reshape(-1))
+        sg = f64(np.asarray(hprior["sigma"], dtype=np.float64).reshape(-1))
+        df = hprior.get("df")
+        df = None if df is None or np.size(df) == 0 else f64(np.asarray(df, dtype=np.float64).reshape(-1))
+        if mu.size != Nhyp or sg.size != Nhyp or (df is not None and df.size != Nhyp):
+            raise ValueError("gplite_train_optimize: hprior.mu / sigma / df need one entry per hyper-parameter")
+        keep += [mu, sg, df]
+        a.prior_mu, a.prior_sigma, a.prior_df = ptr(mu), ptr(sg), ptr(df)
+    a.LB, a.UB, a.design = ptr(lb), ptr(ub), ptr(design)
+    a.Ninit, a.N0, a.Nopts, a.Ncov = (rows if Ninit > 0 else 0), rows, Nopts, D + 1
+    a.TolFun = float(options.get("TolFun", 1e-5))
+    a.MaxIter, a.MaxFunEvals = int(options.get("MaxIter", 1000)), int(options.get("MaxFunEvals", 3000))
+    W = options.get("W")
+    a.W = 0 if W is None else int(W)
+    cap = int(options.get("History", 0))
+    n_o = max(Nopts, 1)
+    fs, fo, wd = np.zeros(rows), np.zeros(rows, dtype=np.int32), np.full(Nhyp, np.nan)
+    hyp, nll, hs = np.zeros((Nhyp, n_o), order="F"), np.zeros(n_o), np.zeros(Nhyp)
+    its, fcs, efs = np.zeros(n_o, dtype=np.int32), np.zeros(n_o, dtype=np.int64), np.zeros(n_o, dtype=np.int32)
+    best, perf = C.c_int32(0), C.c_int64(0)
+    i32p = C.POINTER(C.c_int32)
+    a.fill_fvals, a.fill_order, a.widths_default = ptr(fs), fo.ctypes.data_as(i32p), ptr(wd)
+    a.hyp, a.nll, a.best, a.hyp_start = ptr(hyp), ptr(nll), C.pointer(best), ptr(hs)
+    a.iterations, a.funccount, a.exitflag = its.ctypes.data_as(i32p), fcs.ctypes.data_as(C.POINTER(C.c_int64)), efs.ctypes.data_as(i32p)
+    a.performed = C.pointer(perf)
+    if cap > 0:
+        hx, hf, hk = np.zeros((n_o, cap, Nhyp)), np.zeros((n_o, cap)), np.zeros((n_o, cap), dtype=np.int32)
+        a.hist_cap, a.hist_x, a.hist_f, a.hist_k = cap, ptr(hx), ptr(hf), hk.ctypes.data_as(i32p)
+    ctx.check(ctx.lib.vbmc_gp_train_optimize(ctx.h, C.byref(a)))
+    if Ninit <= 0:   # :255, the zero widths repaired as in :258-267
+        bc = lambda v, dflt: np.broadcast_to(np.asarray(dflt if v is None or np.size(v) == 0 else v, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+        wd = bc(PUB, ub) - bc(PLB, lb)
+        z = wd == 0
+        if np.any(z) and rows > 1:
+            wd[z] = np.std(design[fo], axis=0, ddof=1)[z]
+        z = wd == 0
+        wd[z] = np.minimum(1.0, ub[z] - lb[z])
+    out = {"hyp": hyp, "nll": nll, "best": int(best.value), "hyp_start": hs, "widths_default": wd, "fill_fvals": fs, "fill_order": fo,
+           "design": design, "iterations": its, "funccount": fcs, "exitflag": efs, "performed": int(perf.value)}
+    if cap > 0:
+        out.update(hist_x=hx, hist_f=hf, hist_k=hk)
+    return out
+
+
+def gplite_train(hyp0, Ns, X, y, covfun=1, meanfun=None, noisefun=None, s2=None, hprior=None, options=None, *, LB=None, UB=None,
+                 PLB=None, PUB=None, need_L=True, engine=None):
+    """[gp,hyp,output] = gplite_train(hyp0,Ns,X,y,covfun,meanfun,noisefun,s2,hprior,options)   (gplite/gplite_train.m:1-489)
+    on the device: the optimisation half (gplite_train_optimize), then -- Ns > 0 -- the slice-sampling half from its hyp_start
+    (gplite_train_sample, widths as in :323-327), or -- Ns = 0 -- the best optimised vector (:463-468), and the closing
+    gplite_post (:474).  Out of scope and refused: options.LogP (the ESS short-cut of :179-198), a Sampler other than
+    'slicesample', and the covariance / mean / noise-function bound defaults of :95-158 -- the caller passes LB, UB (hprior.LB /
+    hprior.UB are read too) and PLB, PUB.  options beyond the reference's: W, seed, S, MaxIter, MaxFunEvals."""
+    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+
+    options = dict(options or {})
+    hprior = dict(hprior or {})
+    if options.get("LogP") is not None and np.size(options["LogP"]) > 0:
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train: options.LogP (the ESS short-cut of gplite_train.m:179-198) is not accelerated")
+    if str(options.get("Sampler", "slicesample")).lower() != "slicesample":
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train: only the 'slicesample' sampler is accelerated")
+    if isinstance(hyp0, dict) or options.get("OutwarpFun") is not None or int(np.atleast_1d(covfun)[0]) != 1:
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train: variational hyp0 / output warping / non-SE covariance are not accelerated")
+    LB = hprior.get("LB") if LB is None else LB
+    UB = hprior.get("UB") if UB is None else UB
+    if LB is None or UB is None or np.size(LB) == 0 or np.size(UB) == 0 or np.any(np.isnan(np.asarray(LB, dtype=np.float64))) \
+            or np.any(np.isnan(np.asarray(UB, dtype=np.float64))):
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train: the bound defaults of gplite_train.m:95-158 are not built: pass LB and UB")
+    X = np.asarray(X, dtype=np.float64)
+    s2 = None if s2 is None or np.size(s2) == 0 else s2
+    meanfun = 1 if meanfun is None else meanfun                                  # :22
+    if noisefun is None or np.size(noisefun) == 0:
+        noisefun = [1, 0, 0] if s2 is None else [1, 1, 0]                        # :25-27
+    H0 = np.asarray(hyp0, dtype=np.float64)
+    H0 = H0.reshape(H0.shape[0], -1)
+    Nhyp = H0.shape[0]
+    Ns = int(Ns)
+    nfl = [int(v) for v in (list(noisefun) + [0, 0, 0])[:3]]
+    D = X.shape[1]
+    Nnoise = (nfl[0] == 1) + (nfl[1] == 2) + 2 * (nfl[2] == 1)
+    gp = {"X": X, "y": np.asarray(y, dtype=np.float64).reshape(-1), "s2": s2, "covfun": 1, "meanfun": int(meanfun), "noisefun": nfl,
+          "Ncov": D + 1, "Nnoise": Nnoise, "Nmean": Nhyp - D - 1 - Nnoise}
+    prior = None
+    if hprior.get("mu") is not None and np.size(hprior["mu"]) > 0:
+        pad = lambda v: np.concatenate([np.asarray([] if v is None else v, dtype=np.float64).reshape(-1), np.full(Nhyp, np.nan)])[:Nhyp]
+        df = pad(hprior.get("df"))
+        df[np.isnan(df)] = float(options.get("DfBase", 7))                       # :113-117
+        prior = {"mu": pad(hprior.get("mu")), "sigma": pad(hprior.get("sigma")), "df": df}
+    LBv = np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+    UBv = np.maximum(LBv, np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (Nhyp,)))   # :142
+    Thin = int(options.get("Thin", 5))
+    tol = float(options.get("TolOptMCMC", 1e-3)) if Ns > 0 else float(options.get("TolOpt", 1e-5))     # :163-167
+    oo = {"Ninit": int(options.get("Ninit", 2 ** 10)), "Nopts": int(options.get("Nopts", 3)), "TolFun": tol}
+    for k in ("W", "seed", "S", "MaxIter", "MaxFunEvals", "Design"):
+        if options.get(k) is not None:
+            oo[k] = options[k]
+    opt = gplite_train_optimize(gp, H0, LBv, UBv, PLB, PUB, prior, oo, engine=engine)
+    output = {"LB": LBv, "UB": UBv, "PLB": PLB, "PUB": PUB, "optimize": opt}
+    if Ns > 0:
+        widths = opt["widths_default"]
+        if options.get("Widths") is not None and np.size(options["Widths"]) > 0:
+            widths = np.minimum(np.asarray(options["Widths"], dtype=np.float64).reshape(-1), widths)   # :326
+        Burnin = options.get("Burnin")
+        new, hyp, so = gplite_train_sample(gp, opt["hyp_start"], Ns, prior, LBv, UBv, widths, Thin=Thin, Burnin=Burnin,
+                                           seed=int(options.get("seed", 0)), W=options.get("W"), need_L=need_L, engine=engine)
+        output.update(hyp_prethin=so["hyp_prethin"], logp=so["logp"], logp_prethin=so["logp_prethin"])
+        return new, hyp, output
+    idx = opt["best"]
+    hyp = opt["hyp"][:, idx:idx + 1].copy()                                      # :464-467
+    new = gplite_post(hyp, X, gp["y"], 1, gp["meanfun"], nfl, s2, need_L=need_L, engine=engine)
+    output.update(hyp_prethin=hyp, logp=-opt["nll"][idx], logp_prethin=-opt["nll"])
+    return new, hyp, output
