@@ -1,6 +1,7 @@
-"""CPU check on the slice sampler's kernels (vbmc_amd/csrc/slice_kernels.h): k_slice_propose, k_slice_retry and k_slice_decide
-compile for gfx950 with no spilled registers and no private segment (the decide kernel keeps the chain's scalars in registers
-across its whole body; a spill there would put the sequential tail of every round through scratch memory)."""
+"""CPU check on the slice sampler's kernels: k_slice_propose and k_slice_decide (vbmc_amd/csrc/slice_kernels.h) and k_gpobj_retry
+(gpobj_kernels.h, which it includes) compile for gfx950 with no spilled registers and no private segment (the decide kernel keeps
+the chain's scalars in registers across its whole body; a spill there would put the sequential tail of every round through scratch
+memory)."""
 import os
 import re
 import subprocess
@@ -8,7 +9,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNELS = ("k_slice_propose", "k_slice_retry", "k_slice_decide")
+KERNELS = ("k_slice_propose", "k_gpobj_retry", "k_slice_decide")
 
 
 def test_slice_kernels_do_not_spill(tmp_path):
@@ -20,7 +21,7 @@ def test_slice_kernels_do_not_spill(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     asm = open(os.path.join(str(tmp_path), "sl-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
     seen = set()
-    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_slice_\S*)\n(.*?)\.wavefront_size", asm, re.S):
+    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_(?:slice|gpobj)_\S*)\n(.*?)\.wavefront_size", asm, re.S):
         name, meta = m.group(2)[: int(m.group(1))], m.group(3)
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
         sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", meta).group(1))
@@ -31,5 +32,6 @@ def test_slice_kernels_do_not_spill(tmp_path):
 
 
 def test_slice_sources_use_no_inline_assembly():
-    txt = open(os.path.join(CSRC, "slice_kernels.h")).read()
-    assert "asm" not in re.sub(r"//.*", "", txt)
+    for name in ("slice_kernels.h", "gpobj_kernels.h"):
+        txt = open(os.path.join(CSRC, name)).read()
+        assert "asm" not in re.sub(r"//.*", "", txt), name

@@ -227,7 +227,7 @@ def test_symbol_in_header_library_and_ctypes():
     a = _lib.GpTrainArgs()
     a.struct_size = C.sizeof(_lib.GpTrainArgs) - 8
     assert lib.vbmc_gp_train_optimize(None, C.byref(a)) == _lib.VBMC_ERR_INVALID
-    src = open(os.path.join(CSRC, "abi_gp.hip")).read()
+    src = open(os.path.join(CSRC, "abi_gp_train.hip")).read()
     assert "args->struct_size != sizeof(vbmc_gptrain_args)" in src
 
 
@@ -240,9 +240,9 @@ def test_trainopt_kernels_compile_for_gfx950_without_scratch(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     asm = open(os.path.join(str(tmp_path), "topt-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
     seen = set()
-    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_topt_\w+)\n(.*?)\.wavefront_size", asm, re.S):
+    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_(?:topt|gpobj)_\w+)\n(.*?)\.wavefront_size", asm, re.S):
         meta = m.group(3)
         assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) == 0, m.group(2)
         assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0, m.group(2)
         seen.add(m.group(2)[:int(m.group(1))])
-    assert seen == {"k_topt_propose", "k_topt_retry", "k_topt_fill_collect", "k_topt_fill_sort", "k_topt_decide", "k_topt_close"}, seen
+    assert seen == {"k_topt_propose", "k_gpobj_retry", "k_topt_fill_collect", "k_topt_fill_sort", "k_topt_decide", "k_topt_close"}, seen

@@ -8,8 +8,7 @@
 // kernels walk that recursion with the same exactly rounded operations (slice_prop), the decide kernel consumes candidates in order,
 // so the chain is the sequential one for every W, bit for bit.
 #pragma once
-#include "common.h"
-#include "device_math.h"
+#include "gpobj_kernels.h"
 
 struct SliceChainState {
   int phase;            // 0: the evaluation at hyp_start is pending, 1: running, 2: finished, 3: stopped with an error
@@ -27,19 +26,15 @@ enum { SLICE_ERR_NONE = 0, SLICE_ERR_COLLAPSE = 1, SLICE_ERR_X0 = 2, SLICE_ERR_U
 #define SLICE_MAXHYP 128
 static_assert(SLICE_MAXHYP >= (VBMC_LIM_D + 1) + 4 + (2 * VBMC_LIM_D + 1), "k_slice_decide keeps Nhyp doubles in LDS arrays of SLICE_MAXHYP");
 
-struct SliceKernelArgs {
-  int N, D, Nhyp, Ncov, W, Kmax, Ns, thin, burn, adaptive, total, parity, nf0, nf1, nf2, has_base, has_prior;
+struct SliceKernelArgs : GpObjArgs {           // (hyp, sn2, scal, lp: one row per speculative candidate, W of them)
+  int D, W, Kmax, Ns, thin, burn, adaptive, total, parity, has_base;
   unsigned long long seed;
-  const double *y, *s2;                       // N (s2 may be null)
   const double *LB, *UB, *LBo, *UBo;          // Nhyp: bounds, LB - eps(LB), UB + eps(UB)
-  const double *pmu, *psig, *pdf, *pc;        // Nhyp: hyper-prior location, scale, degrees of freedom, normalising term
-  const int* ptype;                           // Nhyp: 0 flat, 1 Gaussian, 2 Student-t
   const double* basew;                        // Nhyp: the caller's widths (:166)
   const int* perms;                           // total x Nhyp, 0-based
   const double* U;                            // parity: total x Nhyp x (2 + Kmax)
   SliceChainState* st;
   double *xx, *widths, *xsum, *xsq;           // Nhyp each
-  double *hyp, *sn2, *scal, *lp;              // W x Nhyp, W x N, W x 4, W
   unsigned char *act, *on;                    // W: factorise / solve this candidate
   const double* out;                          // [nlZ W | failure index W] of k_nlz_final
   double *samples, *logp;                     // Ns x Nhyp (column-major), Ns
@@ -85,15 +80,6 @@ __device__ __forceinline__ double slice_prop(double u, double xl, double xr) {
   return u * (xr - xl) + xl;
 }
 
-// MATLAB's eps(x) for a finite x
-__device__ __forceinline__ double slice_eps(double x) {
-  const double ax = fabs(x);
-  if (ax < 2.2250738585072014e-308) return 4.9406564584124654e-324;
-  int e;
-  (void)frexp(ax, &e);
-  return ldexp(1.0, e - 53);
-}
-
 // One workgroup per candidate w: the candidate's hyper-parameter vector, its noise vector / Cholesky branch (gplite_core.m:33-40,67,
 // gplite_noisefun.m:176-210) and its hyper-prior (gplite_hypprior.m:17-65).  checked != 0: the host's answer to a stall.
 __global__ void __launch_bounds__(256) k_slice_propose(SliceKernelArgs a, int checked) {
@@ -123,63 +109,7 @@ __global__ void __launch_bounds__(256) k_slice_propose(SliceKernelArgs a, int ch
   }
   if (tid == 0) { a.act[w] = active; a.on[w] = active; }
   if (!active) return;                                    // (workgroup-uniform)
-  double* h = a.hyp + (size_t)w * a.Nhyp;
-  for (int i = tid; i < a.Nhyp; i += 256) h[i] = i == dd ? xp : a.xx[i];
-  auto hv = [&](int i) { return i == dd ? xp : a.xx[i]; };
-  // noise variance per training point
-  int idx = a.Ncov;
-  double base = 2.220446049250313e-16, c1 = 0.0, ythr = 0.0, w2 = 0.0;
-  if (a.nf0 == 1) { base = exp(2.0 * hv(idx)); idx++; }
-  if (a.nf1 == 2) { c1 = exp(hv(idx)); idx++; }
-  if (a.nf2 == 1) { ythr = hv(idx); w2 = exp(2.0 * hv(idx + 1)); }
-  double mn = __builtin_inf();
-  for (int n = tid; n < a.N; n += 256) {
-    double v = base;
-    if (a.nf1 == 1 && a.s2) v += a.s2[n];
-    else if (a.nf1 == 2 && a.s2) v += c1 * a.s2[n];
-    if (a.nf2 == 1) { const double zz = fmax(0.0, ythr - a.y[n]); v += w2 * zz * zz; }
-    a.sn2[(size_t)w * a.N + n] = v;
-    mn = fmin(mn, v);
-  }
-  __shared__ double red[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
-  if (lane == 0) red[wave] = mn;
-  __syncthreads();
-  if (tid == 0) {
-    mn = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-    const bool lch = mn >= 1e-6;
-    double* sc = a.scal + (size_t)w * 4;
-    sc[0] = lch ? mn : 1.0;      // sn2div
-    sc[1] = 1.0;                 // sn2_mult
-    sc[2] = lch ? 1.0 : 0.0;
-    sc[3] = lch ? mn : 1.0;      // sl = sn2div * sn2_mult
-  }
-  if (wave == 0) {
-    double t = 0.0;
-    if (a.has_prior)
-      for (int i = lane; i < a.Nhyp; i += 64) {
-        const int ty = a.ptype[i];
-        if (ty == 0) continue;
-        const double z = (hv(i) - a.pmu[i]) / a.psig[i], z2 = z * z;
-        if (ty == 1) t += -0.5 * (a.pc[i] + z2);
-        else t += a.pc[i] - 0.5 * (a.pdf[i] + 1.0) * log1p(z2 / a.pdf[i]);
-      }
-    t = wave_sum(t);
-    if (lane == 0) a.lp[w] = t;
-  }
-}
-
-// The x10 noise inflation of a checked round (gplite_core.m:77-80,91-94) between two tries of the factorisation: a matrix that
-// came out positive definite is switched off, one that failed gets ten times the jitter.
-__global__ void k_slice_retry(int W, const int* __restrict__ pf, double* __restrict__ scal, unsigned char* __restrict__ act) {
-  const int w = threadIdx.x;
-  if (w >= W || !act[w]) return;
-  if (pf[w] > 0) {
-    const double m = scal[w * 4 + 1] * 10.0;
-    scal[w * 4 + 1] = m;
-    scal[w * 4 + 3] = scal[w * 4 + 2] != 0.0 ? scal[w * 4 + 0] * m : 1.0;
-  } else act[w] = 0;
+  gpobj_emit<false>(a, w, [&](int i) { return i == dd ? xp : a.xx[i]; });
 }
 
 // One wave.  Lane j judges candidate j; the first terminal event in candidate order (accept, exhausted uniforms, a failed first try,
@@ -260,7 +190,7 @@ __global__ void __launch_bounds__(64) k_slice_decide(SliceKernelArgs a, int chec
         if (sweep + 1 <= a.burn && a.adaptive && lane == 0) {
           const double delta = a.UB[dd] - a.LB[dd];
           const bool fin = delta > ninf && delta < __builtin_inf();
-          if (shrink > 3) wd[dd] = fmax(wd[dd] / 1.1, fin ? slice_eps(delta) : 2.220446049250313e-16);
+          if (shrink > 3) wd[dd] = fmax(wd[dd] / 1.1, fin ? matlab_eps(delta) : 2.220446049250313e-16);
           else if (shrink < 2) wd[dd] = fmin(wd[dd] * 1.2, delta);
         }
         if (lane == 0) xx[dd] = f_xp;                                // (:325)

@@ -11,8 +11,7 @@
 // candidates in order, so iterates, values, iterations and funccount are the sequential algorithm's for every W, bit for bit.
 // The optimiser's own arithmetic is written with plain operators in scopes with contraction off (see slice_prop in slice_kernels.h).
 #pragma once
-#include "common.h"
-#include "device_math.h"
+#include "gpobj_kernels.h"
 
 #define TOPT_MAXHYP 128
 #define TOPT_MAXOPTS 16
@@ -38,18 +37,14 @@ struct ToptStart {      // the progress word of one start (the host reads the No
   double f, t0;
 };
 
-struct ToptArgs {
-  int N, D, Nhyp, Ncov, Nnoise, Nopts, W, Ninit, nf0, nf1, nf2, has_prior, max_iter, hist_cap, lownoise;
+struct ToptArgs : GpObjArgs {                  // (hyp .. dsn2: one row per candidate, B = max(Nopts x W, fill chunk) of them)
+  int D, Nopts, W, Ninit, max_iter, hist_cap, lownoise;
   long long max_evals;
   double tol;
-  const double *y, *s2;                       // N (s2 may be null)
   const double *LB, *UB;                      // Nhyp
-  const double *pmu, *psig, *pdf, *pc;        // Nhyp: hyper-prior location, scale, degrees of freedom, normalising term
-  const int* ptype;                           // Nhyp: 0 flat, 1 Gaussian, 2 Student-t
   const double* design;                       // Ninit x Nhyp, column-major
   ToptStart* st;                              // Nopts
   double *x, *g, *d, *H;                      // Nopts x Nhyp (x 3), Nopts x Nhyp x Nhyp
-  double *hyp, *sn2, *scal, *lp, *dlp, *dsn2; // B x Nhyp, B x N, B x 4, B, B x Nhyp, B x Nnoise x N
   unsigned char *act, *on;                    // B: factorise / solve this candidate
   int* code;                                  // B: TOPT_*
   const double* out;                          // [nlZ B | failure index B | dnlZ B x Nhyp] of k_nlz_final
@@ -62,20 +57,12 @@ struct ToptArgs {
   int* best;
 };
 
-// MATLAB's eps(x) for a finite x
-__device__ __forceinline__ double topt_eps(double x) {
-  const double ax = fabs(x);
-  if (ax < 2.2250738585072014e-308) return 4.9406564584124654e-324;
-  int e;
-  (void)frexp(ax, &e);
-  return ldexp(1.0, e - 53);
-}
 __device__ __forceinline__ bool topt_finite(double v) { return v > -__builtin_inf() && v < __builtin_inf(); }
 // min(UB - eps(UB), max(LB + eps(LB), v))   (:272,304): MATLAB's min / max pass over the NaN that eps(Inf) produces
 __device__ __forceinline__ double topt_clamp_in(double v, double lb, double ub) {
 #pragma clang fp contract(off)
-  if (topt_finite(lb)) v = fmax(lb + topt_eps(lb), v);
-  if (topt_finite(ub)) v = fmin(ub - topt_eps(ub), v);
+  if (topt_finite(lb)) v = fmax(lb + matlab_eps(lb), v);
+  if (topt_finite(ub)) v = fmin(ub - matlab_eps(ub), v);
   return v;
 }
 __device__ __forceinline__ double topt_clip(double v, double lb, double ub) { return fmin(fmax(v, lb), ub); }
@@ -85,71 +72,6 @@ __device__ __forceinline__ double topt_wave_max(double v) {
   return v;
 }
 
-// One workgroup writes everything the batched gplite_nlZ path needs for candidate b, whose hyper-parameters hv(i) returns.
-template <class HV>
-__device__ __forceinline__ void topt_emit(const ToptArgs& a, int b, HV hv) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = a.N;
-  double* h = a.hyp + (size_t)b * a.Nhyp;
-  for (int i = tid; i < a.Nhyp; i += 256) h[i] = hv(i);
-  // noise variance per training point and its derivatives
-  int idx = a.Ncov, i0 = -1, i1 = -1, i2 = -1;
-  double base = 2.220446049250313e-16, c1 = 0.0, ythr = 0.0, w2 = 0.0;
-  if (a.nf0 == 1) { base = exp(2.0 * hv(idx)); i0 = idx - a.Ncov; idx++; }
-  if (a.nf1 == 2) { c1 = exp(hv(idx)); i1 = idx - a.Ncov; idx++; }
-  if (a.nf2 == 1) { ythr = hv(idx); w2 = exp(2.0 * hv(idx + 1)); i2 = idx - a.Ncov; }
-  double* ds = a.dsn2 + (size_t)b * a.Nnoise * N;
-  double mn = __builtin_inf();
-  for (int n = tid; n < N; n += 256) {
-    double v = base;
-    if (a.nf1 == 1 && a.s2) v += a.s2[n];
-    else if (a.nf1 == 2 && a.s2) v += c1 * a.s2[n];
-    if (i0 >= 0) ds[(size_t)i0 * N + n] = 2.0 * base;
-    if (i1 >= 0) ds[(size_t)i1 * N + n] = a.s2 ? c1 * a.s2[n] : 0.0;
-    if (i2 >= 0) {
-      const double df = ythr - a.y[n], zz = fmax(0.0, df);
-      v += w2 * zz * zz;
-      ds[(size_t)i2 * N + n] = zz > 0.0 ? 2.0 * w2 * df : 0.0;
-      ds[(size_t)(i2 + 1) * N + n] = 2.0 * w2 * zz * zz;
-    }
-    a.sn2[(size_t)b * N + n] = v;
-    mn = fmin(mn, v);
-  }
-  __shared__ double red[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
-  if (lane == 0) red[wave] = mn;
-  __syncthreads();
-  if (tid == 0) {
-    mn = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-    const bool lch = mn >= 1e-6;
-    double* sc = a.scal + (size_t)b * 4;
-    sc[0] = lch ? mn : 1.0;      // sn2div
-    sc[1] = 1.0;                 // sn2_mult
-    sc[2] = lch ? 1.0 : 0.0;
-    sc[3] = lch ? mn : 1.0;      // sl = sn2div * sn2_mult
-  }
-  if (wave == 0) {
-    double t = 0.0;
-    for (int i = lane; i < a.Nhyp; i += 64) {
-      const int ty = a.has_prior ? a.ptype[i] : 0;
-      double dl = 0.0;
-      if (ty != 0) {
-        const double z = (hv(i) - a.pmu[i]) / a.psig[i], z2 = z * z;
-        if (ty == 1) { t += -0.5 * (a.pc[i] + z2); dl = -z / a.psig[i]; }
-        else {
-          const double nu = a.pdf[i];
-          t += a.pc[i] - 0.5 * (nu + 1.0) * log1p(z2 / nu);
-          dl = -(nu + 1.0) / nu / (1.0 + z2 / nu) * z / a.psig[i];
-        }
-      }
-      a.dlp[(size_t)b * a.Nhyp + i] = dl;
-    }
-    t = wave_sum(t);
-    if (lane == 0) a.lp[b] = t;
-  }
-}
-
 // mode 1: rows c0 + b of the design (the fill stage).  mode 0: candidate j = b % W of start s = b / W.
 __global__ void __launch_bounds__(256) k_topt_propose(ToptArgs a, int mode, int c0, int checked) {
 #pragma clang fp contract(off)
@@ -157,7 +79,7 @@ __global__ void __launch_bounds__(256) k_topt_propose(ToptArgs a, int mode, int 
   if (mode == 1) {
     if (tid == 0) { a.act[b] = 1; a.on[b] = 1; }
     const int r = c0 + b;
-    topt_emit(a, b, [&](int i) { return a.design[(size_t)r + (size_t)a.Ninit * i]; });
+    gpobj_emit<true>(a, b, [&](int i) { return a.design[(size_t)r + (size_t)a.Ninit * i]; });
     return;
   }
   const int s = b / a.W, j = b - s * a.W;
@@ -179,18 +101,7 @@ __global__ void __launch_bounds__(256) k_topt_propose(ToptArgs a, int mode, int 
   }
   if (tid == 0) { a.code[b] = code; a.act[b] = code == TOPT_EVAL; a.on[b] = code == TOPT_EVAL; }
   if (code != TOPT_EVAL) return;                           // (workgroup-uniform)
-  topt_emit(a, b, cand);
-}
-
-// The x10 noise inflation between two tries of a checked factorisation (gplite_core.m:77-80,91-94)
-__global__ void k_topt_retry(int B, const int* __restrict__ pf, double* __restrict__ scal, unsigned char* __restrict__ act) {
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= B || !act[w]) return;
-  if (pf[w] > 0) {
-    const double m = scal[w * 4 + 1] * 10.0;
-    scal[w * 4 + 1] = m;
-    scal[w * 4 + 3] = scal[w * 4 + 2] != 0.0 ? scal[w * 4 + 0] * m : 1.0;
-  } else act[w] = 0;
+  gpobj_emit<true>(a, b, cand);
 }
 
 // fill values of a chunk: gp_objfun, NaN for a matrix that is not positive definite after the retries (gplite_train.m:542-546)

@@ -1,4 +1,5 @@
-// Single translation unit of libvbmc_hip.so: the kernels live in headers shared by both ABI files.
+// Single translation unit of libvbmc_hip.so: the kernels live in headers shared by the ABI files.
 #include "abi_elbo.hip"
 #include "abi_gp.hip"
+#include "abi_gp_train.hip"
 #include "abi_comm.hip"
