@@ -123,7 +123,7 @@ vbmc_status vbmc_gp_post(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, int meanf
 
 /*
  * acq = acqwrapper_vbmc(Xs,vp,gp,optimState,0,acqFun,acqInfo)   (acq/acqwrapper_vbmc.m:11-46) for the
- * density-based acquisition functions, with vp.delta = 0: gplite_pred for every hyper-sample (:17), fbar / vtot
+ * density-based acquisition functions, with vp.delta = 0 (vbmc_acq_eval_delta otherwise): gplite_pred for every hyper-sample (:17), fbar / vtot
  * (:21-29), p = max(vbmc_pdf(vp,Xs,0),realmin), then
  *   acq_id 0  acqf_vbmc     -vtot .* exp(fbar - ymax) .* p                       (acq/acqf_vbmc.m:9-10)
  *   acq_id 1  acqflog_vbmc  -(log(vtot) + fbar - ymax + log(p))                  (acq/acqflog_vbmc.m:17-18)
@@ -139,6 +139,18 @@ vbmc_status vbmc_acq_eval(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const dou
                           const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
                           double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
                           const double* X_rescaled, const double* sn2new, double* acq, double* fbar, double* vtot);
+/*
+ * The same sweep with vp.delta > 0 (acq/acqwrapper_vbmc.m:12-14): the mean and variance per hyper-sample come from
+ * gplite_quad(gp,Xs,vp.delta',1) -- the quadrature pass of vbmc_gp_quad, left on the device -- instead of gplite_pred, and
+ * everything from fbar / vtot on is unchanged.  delta: D values, non-negative.  acq_id 0-3; a delta that is all zero is
+ * VBMC_ERR_INVALID (the reference takes the gplite_pred branch then: call vbmc_acq_eval).  The importance-sampled IQR
+ * functions with delta > 0 are not accelerated.
+ */
+vbmc_status vbmc_acq_eval_delta(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
+                                const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
+                                double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
+                                const double* X_rescaled, const double* sn2new, double* acq, double* fbar, double* vtot,
+                                const double* delta);
 
 /*
  * Importance-sampled IQR acquisition functions: acqviqr_vbmc (acq/acqviqr_vbmc.m:36-109) and acqimiqr_vbmc
@@ -334,6 +346,21 @@ vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_args* args)
  */
 vbmc_status vbmc_gp_pred(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* Xstar, const double* ystar,
                          const double* s2star, int ssflag, double* ymu, double* ys2, double* fmu, double* fs2);
+
+/*
+ * [F,varF] = gplite_quad(gp, mu, sigma, ssflag)   (gplite/gplite_quad.m:1-119): the Bayesian-quadrature integral of the GP
+ * against N(mu_i, diag sigma^2) for every row mu_i of mu (Nstar x D, column-major), per hyper-sample
+ *   z = exp(lnnf - 1/2 sum_d ((mu_id - X_nd) / tau_d)^2), tau = sqrt(sigma^2 + ell^2)      (:70-76)
+ *   F = z alpha + m0 + nu                                                                    (:77-82)
+ *   varF = max(eps, nf_kk - z inv(K) z')                                                     (:98-106)
+ * with the same kernels, launch forms and limits as vbmc_gp_pred (needs L on the device and vbmc_gp_set_noise).
+ * sigma is sigma_rows x D with sigma_rows = 1 (one row shared by all points: the only form a reference caller uses) or
+ * sigma_rows = Nstar with all rows equal; distinct rows are VBMC_ERR_UNSUPPORTED (the distance is then no longer one scaled
+ * product).  Mean functions 0, 1 and 4.  ssflag = 0: Nstar values averaged over the hyper-samples with the between-sample
+ * variance added (:112-119); ssflag = 1: Nstar x S.  varF may be NULL.
+ */
+vbmc_status vbmc_gp_quad(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* mu, const double* sigma, int sigma_rows,
+                         int ssflag, double* F, double* varF);
 
 /*
  * The O(N^2) pieces of gplite_post's rank-1 append of one training point x* (gplite/gplite_post.m:173-251),

@@ -24,6 +24,10 @@
 //     [alpha,L,sW,sn2_mult,Lchol,h] = vbmc_hip_mex('gp_post', hyp, X, y, s2, meanfun, noisefun)
 //     [ymu,ys2,fmu,fs2] = vbmc_hip_mex('gp_pred', h, Xstar, s2star, ssflag)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq', h, Xs, acq_id, vp, ymax, var_regularized, TolGPVar, gplengthscale, X_rescaled, sn2new)
+//     [acq,fbar,vtot] = vbmc_hip_mex('acq_delta', h, Xs, acq_id, vp, ymax, var_regularized, TolGPVar, delta, gplengthscale, X_rescaled, sn2new)
+//                                ('acq' with vp.delta > 0: mean and variance per hyper-sample from gplite_quad(gp,Xs,delta,1),
+//                                 acqwrapper_vbmc.m:12-14; delta: D values; the last three only for acqfsn2)
+//     [F,varF] = vbmc_hip_mex('gp_quad', h, mu, sigma, ssflag, numel(gp.post))   (gplite_quad: sigma 1 x D, or Nstar x D of equal rows)
 //     his = vbmc_hip_mex('is_create', h, Xa, lnw_or_empty, fs2a_or_empty, Ctmp_or_empty)   (ActiveImportanceSampling state)
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
@@ -238,7 +242,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad"};
     for (const char* w : with_handle)
       if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || (!strcmp(cmd, "acq_iqr") && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
@@ -487,6 +491,42 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     if (st != VBMC_OK) return fail(st);
     if (nlhs > 1) plhs[1] = fb;
     if (nlhs > 2) plhs[2] = vt;
+    return 0;
+  }
+
+  if (!strcmp(cmd, "acq_delta")) {
+    if (nrhs < 9) return raise("vbmc_hip:usage", "acq_delta: h, Xs, acq_id, vp, ymax, var_regularized, TolGPVar, delta");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    const mxArray *Xs = prhs[2], *vp = prhs[4];
+    const int Nstar = (int)mxGetM(Xs), D = (int)mxGetN(Xs);
+    if ((int)mxGetNumberOfElements(prhs[8]) != D) return raise("vbmc_hip:usage", "acq_delta: delta must hold one value per dimension");
+    plhs[0] = mxCreateDoubleMatrix(Nstar, 1, mxREAL);
+    mxArray *fb = mxCreateDoubleMatrix(Nstar, 1, mxREAL), *vt = mxCreateDoubleMatrix(Nstar, 1, mxREAL);
+    vbmc_status st = vbmc_acq_eval_delta(g_ctx, h, Nstar, mxGetDoubles(Xs), (int)mxGetScalar(prhs[3]), (int)scalar_field(vp, "K", 0),
+                                         dbl(field(vp, "mu")), dbl(field(vp, "sigma")), dbl(field(vp, "lambda")), dbl(field(vp, "w")),
+                                         mxGetScalar(prhs[5]), (int)mxGetScalar(prhs[6]), mxGetScalar(prhs[7]),
+                                         nrhs > 9 ? dbl(prhs[9]) : nullptr, nrhs > 10 ? dbl(prhs[10]) : nullptr, nrhs > 11 ? dbl(prhs[11]) : nullptr,
+                                         mxGetDoubles(plhs[0]), mxGetDoubles(fb), mxGetDoubles(vt), mxGetDoubles(prhs[8]));
+    if (nlhs > 1) plhs[1] = fb; else mxDestroyArray(fb);
+    if (nlhs > 2) plhs[2] = vt; else mxDestroyArray(vt);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "gp_quad")) {
+    if (nrhs < 6) return raise("vbmc_hip:usage", "gp_quad: h, mu, sigma, ssflag, numel(gp.post)");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    const mxArray *mu = prhs[2], *sg = prhs[3];
+    const int Nstar = (int)mxGetM(mu), D = (int)mxGetN(mu), ss = (int)mxGetScalar(prhs[4]), S = (int)mxGetScalar(prhs[5]);
+    const int rows = (int)mxGetM(sg);
+    if ((int)mxGetN(sg) != D || (rows != 1 && rows != Nstar)) return raise("vbmc_hip:usage", "gp_quad: sigma must be 1 x D or Nstar x D");
+    const int nc = (ss && S > 1) ? S : 1;
+    plhs[0] = mxCreateDoubleMatrix(Nstar, nc, mxREAL);
+    mxArray* vf = nlhs > 1 ? mxCreateDoubleMatrix(Nstar, nc, mxREAL) : nullptr;
+    vbmc_status st = vbmc_gp_quad(g_ctx, h, Nstar, mxGetDoubles(mu), mxGetDoubles(sg), rows, ss || S == 1, mxGetDoubles(plhs[0]),
+                                  vf ? mxGetDoubles(vf) : nullptr);
+    if (vf) plhs[1] = vf;
+    if (st != VBMC_OK) return fail(st);
     return 0;
   }
 

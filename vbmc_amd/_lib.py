@@ -167,6 +167,8 @@ def load():
     lib.vbmc_gp_rank1_update.argtypes = [vp, vp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, C.POINTER(vp)]
     lib.vbmc_acq_eval.argtypes = [vp, vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_int, C.c_double,
                                   _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.vbmc_acq_eval_delta.argtypes = lib.vbmc_acq_eval.argtypes + [_dp]
+    lib.vbmc_gp_quad.argtypes = [vp, vp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_acq_is_create.argtypes = [vp, vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.POINTER(vp)]
     lib.vbmc_acq_is_free.argtypes = [vp, vp]
     lib.vbmc_acq_is_free.restype = None

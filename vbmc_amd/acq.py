@@ -72,16 +72,21 @@ def acq_info(acqFun):
 
 
 def acqwrapper_vbmc(Xs, vp, gp, optimState, transpose_flag=False, acqFun="acqf_vbmc", acqInfo=None, *, outside=None,
-                    nargout=1, engine=None, shard=None):
+                    nargout=1, engine=None, shard=None, delta_quad=False):
     """acq = acqwrapper_vbmc(Xs,vp,gp,optimState,transpose_flag,acqFun,acqInfo).
 
     ``optimState`` keys used: ymax, VarianceRegularizedAcqFcn, TolGPVar (+ gplengthscale for acqfsn2 / acqviqr /
     acqimiqr, whose gp needs X_rescaled and sn2new, + ActiveImportanceSampling for the IQR functions).
     ``nargout=3`` also returns (fbar, vtot) of :21-29.
 
+    ``delta_quad=True``: with any(vp.delta > 0) the mean and variance per hyper-sample come from the quadrature pass
+    gplite_quad(gp,Xs,vp.delta',1) (:12-14) on the device (``vbmc_acq_eval_delta``; the four density-based functions).  The default
+    keeps refusing vp.delta > 0 with VbmcUnsupported.
+
     Sharded form: ``shard`` = (rank, world, allgather) from vbmc_amd.dist.shard_spec() makes every rank evaluate the
     test points i = rank (mod world) on its own GPU (full GP replica) and all-gather the acquisition values, so that
     all ranks hold the identical vector and pick the identical argmin (private/activesample_vbmc.m:227-233)."""
+    quad_kw = {"delta_quad": True} if delta_quad else {}
     if shard is not None:
         rank, world, allgather = shard
         X_ = np.asarray(Xs, dtype=np.float64)
@@ -92,24 +97,27 @@ def acqwrapper_vbmc(Xs, vp, gp, optimState, transpose_flag=False, acqFun="acqf_v
         idx = np.arange(n)[rank::world]
         out_l = None if outside is None else np.asarray(outside, dtype=bool).reshape(-1)[idx]
         if idx.size:
-            loc = _acq_local(X_[idx], vp, gp, optimState, acqFun, out_l, 3, engine)
+            loc = _acq_local(X_[idx], vp, gp, optimState, acqFun, out_l, 3, engine, **quad_kw)
         else:
             loc = (np.zeros(0), np.zeros(0), np.zeros(0))
         full = [allgather(v, idx, n) for v in (loc if nargout >= 3 else loc[:1])]
         acq = full[0].reshape(1, -1) if transpose_flag else full[0]
         return (acq, full[1], full[2]) if nargout >= 3 else acq
-    return _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpose_flag)
+    return _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpose_flag, **quad_kw)
 
 
-def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpose_flag=False):
+def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpose_flag=False, delta_quad=False):
     """The single-GPU evaluation behind acqwrapper_vbmc (one fused device pass)."""
     engine = engine or default_engine()
     ctx = engine.ctx
     info = acq_info(acqFun)
     acq_id = ACQ_IDS[info["name"]]
     delta = vp.get("delta")
-    if delta is not None and np.any(np.asarray(delta) > 0):
+    use_quad = delta is not None and np.size(delta) > 0 and bool(np.any(np.asarray(delta) > 0))    # :12
+    if use_quad and not delta_quad:
         raise VbmcUnsupported(-1, "vp.delta > 0 (gplite_quad, acqwrapper_vbmc.m:12-14) is not accelerated")
+    if use_quad and acq_id >= 10:
+        raise VbmcUnsupported(-1, "vp.delta > 0 with %s is not accelerated" % info["name"])
     Xs = np.asarray(Xs, dtype=np.float64)
     if transpose_flag:
         Xs = Xs.T
@@ -145,9 +153,15 @@ def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpo
     acq = np.zeros(Nstar)
     fbar = np.zeros(Nstar)
     vtot = np.zeros(Nstar)
-    ctx.check(ctx.lib.vbmc_acq_eval(ctx.h, dgp.h, Nstar, ptr(Xs), acq_id, K, ptr(mu), ptr(sigma), ptr(lam), ptr(w),
-                                    float(optimState.get("ymax", 0.0)), int(bool(optimState.get("VarianceRegularizedAcqFcn", False))),
-                                    float(optimState.get("TolGPVar", 0.0)), ptr(gl), ptr(xr), ptr(sn), ptr(acq), ptr(fbar), ptr(vtot)))
+    args = (ctx.h, dgp.h, Nstar, ptr(Xs), acq_id, K, ptr(mu), ptr(sigma), ptr(lam), ptr(w),
+            float(optimState.get("ymax", 0.0)), int(bool(optimState.get("VarianceRegularizedAcqFcn", False))),
+            float(optimState.get("TolGPVar", 0.0)), ptr(gl), ptr(xr), ptr(sn), ptr(acq), ptr(fbar), ptr(vtot))
+    if use_quad:
+        dl = np.asarray(delta, dtype=np.float64).reshape(-1)
+        dl = f64(np.full(D, dl[0]) if dl.size == 1 else dl.reshape(D))     # gplite_quad's bsxfun admits a scalar (:70)
+        ctx.check(ctx.lib.vbmc_acq_eval_delta(*args, ptr(dl)))
+    else:
+        ctx.check(ctx.lib.vbmc_acq_eval(*args))
     if outside is not None:
         acq = np.where(np.asarray(outside, dtype=bool).reshape(-1), np.inf, acq)   # :49-51
     if transpose_flag:

@@ -1,4 +1,4 @@
-// C-ABI entry points for the gplite GP surrogate: vbmc_sq_dist, vbmc_gp_post, vbmc_gp_pred
+// C-ABI entry points for the gplite GP surrogate: vbmc_sq_dist, vbmc_gp_post, vbmc_gp_pred, vbmc_gp_quad
 // (include/vbmc_hip.h).  Host side: O(N) hyper-parameter transforms, the Cholesky jitter-retry
 // loop (gplite_core.m:77-80,91-94), launches, D2H of the posterior.
 #include <functional>
@@ -576,15 +576,17 @@ extern "C" vbmc_status vbmc_gp_set_noise(vbmc_ctx* ctx, vbmc_gp* gp, const int32
 // ------------------------------------------------------------------------------------------
 namespace {
 struct PredBufs {
-  TmpBuf dXs, ds2, dys, dmb, dout, dXc, daa, dmuv, dgrp, dpV, dpF, dKs;
+  TmpBuf dXs, ds2, dys, dmb, dout, dXc, daa, dmuv, dgrp, dpV, dpF, dKs, dqs, dqn;
   double *fmu = nullptr, *fs2 = nullptr, *ys2 = nullptr;   // Nstar x S each, inside dout
 };
 
 // gplite_pred for every hyper-sample, results left on the device (shared by vbmc_gp_pred and vbmc_acq_eval)
 // want_ks: the caller reads the sW-scaled cross-kernel matrix itself (the IQR acquisition functions); otherwise the variance comes from
 // k_pred_fused and that matrix is never written (round 6).  VBMC_PRED_FUSED=0 keeps the two-kernel form (A/B runs, tests).
+// qsigma (D values, host): the Bayesian-quadrature form instead (gplite_quad.m) -- Xstar holds the means mu_i, pb.fmu / pb.fs2 receive
+// F / varF per hyper-sample through the k_quad_* forms of the same kernels, in the same launch forms (fused, two-kernel, slab).
 vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xstar, const double* ystar,
-                           const double* s2star, PredBufs& pb, bool want_ks = false) {
+                           const double* s2star, PredBufs& pb, bool want_ks = false, const double* qsigma = nullptr) {
   if (!gp || Nstar <= 0 || !Xstar) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
   if (!gp->hasL) return set_err(ctx, VBMC_ERR_INVALID, "%s needs gp.post(s).L on the device", who);
   if (!gp->has_noise) return set_err(ctx, VBMC_ERR_INVALID, "%s: call vbmc_gp_set_noise (noisefun, sn2_mult) first", who);
@@ -593,6 +595,12 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   // an empty s2star counts as zero (gplite_noisefun.m:51): the kernels add nothing when the pointer is null
   const int N = gp->N, D = gp->D, S = gp->S;
   if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
+  const bool quad = qsigma != nullptr;
+  if (quad && gp->meanfun != 0 && gp->meanfun != 1 && gp->meanfun != 4)
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: mean function %d not accelerated (0, 1, 4)", who, gp->meanfun);
+  // gplite_quad.m:66-67,101 divides by the scalar sn2_eff = exp(2 hyp(Ncov+1)) sn2_mult: the constant-noise model, whose sW is that scalar
+  if (quad && !(gp->noisefun[0] == 1 && gp->noisefun[1] == 0 && gp->noisefun[2] == 0))
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: only the constant noise model (noisefun [1 0 0]) is accelerated", who);
   const int Np = ((N + 15) >> 4) << 4, nblk = Np >> 4;
   // beyond N = 1248 a 16-row tile of inv(L') no longer fits the LDS: the variance then comes from slab solves (k_pred_slab)
   const bool slab_pred = (size_t)16 * Np * 8 > PRED_LDS_MAX || nblk > PRED_MAXG || trsm_cw_for(N) != 16;
@@ -636,7 +644,19 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   pa.mean_a = gp->d_meanX; pa.mean_b = dmb.as<double>(); pa.finv = gp->d_finv; pa.tinv = gp->d_tinv;
   pa.fmu = dout.as<double>(); pa.fs2 = pa.fmu + (size_t)Nstar * S; pa.ys2 = pa.fs2 + (size_t)Nstar * S;
   pb.fmu = pa.fmu; pb.fs2 = pa.fs2; pb.ys2 = pa.ys2;
-  hipLaunchKernelGGL(k_pred_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
+  if (quad) {
+    HIP_TRY(ctx, pb.dqs.alloc(ctx, (size_t)D * 8));
+    HIP_TRY(ctx, pb.dqn.alloc(ctx, (size_t)S * 2 * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(pb.dqs.p, qsigma, (size_t)D * 8, hipMemcpyHostToDevice, st));
+    pa.qsig = pb.dqs.as<double>(); pa.qnf = pb.dqn.as<double>();
+    hipLaunchKernelGGL(k_quad_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
+  } else {
+    hipLaunchKernelGGL(k_pred_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
+  }
+  auto launch_final = [&] {
+    if (quad) hipLaunchKernelGGL(k_quad_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+    else hipLaunchKernelGGL(k_pred_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+  };
   // resident row blocks of Tinv per hyper-sample: consecutive 16-row tiles, balanced by area (tile b costs b + 1),
   // bounded by PRED_MAXR tiles and PRED_LDS_MAX bytes of LDS (two workgroups per CU)
   std::vector<int> grp((size_t)S + 2 * (size_t)S * PRED_MAXG, 0);
@@ -687,14 +707,15 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   HIP_TRY(ctx, pb.dpF.alloc(ctx, (size_t)S * Nstar * 8));
   HIP_TRY(ctx, hipMemcpyAsync(pb.dgrp.p, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice, st));
   if (fused) {
-    const size_t fl = (size_t)fused_pt * Np * 16 * 8;
+    const size_t fl = PREDF_LDS_BYTES(fused_pt, Np);   // the tiles, and no less than the per-wave sums that reuse the block
     const int npass = (ntile_ + fused_pt - 1) / fused_pt;
     // one workgroup per compute unit (its LDS is full), each walking the (hyper-sample, pass) units b, b + grid, ...
     const int gxf = std::max(1, std::min(npass * S * fused_rs, ctx->num_cu));
-#define PRED_FUSED_PT(QSV, PTV) { \
-      if (fl > 64 * 1024) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_pred_fused<QSV, PTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl)); \
-      hipLaunchKernelGGL((k_pred_fused<QSV, PTV>), dim3(gxf), dim3(PREDF_THREADS), fl, st, pa, dXc.as<double>(), daa.as<double>(), \
+#define PRED_FUSED_K(KERN, QSV, PTV) { \
+      if (fl > 64 * 1024) HIP_TRY(ctx, hipFuncSetAttribute((const void*)KERN<QSV, PTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl)); \
+      hipLaunchKernelGGL((KERN<QSV, PTV>), dim3(gxf), dim3(PREDF_THREADS), fl, st, pa, dXc.as<double>(), daa.as<double>(), \
                          dmuv.as<double>(), pb.dpV.as<double>(), pb.dpF.as<double>(), fused_rs); }
+#define PRED_FUSED_PT(QSV, PTV) { if (quad) PRED_FUSED_K(k_quad_fused, QSV, PTV) else PRED_FUSED_K(k_pred_fused, QSV, PTV) }
 #define PRED_FUSED(QSV) case QSV: \
       if (fused_pt >= 3) { if constexpr (PREDF_PT_FOR_QS(QSV) >= 3) PRED_FUSED_PT(QSV, 3) } \
       else if (fused_pt == 2) { if constexpr (PREDF_PT_FOR_QS(QSV) >= 2) PRED_FUSED_PT(QSV, 2) } \
@@ -702,17 +723,20 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
       break;
     switch ((D + 3) / 4) { PRED_FUSED(1) PRED_FUSED(2) PRED_FUSED(3) PRED_FUSED(4) PRED_FUSED(5) PRED_FUSED(6) PRED_FUSED(7) PRED_FUSED(8) default: break; }
 #undef PRED_FUSED_PT
+#undef PRED_FUSED_K
 #undef PRED_FUSED
-    hipLaunchKernelGGL(k_pred_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+    launch_final();
     HIP_TRY(ctx, hipGetLastError());
     return VBMC_OK;
   }
   HIP_TRY(ctx, pb.dKs.alloc(ctx, (size_t)S * N * (((size_t)Nstar + 15) / 16) * 16 * 8));   // tiled by 16 points
   // inner dimension of the MFMA distance blocks: QS = ceil(D / 4) steps
-#define PRED_KS(QSV) case QSV: hipLaunchKernelGGL((k_pred_ks<QSV>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(), \
-                                                  daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>()); break;
+#define PRED_KS_K(KERN, QSV) hipLaunchKernelGGL((KERN<QSV>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(), \
+                                               daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>())
+#define PRED_KS(QSV) case QSV: if (quad) PRED_KS_K(k_quad_ks, QSV); else PRED_KS_K(k_pred_ks, QSV); break;
   switch ((D + 3) / 4) { PRED_KS(1) PRED_KS(2) PRED_KS(3) PRED_KS(4) PRED_KS(5) PRED_KS(6) PRED_KS(7) PRED_KS(8) default: break; }
 #undef PRED_KS
+#undef PRED_KS_K
   if (slab_pred) {
     TRSM_DISPATCH_CW(trsm_cw_for(N), {
       const size_t sl = TRSM_LDS_BYTES_CW(N, CW);
@@ -725,7 +749,7 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
       HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_gp_pred, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxlds));
     hipLaunchKernelGGL(k_gp_pred, dim3(maxg, S, PZ), dim3(PRED_THREADS), maxlds, st, pa, pb.dKs.as<double>(), pb.dgrp.as<int>(), pb.dpV.as<double>());
   }
-  hipLaunchKernelGGL(k_pred_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+  launch_final();
   HIP_TRY(ctx, hipGetLastError());
   return VBMC_OK;
 }
@@ -803,15 +827,114 @@ extern "C" vbmc_status vbmc_gp_pred(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar,
 }
 
 // ------------------------------------------------------------------------------------------
+// gplite_quad (gplite/gplite_quad.m:1-119) with one sigma row shared by all points
+namespace {
+// the shared row of an Nstar x D (or 1 x D) column-major sigma; false when the rows differ
+bool quad_shared_sigma(const double* sigma, int sigma_rows, int D, std::vector<double>& row) {
+  row.resize(D);
+  for (int d = 0; d < D; ++d) {
+    row[d] = sigma[(size_t)sigma_rows * d];
+    for (int i = 1; i < sigma_rows; ++i)
+      if (sigma[i + (size_t)sigma_rows * d] != row[d]) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" vbmc_status vbmc_gp_quad(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* mu, const double* sigma, int sigma_rows,
+                                    int ssflag, double* F, double* varF) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  if (!gp || Nstar <= 0 || !mu || !sigma || !F || (sigma_rows != 1 && sigma_rows != Nstar))
+    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_quad: bad arguments");
+  const int D = gp->D, S = gp->S;
+  std::vector<double> sg;
+  if (!quad_shared_sigma(sigma, sigma_rows, D, sg))
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_gp_quad: a sigma row per point is not accelerated (one shared row only)");
+  for (int d = 0; d < D; ++d)
+    if (!(sg[d] >= 0.0) || !std::isfinite(sg[d])) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_quad: sigma must be finite and non-negative");
+  const int nc = (ssflag && S > 1) ? S : 1;
+  if (Nstar > pred_chunk_points(gp, Nstar)) {
+    const int CH = pred_chunk_points(gp, Nstar);
+    std::vector<double> xs, o[2];
+    for (int i0 = 0; i0 < Nstar; i0 += CH) {
+      const int n = std::min(CH, Nstar - i0);
+      gather_rows(mu, Nstar, D, i0, n, xs);
+      for (auto& v : o) v.assign((size_t)n * nc, 0.0);
+      vbmc_status st_ = vbmc_gp_quad(ctx, gp, n, xs.data(), sg.data(), 1, ssflag, o[0].data(), varF ? o[1].data() : nullptr);
+      if (st_ != VBMC_OK) return st_;
+      scatter_rows(o[0], Nstar, nc, i0, n, F); scatter_rows(o[1], Nstar, nc, i0, n, varF);
+    }
+    return VBMC_OK;
+  }
+  PredBufs pb;
+  VB_TRY(pred_on_device(ctx, "vbmc_gp_quad", gp, Nstar, mu, nullptr, nullptr, pb, false, sg.data()));
+  hipStream_t st = ctx->stream;
+  const size_t ns = (size_t)Nstar * S;
+  if (S > 1 && !ssflag) {   // :112-119: k_pred_avg's fmu / fs2 columns (its ys2 column repeats fs2 here and is not read)
+    TmpBuf davg;
+    HIP_TRY(ctx, davg.alloc(ctx, (size_t)4 * Nstar * 8));
+    hipLaunchKernelGGL(k_pred_avg, dim3((Nstar + 255) / 256), dim3(256), 0, st, Nstar, S, pb.fmu, pb.fs2, pb.fs2, davg.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> h((size_t)2 * Nstar);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), davg.as<double>() + 2 * (size_t)Nstar, h.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    memcpy(F, h.data(), (size_t)Nstar * 8);
+    if (varF) memcpy(varF, h.data() + Nstar, (size_t)Nstar * 8);
+  } else {
+    std::vector<double> h(2 * ns);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), pb.dout.p, h.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    memcpy(F, h.data(), ns * 8);
+    if (varF) memcpy(varF, h.data() + ns, ns * 8);
+  }
+  return VBMC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// vbmc_acq_eval and vbmc_acq_eval_delta: delta (D values) switches the per-hyper-sample mean and variance from gplite_pred to
+// gplite_quad(gp,Xs,vp.delta',1) (acqwrapper_vbmc.m:12-17); everything from fbar / vtot on is the same k_acq
+namespace {
+vbmc_status acq_eval_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
+                          const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
+                          double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
+                          const double* X_rescaled, const double* sn2new, const double* delta, double* acq, double* fbar, double* vtot);
+}  // namespace
+
 extern "C" vbmc_status vbmc_acq_eval(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
                                      const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
                                      double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
                                      const double* X_rescaled, const double* sn2new, double* acq, double* fbar, double* vtot) {
   if (!ctx) return VBMC_ERR_INVALID;
-  if (!acq || K <= 0 || !vp_mu || !vp_sigma || !vp_lambda || !vp_w) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_eval: bad arguments");
+  return acq_eval_impl(ctx, "vbmc_acq_eval", gp, Nstar, Xs, acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
+                       gplengthscale, X_rescaled, sn2new, nullptr, acq, fbar, vtot);
+}
+
+extern "C" vbmc_status vbmc_acq_eval_delta(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
+                                           const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
+                                           double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
+                                           const double* X_rescaled, const double* sn2new, double* acq, double* fbar, double* vtot,
+                                           const double* delta) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  if (!gp || !delta) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_eval_delta: bad arguments");
+  bool any = false;
+  for (int d = 0; d < gp->D; ++d) {
+    if (!(delta[d] >= 0.0) || !std::isfinite(delta[d])) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_eval_delta: delta must be finite and non-negative");
+    any = any || delta[d] > 0.0;
+  }
+  if (!any) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_eval_delta: delta is all zero (acqwrapper_vbmc.m:12 takes gplite_pred then: call vbmc_acq_eval)");
+  return acq_eval_impl(ctx, "vbmc_acq_eval_delta", gp, Nstar, Xs, acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
+                       gplengthscale, X_rescaled, sn2new, delta, acq, fbar, vtot);
+}
+
+namespace {
+vbmc_status acq_eval_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
+                          const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
+                          double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
+                          const double* X_rescaled, const double* sn2new, const double* delta, double* acq, double* fbar, double* vtot) {
+  if (!acq || K <= 0 || !vp_mu || !vp_sigma || !vp_lambda || !vp_w) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
   if (acq_id < 0 || acq_id > 3) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "acquisition function id %d not accelerated (0 acqf, 1 acqflog, 2 acqus, 3 acqfsn2)", acq_id);
   if (acq_id == 3 && (!gplengthscale || !X_rescaled || !sn2new))
-    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_eval: acqfsn2 needs gplengthscale, X_rescaled and sn2new");
+    return set_err(ctx, VBMC_ERR_INVALID, "%s: acqfsn2 needs gplengthscale, X_rescaled and sn2new", who);
   if (gp && Xs && Nstar > pred_chunk_points(gp, Nstar)) {
     const int CH = pred_chunk_points(gp, Nstar);
     std::vector<double> xs, o[3];
@@ -819,18 +942,18 @@ extern "C" vbmc_status vbmc_acq_eval(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar
       const int n = std::min(CH, Nstar - i0);
       gather_rows(Xs, Nstar, gp->D, i0, n, xs);
       for (auto& v : o) v.assign(n, 0.0);
-      vbmc_status st_ = vbmc_acq_eval(ctx, gp, n, xs.data(), acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
-                                      gplengthscale, X_rescaled, sn2new, o[0].data(), o[1].data(), o[2].data());
+      vbmc_status st_ = acq_eval_impl(ctx, who, gp, n, xs.data(), acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
+                                      gplengthscale, X_rescaled, sn2new, delta, o[0].data(), o[1].data(), o[2].data());
       if (st_ != VBMC_OK) return st_;
       scatter_rows(o[0], Nstar, 1, i0, n, acq); scatter_rows(o[1], Nstar, 1, i0, n, fbar); scatter_rows(o[2], Nstar, 1, i0, n, vtot);
     }
     return VBMC_OK;
   }
   PredBufs pb;
-  VB_TRY(pred_on_device(ctx, "vbmc_acq_eval", gp, Nstar, Xs, nullptr, nullptr, pb));
+  VB_TRY(pred_on_device(ctx, who, gp, Nstar, Xs, nullptr, nullptr, pb, false, delta));
   hipStream_t st = ctx->stream;
   const int N = gp->N, D = gp->D, S = gp->S;
-  if ((size_t)(2 * K * D + K) * 8 > 64 * 1024) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "vbmc_acq_eval: K*D = %d too large", K * D);
+  if ((size_t)(2 * K * D + K) * 8 > 64 * 1024) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: K*D = %d too large", who, K * D);
   // host: O(K D) constants of vbmc_pdf.m:57-62 in the reference's order of operations
   double prodl = 1.0;
   for (int d = 0; d < D; ++d) prodl *= vp_lambda[d];
@@ -879,6 +1002,7 @@ extern "C" vbmc_status vbmc_acq_eval(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar
   if (vtot) memcpy(vtot, h.data() + 2 * (size_t)Nstar, (size_t)Nstar * 8);
   return VBMC_OK;
 }
+}  // namespace
 
 // ------------------------------------------------------------------------------------------
 // Importance-sampling state of the IQR acquisition functions (optimState.ActiveImportanceSampling)

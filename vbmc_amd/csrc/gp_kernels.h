@@ -3,7 +3,7 @@
 //
 // Reference: utils/sq_dist.m:14-50, gplite/private/gplite_core.m:33-102,278-291,
 // gplite/gplite_post.m:167-251, gplite/gplite_pred.m:52-165, gplite/gplite_meanfun.m:400-436,
-// gplite/gplite_noisefun.m:176-210.
+// gplite/gplite_noisefun.m:176-210, gplite/gplite_quad.m:1-119.
 //
 //   k_sq_dist_mfma  C = max(|a|^2 + |b|^2 - 2 a'b, 0), the a'b contraction on v_mfma_f64_16x16x4_f64
 //   k_gp_build      A_s = K/(sn2div*mult) + diag(sn2/sn2div)   (Lchol)   or  K + mult*diag(sn2)
@@ -14,6 +14,8 @@
 //   k_gp_pred       four waves per 16 test points: cross-kernel slab -> fmu = m* + Ks'alpha, V = inv(L')*(sW.*Ks) as
 //                   MFMA products against the precomputed triangular inverse, fs2 = kss - |V|^2
 //   k_pred_avg      hyper-sample averaging with between-sample variance (gplite_pred.m:154-165)
+//   k_quad_*        the Bayesian-quadrature forms of the prediction kernels (gplite_quad.m): inputs scaled by 1/sqrt(sigma^2 + ell^2),
+//                   the normaliser lnnf in the exponent, nf_kk and the integrated mean function in the closing step
 #pragma once
 #include "common.h"
 #include "device_math.h"
@@ -533,22 +535,47 @@ struct PredArgs {
   double* fmu;           // Nstar x S
   double* fs2;
   double* ys2;
+  // Bayesian quadrature (gplite_quad.m; null for prediction): Xs holds the means mu_i of the Gaussians N(mu_i, diag sigma^2)
+  const double* qsig;    // D      the shared row sigma
+  double* qnf;           // S x 2  ln of the cross normaliser lnnf_s (:71) and nf_kk,s (:99), written by k_quad_prep
 };
 
 // k_pred_prep: per hyper-sample the ell-scaled, sq_dist-centred training inputs and their squared norms:
 // Xc[s][i][d] = X(i,d)/ell_d - mu_d,  aa[s][i] = |Xc_i|^2,  mu = (m/(n+m)) mean(b) + (n/(n+m)) mean(a)  (sq_dist.m:36)
-__global__ void __launch_bounds__(256) k_pred_prep(PredArgs a, double* __restrict__ Xc, double* __restrict__ aa,
-                                                   double* __restrict__ muv /* S x 2D: mu, 1/ell */) {
+// QUAD (k_quad_prep): the scale is 1/tau_d, tau_d = sqrt(sigma_d^2 + ell_d^2) (gplite_quad.m:70,74) -- the kernels downstream read it
+// where they read 1/ell -- and the two normalisers lnnf = ln sf2 + sum ln ell - sum ln tau (:71) and
+// nf_kk = exp(ln sf2 + sum ln ell - sum ln sqrt(2 sigma^2 + ell^2)) (:98-99) go to qnf[s][0..1]
+template <bool QUAD>
+__device__ __forceinline__ void pred_prep_body(const PredArgs& a, double* __restrict__ Xc, double* __restrict__ aa, double* __restrict__ muv) {
   const int s = blockIdx.y, N = a.N, D = a.D;
   const double* h = a.hyp + (size_t)s * a.Nhyp;
   __shared__ double mu[32], iell[32];
   if (threadIdx.x < D) {
     const int d = threadIdx.x;
-    const double ie = 1.0 / exp(h[d]);   // diag(1./ell) * X'   (gplite_pred.m:73)
+    double ie;
+    if constexpr (QUAD) {
+      const double el = exp(h[d]);
+      ie = 1.0 / sqrt(fma(a.qsig[d], a.qsig[d], el * el));   // 1 ./ tau   (gplite_quad.m:70)
+    } else {
+      ie = 1.0 / exp(h[d]);   // diag(1./ell) * X'   (gplite_pred.m:73)
+    }
     const double n = (double)N, m = (double)a.Nstar;
     iell[d] = ie;
     mu[d] = (m / (n + m)) * (a.mean_b[d] * ie) + (n / (n + m)) * (a.mean_a[d] * ie);
     if (blockIdx.x == 0) { muv[(size_t)s * 2 * D + d] = mu[d]; muv[(size_t)s * 2 * D + D + d] = ie; }
+  }
+  if constexpr (QUAD) {
+    if (blockIdx.x == 0 && threadIdx.x == 64) {   // O(D), in the reference's order of summation
+      double sl = 0.0, st = 0.0, sk = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double el2 = exp(h[d]) * exp(h[d]), sg2 = a.qsig[d] * a.qsig[d];
+        sl += h[d];
+        st += log(sqrt(sg2 + el2));
+        sk += log(sqrt(2.0 * sg2 + el2));
+      }
+      a.qnf[2 * s] = 2.0 * h[D] + sl - st;
+      a.qnf[2 * s + 1] = exp(2.0 * h[D] + sl - sk);
+    }
   }
   __syncthreads();
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
@@ -561,15 +588,25 @@ __global__ void __launch_bounds__(256) k_pred_prep(PredArgs a, double* __restric
     aa[(size_t)s * N + i] = acc;
   }
 }
+__global__ void __launch_bounds__(256) k_pred_prep(PredArgs a, double* __restrict__ Xc, double* __restrict__ aa,
+                                                   double* __restrict__ muv /* S x 2D: mu, 1/ell */) {
+  pred_prep_body<false>(a, Xc, aa, muv);
+}
+__global__ void __launch_bounds__(256) k_quad_prep(PredArgs a, double* __restrict__ Xc, double* __restrict__ aa,
+                                                   double* __restrict__ muv /* S x 2D: mu, 1/tau */) {
+  pred_prep_body<true>(a, Xc, aa, muv);
+}
 
 // k_pred_ks: the sW-scaled cross-kernel matrix for every hyper-sample, KsW[s][i/16][n][i%16] = sW_s * k_s(X_n, Xstar_i)
 // (tiled by 16 points), each element computed exactly once, and fmu's data term Ks' alpha (gplite_pred.m:74,83).
 // One wave per (16 test points, hyper-sample).  The inner products of sq_dist's expansion |a|^2 + |b|^2 - 2 a.b
 // (sq_dist.m:45) for a 16 x 16 block of (training point, test point) pairs are QS MFMAs (inner dimension D in steps
 // of 4); the accumulator layout (row n = lg + 4 reg, column point = li) is exactly the coalesced store pattern.
-template <int QS>
-__global__ void __launch_bounds__(64) k_pred_ks(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
-                                                const double* __restrict__ muv, double* __restrict__ KsW, double* __restrict__ partF) {
+// QUAD (k_quad_ks): the same pass over the tau-scaled inputs of k_quad_prep with ln of the normaliser lnnf_s in place of ln sf2:
+// z = exp(lnnf - sumdelta2 / 2) (gplite_quad.m:72-76), F's data term z * alpha (:77)
+template <int QS, bool QUAD>
+__device__ __forceinline__ void pred_ks_body(const PredArgs& a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                             const double* __restrict__ muv, double* __restrict__ KsW, double* __restrict__ partF) {
   __shared__ double tab[VB_EXP_TAB_N];
   const int pt = blockIdx.x, s = blockIdx.y, lane = threadIdx.x, li = lane & 15, lg = lane >> 4;
   const int N = a.N, D = a.D;
@@ -578,7 +615,7 @@ __global__ void __launch_bounds__(64) k_pred_ks(PredArgs a, const double* __rest
   const double* mu = muv + (size_t)s * 2 * D;
   const double* iell = mu + D;
   const double sf2 = exp(2.0 * h[D]);
-  const double lsf2 = 2.0 * h[D];
+  const double lsf2 = QUAD ? a.qnf[2 * s] : 2.0 * h[D];
   const double sW = a.lchol[s] ? 1.0 / sqrt(a.sn2_eff[s]) : 1.0;
   const int jc = pt * 16 + li;
   const bool cv = jc < a.Nstar;
@@ -626,6 +663,16 @@ __global__ void __launch_bounds__(64) k_pred_ks(PredArgs a, const double* __rest
   fm += __shfl_xor(fm, 16, 64);
   fm += __shfl_xor(fm, 32, 64);
   if (lg == 0 && cv) partF[(size_t)s * a.Nstar + jc] = fm;
+}
+template <int QS>
+__global__ void __launch_bounds__(64) k_pred_ks(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                                const double* __restrict__ muv, double* __restrict__ KsW, double* __restrict__ partF) {
+  pred_ks_body<QS, false>(a, Xc, aa, muv, KsW, partF);
+}
+template <int QS>
+__global__ void __launch_bounds__(64) k_quad_ks(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                                const double* __restrict__ muv, double* __restrict__ KsW, double* __restrict__ partF) {
+  pred_ks_body<QS, true>(a, Xc, aa, muv, KsW, partF);
 }
 
 // k_gp_pred: V = L' \ (sW .* Ks) as the product Tinv * (sW .* Ks), Tinv = inv(L') precomputed once per GP
@@ -739,15 +786,19 @@ __global__ void __launch_bounds__(PRED_THREADS, 4) k_gp_pred(PredArgs a, const d
 // per wave, are what the matrix pipe sees).  Low-noise samples (Lchol = false, :103-104) take all columns and accumulate
 // Ks .* (L Ks).  fmu's data term Ks' alpha (:83) is a dot product over the resident tile.  Partial sums: one per hyper-sample and
 // point (block 0 of partV; k_pred_final is told there is one block).
-// dynamic LDS: PT x Np x 16 doubles (beside 2 KB of table and NWV x PT x 16 doubles of per-wave sums).
+// dynamic LDS: PT x Np x 16 doubles (beside 2 KB of table and NWV x PT x 16 doubles of per-wave sums), and at least the
+// NWV x PREDF_MAXPT x 16 doubles of the variance's per-wave sums, which reuse the block once the tiles are dead: PREDF_LDS_BYTES.
 #define PREDF_THREADS 768      // twelve waves, three per SIMD (168 registers: sixteen at 128 spilled 37; eight left the matrix pipe half idle behind the L2)
 #define PREDF_MAXPT 3
 // resident point tiles the registers allow at QS dim-blocks (168 registers at three waves per SIMD; beyond: spills -- tests/test_lane_build.py)
 #define PREDF_PT_FOR_QS(QS_) ((QS_) <= 3 ? 3 : ((QS_) <= 5 ? 2 : 1))
-template <int QS, int PT>
-__global__ void __launch_bounds__(PREDF_THREADS, 1) k_pred_fused(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
-                                                                 const double* __restrict__ muv, double* __restrict__ partV,
-                                                                 double* __restrict__ partF, const int RS) {
+// QUAD (k_quad_fused): the quadrature form (gplite_quad.m:70-77,96-105) is the same pass with the tau-scaled inputs of k_quad_prep and
+// ln of the normaliser lnnf_s in place of ln sf2: the tile value is z, the sums are sum V^2 with V = L' \ (sW .* z') and sum z .* (L z').
+#define PREDF_LDS_BYTES(PT_, NP_) (std::max((size_t)(PT_) * (NP_) * 16, (size_t)(PREDF_THREADS / 64) * PREDF_MAXPT * 16) * sizeof(double))
+template <int QS, int PT, bool QUAD>
+__device__ __forceinline__ void pred_fused_body(const PredArgs& a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                                const double* __restrict__ muv, double* __restrict__ partV,
+                                                double* __restrict__ partF, const int RS) {
   // RS > 1 (few points: the units do not cover the chip): RS workgroups share a unit -- each computes the unit's tiles (cheap) and takes
   // every RS-th row tile of inv(L'); their partial sums are blocks rs of partV, which k_pred_final adds in block order.  The importance
   // sampler's predictions of ~110 points were 60 workgroups walking 25 row tiles each: 74 us a call, 187 dependent calls.
@@ -771,7 +822,7 @@ __global__ void __launch_bounds__(PREDF_THREADS, 1) k_pred_fused(PredArgs a, con
     const double* h = a.hyp + (size_t)s * a.Nhyp;
     const double* mu = muv + (size_t)s * 2 * D;
     const double* iell = mu + D;
-    const double lsf2 = 2.0 * h[D];
+    const double lsf2 = QUAD ? a.qnf[2 * s] : 2.0 * h[D];
     const bool lc = a.lchol[s] != 0;
     const double sW = lc ? 1.0 / sqrt(a.sn2_eff[s]) : 1.0;
     const double* xcs = Xc + (size_t)s * N * D;
@@ -939,6 +990,18 @@ __global__ void __launch_bounds__(PREDF_THREADS, 1) k_pred_fused(PredArgs a, con
     __syncthreads();      // the next unit writes the tiles
   }
 }
+template <int QS, int PT>
+__global__ void __launch_bounds__(PREDF_THREADS, 1) k_pred_fused(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                                                 const double* __restrict__ muv, double* __restrict__ partV,
+                                                                 double* __restrict__ partF, const int RS) {
+  pred_fused_body<QS, PT, false>(a, Xc, aa, muv, partV, partF, RS);
+}
+template <int QS, int PT>
+__global__ void __launch_bounds__(PREDF_THREADS, 1) k_quad_fused(PredArgs a, const double* __restrict__ Xc, const double* __restrict__ aa,
+                                                                 const double* __restrict__ muv, double* __restrict__ partV,
+                                                                 double* __restrict__ partF, const int RS) {
+  pred_fused_body<QS, PT, true>(a, Xc, aa, muv, partV, partF, RS);
+}
 
 // k_pred_slab: the large-N form of the prediction variance (N beyond what k_gp_pred keeps resident: a 16-row tile of the
 // triangular inverse no longer fits the LDS).  One wave per CW test points: their sW-scaled cross-kernel columns form a slab
@@ -1011,6 +1074,32 @@ __global__ void __launch_bounds__(256) k_pred_final(PredArgs a, const int* __res
   a.fmu[i + (size_t)a.Nstar * s] = fmu;
   a.fs2[i + (size_t)a.Nstar * s] = fs2;
   a.ys2[i + (size_t)a.Nstar * s] = fs2 + sn2s * a.sn2_mult[s];
+}
+
+// The quadrature's closing step: F = m0 + nu + z * alpha (gplite_quad.m:77,82), nu = -1/2 sum_d (mu^2 + sigma^2 - 2 mu xm + xm^2) / omega^2
+// for the negative quadratic mean (:80-81), nothing for the zero and constant means; varF = max(eps, nf_kk -/+ the block partials)
+// (:101-106).  Written to fmu / fs2; k_pred_avg's fmu / fs2 columns are the averaging of :112-119.
+__global__ void __launch_bounds__(256) k_quad_final(PredArgs a, const int* __restrict__ grp, const double* __restrict__ partV,
+                                                    const double* __restrict__ partF) {
+  const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (i >= a.Nstar) return;
+  const int D = a.D;
+  const double* hm = a.hyp + (size_t)s * a.Nhyp + a.moff;
+  double pv = 0.0;
+  for (int g = 0; g < grp[s]; ++g) pv += partV[((size_t)g * a.S + s) * a.Nstar + i];
+  double F = partF[(size_t)s * a.Nstar + i] + (a.meanfun > 0 ? hm[0] : 0.0);
+  if (a.meanfun == 4) {
+    double nu = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double m = a.Xs[i + (size_t)a.Nstar * d], xm = hm[1 + d], om = exp(hm[D + 1 + d]);
+      nu += 1.0 / (om * om) * (m * m + a.qsig[d] * a.qsig[d] - 2.0 * m * xm + xm * xm);
+    }
+    F += -0.5 * nu;
+  }
+  const double nfkk = a.qnf[2 * s + 1];
+  const double J = a.lchol[s] ? nfkk - pv : nfkk + pv;
+  a.fmu[i + (size_t)a.Nstar * s] = F;
+  a.fs2[i + (size_t)a.Nstar * s] = fmax(2.220446049250313e-16, J);
 }
 
 // gplite_pred.m:154-165 averaging over hyper-samples (in place into column 0 of the *_avg outputs)

@@ -140,6 +140,40 @@ def gplite_pred(gp, Xstar, ystar=None, s2star=None, ssflag=False, nowarpflag=Fal
     return tuple(outs[: max(1, nargout)])
 
 
+def gplite_quad(gp, mu, sigma, ssflag=False, nargout=2, *, engine=None):
+    """[F,varF] = gplite_quad(gp,mu,sigma,ssflag)  (gplite/gplite_quad.m:1-119): Bayesian quadrature of the GP against
+    N(mu_i, diag sigma^2) for every row of ``mu`` (Nstar x D).  ``sigma`` is a row of D values shared by all points, or an
+    Nstar x D matrix whose rows are all equal (collapsed to that row); distinct rows raise VbmcUnsupported.  Averaged over the
+    hyper-samples unless ``ssflag`` (:112-119); ``nargout=1`` skips the variance's readback."""
+    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    D = gp["X"].shape[1]
+    if int(np.ravel(gp.get("covfun", 1))[0]) != 1:   # :21-24
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_quad: Bayesian quadrature only supports the squared exponential kernel")
+    if int(gp["meanfun"]) not in (0, 1, 4):    # the reference also admits 6 and 8 (:16-19): not accelerated
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_quad: mean function %d is not accelerated (0, 1, 4)" % int(gp["meanfun"]))
+    mu = f64(np.asarray(mu, dtype=np.float64).reshape(-1, D))
+    Nstar = mu.shape[0]
+    sigma = np.asarray(sigma, dtype=np.float64).reshape(-1, D)
+    if sigma.shape[0] not in (1, Nstar):
+        raise ValueError("gplite_quad: SIGMA should be a row of D values or an NSTAR x D matrix")
+    if sigma.shape[0] > 1:
+        if not np.all(sigma == sigma[:1]):
+            raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_quad: a sigma row per point is not accelerated (one shared row only)")
+        sigma = sigma[:1]
+    sigma = f64(sigma)
+    dgp = _device_gp_with_noise(engine, gp)
+    S = dgp.S
+    per = bool(ssflag) or S == 1
+    shape = (Nstar, S) if per else (Nstar,)
+    F = np.zeros(shape, order="F")
+    varF = np.zeros(shape, order="F") if nargout > 1 else None
+    ctx.check(ctx.lib.vbmc_gp_quad(ctx.h, dgp.h, Nstar, ptr(mu), ptr(sigma), 1, 1 if per else 0, ptr(F), ptr(varF)))
+    return (F, varF) if nargout > 1 else F
+
+
 def gplite_post_rank1(gp, xstar, ystar, s2star=None, *, need_L=True, engine=None):
     """gp = gplite_post(gp, xstar, ystar, [], [], [], [], 1): rank-1 append of one observation
     (gplite/gplite_post.m:173-251).  Falls back to the full update when ``s2`` is present, as the
