@@ -363,6 +363,89 @@ vbmc_status vbmc_gp_quad(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const doub
                          int ssflag, double* F, double* varF);
 
 /*
+ * The acquisition search of active sampling (private/activesample_vbmc.m:264-290 with SearchOptimizer = 'cmaes', VBMC's default) with
+ * the WHOLE optimiser on the device: minimise acqwrapper_vbmc(x) -- exactly the function of vbmc_acq_eval, acq_id 0-3, vp.delta = 0 --
+ * over the box [LB, UB] from x0.  The optimiser is the project's plain (mu/mu_w, lambda)-CMA-ES (vbmc_amd/optimize.py::cmaes_batched,
+ * which stands in for the third-party cmaes_modded.m: same constants wts / mueff / cc / cs / c1 / cmu / damps / chiN, same hsig,
+ * rank-one and rank-mu updates, step-size adaptation and the same four stopping rules over a history window of 10 + ceil(30 D / lambda)
+ * values), in its CHOLESKY form (Krause, Arnold & Glasmachers 2016): Y = A Z with A the lower Cholesky factor of C, refreshed every
+ * generation, and ps updated with A^-1 yw -- a factor that is unique, so that a trajectory is a function of Z and can be compared.
+ * A C that has lost positive definiteness gets 1e-14 max diag added to its diagonal once; if it is still indefinite the search stops
+ * with the stop code of MaxIter and the state so far.  Candidates are clamped into [LB, UB]; the clamped points are evaluated, ranked
+ * (a value that is not finite ranks as +Inf, ties keep the index order) and fed to the update as y = (x_clamped - xmean) / sigma.
+ * `evals` counts lambda per generation.  None of cmaes_modded's restarts, active-CMA or noise handling.
+ *
+ * One generation is one launch of the optimiser's kernel, the prediction of the lambda <= 16 points for every hyper-sample and the
+ * acquisition kernel; generations are enqueued in chunks of `chunk` (0: the default, 16) with no host synchronisation inside a chunk,
+ * and the host reads a progress word one chunk behind.  Results do not depend on `chunk`.
+ *
+ * popsize: lambda, 0 = 4 + floor(3 ln D), at most 16 (2 at the least).  MaxFunEvals <= 0: no limit.  MaxIter 0: 1e3 (D + 5)^2 / sqrt(lambda).
+ * RANDOM NUMBERS.  rng_mode 0: Philox4x32-10 keyed by `seed`, counter (generation, point, d), through an inverse normal CDF made of
+ * exactly rounded operations only; vbmc_acq_search_rng_dump -- a pure host function -- writes the D x lam x G block Z[d + D (j + lam g)]
+ * that `seed` stands for.  rng_mode 1 (parity): the caller supplies that block for Gmax generations; a search that needs more ends with
+ * VBMC_ERR_INVALID ("normal block exhausted").  A replay of a dump in parity mode is bit-identical.
+ *
+ * VBMC_ERR_UNSUPPORTED: the IQR acquisition functions (ids >= 10) and any other id outside 0-3, vp_delta with a positive entry, and
+ * whatever vbmc_acq_eval refuses.  VBMC_ERR_INVALID: LB / UB / x0 / insigma not finite, LB >= UB, x0 outside the box, insigma not
+ * positive, popsize outside 2 .. 16 (0 aside).  The context stays usable after any error.
+ * Outputs (any may be NULL): xmin / fmin the LAST generation's best point and value (what cmaes_modded returns first), xbest / fbest the
+ * best ever seen (bestever; x0 and +Inf if no value was ever finite), the final xmean (D), sigma, C (D x D), evals, generations, stop
+ * (VBMC_SEARCH_STOP_*), rounds[2] = {generations, launches of the optimiser's kernel that found the search finished}.  Trace (tests):
+ * for the first trace_cap generations the rank order (lam int32 each, 0-based), the sorted values (lam), xmean (D) and sigma after the
+ * update; all four pointers or none.
+ */
+#define VBMC_SEARCH_STOP_TOLX 1
+#define VBMC_SEARCH_STOP_TOLFUN 2
+#define VBMC_SEARCH_STOP_TOLHISTFUN 3
+#define VBMC_SEARCH_STOP_MAXFUNEVALS 4
+#define VBMC_SEARCH_STOP_MAXITER 5
+typedef struct vbmc_acqsearch_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_acqsearch_args) */
+  int32_t acq_id, K;
+  const double* vp_mu;       /* D x K */
+  const double* vp_sigma;    /* K */
+  const double* vp_lambda;   /* D */
+  const double* vp_w;        /* K */
+  const double* vp_delta;    /* D or NULL; must be all zero */
+  double ymax;
+  int32_t var_regularized;
+  double TolGPVar;
+  const double* gplengthscale; /* acq_id 3 */
+  const double* X_rescaled;    /* acq_id 3 */
+  const double* sn2new;        /* acq_id 3 */
+  const double* x0;          /* D, inside the box */
+  const double* insigma;     /* D, positive */
+  const double* LB;          /* D */
+  const double* UB;          /* D */
+  double TolX, TolFun, TolHistFun;
+  int64_t MaxFunEvals;
+  int32_t MaxIter, popsize;
+  int32_t rng_mode;          /* 0 device generator, 1 parity */
+  int32_t Gmax;              /* rng_mode 1: generations in Z */
+  uint64_t seed;             /* rng_mode 0 */
+  const double* Z;           /* rng_mode 1: D x lam x Gmax */
+  int32_t chunk;             /* generations enqueued between two looks at the progress word (0: default) */
+  int32_t trace_cap;
+  double* xmin;
+  double* fmin;
+  double* xbest;
+  double* fbest;
+  double* xmean;
+  double* sigma;
+  double* C;
+  int64_t* evals;
+  int32_t* generations;
+  int32_t* stop;
+  int64_t* rounds;
+  int32_t* tr_order;
+  double* tr_F;
+  double* tr_xmean;
+  double* tr_sigma;
+} vbmc_acqsearch_args;
+vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acqsearch_args* args);
+vbmc_status vbmc_acq_search_rng_dump(uint64_t seed, int D, int lam, int G, double* Z);
+
+/*
  * The O(N^2) pieces of gplite_post's rank-1 append of one training point x* (gplite/gplite_post.m:173-251),
  * for every hyper-sample: Ks = k(X, x*) (N x S); for Lchol samples v = L' \ Ks and x = L \ v, so that
  * alpha_update = x / sn2_eff (:227) and the new column of L is v / sn2_eff (:228); for low-noise samples

@@ -28,6 +28,8 @@
 //                                ('acq' with vp.delta > 0: mean and variance per hyper-sample from gplite_quad(gp,Xs,delta,1),
 //                                 acqwrapper_vbmc.m:12-14; delta: D values; the last three only for acqfsn2)
 //     [F,varF] = vbmc_hip_mex('gp_quad', h, mu, sigma, ssflag, numel(gp.post))   (gplite_quad: sigma 1 x D, or Nstar x D of equal rows)
+//     [xmin,fmin,out] = vbmc_hip_mex('acq_search', h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new)
+//                                                  (the CMA-ES acquisition search on the device: matlab/vbmc_hip_acqsearch.m)
 //     his = vbmc_hip_mex('is_create', h, Xa, lnw_or_empty, fs2a_or_empty, Ctmp_or_empty)   (ActiveImportanceSampling state)
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
@@ -65,6 +67,7 @@
 // std::vector / std::string temporaries destroyed) with the id and message parked in static character buffers.
 // VBMC_ERR_UNSUPPORTED becomes the id 'vbmc_hip:unsupported' which the shims catch to fall through
 // to the reference .m implementation (SURVEY.md 8b "Errors").
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -242,7 +245,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search"};
     for (const char* w : with_handle)
       if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || (!strcmp(cmd, "acq_iqr") && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
@@ -509,6 +512,68 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
                                          mxGetDoubles(plhs[0]), mxGetDoubles(fb), mxGetDoubles(vt), mxGetDoubles(prhs[8]));
     if (nlhs > 1) plhs[1] = fb; else mxDestroyArray(fb);
     if (nlhs > 2) plhs[2] = vt; else mxDestroyArray(vt);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  // [xmin, fmin, out] = acq_search(h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts [, gplengthscale, X_rescaled, sn2new])
+  // opts: TolX, TolFun, TolHistFun, MaxFunEvals, MaxIter, PopSize, Seed, Chunk, Z (D x lambda x Gmax: parity mode); out: the bestever
+  // point and value, the final xmean / sigma / C, evals, generations, stop (1 TolX .. 5 MaxIter), behind
+  if (!strcmp(cmd, "acq_search")) {
+    if (nrhs < 12 || !mxIsStruct(prhs[3]) || !mxIsStruct(prhs[11]))
+      return raise("vbmc_hip:usage", "acq_search: h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts [, gplengthscale, X_rescaled, sn2new]");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    const mxArray *vp = prhs[3], *op = prhs[11];
+    const int D = (int)mxGetNumberOfElements(prhs[7]);
+    for (int i = 8; i <= 10; ++i)
+      if ((int)mxGetNumberOfElements(prhs[i]) != D) return raise("vbmc_hip:usage", "acq_search: x0, insigma, LB and UB must hold one value per dimension");
+    if (D < 1 || !field(vp, "lambda") || (int)mxGetNumberOfElements(field(vp, "lambda")) != D)
+      return raise("vbmc_hip:usage", "acq_search: vp.lambda must hold one value per dimension");
+    vbmc_acqsearch_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.acq_id = (int)mxGetScalar(prhs[2]); a.K = (int)scalar_field(vp, "K", 0);
+    a.vp_mu = dbl(field(vp, "mu")); a.vp_sigma = dbl(field(vp, "sigma")); a.vp_lambda = dbl(field(vp, "lambda")); a.vp_w = dbl(field(vp, "w"));
+    std::vector<double> delta;
+    if (const mxArray* dl = field(vp, "delta")) {
+      const int nd = (int)mxGetNumberOfElements(dl);
+      if (nd == 1) delta.assign(D, mxGetScalar(dl));
+      else if (nd == D) delta.assign(mxGetDoubles(dl), mxGetDoubles(dl) + D);
+      else if (nd != 0) return raise("vbmc_hip:unsupported", "acq_search: vp.delta must be empty, a scalar or one value per dimension");
+      if (!delta.empty()) a.vp_delta = delta.data();
+    }
+    a.ymax = mxGetScalar(prhs[4]); a.var_regularized = (int)mxGetScalar(prhs[5]); a.TolGPVar = mxGetScalar(prhs[6]);
+    a.x0 = dbl(prhs[7]); a.insigma = dbl(prhs[8]); a.LB = dbl(prhs[9]); a.UB = dbl(prhs[10]);
+    a.gplengthscale = nrhs > 12 ? dbl(prhs[12]) : nullptr; a.X_rescaled = nrhs > 13 ? dbl(prhs[13]) : nullptr; a.sn2new = nrhs > 14 ? dbl(prhs[14]) : nullptr;
+    a.TolX = scalar_field(op, "TolX", 0.0); a.TolFun = scalar_field(op, "TolFun", 0.0); a.TolHistFun = scalar_field(op, "TolHistFun", 0.0);
+    const double mfe = scalar_field(op, "MaxFunEvals", 0.0);
+    a.MaxFunEvals = (mfe > 0.0 && mfe < 9e18) ? (int64_t)mfe : 0;
+    a.MaxIter = (int)scalar_field(op, "MaxIter", 0.0); a.popsize = (int)scalar_field(op, "PopSize", 0.0); a.chunk = (int)scalar_field(op, "Chunk", 0.0);
+    a.seed = (uint64_t)scalar_field(op, "Seed", 0.0);
+    if (const mxArray* z = field(op, "Z")) {
+      if (!mxIsEmpty(z)) {
+        const int lam = a.popsize ? a.popsize : 4 + (int)std::floor(3.0 * std::log((double)D));
+        const size_t nz = mxGetNumberOfElements(z);
+        if (nz % ((size_t)D * lam) != 0) return raise("vbmc_hip:usage", "acq_search: opts.Z must be D x lambda x Gmax");
+        a.rng_mode = 1; a.Z = mxGetDoubles(z); a.Gmax = (int)(nz / ((size_t)D * lam));
+      }
+    }
+    const char* names[] = {"xbest", "fbest", "xmean", "sigma", "C", "evals", "generations", "stop", "behind"};
+    mxArray* out = mxCreateStructMatrix(1, 1, 9, names);
+    mxArray* f[9];
+    const int rows[9] = {D, 1, D, 1, D, 1, 1, 1, 1}, cols[9] = {1, 1, 1, 1, D, 1, 1, 1, 1};
+    for (int i = 0; i < 9; ++i) { f[i] = mxCreateDoubleMatrix(rows[i], cols[i], mxREAL); mxSetField(out, 0, names[i], f[i]); }
+    plhs[0] = mxCreateDoubleMatrix(D, 1, mxREAL);
+    mxArray* fmin = mxCreateDoubleMatrix(1, 1, mxREAL);
+    int64_t evals = 0, rounds[2] = {0, 0};
+    int32_t gens = 0, stop = 0;
+    a.xmin = mxGetDoubles(plhs[0]); a.fmin = mxGetDoubles(fmin);
+    a.xbest = mxGetDoubles(f[0]); a.fbest = mxGetDoubles(f[1]); a.xmean = mxGetDoubles(f[2]); a.sigma = mxGetDoubles(f[3]); a.C = mxGetDoubles(f[4]);
+    a.evals = &evals; a.generations = &gens; a.stop = &stop; a.rounds = rounds;
+    vbmc_status st = vbmc_acq_search(g_ctx, h, &a);
+    mxGetDoubles(f[5])[0] = (double)evals; mxGetDoubles(f[6])[0] = gens; mxGetDoubles(f[7])[0] = stop; mxGetDoubles(f[8])[0] = (double)rounds[1];
+    if (nlhs > 1) plhs[1] = fmin; else mxDestroyArray(fmin);
+    if (nlhs > 2) plhs[2] = out; else mxDestroyArray(out);
     if (st != VBMC_OK) return fail(st);
     return 0;
   }

@@ -1,0 +1,106 @@
+"""Time the acquisition search of one active-sampling point (private/activesample_vbmc.m:264-290) two ways, in one process and
+interleaved, at BASELINE configs[2]'s GP and vp (D = 10, N = 400, S = 20, K = 50), acqf_vbmc, MaxFunEvals = 6000, all tolerances zero
+so that both run 600 generations of lambda = 10 points:
+
+  device loop   vbmc_acq_search: the optimiser on the device, generations enqueued in chunks
+  host loop     what a caller had before it: cmaes_batched (vbmc_amd/optimize.py) on the host, one blocking vbmc_acq_eval round trip
+                of ten points per generation
+
+Prints one JSON line and writes the measured part of profiles/acq_search.md (its hand-written part, from "## Reading" on, survives).
+
+    python tools/bench_acq_search.py [--runs 5] [--quick]
+    python tools/bench_acq_search.py --trace      (one untimed device search to put under rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tools.bench_gp_quad import problem  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "acq_search.md"))
+    a = ap.parse_args()
+    import vbmc_amd as va
+    from vbmc_amd.optimize import cmaes_batched
+
+    N, D, S, K, maxfe = (100, 4, 3, 5, 400) if a.quick else (400, 10, 20, 50, 6000)
+    hyp, X, y, _, _ = problem(N, D, S, 16)
+    gp = va.gplite_post(hyp, X, y, 1, 4)
+    rng = np.random.default_rng(1)
+    vp = {"D": D, "K": K, "mu": X[rng.permutation(N)[:K]].T.copy(), "sigma": 0.4 + 0.2 * rng.random(K), "lambda": np.ones(D),
+          "w": rng.dirichlet(np.ones(K))}
+    st = {"ymax": float(np.max(y)), "VarianceRegularizedAcqFcn": True, "TolGPVar": 1e-4}
+    xr = X.max(axis=0) - X.min(axis=0)
+    LB, UB = X.min(axis=0) - 0.1 * xr, X.max(axis=0) + 0.1 * xr
+    x0 = X[int(np.argmax(y))].copy()
+    _, Sigma = va.vbmc_moments(vp)
+    insigma = np.sqrt(np.diag(Sigma))
+    tol = dict(TolX=0.0, TolFun=0.0, TolHistFun=0.0)
+
+    def device():
+        return va.acq_search(x0, insigma, LB, UB, vp, gp, st, "acqf_vbmc", MaxFunEvals=maxfe, seed=3, **tol)
+
+    def host():
+        f = lambda Xc: va.acqwrapper_vbmc(np.clip(Xc.T, LB, UB), vp, gp, st, False, "acqf_vbmc")  # noqa: E731
+        return cmaes_batched(f, x0, insigma, MaxFunEvals=maxfe, rng=np.random.default_rng(3), **tol)[1]
+
+    for _ in range(2):                                  # warm-up: code objects, inv(L') of the GP, the pooled buffers
+        device()
+        host()
+    if a.trace:
+        device()
+        return
+    ts = {"device": [], "host": []}
+    gens = {}
+    behind = []
+    for _ in range(a.runs):                             # interleaved: drift of the clocks hits both alike
+        t0 = time.perf_counter()
+        r = device()
+        ts["device"].append(time.perf_counter() - t0)
+        gens["device"] = r["generations"]
+        behind.append(r["behind"])
+        t0 = time.perf_counter()
+        h = host()
+        ts["host"].append(time.perf_counter() - t0)
+        gens["host"] = h["generations"]
+    row = {"N": N, "D": D, "S": S, "K": K, "MaxFunEvals": maxfe, "runs": a.runs, "generations": gens, "behind": behind}
+    for k, v in ts.items():
+        us = 1e6 * np.sort(v) / gens[k]
+        row[k] = {"median_us_per_generation": round(float(np.median(us)), 2), "min": round(float(us[0]), 2), "max": round(float(us[-1]), 2),
+                  "spread": round(float(us[-1] - us[0]), 2), "median_ms_per_search": round(1e3 * float(np.median(v)), 3)}
+    gap = row["host"]["median_us_per_generation"] - row["device"]["median_us_per_generation"]
+    row["host_minus_device_us"] = round(gap, 2)
+    row["spreads_together_us"] = round(row["host"]["spread"] + row["device"]["spread"], 2)
+    row["device_below_host_by_more_than_the_spreads"] = bool(gap > row["spreads_together_us"])
+    print(json.dumps(row))
+    keep = ""
+    if os.path.exists(a.out):
+        txt = open(a.out).read()
+        if "\n## Reading" in txt:
+            keep = txt[txt.index("\n## Reading"):]
+    with open(a.out, "w") as f:
+        f.write("# vbmc_acq_search: the acquisition search on the device beside the host loop it replaces\n\n")
+        f.write("`python tools/bench_acq_search.py --runs %d%s`: N = %d, D = %d, S = %d, K = %d, acqf_vbmc, MaxFunEvals = %d, tolerances zero "
+                "(%d generations of lambda = %d both ways); wall time of the whole search, %d runs each, interleaved, after two warm-up runs.\n\n"
+                % (a.runs, " --quick" if a.quick else "", N, D, S, K, maxfe, gens["device"], maxfe // gens["device"], a.runs))
+        f.write("| loop | median, us per generation | min - max | spread | median, ms per search |\n|---|---|---|---|---|\n")
+        for k, label in (("device", "device (`vbmc_acq_search`)"), ("host", "host (`cmaes_batched` + `vbmc_acq_eval`)")):
+            r = row[k]
+            f.write("| %s | %.2f | %.2f - %.2f | %.2f | %.3f |\n" % (label, r["median_us_per_generation"], r["min"], r["max"], r["spread"], r["median_ms_per_search"]))
+        f.write("\nhost - device (medians): %.2f us per generation; the two spreads together: %.2f us; generations enqueued behind the end per "
+                "run: %s\n\n```\n%s\n```\n%s" % (gap, row["spreads_together_us"], behind, json.dumps(row), keep))
+
+
+if __name__ == "__main__":
+    main()

@@ -112,6 +112,28 @@ class GpTrainArgs(C.Structure):
     ]
 
 
+class AcqSearchArgs(C.Structure):
+    """vbmc_acqsearch_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("acq_id", C.c_int32), ("K", C.c_int32),
+        ("vp_mu", _dp), ("vp_sigma", _dp), ("vp_lambda", _dp), ("vp_w", _dp), ("vp_delta", _dp),
+        ("ymax", C.c_double), ("var_regularized", C.c_int32), ("TolGPVar", C.c_double),
+        ("gplengthscale", _dp), ("X_rescaled", _dp), ("sn2new", _dp),
+        ("x0", _dp), ("insigma", _dp), ("LB", _dp), ("UB", _dp),
+        ("TolX", C.c_double), ("TolFun", C.c_double), ("TolHistFun", C.c_double),
+        ("MaxFunEvals", C.c_int64),
+        ("MaxIter", C.c_int32), ("popsize", C.c_int32), ("rng_mode", C.c_int32), ("Gmax", C.c_int32),
+        ("seed", C.c_uint64),
+        ("Z", _dp),
+        ("chunk", C.c_int32), ("trace_cap", C.c_int32),
+        ("xmin", _dp), ("fmin", _dp), ("xbest", _dp), ("fbest", _dp), ("xmean", _dp), ("sigma", _dp), ("C", _dp),
+        ("evals", C.POINTER(C.c_int64)), ("generations", C.POINTER(C.c_int32)), ("stop", C.POINTER(C.c_int32)),
+        ("rounds", C.POINTER(C.c_int64)),
+        ("tr_order", C.POINTER(C.c_int32)), ("tr_F", _dp), ("tr_xmean", _dp), ("tr_sigma", _dp),
+    ]
+
+
 _lib = None
 
 
@@ -177,6 +199,8 @@ def load():
     lib.vbmc_gp_slice_sample.argtypes = [vp, C.POINTER(SliceArgs)]
     lib.vbmc_gp_train_optimize.argtypes = [vp, C.POINTER(GpTrainArgs)]
     lib.vbmc_slice_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp]
+    lib.vbmc_acq_search.argtypes = [vp, vp, C.POINTER(AcqSearchArgs)]
+    lib.vbmc_acq_search_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)

@@ -519,6 +519,185 @@ def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *,
     return {"Xa": Xa, "lnw": lnw, "fs2a": fs2a, "funccount": info_s["funccount"]}
 
 
+# ------------------------------------------------------------------------------------------
+# The acquisition search of active sampling on the device (vbmc_acq_search)
+SEARCH_STOP = {1: "TolX", 2: "TolFun", 3: "TolHistFun", 4: "MaxFunEvals", 5: "MaxIter"}
+
+
+def acq_search_rng_dump(seed, D, lam, G):
+    """Z (D x lam x G) that ``acq_search(..., seed=seed)`` consumes (vbmc_acq_search_rng_dump: a pure host function)."""
+    import ctypes as C
+
+    from ._lib import load
+
+    Z = np.zeros((D, lam, G), order="F")
+    st = load().vbmc_acq_search_rng_dump(C.c_uint64(seed), int(D), int(lam), int(G), ptr(Z))
+    if st != 0:
+        raise ValueError("vbmc_acq_search_rng_dump: bad arguments")
+    return Z
+
+
+def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, TolX, TolFun, TolHistFun, MaxFunEvals=0, MaxIter=0,
+               popsize=0, seed=0, Z=None, chunk=0, trace=0, engine=None):
+    """The thin ctypes call of ``vbmc_acq_search`` (include/vbmc_hip.h): CMA-ES in its Cholesky form on ``acqwrapper_vbmc`` inside
+    the box [LB, UB], started at ``x0`` with the coordinate-wise standard deviations ``insigma``, the whole optimiser on the device.
+    ``acqFun``: a name, or the library's numeric id (what the library does not take it refuses itself).
+    ``Z`` (D x lam x Gmax normals): parity mode, the library's own generator keyed by ``seed`` otherwise.  ``trace`` = n keeps the
+    rank order, the sorted values, xmean and sigma of the first n generations.  Returns a dict: xmin / fmin (the last generation's
+    best), xbest / fbest (the best ever seen), xmean, sigma, C, evals, generations, stop (name), behind (launches enqueued behind
+    the end) and, with ``trace``, tr_order / tr_F / tr_xmean / tr_sigma."""
+    import ctypes as C
+
+    from ._lib import AcqSearchArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    acq_id = int(acqFun) if isinstance(acqFun, (int, np.integer)) else ACQ_IDS[acq_info(acqFun)["name"]]   # a name, or the library's id
+    D = gp["X"].shape[1]
+    K = int(vp["K"])
+    dgp = _device_gp_with_noise(engine, gp)
+    keep = {
+        "mu": f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)), "sigma": f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K)),
+        "lam": f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D)), "w": f64(np.asarray(vp["w"], dtype=np.float64).reshape(K)),
+        "x0": f64(np.asarray(x0, dtype=np.float64).reshape(D)),
+        "insigma": f64(np.broadcast_to(np.asarray(insigma, dtype=np.float64).reshape(-1), (D,)).copy()),
+        "LB": f64(np.asarray(LB, dtype=np.float64).reshape(D)), "UB": f64(np.asarray(UB, dtype=np.float64).reshape(D)),
+    }
+    a = AcqSearchArgs()
+    a.struct_size = C.sizeof(AcqSearchArgs)
+    a.acq_id, a.K = acq_id, K
+    a.vp_mu, a.vp_sigma, a.vp_lambda, a.vp_w = ptr(keep["mu"]), ptr(keep["sigma"]), ptr(keep["lam"]), ptr(keep["w"])
+    delta = vp.get("delta")
+    if delta is not None and np.size(delta) > 0:
+        dl = np.asarray(delta, dtype=np.float64).reshape(-1)
+        keep["delta"] = f64(np.full(D, dl[0]) if dl.size == 1 else dl.reshape(D))
+        a.vp_delta = ptr(keep["delta"])
+    a.ymax = float(optimState.get("ymax", 0.0))
+    a.var_regularized = int(bool(optimState.get("VarianceRegularizedAcqFcn", False)))
+    a.TolGPVar = float(optimState.get("TolGPVar", 0.0))
+    if acq_id == 3:
+        keep["gl"] = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
+        keep["xr"] = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
+        keep["sn"] = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
+        a.gplengthscale, a.X_rescaled, a.sn2new = ptr(keep["gl"]), ptr(keep["xr"]), ptr(keep["sn"])
+    a.x0, a.insigma, a.LB, a.UB = ptr(keep["x0"]), ptr(keep["insigma"]), ptr(keep["LB"]), ptr(keep["UB"])
+    a.TolX, a.TolFun, a.TolHistFun = float(TolX), float(TolFun), float(TolHistFun)
+    a.MaxFunEvals = 0 if (MaxFunEvals is None or not np.isfinite(MaxFunEvals)) else int(MaxFunEvals)
+    a.MaxIter, a.popsize, a.chunk = int(MaxIter or 0), int(popsize or 0), int(chunk or 0)
+    lam = int(popsize) if popsize else 4 + int(np.floor(3 * np.log(D)))
+    if Z is not None:
+        keep["Z"] = f64(np.asarray(Z, dtype=np.float64))
+        if keep["Z"].ndim != 3 or keep["Z"].shape[:2] != (D, lam):
+            raise ValueError("acq_search: Z must be D x lam x Gmax = %d x %d x Gmax" % (D, lam))
+        a.rng_mode, a.Gmax, a.Z = 1, keep["Z"].shape[2], ptr(keep["Z"])
+    else:
+        a.rng_mode, a.seed = 0, int(seed)
+    out = {"xmin": np.zeros(D), "xbest": np.zeros(D), "xmean": np.zeros(D), "C": np.zeros((D, D), order="F")}
+    sc = {k: C.c_double() for k in ("fmin", "fbest", "sigma")}
+    evals, rounds = C.c_int64(), (C.c_int64 * 2)()
+    gens, stop = C.c_int32(), C.c_int32()
+    a.xmin, a.xbest, a.xmean, a.C = ptr(out["xmin"]), ptr(out["xbest"]), ptr(out["xmean"]), ptr(out["C"])
+    a.fmin, a.fbest, a.sigma = C.pointer(sc["fmin"]), C.pointer(sc["fbest"]), C.pointer(sc["sigma"])
+    a.evals, a.generations, a.stop = C.pointer(evals), C.pointer(gens), C.pointer(stop)
+    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    n = int(trace or 0)
+    if n > 0:
+        out.update(tr_order=np.zeros((lam, n), dtype=np.int32, order="F"), tr_F=np.zeros((lam, n), order="F"),
+                   tr_xmean=np.zeros((D, n), order="F"), tr_sigma=np.zeros(n))
+        a.trace_cap = n
+        a.tr_order = out["tr_order"].ctypes.data_as(C.POINTER(C.c_int32))
+        a.tr_F, a.tr_xmean, a.tr_sigma = ptr(out["tr_F"]), ptr(out["tr_xmean"]), ptr(out["tr_sigma"])
+    ctx.check(ctx.lib.vbmc_acq_search(ctx.h, dgp.h, C.byref(a)))
+    out.update(fmin=sc["fmin"].value, fbest=sc["fbest"].value, sigma=sc["sigma"].value, evals=int(evals.value),
+               generations=int(gens.value), stop=SEARCH_STOP.get(int(stop.value), "MaxIter"), behind=int(rounds[1]), popsize=lam)
+    return out
+
+
+def vbmc_moments(vp, origflag=False):
+    """[mubar,Sigma] = vbmc_moments(vp,0)  (vbmc_moments.m:30-43): mean and covariance of the Gaussian-mixture variational posterior
+    in the TRANSFORMED space, analytically (origflag = 1 samples through warpvars_vbmc, the caller's side)."""
+    if origflag:
+        raise VbmcUnsupported(-1, "vbmc_moments: origflag = 1 needs warpvars_vbmc (caller's side)")
+    D, K = int(vp["D"]), int(vp["K"])
+    w = np.asarray(vp["w"], dtype=np.float64).reshape(1, K)
+    mu = np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)
+    sigma = np.asarray(vp["sigma"], dtype=np.float64).reshape(1, K)
+    lam = np.asarray(vp["lambda"], dtype=np.float64).reshape(D)
+    mubar = np.sum(w * mu, axis=1)
+    Sigma = np.sum(w * sigma ** 2) * np.diag(lam ** 2)
+    for k in range(K):
+        dk = (mu[:, k] - mubar).reshape(D, 1)
+        Sigma = Sigma + w[0, k] * (dk @ dk.T)
+    return mubar, Sigma
+
+
+SEARCH_DEFAULT_OPTIONS = {
+    "SearchOptimizer": "cmaes", "SearchCMAESVPInit": True, "SearchCMAESbest": False, "SearchMaxFunEvals": None, "HPDFrac": 0.8,
+    # misc/setupoptions_vbmc.m:168-170
+    "CMAESopts": {"TolX": lambda insigma: 1e-11 * float(np.max(insigma)), "TolHistFun": 1e-13},
+}
+
+
+def active_search(Xsearch, vp, gp, optimState, options=None, acqFun="acqf_vbmc", *, outside=None, seed=0, engine=None, info=None):
+    """The search for ONE new point of private/activesample_vbmc.m:227-329: the acquisition sweep over ``Xsearch`` and its argmin x0
+    (:228-238), the box (:249-255: optimState.LB_search / UB_search widened to hold x0, or the training inputs' range + 10 %), TolFun
+    (:257-262), insigma from vbmc_moments (SearchCMAESVPInit, :268,275) or the covariance of the HPD training inputs (:272-273), CMA-ES on
+    the device (``acq_search``), SearchCMAESbest (:285-288) and the acceptance test fval_optim < fval_old (:324).
+
+    Returns (Xacq (D,), fval, info) with info = {"x0", "fval_old", "accepted", "search": acq_search's dict or None, "idx"}.  Integer
+    variables (real2int_vbmc, :219,248,325) and the hard-bound mask in the original space are the caller's: ``outside`` marks sweep
+    points outside the hard bounds, optimState.integervars must be empty."""
+    from .optimize import gethpd_vbmc
+
+    opts = dict(SEARCH_DEFAULT_OPTIONS, **(options or {}))
+    iv = optimState.get("integervars")
+    if iv is not None and np.any(np.asarray(iv)):
+        raise VbmcUnsupported(-1, "active_search: integer variables (real2int_vbmc) are the caller's side")
+    engine = engine or default_engine()
+    X = np.asarray(gp["X"], dtype=np.float64)
+    D = X.shape[1]
+    Xsearch = np.asarray(Xsearch, dtype=np.float64).reshape(-1, D)
+    acq_fast = acqwrapper_vbmc(Xsearch, vp, gp, optimState, False, acqFun, outside=outside, engine=engine)       # :228
+    idx = int(np.argmin(acq_fast))       # :230-236 (the first minimum either way; optimState.SearchCache of :232 is the caller's to keep)
+    x0 = Xsearch[idx].copy()
+    res = {"x0": x0, "idx": idx, "accepted": False, "search": None}
+    if str(opts["SearchOptimizer"]).lower() == "none":                                                    # :246
+        res["fval_old"] = float(acq_fast[idx])
+        return x0, float(acq_fast[idx]), res
+    if str(opts["SearchOptimizer"]).lower() != "cmaes":
+        raise VbmcUnsupported(-1, "active_search: SearchOptimizer '%s' is not accelerated ('cmaes' is)" % opts["SearchOptimizer"])
+    fval_old = float(acqwrapper_vbmc(x0[None, :], vp, gp, optimState, False, acqFun, engine=engine)[0])   # :247
+    res["fval_old"] = fval_old
+    lbs, ubs = optimState.get("LB_search"), optimState.get("UB_search")
+    if lbs is not None and ubs is not None and np.all(np.isfinite(lbs)) and np.all(np.isfinite(ubs)):     # :249-251
+        LB = np.minimum(x0, np.asarray(lbs, dtype=np.float64).reshape(D))
+        UB = np.maximum(x0, np.asarray(ubs, dtype=np.float64).reshape(D))
+    else:                                                                                                 # :253-254
+        xrange = np.max(X, axis=0) - np.min(X, axis=0)
+        LB = np.minimum(np.min(X, axis=0), x0) - 0.1 * xrange
+        UB = np.maximum(np.max(X, axis=0), x0) + 0.1 * xrange
+    info = info or acq_info(acqFun)
+    TolFun = 1e-2 if info.get("log_flag") else max(1e-12, abs(fval_old * 1e-3))                           # :257-262
+    if opts["SearchCMAESVPInit"]:
+        _, Sigma = vbmc_moments(vp, False)                                                                # :268
+    else:
+        X_hpd, _ = gethpd_vbmc(X, gp["y"], opts["HPDFrac"])                                               # :272-273
+        Sigma = np.cov(X_hpd, rowvar=False, bias=True).reshape(D, D)
+    insigma = np.sqrt(np.diag(Sigma))                                                                     # :275
+    co = dict(SEARCH_DEFAULT_OPTIONS["CMAESopts"], **(opts.get("CMAESopts") or {}))
+    TolX = co["TolX"](insigma) if callable(co["TolX"]) else float(co["TolX"])
+    maxfe = opts["SearchMaxFunEvals"]
+    maxfe = 500 * (D + 2) if maxfe is None else int(maxfe(D) if callable(maxfe) else maxfe)               # vbmc.m:283
+    sr = acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun, TolX=TolX, TolFun=TolFun, TolHistFun=float(co["TolHistFun"]),
+                    MaxFunEvals=maxfe, popsize=int(co.get("PopSize") or 0), seed=seed, engine=engine)
+    res["search"] = sr
+    x_opt, f_opt = (sr["xbest"], sr["fbest"]) if opts["SearchCMAESbest"] else (sr["xmin"], sr["fmin"])    # :285-288
+    if f_opt < fval_old:                                                                                  # :324
+        res["accepted"] = True
+        return np.asarray(x_opt, dtype=np.float64).copy(), float(f_opt), res
+    return x0, fval_old, res
+
+
 def delta_positive(vp):
     d = vp.get("delta")
     return d is not None and bool(np.any(np.asarray(d) > 0))

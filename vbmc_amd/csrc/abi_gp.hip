@@ -585,61 +585,59 @@ struct PredBufs {
 // k_pred_fused and that matrix is never written (round 6).  VBMC_PRED_FUSED=0 keeps the two-kernel form (A/B runs, tests).
 // qsigma (D values, host): the Bayesian-quadrature form instead (gplite_quad.m) -- Xstar holds the means mu_i, pb.fmu / pb.fs2 receive
 // F / varF per hyper-sample through the k_quad_* forms of the same kernels, in the same launch forms (fused, two-kernel, slab).
-vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xstar, const double* ystar,
-                           const double* s2star, PredBufs& pb, bool want_ks = false, const double* qsigma = nullptr) {
-  if (!gp || Nstar <= 0 || !Xstar) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+//
+// Three layers.  pred_on_device takes host pointers, computes the points' column means and uploads both.  pred_on_device_resident takes
+// the points (pb.dXs, Nstar x D) and their column means (pb.dmb) where they already are, on the device; it is pred_plan -- every
+// allocation, every choice of a launch form, the one upload of the row-group table -- followed by pred_launch, which only enqueues
+// kernels and which a caller whose points change in place (vbmc_acq_search) repeats.
+struct PredPlan {
+  PredArgs pa{};
+  bool quad = false, slab_pred = false, fused = false;
+  int Nstar = 0, Np = 0, maxg = 0, PZ = 1, fused_pt = 0, fused_rs = 1;
+  size_t maxlds = 0;
+};
+
+vbmc_status pred_check(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, bool quad) {
+  if (!gp || Nstar <= 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
   if (!gp->hasL) return set_err(ctx, VBMC_ERR_INVALID, "%s needs gp.post(s).L on the device", who);
   if (!gp->has_noise) return set_err(ctx, VBMC_ERR_INVALID, "%s: call vbmc_gp_set_noise (noisefun, sn2_mult) first", who);
-  // output-dependent noise (noisefun(3) = 1) enters ys2 only, and only with a non-empty ystar (gplite_noisefun.m:198-207);
-  // fmu / fs2 -- all the acquisition functions read (acqwrapper_vbmc.m:17) -- never depend on it
-  // an empty s2star counts as zero (gplite_noisefun.m:51): the kernels add nothing when the pointer is null
-  const int N = gp->N, D = gp->D, S = gp->S;
-  if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
-  const bool quad = qsigma != nullptr;
+  if (gp->D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", gp->D, VBMC_LIM_D);
   if (quad && gp->meanfun != 0 && gp->meanfun != 1 && gp->meanfun != 4)
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: mean function %d not accelerated (0, 1, 4)", who, gp->meanfun);
   // gplite_quad.m:66-67,101 divides by the scalar sn2_eff = exp(2 hyp(Ncov+1)) sn2_mult: the constant-noise model, whose sW is that scalar
   if (quad && !(gp->noisefun[0] == 1 && gp->noisefun[1] == 0 && gp->noisefun[2] == 0))
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: only the constant noise model (noisefun [1 0 0]) is accelerated", who);
+  if (trsm_cw_for(gp->N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d too large for the prediction kernels", gp->N);
+  return VBMC_OK;
+}
+
+// pb.dXs, pb.dmb (and pb.ds2 / pb.dys where the caller has them) are allocated; their contents are read by pred_launch only
+vbmc_status pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, PredBufs& pb, bool want_ks, const double* qsigma, PredPlan& pl) {
+  // output-dependent noise (noisefun(3) = 1) enters ys2 only, and only with a non-empty ystar (gplite_noisefun.m:198-207);
+  // fmu / fs2 -- all the acquisition functions read (acqwrapper_vbmc.m:17) -- never depend on it
+  // an empty s2star counts as zero (gplite_noisefun.m:51): the kernels add nothing when the pointer is null
+  const int N = gp->N, D = gp->D, S = gp->S;
+  const bool quad = qsigma != nullptr;
   const int Np = ((N + 15) >> 4) << 4, nblk = Np >> 4;
   // beyond N = 1248 a 16-row tile of inv(L') no longer fits the LDS: the variance then comes from slab solves (k_pred_slab)
   const bool slab_pred = (size_t)16 * Np * 8 > PRED_LDS_MAX || nblk > PRED_MAXG || trsm_cw_for(N) != 16;
-  if (trsm_cw_for(N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d too large for the prediction kernels", N);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   if (!slab_pred) {   // Tinv = inv(L') = L' \ I for the Lchol samples, once per GP (the kernels skip the others)
     bool have = false;
     VB_TRY(ensure_tinv(ctx, gp, &have));
   }
-  // column means for sq_dist's centring (sq_dist.m:36), O((N + Nstar) D) on the host in MATLAB's order
-  std::vector<double> mb(D);
-  for (int d = 0; d < D; ++d) {
-    double sb = 0.0;
-    for (int j = 0; j < Nstar; ++j) sb += Xstar[j + (size_t)Nstar * d];
-    mb[d] = sb / Nstar;
-  }
   TmpBuf &dXs = pb.dXs, &ds2 = pb.ds2, &dmb = pb.dmb, &dout = pb.dout, &dXc = pb.dXc, &daa = pb.daa, &dmuv = pb.dmuv;
   HIP_TRY(ctx, dXc.alloc(ctx, (size_t)S * N * D * 8));
   HIP_TRY(ctx, daa.alloc(ctx, (size_t)S * N * 8));
   HIP_TRY(ctx, dmuv.alloc(ctx, (size_t)S * 2 * D * 8));
-  HIP_TRY(ctx, dXs.alloc(ctx, (size_t)Nstar * D * 8));
-  HIP_TRY(ctx, dmb.alloc(ctx, (size_t)D * 8));
   HIP_TRY(ctx, dout.alloc(ctx, (size_t)3 * Nstar * S * 8));
-  HIP_TRY(ctx, hipMemcpyAsync(dXs.p, Xstar, (size_t)Nstar * D * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dmb.p, mb.data(), (size_t)D * 8, hipMemcpyHostToDevice, st));
-  if (s2star) {
-    HIP_TRY(ctx, ds2.alloc(ctx, (size_t)Nstar * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(ds2.p, s2star, (size_t)Nstar * 8, hipMemcpyHostToDevice, st));
-  }
-  if (ystar && gp->noisefun[2] == 1) {
-    HIP_TRY(ctx, pb.dys.alloc(ctx, (size_t)Nstar * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(pb.dys.p, ystar, (size_t)Nstar * 8, hipMemcpyHostToDevice, st));
-  }
-  PredArgs pa{};
+  PredArgs& pa = pl.pa;
+  pa = PredArgs{};
   pa.N = N; pa.D = D; pa.S = S; pa.Nhyp = gp->Nhyp; pa.Nstar = Nstar; pa.meanfun = gp->meanfun;
   pa.moff = gp->Ncov + gp->Nnoise; pa.noff = gp->Ncov; pa.nf0 = gp->noisefun[0]; pa.nf1 = gp->noisefun[1]; pa.nf2 = gp->noisefun[2];
-  pa.X = gp->X; pa.Xs = dXs.as<double>(); pa.s2s = s2star ? ds2.as<double>() : nullptr; pa.hyp = gp->hyp;
-  pa.ys = (ystar && gp->noisefun[2] == 1) ? pb.dys.as<double>() : nullptr;
+  pa.X = gp->X; pa.Xs = dXs.as<double>(); pa.s2s = ds2.p ? ds2.as<double>() : nullptr; pa.hyp = gp->hyp;
+  pa.ys = pb.dys.p ? pb.dys.as<double>() : nullptr;
   pa.alpha = gp->alpha; pa.L = gp->L; pa.sn2_eff = gp->d_sn2; pa.sn2_mult = gp->d_mult; pa.lchol = gp->d_lchol;
   pa.mean_a = gp->d_meanX; pa.mean_b = dmb.as<double>(); pa.finv = gp->d_finv; pa.tinv = gp->d_tinv;
   pa.fmu = dout.as<double>(); pa.fs2 = pa.fmu + (size_t)Nstar * S; pa.ys2 = pa.fs2 + (size_t)Nstar * S;
@@ -649,14 +647,7 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
     HIP_TRY(ctx, pb.dqn.alloc(ctx, (size_t)S * 2 * 8));
     HIP_TRY(ctx, hipMemcpyAsync(pb.dqs.p, qsigma, (size_t)D * 8, hipMemcpyHostToDevice, st));
     pa.qsig = pb.dqs.as<double>(); pa.qnf = pb.dqn.as<double>();
-    hipLaunchKernelGGL(k_quad_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
-  } else {
-    hipLaunchKernelGGL(k_pred_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
   }
-  auto launch_final = [&] {
-    if (quad) hipLaunchKernelGGL(k_quad_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
-    else hipLaunchKernelGGL(k_pred_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
-  };
   // resident row blocks of Tinv per hyper-sample: consecutive 16-row tiles, balanced by area (tile b costs b + 1),
   // bounded by PRED_MAXR tiles and PRED_LDS_MAX bytes of LDS (two workgroups per CU)
   std::vector<int> grp((size_t)S + 2 * (size_t)S * PRED_MAXG, 0);
@@ -706,6 +697,26 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   HIP_TRY(ctx, pb.dpV.alloc(ctx, (size_t)maxg * S * Nstar * 8));
   HIP_TRY(ctx, pb.dpF.alloc(ctx, (size_t)S * Nstar * 8));
   HIP_TRY(ctx, hipMemcpyAsync(pb.dgrp.p, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  if (!fused) HIP_TRY(ctx, pb.dKs.alloc(ctx, (size_t)S * N * (((size_t)Nstar + 15) / 16) * 16 * 8));   // tiled by 16 points
+  pl.quad = quad; pl.slab_pred = slab_pred; pl.fused = fused; pl.Nstar = Nstar; pl.Np = Np; pl.maxg = maxg; pl.PZ = PZ;
+  pl.fused_pt = fused_pt; pl.fused_rs = fused_rs; pl.maxlds = maxlds;
+  return VBMC_OK;
+}
+
+vbmc_status pred_launch(vbmc_ctx* ctx, PredBufs& pb, const PredPlan& pl) {
+  const PredArgs& pa = pl.pa;
+  const int N = pa.N, D = pa.D, S = pa.S, Nstar = pl.Nstar, Np = pl.Np, maxg = pl.maxg, PZ = pl.PZ, fused_pt = pl.fused_pt, fused_rs = pl.fused_rs;
+  const bool quad = pl.quad, slab_pred = pl.slab_pred, fused = pl.fused;
+  const size_t maxlds = pl.maxlds;
+  const int ntile_ = (Nstar + 15) / 16;
+  hipStream_t st = ctx->stream;
+  TmpBuf &dXc = pb.dXc, &daa = pb.daa, &dmuv = pb.dmuv;
+  if (quad) hipLaunchKernelGGL(k_quad_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
+  else hipLaunchKernelGGL(k_pred_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
+  auto launch_final = [&] {
+    if (quad) hipLaunchKernelGGL(k_quad_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+    else hipLaunchKernelGGL(k_pred_final, dim3((Nstar + 255) / 256, S), dim3(256), 0, st, pa, pb.dgrp.as<int>(), pb.dpV.as<double>(), pb.dpF.as<double>());
+  };
   if (fused) {
     const size_t fl = PREDF_LDS_BYTES(fused_pt, Np);   // the tiles, and no less than the per-wave sums that reuse the block
     const int npass = (ntile_ + fused_pt - 1) / fused_pt;
@@ -729,7 +740,6 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
     HIP_TRY(ctx, hipGetLastError());
     return VBMC_OK;
   }
-  HIP_TRY(ctx, pb.dKs.alloc(ctx, (size_t)S * N * (((size_t)Nstar + 15) / 16) * 16 * 8));   // tiled by 16 points
   // inner dimension of the MFMA distance blocks: QS = ceil(D / 4) steps
 #define PRED_KS_K(KERN, QSV) hipLaunchKernelGGL((KERN<QSV>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(), \
                                                daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>())
@@ -752,6 +762,44 @@ vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, in
   launch_final();
   HIP_TRY(ctx, hipGetLastError());
   return VBMC_OK;
+}
+
+vbmc_status pred_on_device_resident(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, PredBufs& pb, bool want_ks = false,
+                                    const double* qsigma = nullptr) {
+  VB_TRY(pred_check(ctx, who, gp, Nstar, qsigma != nullptr));
+  if (!pb.dXs.p || !pb.dmb.p) return set_err(ctx, VBMC_ERR_INVALID, "%s: the points and their column means are not on the device", who);
+  PredPlan pl;
+  VB_TRY(pred_plan(ctx, gp, Nstar, pb, want_ks, qsigma, pl));
+  return pred_launch(ctx, pb, pl);
+}
+
+vbmc_status pred_on_device(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xstar, const double* ystar,
+                           const double* s2star, PredBufs& pb, bool want_ks = false, const double* qsigma = nullptr) {
+  if (!Xstar) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+  VB_TRY(pred_check(ctx, who, gp, Nstar, qsigma != nullptr));
+  const int D = gp->D;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // column means for sq_dist's centring (sq_dist.m:36), O((N + Nstar) D) on the host in MATLAB's order
+  std::vector<double> mb(D);
+  for (int d = 0; d < D; ++d) {
+    double sb = 0.0;
+    for (int j = 0; j < Nstar; ++j) sb += Xstar[j + (size_t)Nstar * d];
+    mb[d] = sb / Nstar;
+  }
+  HIP_TRY(ctx, pb.dXs.alloc(ctx, (size_t)Nstar * D * 8));
+  HIP_TRY(ctx, pb.dmb.alloc(ctx, (size_t)D * 8));
+  HIP_TRY(ctx, hipMemcpyAsync(pb.dXs.p, Xstar, (size_t)Nstar * D * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(pb.dmb.p, mb.data(), (size_t)D * 8, hipMemcpyHostToDevice, st));
+  if (s2star) {
+    HIP_TRY(ctx, pb.ds2.alloc(ctx, (size_t)Nstar * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(pb.ds2.p, s2star, (size_t)Nstar * 8, hipMemcpyHostToDevice, st));
+  }
+  if (ystar && gp->noisefun[2] == 1) {
+    HIP_TRY(ctx, pb.dys.alloc(ctx, (size_t)Nstar * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(pb.dys.p, ystar, (size_t)Nstar * 8, hipMemcpyHostToDevice, st));
+  }
+  return pred_on_device_resident(ctx, who, gp, Nstar, pb, want_ks, qsigma);
 }
 }  // namespace
 
@@ -927,6 +975,77 @@ extern "C" vbmc_status vbmc_acq_eval_delta(vbmc_ctx* ctx, const vbmc_gp* gp, int
 }
 
 namespace {
+// the caller's side of an acquisition evaluation: the variational posterior and the optimState fields acqwrapper_vbmc reads
+struct AcqInputs {
+  int acq_id, K;
+  const double *vp_mu, *vp_sigma, *vp_lambda, *vp_w;
+  double ymax;
+  int var_regularized;
+  double TolGPVar;
+  const double *gplengthscale, *X_rescaled, *sn2new;   // acq_id 3
+};
+
+// What k_acq reads besides the prediction: the O(K D) constants of the variational posterior's density and, for acqfsn2, the inputs of
+// the nearest-neighbour noise.  upload() fills everything of `a` but Xs / fmu / fs2 and the outputs; launch() enqueues k_nn_noise (acq_id 3)
+// and k_acq on the points a.Xs holds at that moment (shared by the sweep, vbmc_acq_eval, and the search, vbmc_acq_search).
+struct AcqConsts {
+  TmpBuf dmu, dhb, dgl, dXr, dsn, dsx;
+  std::vector<double> hb;   // staging of the constants: alive until the caller has synchronised
+  AcqArgs a{};
+  vbmc_status upload(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const AcqInputs& in) {
+    const int acq_id = in.acq_id, K = in.K, var_regularized = in.var_regularized;
+    const double *vp_mu = in.vp_mu, *vp_sigma = in.vp_sigma, *vp_lambda = in.vp_lambda, *vp_w = in.vp_w;
+    const double *gplengthscale = in.gplengthscale, *X_rescaled = in.X_rescaled, *sn2new = in.sn2new;
+    const double ymax = in.ymax, TolGPVar = in.TolGPVar;
+    hipStream_t st = ctx->stream;
+    const int N = gp->N, D = gp->D, S = gp->S;
+    if ((size_t)(2 * K * D + K) * 8 > 64 * 1024) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: K*D = %d too large", who, K * D);
+    // host: O(K D) constants of vbmc_pdf.m:57-62 in the reference's order of operations
+    double prodl = 1.0;
+    for (int d = 0; d < D; ++d) prodl *= vp_lambda[d];
+    const double nf = 1.0 / std::pow(2.0 * 3.14159265358979323846, D / 2.0) / prodl;
+    hb.assign((size_t)K * D + K, 0.0);
+    for (int k = 0; k < K; ++k) {
+      for (int d = 0; d < D; ++d) hb[(size_t)k * D + d] = 1.0 / (vp_sigma[k] * vp_lambda[d]);
+      hb[(size_t)K * D + k] = nf * vp_w[k] / std::pow(vp_sigma[k], D);
+    }
+    HIP_TRY(ctx, dmu.alloc(ctx, (size_t)D * K * 8));
+    HIP_TRY(ctx, dhb.alloc(ctx, hb.size() * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(dmu.p, vp_mu, (size_t)D * K * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dhb.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
+    a = AcqArgs{};
+    a.Nstar = Nstar; a.S = S; a.D = D; a.K = K; a.N = N; a.acq_id = acq_id; a.reg = var_regularized ? 1 : 0;
+    a.ymax = ymax; a.TolVar = TolGPVar;
+    a.mu = dmu.as<double>(); a.isl = dhb.as<double>(); a.coef = dhb.as<double>() + (size_t)K * D;
+    if (acq_id == 3) {
+      HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
+      HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
+      HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
+      HIP_TRY(ctx, hipMemcpyAsync(dgl.p, gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(dXr.p, X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(dsn.p, sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, dsx.alloc(ctx, (size_t)Nstar * 8));
+      a.sn2x = dsx.as<double>();
+    }
+    return VBMC_OK;
+  }
+  void launch(hipStream_t st) {
+    const int Nstar = a.Nstar, N = a.N, D = a.D, K = a.K;
+    if (a.acq_id == 3) {
+      switch ((D + 3) / 4) {
+#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nstar + 15) / 16), dim3(64), 0, st, Nstar, N, D, a.Xs, \
+                                                 dgl.as<double>(), dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
+        NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
+#undef NN_CASE
+        default: break;
+      }
+    }
+    hipLaunchKernelGGL(k_acq, dim3((Nstar + 255) / 256), dim3(256), (size_t)(2 * K * D + K) * 8, st, a);
+  }
+};
+}  // namespace
+
+namespace {
 vbmc_status acq_eval_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const double* Xs, int acq_id, int K,
                           const double* vp_mu, const double* vp_sigma, const double* vp_lambda, const double* vp_w,
                           double ymax, int var_regularized, double TolGPVar, const double* gplengthscale,
@@ -952,47 +1071,14 @@ vbmc_status acq_eval_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int
   PredBufs pb;
   VB_TRY(pred_on_device(ctx, who, gp, Nstar, Xs, nullptr, nullptr, pb, false, delta));
   hipStream_t st = ctx->stream;
-  const int N = gp->N, D = gp->D, S = gp->S;
-  if ((size_t)(2 * K * D + K) * 8 > 64 * 1024) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: K*D = %d too large", who, K * D);
-  // host: O(K D) constants of vbmc_pdf.m:57-62 in the reference's order of operations
-  double prodl = 1.0;
-  for (int d = 0; d < D; ++d) prodl *= vp_lambda[d];
-  const double nf = 1.0 / std::pow(2.0 * 3.14159265358979323846, D / 2.0) / prodl;
-  std::vector<double> hb((size_t)K * D + K);
-  for (int k = 0; k < K; ++k) {
-    for (int d = 0; d < D; ++d) hb[(size_t)k * D + d] = 1.0 / (vp_sigma[k] * vp_lambda[d]);
-    hb[(size_t)K * D + k] = nf * vp_w[k] / std::pow(vp_sigma[k], D);
-  }
-  TmpBuf dmu, dhb, dgl, dXr, dsn, dsx, dres;
-  HIP_TRY(ctx, dmu.alloc(ctx, (size_t)D * K * 8));
-  HIP_TRY(ctx, dhb.alloc(ctx, hb.size() * 8));
+  AcqConsts ac;
+  TmpBuf dres;
+  const AcqInputs in{acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar, gplengthscale, X_rescaled, sn2new};
+  VB_TRY(ac.upload(ctx, who, gp, Nstar, in));
   HIP_TRY(ctx, dres.alloc(ctx, (size_t)3 * Nstar * 8));
-  HIP_TRY(ctx, hipMemcpyAsync(dmu.p, vp_mu, (size_t)D * K * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dhb.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
-  AcqArgs a{};
-  a.Nstar = Nstar; a.S = S; a.D = D; a.K = K; a.N = N; a.acq_id = acq_id; a.reg = var_regularized ? 1 : 0;
-  a.ymax = ymax; a.TolVar = TolGPVar;
-  a.Xs = pb.dXs.as<double>(); a.fmu = pb.fmu; a.fs2 = pb.fs2;
-  a.mu = dmu.as<double>(); a.isl = dhb.as<double>(); a.coef = dhb.as<double>() + (size_t)K * D;
-  if (acq_id == 3) {
-    HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
-    HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
-    HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(dgl.p, gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dXr.p, X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dsn.p, sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, dsx.alloc(ctx, (size_t)Nstar * 8));
-    switch ((D + 3) / 4) {
-#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nstar + 15) / 16), dim3(64), 0, st, Nstar, N, D, pb.dXs.as<double>(), \
-                                                 dgl.as<double>(), dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
-      NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
-#undef NN_CASE
-      default: break;
-    }
-    a.sn2x = dsx.as<double>();
-  }
-  a.acq = dres.as<double>(); a.fbar = a.acq + Nstar; a.vtot = a.fbar + Nstar;
-  hipLaunchKernelGGL(k_acq, dim3((Nstar + 255) / 256), dim3(256), (size_t)(2 * K * D + K) * 8, st, a);
+  ac.a.Xs = pb.dXs.as<double>(); ac.a.fmu = pb.fmu; ac.a.fs2 = pb.fs2;
+  ac.a.acq = dres.as<double>(); ac.a.fbar = ac.a.acq + Nstar; ac.a.vtot = ac.a.fbar + Nstar;
+  ac.launch(st);
   HIP_TRY(ctx, hipGetLastError());
   std::vector<double> h((size_t)3 * Nstar);
   HIP_TRY(ctx, hipMemcpyAsync(h.data(), dres.p, h.size() * 8, hipMemcpyDeviceToHost, st));

@@ -94,15 +94,16 @@ struct GpObjWork {
 // reads a landed slot.  On a stall the rounds already enqueued are no-ops: the queue is drained, ONE checked round enqueued, and
 // the read-behind starts again.
 // (rounds enqueued behind the end of the chain, or behind a stall, launch nothing in propose / build / factorise / solve / decide,
-// but k_gp_scale and k_nlz_final still run their workgroups: the chunks start at 4 rounds and double up to cap, so that
+// but k_gp_scale and k_nlz_final still run their workgroups: the chunks start at `first` = 4 rounds and double up to cap, so that
 // a short chain wastes a handful of such rounds and a long one at most two chunks of them)
 enum class Progress { running, finished, stalled };
 template <class Round, class Classify>
-vbmc_status drive_rounds(vbmc_ctx* ctx, const char* who, int cap, Round round, const void* d_state, size_t bytes, size_t stride, Classify classify) {
+vbmc_status drive_rounds(vbmc_ctx* ctx, const char* who, int cap, Round round, const void* d_state, size_t bytes, size_t stride, Classify classify,
+                         int first = 4) {
   hipStream_t st = ctx->stream;
   hipEvent_t ev[2] = {ctx->ev_fork, ctx->ev_join};
   if (!ev[0] || !ev[1]) return set_err(ctx, VBMC_ERR_HIP, "%s: the context has no events", who);
-  int k = 0, chunk = 4;
+  int k = 0, chunk = first;
   bool have_prev = false, finished = false;
   vbmc_status rs = VBMC_OK;
   while (!finished && rs == VBMC_OK) {

@@ -2,4 +2,5 @@
 #include "abi_elbo.hip"
 #include "abi_gp.hip"
 #include "abi_gp_train.hip"
+#include "abi_acq_search.hip"
 #include "abi_comm.hip"
