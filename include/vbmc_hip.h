@@ -385,7 +385,7 @@ vbmc_status vbmc_gp_quad(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, const doub
  * that `seed` stands for.  rng_mode 1 (parity): the caller supplies that block for Gmax generations; a search that needs more ends with
  * VBMC_ERR_INVALID ("normal block exhausted").  A replay of a dump in parity mode is bit-identical.
  *
- * VBMC_ERR_UNSUPPORTED: the IQR acquisition functions (ids >= 10) and any other id outside 0-3, vp_delta with a positive entry, and
+ * VBMC_ERR_UNSUPPORTED: the IQR acquisition functions (ids >= 10: vbmc_acq_search_iqr searches those) and any other id outside 0-3, vp_delta with a positive entry, and
  * whatever vbmc_acq_eval refuses.  VBMC_ERR_INVALID: LB / UB / x0 / insigma not finite, LB >= UB, x0 outside the box, insigma not
  * positive, popsize outside 2 .. 16 (0 aside).  The context stays usable after any error.
  * Outputs (any may be NULL): xmin / fmin the LAST generation's best point and value (what cmaes_modded returns first), xbest / fbest the
@@ -410,9 +410,9 @@ typedef struct vbmc_acqsearch_args {
   double ymax;
   int32_t var_regularized;
   double TolGPVar;
-  const double* gplengthscale; /* acq_id 3 */
-  const double* X_rescaled;    /* acq_id 3 */
-  const double* sn2new;        /* acq_id 3 */
+  const double* gplengthscale; /* acq_id 3, 10, 11 */
+  const double* X_rescaled;    /* acq_id 3, 10, 11 */
+  const double* sn2new;        /* acq_id 3, 10, 11 */
   const double* x0;          /* D, inside the box */
   const double* insigma;     /* D, positive */
   const double* LB;          /* D */
@@ -444,6 +444,21 @@ typedef struct vbmc_acqsearch_args {
 } vbmc_acqsearch_args;
 vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acqsearch_args* args);
 vbmc_status vbmc_acq_search_rng_dump(uint64_t seed, int D, int lam, int G, double* Z);
+
+/*
+ * The same search on the importance-sampled IQR acquisition functions of noisy targets (misc/setupoptions_vbmc.m:144-159): the objective
+ * is exactly the function of vbmc_acq_iqr_eval -- acqwrapper_vbmc with acqviqr_vbmc / acqimiqr_vbmc on the state `is`
+ * (vbmc_acq_is_create), log-valued, with the wrapper's variance regulariser and clamp.  Same argument struct, optimiser, random-number
+ * contract (vbmc_acq_search_rng_dump, parity replay), outputs, trace, stop codes, chunked driving and box / start / popsize validation as
+ * vbmc_acq_search.  acq_id must be 10 or 11 (both mean the same computation; the state decides: no lnw is VIQR, lnw and / or
+ * per-hyper-sample Xa is IMIQR), anything else is VBMC_ERR_UNSUPPORTED, as is vp_delta with a non-zero entry.  gplengthscale, X_rescaled
+ * and sn2new are required (VBMC_ERR_INVALID without them); K, vp_mu, vp_sigma, vp_lambda, vp_w and ymax are not read.  A state created
+ * for another GP is VBMC_ERR_INVALID.  One generation is the optimiser's kernel, the prediction of the one point tile (which leaves its
+ * sW-scaled cross-kernel tile), the nearest-neighbour noise, the tile kernel -- one workgroup per 16 importance points and hyper-sample,
+ * its waves splitting the sum over the training points -- and a closing kernel.  The prediction's sq_dist centring constant is the
+ * training inputs' mean alone here, so that a point's value depends neither on its slot among the lambda points nor on the other points.
+ */
+vbmc_status vbmc_acq_search_iqr(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, const vbmc_acqsearch_args* args);
 
 /*
  * The O(N^2) pieces of gplite_post's rank-1 append of one training point x* (gplite/gplite_post.m:173-251),

@@ -30,6 +30,7 @@
 //     [F,varF] = vbmc_hip_mex('gp_quad', h, mu, sigma, ssflag, numel(gp.post))   (gplite_quad: sigma 1 x D, or Nstar x D of equal rows)
 //     [xmin,fmin,out] = vbmc_hip_mex('acq_search', h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new)
 //                                                  (the CMA-ES acquisition search on the device: matlab/vbmc_hip_acqsearch.m)
+//     [xmin,fmin,out] = vbmc_hip_mex('acq_search_iqr', h, his, acq_id, vp, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new)
 //     his = vbmc_hip_mex('is_create', h, Xa, lnw_or_empty, fs2a_or_empty, Ctmp_or_empty)   (ActiveImportanceSampling state)
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
@@ -245,9 +246,9 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr"};
     for (const char* w : with_handle)
-      if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || (!strcmp(cmd, "acq_iqr") && (nrhs < 3 || !is_handle(prhs[2])))))
+      if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || ((!strcmp(cmd, "acq_iqr") || !strcmp(cmd, "acq_search_iqr")) && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
   }
 
@@ -519,11 +520,16 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   // [xmin, fmin, out] = acq_search(h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts [, gplengthscale, X_rescaled, sn2new])
   // opts: TolX, TolFun, TolHistFun, MaxFunEvals, MaxIter, PopSize, Seed, Chunk, Z (D x lambda x Gmax: parity mode); out: the bestever
   // point and value, the final xmean / sigma / C, evals, generations, stop (1 TolX .. 5 MaxIter), behind
-  if (!strcmp(cmd, "acq_search")) {
-    if (nrhs < 12 || !mxIsStruct(prhs[3]) || !mxIsStruct(prhs[11]))
+  // [xmin, fmin, out] = acq_search_iqr(h, his, acq_id, vp, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new)
+  // the same opts and out on the IQR functions (vbmc_acq_search_iqr): from var_regularized on the arguments sit where acq_search has them
+  const bool search_iqr = !strcmp(cmd, "acq_search_iqr");
+  if (!strcmp(cmd, "acq_search") || search_iqr) {
+    if (search_iqr && (nrhs < 15 || !mxIsStruct(prhs[4]) || !mxIsStruct(prhs[11])))
+      return raise("vbmc_hip:usage", "acq_search_iqr: h, his, acq_id, vp, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new");
+    if (!search_iqr && (nrhs < 12 || !mxIsStruct(prhs[3]) || !mxIsStruct(prhs[11])))
       return raise("vbmc_hip:usage", "acq_search: h, acq_id, vp, ymax, var_regularized, TolGPVar, x0, insigma, LB, UB, opts [, gplengthscale, X_rescaled, sn2new]");
     vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
-    const mxArray *vp = prhs[3], *op = prhs[11];
+    const mxArray *vp = prhs[search_iqr ? 4 : 3], *op = prhs[11];
     const int D = (int)mxGetNumberOfElements(prhs[7]);
     for (int i = 8; i <= 10; ++i)
       if ((int)mxGetNumberOfElements(prhs[i]) != D) return raise("vbmc_hip:usage", "acq_search: x0, insigma, LB and UB must hold one value per dimension");
@@ -532,7 +538,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     vbmc_acqsearch_args a;
     memset(&a, 0, sizeof a);
     a.struct_size = sizeof a;
-    a.acq_id = (int)mxGetScalar(prhs[2]); a.K = (int)scalar_field(vp, "K", 0);
+    a.acq_id = (int)mxGetScalar(prhs[search_iqr ? 3 : 2]); a.K = (int)scalar_field(vp, "K", 0);
     a.vp_mu = dbl(field(vp, "mu")); a.vp_sigma = dbl(field(vp, "sigma")); a.vp_lambda = dbl(field(vp, "lambda")); a.vp_w = dbl(field(vp, "w"));
     std::vector<double> delta;
     if (const mxArray* dl = field(vp, "delta")) {
@@ -542,7 +548,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
       else if (nd != 0) return raise("vbmc_hip:unsupported", "acq_search: vp.delta must be empty, a scalar or one value per dimension");
       if (!delta.empty()) a.vp_delta = delta.data();
     }
-    a.ymax = mxGetScalar(prhs[4]); a.var_regularized = (int)mxGetScalar(prhs[5]); a.TolGPVar = mxGetScalar(prhs[6]);
+    a.ymax = search_iqr ? 0.0 : mxGetScalar(prhs[4]); a.var_regularized = (int)mxGetScalar(prhs[5]); a.TolGPVar = mxGetScalar(prhs[6]);
     a.x0 = dbl(prhs[7]); a.insigma = dbl(prhs[8]); a.LB = dbl(prhs[9]); a.UB = dbl(prhs[10]);
     a.gplengthscale = nrhs > 12 ? dbl(prhs[12]) : nullptr; a.X_rescaled = nrhs > 13 ? dbl(prhs[13]) : nullptr; a.sn2new = nrhs > 14 ? dbl(prhs[14]) : nullptr;
     a.TolX = scalar_field(op, "TolX", 0.0); a.TolFun = scalar_field(op, "TolFun", 0.0); a.TolHistFun = scalar_field(op, "TolHistFun", 0.0);
@@ -570,7 +576,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     a.xmin = mxGetDoubles(plhs[0]); a.fmin = mxGetDoubles(fmin);
     a.xbest = mxGetDoubles(f[0]); a.fbest = mxGetDoubles(f[1]); a.xmean = mxGetDoubles(f[2]); a.sigma = mxGetDoubles(f[3]); a.C = mxGetDoubles(f[4]);
     a.evals = &evals; a.generations = &gens; a.stop = &stop; a.rounds = rounds;
-    vbmc_status st = vbmc_acq_search(g_ctx, h, &a);
+    vbmc_status st = search_iqr ? vbmc_acq_search_iqr(g_ctx, h, (vbmc_acq_is*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[2])), &a) : vbmc_acq_search(g_ctx, h, &a);
     mxGetDoubles(f[5])[0] = (double)evals; mxGetDoubles(f[6])[0] = gens; mxGetDoubles(f[7])[0] = stop; mxGetDoubles(f[8])[0] = (double)rounds[1];
     if (nlhs > 1) plhs[1] = fmin; else mxDestroyArray(fmin);
     if (nlhs > 2) plhs[2] = out; else mxDestroyArray(out);

@@ -10,6 +10,9 @@ Prints one JSON line and writes the measured part of profiles/acq_search.md (its
 
     python tools/bench_acq_search.py [--runs 5] [--quick]
     python tools/bench_acq_search.py --trace      (one untimed device search to put under rocprofv3 --kernel-trace --stats)
+    python tools/bench_acq_search.py --acq acqviqr_vbmc --Na 100 [--N 800 --D 20 --S 1]
+        the same two loops on the IQR function of noisy targets (vbmc_acq_search_iqr; the host loop calls acqwrapper_vbmc(acqviqr) once
+        per generation), importance points drawn around the start; writes profiles/acq_search_iqr_N<N>_D<D>_S<S>.md unless --out is given
 """
 import argparse
 import json
@@ -29,12 +32,23 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "acq_search.md"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--acq", default="acqf_vbmc", choices=["acqf_vbmc", "acqviqr_vbmc"])
+    ap.add_argument("--Na", type=int, default=100)
+    ap.add_argument("--N", type=int, default=0)
+    ap.add_argument("--D", type=int, default=0)
+    ap.add_argument("--S", type=int, default=0)
     a = ap.parse_args()
+    iqr = a.acq == "acqviqr_vbmc"
     import vbmc_amd as va
     from vbmc_amd.optimize import cmaes_batched
 
     N, D, S, K, maxfe = (100, 4, 3, 5, 400) if a.quick else (400, 10, 20, 50, 6000)
+    N, D, S = a.N or N, a.D or D, a.S or S
+    if a.D and not a.quick:
+        maxfe = 600 * (4 + int(np.floor(3 * np.log(D))))   # 600 generations at any D
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "acq_search_iqr_N%d_D%d_S%d.md" % (N, D, S) if iqr else "acq_search.md")
     hyp, X, y, _, _ = problem(N, D, S, 16)
     gp = va.gplite_post(hyp, X, y, 1, 4)
     rng = np.random.default_rng(1)
@@ -47,12 +61,16 @@ def main():
     _, Sigma = va.vbmc_moments(vp)
     insigma = np.sqrt(np.diag(Sigma))
     tol = dict(TolX=0.0, TolFun=0.0, TolHistFun=0.0)
+    if iqr:                                             # noisy-target inputs; Ctmp and fs2a are computed by vbmc_acq_is_create
+        gl = np.exp(np.mean(np.stack([np.asarray(q["hyp"])[:D] for q in gp["post"]], axis=1), axis=1))
+        gp = dict(gp, X_rescaled=X / gl[None, :], sn2new=0.02 + 0.1 * rng.random(N))
+        st.update(gplengthscale=gl, ActiveImportanceSampling={"Xa": x0 + gl / np.sqrt(D) * rng.standard_normal((a.Na, D))})
 
     def device():
-        return va.acq_search(x0, insigma, LB, UB, vp, gp, st, "acqf_vbmc", MaxFunEvals=maxfe, seed=3, **tol)
+        return va.acq_search(x0, insigma, LB, UB, vp, gp, st, a.acq, MaxFunEvals=maxfe, seed=3, **tol)
 
     def host():
-        f = lambda Xc: va.acqwrapper_vbmc(np.clip(Xc.T, LB, UB), vp, gp, st, False, "acqf_vbmc")  # noqa: E731
+        f = lambda Xc: va.acqwrapper_vbmc(np.clip(Xc.T, LB, UB), vp, gp, st, False, a.acq)  # noqa: E731
         return cmaes_batched(f, x0, insigma, MaxFunEvals=maxfe, rng=np.random.default_rng(3), **tol)[1]
 
     for _ in range(2):                                  # warm-up: code objects, inv(L') of the GP, the pooled buffers
@@ -74,7 +92,7 @@ def main():
         h = host()
         ts["host"].append(time.perf_counter() - t0)
         gens["host"] = h["generations"]
-    row = {"N": N, "D": D, "S": S, "K": K, "MaxFunEvals": maxfe, "runs": a.runs, "generations": gens, "behind": behind}
+    row = {"acq": a.acq, "Na": a.Na if iqr else 0, "N": N, "D": D, "S": S, "K": K, "MaxFunEvals": maxfe, "runs": a.runs, "generations": gens, "behind": behind}
     for k, v in ts.items():
         us = 1e6 * np.sort(v) / gens[k]
         row[k] = {"median_us_per_generation": round(float(np.median(us)), 2), "min": round(float(us[0]), 2), "max": round(float(us[-1]), 2),
@@ -90,12 +108,14 @@ def main():
         if "\n## Reading" in txt:
             keep = txt[txt.index("\n## Reading"):]
     with open(a.out, "w") as f:
-        f.write("# vbmc_acq_search: the acquisition search on the device beside the host loop it replaces\n\n")
-        f.write("`python tools/bench_acq_search.py --runs %d%s`: N = %d, D = %d, S = %d, K = %d, acqf_vbmc, MaxFunEvals = %d, tolerances zero "
+        entry = "vbmc_acq_search_iqr" if iqr else "vbmc_acq_search"
+        f.write("# %s: the acquisition search on the device beside the host loop it replaces\n\n" % entry)
+        f.write("`python tools/bench_acq_search.py --runs %d%s%s`: N = %d, D = %d, S = %d, K = %d, %s, MaxFunEvals = %d, tolerances zero "
                 "(%d generations of lambda = %d both ways); wall time of the whole search, %d runs each, interleaved, after two warm-up runs.\n\n"
-                % (a.runs, " --quick" if a.quick else "", N, D, S, K, maxfe, gens["device"], maxfe // gens["device"], a.runs))
+                % (a.runs, " --quick" if a.quick else "", " --acq %s --Na %d --N %d --D %d --S %d" % (a.acq, a.Na, N, D, S) if iqr else "",
+                   N, D, S, K, a.acq + (" (Na = %d)" % a.Na if iqr else ""), maxfe, gens["device"], maxfe // gens["device"], a.runs))
         f.write("| loop | median, us per generation | min - max | spread | median, ms per search |\n|---|---|---|---|---|\n")
-        for k, label in (("device", "device (`vbmc_acq_search`)"), ("host", "host (`cmaes_batched` + `vbmc_acq_eval`)")):
+        for k, label in (("device", "device (`%s`)" % entry), ("host", "host (`cmaes_batched` + `%s`)" % ("vbmc_acq_iqr_eval" if iqr else "vbmc_acq_eval"))):
             r = row[k]
             f.write("| %s | %.2f | %.2f - %.2f | %.2f | %.3f |\n" % (label, r["median_us_per_generation"], r["min"], r["max"], r["spread"], r["median_ms_per_search"]))
         f.write("\nhost - device (medians): %.2f us per generation; the two spreads together: %.2f us; generations enqueued behind the end per "

@@ -200,6 +200,7 @@ def load():
     lib.vbmc_gp_train_optimize.argtypes = [vp, C.POINTER(GpTrainArgs)]
     lib.vbmc_slice_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp]
     lib.vbmc_acq_search.argtypes = [vp, vp, C.POINTER(AcqSearchArgs)]
+    lib.vbmc_acq_search_iqr.argtypes = [vp, vp, vp, C.POINTER(AcqSearchArgs)]
     lib.vbmc_acq_search_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]

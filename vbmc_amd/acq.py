@@ -538,10 +538,13 @@ def acq_search_rng_dump(seed, D, lam, G):
 
 
 def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, TolX, TolFun, TolHistFun, MaxFunEvals=0, MaxIter=0,
-               popsize=0, seed=0, Z=None, chunk=0, trace=0, engine=None):
+               popsize=0, seed=0, Z=None, chunk=0, trace=0, engine=None, iqr=None):
     """The thin ctypes call of ``vbmc_acq_search`` (include/vbmc_hip.h): CMA-ES in its Cholesky form on ``acqwrapper_vbmc`` inside
     the box [LB, UB], started at ``x0`` with the coordinate-wise standard deviations ``insigma``, the whole optimiser on the device.
     ``acqFun``: a name, or the library's numeric id (what the library does not take it refuses itself).
+    The IQR functions (``acqviqr_vbmc`` / ``acqimiqr_vbmc``, ids 10 / 11) with ``optimState["ActiveImportanceSampling"]`` present go to
+    ``vbmc_acq_search_iqr`` on the device copy of that state (built or reused as ``acqwrapper_vbmc`` does); without the state the call
+    reaches ``vbmc_acq_search``, which refuses them.  ``iqr`` = True / False forces the entry point (tests of the library's refusals).
     ``Z`` (D x lam x Gmax normals): parity mode, the library's own generator keyed by ``seed`` otherwise.  ``trace`` = n keeps the
     rank order, the sorted values, xmean and sigma of the first n generations.  Returns a dict: xmin / fmin (the last generation's
     best), xbest / fbest (the best ever seen), xmean, sigma, C, evals, generations, stop (name), behind (launches enqueued behind
@@ -575,11 +578,17 @@ def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, T
     a.ymax = float(optimState.get("ymax", 0.0))
     a.var_regularized = int(bool(optimState.get("VarianceRegularizedAcqFcn", False)))
     a.TolGPVar = float(optimState.get("TolGPVar", 0.0))
-    if acq_id == 3:
-        keep["gl"] = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
-        keep["xr"] = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
-        keep["sn"] = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
-        a.gplengthscale, a.X_rescaled, a.sn2new = ptr(keep["gl"]), ptr(keep["xr"]), ptr(keep["sn"])
+    ais = optimState.get("ActiveImportanceSampling")
+    if iqr is None:
+        iqr = acq_id in (10, 11) and ais is not None
+    if acq_id == 3 or iqr:
+        if optimState.get("gplengthscale") is not None:
+            keep["gl"] = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
+            a.gplengthscale = ptr(keep["gl"])
+        if gp.get("X_rescaled") is not None and gp.get("sn2new") is not None:
+            keep["xr"] = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
+            keep["sn"] = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
+            a.X_rescaled, a.sn2new = ptr(keep["xr"]), ptr(keep["sn"])
     a.x0, a.insigma, a.LB, a.UB = ptr(keep["x0"]), ptr(keep["insigma"]), ptr(keep["LB"]), ptr(keep["UB"])
     a.TolX, a.TolFun, a.TolHistFun = float(TolX), float(TolFun), float(TolHistFun)
     a.MaxFunEvals = 0 if (MaxFunEvals is None or not np.isfinite(MaxFunEvals)) else int(MaxFunEvals)
@@ -607,7 +616,11 @@ def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, T
         a.trace_cap = n
         a.tr_order = out["tr_order"].ctypes.data_as(C.POINTER(C.c_int32))
         a.tr_F, a.tr_xmean, a.tr_sigma = ptr(out["tr_F"]), ptr(out["tr_xmean"]), ptr(out["tr_sigma"])
-    ctx.check(ctx.lib.vbmc_acq_search(ctx.h, dgp.h, C.byref(a)))
+    if iqr:
+        ist = _importance_state(engine, dgp, ais)
+        ctx.check(ctx.lib.vbmc_acq_search_iqr(ctx.h, dgp.h, ist.h, C.byref(a)))
+    else:
+        ctx.check(ctx.lib.vbmc_acq_search(ctx.h, dgp.h, C.byref(a)))
     out.update(fmin=sc["fmin"].value, fbest=sc["fbest"].value, sigma=sc["sigma"].value, evals=int(evals.value),
                generations=int(gens.value), stop=SEARCH_STOP.get(int(stop.value), "MaxIter"), behind=int(rounds[1]), popsize=lam)
     return out

@@ -1,11 +1,13 @@
-// C-ABI entry points of the device-resident acquisition search: vbmc_acq_search and vbmc_acq_search_rng_dump (include/vbmc_hip.h).
-// The optimiser is search_kernels.h; the objective is the prediction (abi_gp.hip: pred_plan once, pred_launch per generation, on
-// points and column means the optimiser's kernel writes into the prediction's own buffers) and k_acq (AcqConsts).  Generations are
-// driven in chunks by drive_rounds (abi_gp_train.hip), the progress word read one chunk behind the one being enqueued.
-// Included after abi_gp_train.hip.
+// C-ABI entry points of the device-resident acquisition search: vbmc_acq_search, vbmc_acq_search_iqr and vbmc_acq_search_rng_dump
+// (include/vbmc_hip.h).  The optimiser is search_kernels.h; the objective is the prediction (abi_gp.hip: pred_plan once, pred_launch
+// per generation, on points and column means the optimiser's kernel writes into the prediction's own buffers) followed by k_acq
+// (AcqConsts: the density-based functions) or by the tile form of the IQR functions (IqrTileObjective, iqr_tile_kernels.h).  Both entry
+// points are search_impl; generations are driven in chunks by drive_rounds (abi_gp_train.hip), the progress word read one chunk behind
+// the one being enqueued.  Included after abi_gp_train.hip.
 #include <algorithm>
 #include <cmath>
 
+#include "iqr_tile_kernels.h"
 #include "search_kernels.h"
 
 #define SEARCH_DEFAULT_CHUNK 16
@@ -18,18 +20,68 @@ extern "C" vbmc_status vbmc_acq_search_rng_dump(uint64_t seed, int D, int lam, i
   return VBMC_OK;
 }
 
-extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acqsearch_args* args) {
-  if (!ctx) return VBMC_ERR_INVALID;
-  const char* who = "vbmc_acq_search";
+namespace {
+// What the IQR objective reads besides the prediction and the importance-sampling state: the inputs of the nearest-neighbour noise,
+// uploaded once per search.  launch() enqueues k_nn_noise, the tile kernel and the closing kernel on the points a.Xs holds.
+struct IqrTileObjective {
+  TmpBuf dgl, dXr, dsn, dsx, drec, dacqs;
+  IqrTileArgs a{};
+  int NT = 1, W = 1;
+  vbmc_status upload(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, int lam, const vbmc_acqsearch_args& g) {
+    hipStream_t st = ctx->stream;
+    const int N = gp->N, D = gp->D, S = gp->S;
+    NT = is->Nap / 16;
+    W = std::max(1, std::min(IQRT_MAXW, (N + 15) / 16));
+    HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
+    HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
+    HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
+    HIP_TRY(ctx, dsx.alloc(ctx, (size_t)lam * 8));
+    HIP_TRY(ctx, drec.alloc(ctx, (size_t)S * NT * 32 * 8));
+    HIP_TRY(ctx, dacqs.alloc(ctx, (size_t)lam * S * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(dgl.p, g.gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dXr.p, g.X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dsn.p, g.sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
+    a = IqrTileArgs{};
+    a.N = N; a.D = D; a.S = S; a.Nhyp = gp->Nhyp; a.lam = lam; a.Na = is->Na; a.Nap = is->Nap; a.per_s = is->per_s;
+    a.reg = g.var_regularized ? 1 : 0; a.TolVar = g.TolGPVar;
+    a.Xa = is->Xa; a.hyp = gp->hyp; a.CT = is->CT; a.fs2a = is->fs2a; a.lnw = is->has_lnw ? is->lnw : nullptr;
+    a.sn2_eff = gp->d_sn2; a.lchol = gp->d_lchol; a.sn2x = dsx.as<double>(); a.rec = drec.as<double>(); a.acqs = dacqs.as<double>();
+    return VBMC_OK;
+  }
+  void launch(hipStream_t st) {
+    switch ((a.D + 3) / 4) {
+#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3(1), dim3(64), 0, st, a.lam, a.N, a.D, a.Xs, dgl.as<double>(), \
+                                                 dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
+      NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
+#undef NN_CASE
+      default: break;
+    }
+    hipLaunchKernelGGL(k_acq_iqr_tile, dim3(NT, a.S), dim3(64 * W), IQRT_LDS_BYTES(W), st, a);
+    hipLaunchKernelGGL(k_iqr_tile_final, dim3(1), dim3(64), 0, st, a, NT);
+  }
+};
+
+// is == nullptr: the density-based functions (vbmc_acq_search); otherwise the IQR functions on that state (vbmc_acq_search_iqr)
+vbmc_status search_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, const vbmc_acq_is* is, bool iqr, const vbmc_acqsearch_args* args) {
   if (!args || args->struct_size != sizeof(vbmc_acqsearch_args)) return set_err(ctx, VBMC_ERR_INVALID, "%s: struct_size mismatch", who);
   const vbmc_acqsearch_args& g = *args;
-  if (!gp || g.K <= 0 || !g.vp_mu || !g.vp_sigma || !g.vp_lambda || !g.vp_w || !g.x0 || !g.insigma || !g.LB || !g.UB)
-    return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
-  if (g.acq_id >= 10) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: the importance-sampled IQR acquisition functions (id %d) are not searched on the device", who, g.acq_id);
-  if (g.acq_id < 0 || g.acq_id > 3)
-    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "acquisition function id %d not accelerated (0 acqf, 1 acqflog, 2 acqus, 3 acqfsn2)", g.acq_id);
-  if (g.acq_id == 3 && (!g.gplengthscale || !g.X_rescaled || !g.sn2new))
-    return set_err(ctx, VBMC_ERR_INVALID, "%s: acqfsn2 needs gplengthscale, X_rescaled and sn2new", who);
+  if (!gp || !g.x0 || !g.insigma || !g.LB || !g.UB) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+  if (iqr) {
+    if (!is) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+    if (g.acq_id != 10 && g.acq_id != 11)
+      return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: acquisition function id %d is not an IQR function (10 acqviqr, 11 acqimiqr)", who, g.acq_id);
+    if (!g.gplengthscale || !g.X_rescaled || !g.sn2new)
+      return set_err(ctx, VBMC_ERR_INVALID, "%s: the IQR functions need gplengthscale, X_rescaled and sn2new", who);
+    if (is->N != gp->N || is->S != gp->S || is->D != gp->D)
+      return set_err(ctx, VBMC_ERR_INVALID, "%s: importance-sampling state belongs to a different GP", who);
+  } else {
+    if (g.K <= 0 || !g.vp_mu || !g.vp_sigma || !g.vp_lambda || !g.vp_w) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+    if (g.acq_id >= 10) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: the importance-sampled IQR acquisition functions (id %d) are not searched on the device", who, g.acq_id);
+    if (g.acq_id < 0 || g.acq_id > 3)
+      return set_err(ctx, VBMC_ERR_UNSUPPORTED, "acquisition function id %d not accelerated (0 acqf, 1 acqflog, 2 acqus, 3 acqfsn2)", g.acq_id);
+    if (g.acq_id == 3 && (!g.gplengthscale || !g.X_rescaled || !g.sn2new))
+      return set_err(ctx, VBMC_ERR_INVALID, "%s: acqfsn2 needs gplengthscale, X_rescaled and sn2new", who);
+  }
   const int D = gp->D;
   if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
   if (g.vp_delta)
@@ -56,6 +108,7 @@ extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const v
   if (trace && !(g.tr_order && g.tr_F && g.tr_xmean && g.tr_sigma && g.trace_cap > 0))
     return set_err(ctx, VBMC_ERR_INVALID, "%s: the trace needs tr_order, tr_F, tr_xmean, tr_sigma and trace_cap > 0", who);
   VB_TRY(pred_check(ctx, who, gp, lam, false));
+  if (iqr && (is->Nap < 16 || is->Nap > VBMC_LIM_NA || is->Nap % 16)) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Na = %d not accelerated", is->Na);
 
   // ---- the constants of cmaes_batched (vbmc_amd/optimize.py), in its order of operations
   const int mu = lam / 2;
@@ -83,11 +136,18 @@ extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const v
   PredBufs pb;
   PredPlan pl;
   AcqConsts ac;
+  IqrTileObjective iq;
   HIP_TRY(ctx, pb.dXs.alloc(ctx, (size_t)lam * D * 8));
   HIP_TRY(ctx, pb.dmb.alloc(ctx, (size_t)D * 8));
-  VB_TRY(pred_plan(ctx, gp, lam, pb, false, nullptr, pl));
-  const AcqInputs in{g.acq_id, g.K, g.vp_mu, g.vp_sigma, g.vp_lambda, g.vp_w, g.ymax, g.var_regularized, g.TolGPVar, g.gplengthscale, g.X_rescaled, g.sn2new};
-  VB_TRY(ac.upload(ctx, who, gp, lam, in));
+  // the IQR form keeps the sW-scaled cross-kernel tile (want_ks) and centres sq_dist on the training inputs alone (PredArgs::mc)
+  VB_TRY(pred_plan(ctx, gp, lam, pb, iqr, nullptr, pl));
+  if (iqr) {
+    pl.pa.mc = 0;
+    VB_TRY(iq.upload(ctx, gp, is, lam, g));
+  } else {
+    const AcqInputs in{g.acq_id, g.K, g.vp_mu, g.vp_sigma, g.vp_lambda, g.vp_w, g.ymax, g.var_regularized, g.TolGPVar, g.gplengthscale, g.X_rescaled, g.sn2new};
+    VB_TRY(ac.upload(ctx, who, gp, lam, in));
+  }
   // one block of fp64 state:  wts | LB | UB | xmean ps pc xbest xlast | C | A | Y | hist | F fbar vtot | Z
   const size_t nZ = g.rng_mode == 1 ? (size_t)D * lam * g.Gmax : 0;
   const size_t n_fixed = (size_t)mu + 7 * (size_t)D + 2 * (size_t)D * D + (size_t)D * lam + a.nh + 3 * (size_t)lam;
@@ -119,7 +179,7 @@ extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const v
     a.A = q; h += (size_t)D * D; q += (size_t)D * D;
     a.Y = q; h += (size_t)D * lam; q += (size_t)D * lam;
     a.hist = q; h += a.nh; q += a.nh;
-    a.F = q; ac.a.acq = q; ac.a.fbar = q + lam; ac.a.vtot = q + 2 * lam; q += 3 * (size_t)lam;
+    a.F = q; ac.a.acq = iq.a.acq = q; ac.a.fbar = iq.a.fbar = q + lam; ac.a.vtot = iq.a.vtot = q + 2 * lam; q += 3 * (size_t)lam;
     a.Z = nZ ? q : nullptr;
   }
   HIP_TRY(ctx, hipMemcpyAsync(dW.p, hw.data(), n_fixed * 8, hipMemcpyHostToDevice, st));
@@ -130,16 +190,18 @@ extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const v
   a.st = dState.as<SearchState>();
   a.Xs = pb.dXs.as<double>(); a.mb = pb.dmb.as<double>();
   ac.a.Xs = pb.dXs.as<double>(); ac.a.fmu = pb.fmu; ac.a.fs2 = pb.fs2;
+  iq.a.Xs = pb.dXs.as<double>(); iq.a.fmu = pb.fmu; iq.a.fs2 = pb.fs2; iq.a.muv = pb.dmuv.as<double>(); iq.a.KsW = pb.dKs.as<double>();
   if (tcap) {
     a.tr_order = dTrI.as<int>();
     a.tr_F = dTrD.as<double>(); a.tr_xmean = a.tr_F + tcap * lam; a.tr_sigma = a.tr_xmean + tcap * D;
   }
   // a generation: the optimiser's step, then the objective at the points it wrote.  A step that finds the search finished does
-  // nothing; the prediction and k_acq behind it still run on the last points (their results are never read).
+  // nothing; the prediction and the acquisition kernels behind it still run on the last points (their results are never read).
   auto round = [&](int) -> vbmc_status {
     hipLaunchKernelGGL(k_search_step, dim3(1), dim3(64), 0, st, a);
     VB_TRY(pred_launch(ctx, pb, pl));
-    ac.launch(st);
+    if (iqr) iq.launch(st);
+    else ac.launch(st);
     HIP_TRY(ctx, hipGetLastError());
     return VBMC_OK;
   };
@@ -170,4 +232,15 @@ extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const v
   if (g.stop) *g.stop = fin.stop;
   if (g.rounds) { g.rounds[0] = fin.gen; g.rounds[1] = fin.behind; }
   return VBMC_OK;
+}
+}  // namespace
+
+extern "C" vbmc_status vbmc_acq_search(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acqsearch_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  return search_impl(ctx, "vbmc_acq_search", gp, nullptr, false, args);
+}
+
+extern "C" vbmc_status vbmc_acq_search_iqr(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, const vbmc_acqsearch_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  return search_impl(ctx, "vbmc_acq_search_iqr", gp, is, true, args);
 }

@@ -634,7 +634,7 @@ vbmc_status pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, PredBufs& pb,
   HIP_TRY(ctx, dout.alloc(ctx, (size_t)3 * Nstar * S * 8));
   PredArgs& pa = pl.pa;
   pa = PredArgs{};
-  pa.N = N; pa.D = D; pa.S = S; pa.Nhyp = gp->Nhyp; pa.Nstar = Nstar; pa.meanfun = gp->meanfun;
+  pa.N = N; pa.D = D; pa.S = S; pa.Nhyp = gp->Nhyp; pa.Nstar = Nstar; pa.mc = Nstar; pa.meanfun = gp->meanfun;
   pa.moff = gp->Ncov + gp->Nnoise; pa.noff = gp->Ncov; pa.nf0 = gp->noisefun[0]; pa.nf1 = gp->noisefun[1]; pa.nf2 = gp->noisefun[2];
   pa.X = gp->X; pa.Xs = dXs.as<double>(); pa.s2s = ds2.p ? ds2.as<double>() : nullptr; pa.hyp = gp->hyp;
   pa.ys = pb.dys.p ? pb.dys.as<double>() : nullptr;

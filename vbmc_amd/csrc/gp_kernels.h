@@ -518,6 +518,8 @@ __global__ void k_negate_copy(size_t n, const double* __restrict__ src, double* 
 // ------------------------------------------------------------------------------------------
 struct PredArgs {
   int N, D, S, Nhyp, Nstar, meanfun, moff, noff, nf0, nf1, nf2;
+  int mc;                // weight m of mean(b) in sq_dist's centring constant: Nstar; 0 centres on the training inputs alone, so that
+                         // a point's prediction does not depend on the batch it is evaluated in (the IQR acquisition search)
   const double* X;       // N x D
   const double* Xs;      // Nstar x D (column-major)
   const double* s2s;     // Nstar or null
@@ -559,7 +561,7 @@ __device__ __forceinline__ void pred_prep_body(const PredArgs& a, double* __rest
     } else {
       ie = 1.0 / exp(h[d]);   // diag(1./ell) * X'   (gplite_pred.m:73)
     }
-    const double n = (double)N, m = (double)a.Nstar;
+    const double n = (double)N, m = (double)a.mc;
     iell[d] = ie;
     mu[d] = (m / (n + m)) * (a.mean_b[d] * ie) + (n / (n + m)) * (a.mean_a[d] * ie);
     if (blockIdx.x == 0) { muv[(size_t)s * 2 * D + d] = mu[d]; muv[(size_t)s * 2 * D + D + d] = ie; }
@@ -1698,11 +1700,8 @@ __global__ void __launch_bounds__(IQR_THREADS) k_acq_iqr(IqrArgs a) {
 
 // acq = M + log(sum(exp(acq_s - M))/Ns) over hyper-samples (:104-107), then the log-flag variance regulariser and the
 // clamp of acq/acqwrapper_vbmc.m:35-46; also fbar / vtot (:21-29)
-__global__ void __launch_bounds__(256) k_iqr_final(int Nstar, int S, int reg, double TolVar, const double* __restrict__ acqs,
-                                                   const double* __restrict__ fmu, const double* __restrict__ fs2,
-                                                   double* __restrict__ acq, double* __restrict__ fbar_o, double* __restrict__ vtot_o) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= Nstar) return;
+__device__ __forceinline__ void iqr_final_point(int i, int Nstar, int S, int reg, double TolVar, const double* acqs, const double* fmu,
+                                                const double* fs2, double* acq, double* fbar_o, double* vtot_o) {
   double fbar = 0.0, vbar = 0.0;
   for (int s = 0; s < S; ++s) { fbar += fmu[i + (size_t)Nstar * s]; vbar += fs2[i + (size_t)Nstar * s]; }
   fbar /= S; vbar /= S;
@@ -1725,4 +1724,12 @@ __global__ void __launch_bounds__(256) k_iqr_final(int Nstar, int S, int reg, do
   acq[i] = v;
   if (fbar_o) fbar_o[i] = fbar;
   if (vtot_o) vtot_o[i] = vtot;
+}
+
+__global__ void __launch_bounds__(256) k_iqr_final(int Nstar, int S, int reg, double TolVar, const double* __restrict__ acqs,
+                                                   const double* __restrict__ fmu, const double* __restrict__ fs2,
+                                                   double* __restrict__ acq, double* __restrict__ fbar_o, double* __restrict__ vtot_o) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Nstar) return;
+  iqr_final_point(i, Nstar, S, reg, TolVar, acqs, fmu, fs2, acq, fbar_o, vtot_o);
 }
