@@ -461,6 +461,84 @@ vbmc_status vbmc_acq_search_rng_dump(uint64_t seed, int D, int lam, int G, doubl
 vbmc_status vbmc_acq_search_iqr(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, const vbmc_acqsearch_args* args);
 
 /*
+ * The MCMC of the IMIQR importance sampler (private/activeimportancesampling_vbmc.m:153-235, Step 2) with the WHOLE sampler on the
+ * device: for each of the S GP hyper-samples an ensemble of W walkers samples the log base density of acqimiqr_vbmc
+ * (acq/acqimiqr_vbmc.m:22-25 with importance_sampling_vp = false; importance_sampling_vp = true is not offered),
+ *     logp(x) = ymu + u ys + log1p(-exp(-2 u ys)),   ys = sqrt(max(ys2, realmin)),   u = 0.6745,
+ * where [ymu, ys2] are the first two outputs of gplite_pred for hyper-sample s ALONE (:346 reads the noisy pair, not fmu / fs2) -- what
+ * vbmc_gp_pred(..., ystar = NULL, s2star = NULL, ssflag = 1) returns in column s.  A value that is not finite is -Inf.  A point outside
+ * [LB, UB] has density -Inf, costs no evaluation and is not counted.  A starting walker with -Inf density is VBMC_ERR_INVALID ("a
+ * starting point has zero density"): the caller replaces such walkers before the call.
+ *
+ * THE ALGORITHM is the library's ensemble slice sampler (vbmc_amd/acq.py::ensemble_slice_sample, which stands in for the third-party
+ * eissample_lite.m): the two halves of an ensemble move in turn; a walker of the moving half takes its direction x_other[b] - x_other[a]
+ * from two distinct walkers of the complementary half as it stands when the half-move begins (sigma_factor = 1), places a unit interval
+ * around itself, steps both ends out (at most max_steps unit steps each; an end stops at the first step below the slice level) and
+ * shrinks (at most max_shrink proposals; the first one above the level is accepted).  A walker whose slice collapsed stays where it is.
+ * After a half-move each of its H = W / 2 walkers counts as one move; after `burnin` moves every thin-th moved walker is recorded, until
+ * Nm are.  All randomness comes from an INDEXED UNIFORM BLOCK  U[slot + 64 (j + H (e + S m))]  with m the half-move counted from 0 (half
+ * m mod 2 moves), e the ensemble and j the walker's position inside the moving half:
+ *     slot 0      a = floor(u H)
+ *     slot 1      b = (a + 1 + floor(u (H - 1))) mod H        (H = 2: b = 1 - a; the slot is still reserved)
+ *     slot 2      slice level y = logp(x) + log(u)
+ *     slot 3      interval placement L = -u, R = L + 1
+ *     slot 4 + q  the q-th shrink proposal t = L + u (R - L); a rejected t < 0 becomes L, otherwise R
+ * The left end after k steps is L - k, the right end R + k, a candidate is x + t (x_other[b] - x_other[a]), every operation rounded on
+ * its own.  rng_mode 0: slot (m, e H + j, slot) is generated with Philox4x32-10 keyed by `seed`, through the 52-bit uniform of
+ * vbmc_gp_slice_sample, strictly inside (0, 1); vbmc_acq_is_sample_rng_dump -- a pure host function -- writes the 64 x H x S x M block
+ * a seed stands for.  rng_mode 1 (parity): the caller supplies the block for Mmax half-moves; a chain that needs more ends with
+ * VBMC_ERR_INVALID ("uniform block exhausted"), as does a block with a value outside the open interval (0, 1).  A replay of a dump in
+ * parity mode is bit-identical.  The target's exponentials and logarithms are the library's own (the table exponential, the
+ * logarithm of the search's generator, ln(1 - e) from it by exactly rounded operations), none the device library's.
+ *
+ * One ROUND is one launch each of the sampler's kernel (one workgroup per ensemble: it consumes the previous round's values in candidate
+ * order, commits and records, and writes up to 2 spec candidates per walker while stepping out and spec while shrinking, with an in-bounds
+ * mask, straight into the prediction's point buffer) and of the prediction, which evaluates every candidate under its own hyper-sample
+ * only and closes with the target.  spec (1..4, 0: 3) changes the number of rounds, never a bit of the results.  Rounds are enqueued in
+ * chunks of `chunk` (0: 16) and the progress words are read one chunk behind; results do not depend on `chunk`.  funccount counts the
+ * in-bounds evaluations the one-at-a-time procedure (spec = 1) consumes, the W S starting walkers included; performed all in-bounds
+ * evaluations launched.
+ *
+ * Inputs: x0 (W x D x S, column-major: the W starting walkers of each ensemble, inside the box), LB / UB (D, finite, LB < UB), W even
+ * with 4 <= W <= 2 (D + 1), Nm (1 .. 256 recorded samples per ensemble), thin >= 1, burnin (-1: ceil(thin Nm / 2)), max_steps /
+ * max_shrink (0: 20 and 60, which are also the caps).  Outputs (any may be NULL): Xa (Nm x D x S) the recorded walkers, logp (S x Nm) the
+ * chain's own value at each, fs2a (Nm x S) the latent fs2 at the recorded points under their own hyper-sample from one closing
+ * prediction, lnw (S x Nm) = fmu - logp (:218-230: islogf1 of IMIQR is fmu), funccount, performed, rounds[2] = {rounds that did work (the
+ * slowest ensemble's), launches that found every chain finished}, and `state`: the importance-sampling state of those device buffers
+ * with per_sample_inputs = 1, built without a host round trip (free it with vbmc_acq_is_free); it is what vbmc_acq_is_create makes of
+ * the downloaded arrays.
+ *
+ * VBMC_ERR_UNSUPPORTED: whatever vbmc_gp_pred refuses, and a GP beyond the range in which the prediction keeps inv(L') resident (the
+ * slab form of large N).  VBMC_ERR_INVALID: W odd or outside 4 .. 2 (D + 1), LB >= UB or not finite, a start outside the box or with zero
+ * density, D / S that are not the GP's, Nm outside 1 .. 256, thin < 1, spec outside 0 .. 4, max_steps / max_shrink beyond their caps, an exhausted uniform block, a GP
+ * without vbmc_gp_set_noise.  The context stays usable after any error.
+ */
+typedef struct vbmc_is_sample_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_is_sample_args) */
+  int32_t W, Nm, thin, burnin, spec, max_steps, max_shrink;
+  const double* x0;          /* W x D x S */
+  const double* LB;          /* D */
+  const double* UB;          /* D */
+  int32_t rng_mode;          /* 0 device generator, 1 parity */
+  int32_t Mmax;              /* rng_mode 1: half-moves in U */
+  uint64_t seed;             /* rng_mode 0 */
+  const double* U;           /* rng_mode 1: 64 x H x S x Mmax */
+  int32_t chunk;             /* rounds enqueued between two looks at the progress words (0: default) */
+  int32_t D, S;              /* the dimensions x0 and U are laid out for: they must be the GP's (VBMC_ERR_INVALID otherwise) */
+  int32_t reserved_;
+  double* Xa;                /* Nm x D x S */
+  double* lnw;               /* S x Nm */
+  double* fs2a;              /* Nm x S */
+  double* logp;              /* S x Nm */
+  int64_t* funccount;
+  int64_t* performed;
+  int64_t* rounds;           /* 2 */
+  vbmc_acq_is** state;
+} vbmc_is_sample_args;
+vbmc_status vbmc_acq_is_sample(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_is_sample_args* args);
+vbmc_status vbmc_acq_is_sample_rng_dump(uint64_t seed, int S, int H, int M, double* U);
+
+/*
  * The O(N^2) pieces of gplite_post's rank-1 append of one training point x* (gplite/gplite_post.m:173-251),
  * for every hyper-sample: Ks = k(X, x*) (N x S); for Lchol samples v = L' \ Ks and x = L \ v, so that
  * alpha_update = x / sn2_eff (:227) and the new column of L is v / sn2_eff (:228); for low-noise samples

@@ -32,6 +32,10 @@
 //                                                  (the CMA-ES acquisition search on the device: matlab/vbmc_hip_acqsearch.m)
 //     [xmin,fmin,out] = vbmc_hip_mex('acq_search_iqr', h, his, acq_id, vp, var_regularized, TolGPVar, x0, insigma, LB, UB, opts, gplengthscale, X_rescaled, sn2new)
 //     his = vbmc_hip_mex('is_create', h, Xa, lnw_or_empty, fs2a_or_empty, Ctmp_or_empty)   (ActiveImportanceSampling state)
+//     [Xa,lnw,fs2a,his,out] = vbmc_hip_mex('acq_is_sample', h, x0 /*W x D x S*/, LB, UB, Nm, opts)
+//                                (the MCMC of the IMIQR importance sampler on the device: vbmc_acq_is_sample, matlab/vbmc_hip_importance_sample.m.
+//                                 opts: Thin, Burnin, Spec, MaxSteps, MaxShrink, Seed, Chunk, U (64 x H x S x Mmax: parity mode); out: logp,
+//                                 funccount, performed, rounds, behind; his: the state of those device buffers, freed with 'is_free')
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
@@ -246,7 +250,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr", "acq_is_sample"};
     for (const char* w : with_handle)
       if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || ((!strcmp(cmd, "acq_iqr") || !strcmp(cmd, "acq_search_iqr")) && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
@@ -597,6 +601,57 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     vbmc_status st = vbmc_gp_quad(g_ctx, h, Nstar, mxGetDoubles(mu), mxGetDoubles(sg), rows, ss || S == 1, mxGetDoubles(plhs[0]),
                                   vf ? mxGetDoubles(vf) : nullptr);
     if (vf) plhs[1] = vf;
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "acq_is_sample")) {
+    if (nrhs < 7 || !mxIsStruct(prhs[6])) return raise("vbmc_hip:usage", "acq_is_sample: h, x0, LB, UB, Nm, opts");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    const mxArray *x0 = prhs[2], *op = prhs[6];
+    const mwSize nd = mxGetNumberOfDimensions(x0);
+    const mwSize* dm = mxGetDimensions(x0);
+    const int W = (int)dm[0], D = (int)dm[1], S = nd > 2 ? (int)dm[2] : 1, Nm = (int)mxGetScalar(prhs[5]);
+    if ((int)mxGetNumberOfElements(prhs[3]) != D || (int)mxGetNumberOfElements(prhs[4]) != D || Nm < 1)
+      return raise("vbmc_hip:usage", "acq_is_sample: x0 must be W x D x S, LB and UB must hold one value per dimension, Nm must be positive");
+    vbmc_is_sample_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.W = W; a.D = D; a.S = S; a.Nm = Nm; a.thin = (int)scalar_field(op, "Thin", 1.0); a.burnin = (int)scalar_field(op, "Burnin", -1.0);
+    a.spec = (int)scalar_field(op, "Spec", 0.0); a.max_steps = (int)scalar_field(op, "MaxSteps", 0.0); a.max_shrink = (int)scalar_field(op, "MaxShrink", 0.0);
+    a.chunk = (int)scalar_field(op, "Chunk", 0.0); a.seed = (uint64_t)scalar_field(op, "Seed", 0.0);
+    a.x0 = mxGetDoubles(x0); a.LB = dbl(prhs[3]); a.UB = dbl(prhs[4]);
+    if (const mxArray* u = field(op, "U")) {
+      if (!mxIsEmpty(u)) {
+        const size_t nu = mxGetNumberOfElements(u), per = (size_t)64 * (size_t)(W / 2) * (size_t)S;
+        if (per == 0 || nu % per != 0) return raise("vbmc_hip:usage", "acq_is_sample: opts.U must be 64 x H x S x Mmax");
+        a.rng_mode = 1; a.U = mxGetDoubles(u); a.Mmax = (int)(nu / per);
+      }
+    }
+    const mwSize dx[3] = {(mwSize)Nm, (mwSize)D, (mwSize)S};
+    mxArray* Xa = mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL);
+    mxArray* lnw = mxCreateDoubleMatrix(S, Nm, mxREAL);
+    mxArray* fs2a = mxCreateDoubleMatrix(Nm, S, mxREAL);
+    const char* names[] = {"logp", "funccount", "performed", "rounds", "behind"};
+    mxArray* out = mxCreateStructMatrix(1, 1, 5, names);
+    mxArray* f[5];
+    for (int i = 0; i < 5; ++i) { f[i] = mxCreateDoubleMatrix(i == 0 ? S : 1, i == 0 ? Nm : 1, mxREAL); mxSetField(out, 0, names[i], f[i]); }
+    int64_t funccount = 0, performed = 0, rounds[2] = {0, 0};
+    vbmc_acq_is* is = nullptr;
+    a.Xa = mxGetDoubles(Xa); a.lnw = mxGetDoubles(lnw); a.fs2a = mxGetDoubles(fs2a); a.logp = mxGetDoubles(f[0]);
+    a.funccount = &funccount; a.performed = &performed; a.rounds = rounds;
+    if (nlhs > 3) a.state = &is;
+    vbmc_status st = vbmc_acq_is_sample(g_ctx, h, &a);
+    mxGetDoubles(f[1])[0] = (double)funccount; mxGetDoubles(f[2])[0] = (double)performed;
+    mxGetDoubles(f[3])[0] = (double)rounds[0]; mxGetDoubles(f[4])[0] = (double)rounds[1];
+    plhs[0] = Xa;
+    if (nlhs > 1) plhs[1] = lnw; else mxDestroyArray(lnw);
+    if (nlhs > 2) plhs[2] = fs2a; else mxDestroyArray(fs2a);
+    if (nlhs > 3) {
+      plhs[3] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
+      *(uint64_t*)mxGetData(plhs[3]) = (uint64_t)(uintptr_t)is;
+    }
+    if (nlhs > 4) plhs[4] = out; else mxDestroyArray(out);
     if (st != VBMC_OK) return fail(st);
     return 0;
   }

@@ -14,6 +14,6 @@ from .elbo import (Engine, PreparedObjective, default_engine, entlb_vbmc, entmc_
 from .gplite import (fminfill_design, gplite_hypprior, gplite_nlZ, gplite_post, gplite_post_rank1, gplite_pred, gplite_quad, gplite_train,  # noqa: F401,E402
                      gplite_train_optimize, gplite_train_sample, slice_rng_dump, slicesamplebnd_gp, sq_dist)
 from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, active_search, activeimportancesampling_vbmc,  # noqa: F401,E402
-                  ensemble_slice_sample, vbmc_moments, vbmc_rnd)
+                  ensemble_slice_sample, importance_sample_device, importance_sample_rng_dump, vbmc_moments, vbmc_rnd)
 from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
                        vpsieve_vbmc)

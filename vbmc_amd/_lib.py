@@ -134,6 +134,23 @@ class AcqSearchArgs(C.Structure):
     ]
 
 
+class IsSampleArgs(C.Structure):
+    """vbmc_is_sample_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("W", C.c_int32), ("Nm", C.c_int32), ("thin", C.c_int32), ("burnin", C.c_int32), ("spec", C.c_int32),
+        ("max_steps", C.c_int32), ("max_shrink", C.c_int32),
+        ("x0", _dp), ("LB", _dp), ("UB", _dp),
+        ("rng_mode", C.c_int32), ("Mmax", C.c_int32),
+        ("seed", C.c_uint64),
+        ("U", _dp),
+        ("chunk", C.c_int32), ("D", C.c_int32), ("S", C.c_int32), ("reserved_", C.c_int32),
+        ("Xa", _dp), ("lnw", _dp), ("fs2a", _dp), ("logp", _dp),
+        ("funccount", C.POINTER(C.c_int64)), ("performed", C.POINTER(C.c_int64)), ("rounds", C.POINTER(C.c_int64)),
+        ("state", C.POINTER(C.c_void_p)),
+    ]
+
+
 _lib = None
 
 
@@ -202,6 +219,8 @@ def load():
     lib.vbmc_acq_search.argtypes = [vp, vp, C.POINTER(AcqSearchArgs)]
     lib.vbmc_acq_search_iqr.argtypes = [vp, vp, vp, C.POINTER(AcqSearchArgs)]
     lib.vbmc_acq_search_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
+    lib.vbmc_acq_is_sample.argtypes = [vp, vp, C.POINTER(IsSampleArgs)]
+    lib.vbmc_acq_is_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)

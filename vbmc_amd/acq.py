@@ -21,6 +21,14 @@ ACQ_IDS = {"acqf_vbmc": 0, "acqflog_vbmc": 1, "acqus_vbmc": 2, "acqfsn2_vbmc": 3
 class ImportanceState:
     """Device copy of optimState.ActiveImportanceSampling (vbmc_acq_is_create); freed with the object."""
 
+    @classmethod
+    def from_handle(cls, engine, handle):
+        """Wrap a state the library built on the device (vbmc_acq_is_sample); owned, and freed, like an uploaded one."""
+        self = cls.__new__(cls)
+        self.ctx = engine.ctx
+        self.h = handle
+        return self
+
     def __init__(self, engine, dgp, ais):
         import ctypes as C
 
@@ -403,7 +411,73 @@ def ensemble_slice_sample(logp, x0, N, LB, UB, *, thin=1, burnin=None, sigma_fac
     return (out_x, out_lp, {"funccount": count[0]}) if return_info else (out_x, out_lp)
 
 
-def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *, rng=None, engine=None):
+def importance_sample_rng_dump(seed, S, H, M):
+    """U (64 x H x S x M) that ``importance_sample_device(..., seed=seed)`` consumes (vbmc_acq_is_sample_rng_dump: a pure host function)."""
+    import ctypes as C
+
+    from ._lib import load
+
+    U = np.zeros((64, H, S, M), order="F")
+    st = load().vbmc_acq_is_sample_rng_dump(C.c_uint64(seed), int(S), int(H), int(M), ptr(U))
+    if st != 0:
+        raise ValueError("vbmc_acq_is_sample_rng_dump: bad arguments")
+    return U
+
+
+def importance_sample_device(gp, x0, LB, UB, Nm, *, thin=1, burnin=None, spec=0, seed=0, uniforms=None, chunk=0, max_steps=0,
+                             max_shrink=0, engine=None, want_state=True):
+    """The thin ctypes call of ``vbmc_acq_is_sample`` (include/vbmc_hip.h): the MCMC of the IMIQR importance sampler, one ensemble of
+    W walkers per GP hyper-sample, the whole sampler on the device.  ``x0``: S x W x D starting walkers (as ``ensemble_slice_sample``
+    takes them).  ``uniforms`` (64 x H x S x Mmax): parity mode, the library's own generator keyed by ``seed`` otherwise.
+    Returns a dict: Xa (Nm x D x S), lnw (S x Nm), fs2a (Nm x S), logp (S x Nm), funccount, performed, rounds, behind and ``state``,
+    the ``ImportanceState`` of those device buffers (None without ``want_state``)."""
+    import ctypes as C
+
+    from ._lib import IsSampleArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    dgp = _device_gp_with_noise(engine, gp)
+    x0 = np.asarray(x0, dtype=np.float64)
+    if x0.ndim != 3:
+        raise ValueError("importance_sample_device: x0 must be S x W x D")
+    S, W, D = x0.shape
+    if (S, D) != (len(gp["post"]), np.asarray(gp["X"]).shape[1]):
+        raise ValueError("importance_sample_device: x0 is S x W x D = %d x %d x %d, the GP has S = %d hyper-samples and D = %d"
+                         % (S, W, D, len(gp["post"]), np.asarray(gp["X"]).shape[1]))
+    Nm = int(Nm)
+    keep = {"x0": f64(np.transpose(x0, (1, 2, 0))),      # W x D x S
+            "LB": f64(np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (D,)).copy()),
+            "UB": f64(np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (D,)).copy())}
+    a = IsSampleArgs()
+    a.struct_size = C.sizeof(IsSampleArgs)
+    a.W, a.D, a.S, a.Nm, a.thin, a.burnin, a.spec = int(W), int(D), int(S), Nm, int(thin), -1 if burnin is None else int(burnin), int(spec)
+    a.max_steps, a.max_shrink, a.chunk = int(max_steps), int(max_shrink), int(chunk)
+    a.x0, a.LB, a.UB = ptr(keep["x0"]), ptr(keep["LB"]), ptr(keep["UB"])
+    if uniforms is not None:
+        keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
+        if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, W // 2, S):
+            raise ValueError("importance_sample_device: uniforms must be 64 x H x S x Mmax = 64 x %d x %d x Mmax" % (W // 2, S))
+        a.rng_mode, a.Mmax, a.U = 1, keep["U"].shape[3], ptr(keep["U"])
+    else:
+        a.rng_mode, a.seed = 0, int(seed)
+    n = max(Nm, 1)
+    out = {"Xa": np.zeros((n, D, S), order="F"), "lnw": np.zeros((S, n), order="F"), "fs2a": np.zeros((n, S), order="F"),
+           "logp": np.zeros((S, n), order="F")}
+    fc, pf, rounds = C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
+    handle = C.c_void_p()
+    a.Xa, a.lnw, a.fs2a, a.logp = ptr(out["Xa"]), ptr(out["lnw"]), ptr(out["fs2a"]), ptr(out["logp"])
+    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
+    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    if want_state:
+        a.state = C.pointer(handle)
+    ctx.check(ctx.lib.vbmc_acq_is_sample(ctx.h, dgp.h, C.byref(a)))
+    out.update(funccount=int(fc.value), performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]),
+               state=ImportanceState.from_handle(engine, handle) if want_state else None, _dgp=dgp)
+    return out
+
+
+def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *, rng=None, engine=None, device=False, seed=None):
     """ActiveImportanceSampling = activeimportancesampling_vbmc(vp,gp,acqfun,acqinfo,options)
     (private/activeimportancesampling_vbmc.m).
 
@@ -505,6 +579,14 @@ def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *,
             if np.isfinite(logp(cand[None, :], np.array([s]))[0]):
                 x0[s, i] = cand
                 break
+    if device and name == "acqimiqr_vbmc" and not isamplevp:      # (the device target is IMIQR's log base density and nothing else)
+        try:
+            sd = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
+            r = importance_sample_device(gp, x0, LB, UB, Nm, thin=thin, burnin=burnin, seed=sd, engine=engine)
+            return {"Xa": r["Xa"], "lnw": r["lnw"], "fs2a": r["fs2a"], "logp": r["logp"], "funccount": r["funccount"], "performed": r["performed"],
+                    "rounds": r["rounds"], "_device": (r["_dgp"], r["state"])}
+        except VbmcUnsupported:
+            pass                                                  # beyond the device sampler's range: the host-driven one below
     Xs, lps, info_s = ensemble_slice_sample(logp, x0, Nm, LB, UB, thin=thin, burnin=burnin, rng=rng, return_info=True)
     Xa = np.transpose(Xs, (1, 2, 0)).copy()                       # Na x D x S
     lnw = np.empty((S, Nm))

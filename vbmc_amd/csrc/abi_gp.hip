@@ -1106,6 +1106,51 @@ extern "C" void vbmc_acq_is_free(vbmc_ctx* ctx, vbmc_acq_is* h) {
   delete h;
 }
 
+namespace {
+#define IS_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(set_err(ctx, VBMC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_))); } while (0)
+// The state's device blocks (Xa, CT, fs2a and, with has_lnw, lnw), empty.  The caller fills Xa (Na x D [x S]), fs2a and lnw (S x Nap rows,
+// 0 / -inf in the padding) where they are, on the device, and closes with acq_is_ctmp_resident.
+vbmc_status acq_is_new(vbmc_ctx* ctx, const vbmc_gp* gp, int Na, int per_sample_inputs, bool has_lnw, vbmc_acq_is** out) {
+  const int N = gp->N, D = gp->D, S = gp->S;
+  const int Nap = ((Na + 15) / 16) * 16;
+  if (Nap > VBMC_LIM_NA) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Na = %d > %d importance points not accelerated", Na, VBMC_LIM_NA);
+  if (trsm_cw_for(N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d too large", N);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  vbmc_acq_is* h = new vbmc_acq_is();
+  h->Na = Na; h->Nap = Nap; h->per_s = per_sample_inputs ? 1 : 0; h->S = S; h->N = N; h->D = D;
+  const size_t nxa = (size_t)Na * D * (per_sample_inputs ? S : 1);
+  auto fail = [&](vbmc_status st_) { vbmc_acq_is_free(ctx, h); return st_; };
+  IS_TRY(hipMalloc((void**)&h->Xa, nxa * 8));
+  IS_TRY(hipMalloc((void**)&h->CT, (size_t)S * N * Nap * 8));
+  IS_TRY(hipMalloc((void**)&h->fs2a, (size_t)S * Nap * 8));
+  if (has_lnw) {
+    h->has_lnw = true;
+    IS_TRY(hipMalloc((void**)&h->lnw, (size_t)S * Nap * 8));
+  }
+  *out = h;
+  return VBMC_OK;
+}
+
+// Ctmp = (L\(L'\Kax'))/sn2_eff | L*Kax' (activeimportancesampling_vbmc.m:255-275) from the importance points h->Xa already on the
+// device, packed into h->CT.  On failure the state is the caller's to free.
+vbmc_status acq_is_ctmp_resident(vbmc_ctx* ctx, const vbmc_gp* gp, vbmc_acq_is* h) {
+  const int N = gp->N, D = gp->D, S = gp->S, Na = h->Na, Nap = h->Nap;
+  hipStream_t st = ctx->stream;
+  TmpBuf dZ, dU;
+  HIP_TRY(ctx, dZ.alloc(ctx, (size_t)S * N * Na * 8));
+  HIP_TRY(ctx, dU.alloc(ctx, (size_t)S * N * Na * 8));
+  hipLaunchKernelGGL(k_cross_kernel, dim3(64, S), dim3(256), 0, st, N, D, gp->Nhyp, Na, h->per_s, gp->X, h->Xa, gp->hyp, dZ.as<double>());
+  hipLaunchKernelGGL(k_symm, dim3(64, S, 1), dim3(256), 0, st, N, Na, S, gp->L, gp->d_lchol, dZ.as<double>(), dU.as<double>());
+  HIP_TRY(ctx, trsm_fwd_launch(st, N, Na, S, 1, gp->L, gp->d_finv, gp->d_lchol, dZ.as<double>()));
+  HIP_TRY(ctx, trsm_bwd_launch(st, N, Na, S, 1, gp->L, gp->d_finv, gp->d_lchol, dZ.as<double>(), dU.as<double>()));
+  hipLaunchKernelGGL(k_ctmp_pack, dim3(64, S), dim3(256), 0, st, N, Na, Nap, dU.as<double>(), gp->d_sn2, gp->d_lchol, h->CT);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return VBMC_OK;
+}
+}  // namespace
+
+// the host-pointer entry: its uploads, then the device-resident routine (the way pred_on_device / pred_on_device_resident are split)
 extern "C" vbmc_status vbmc_acq_is_create(vbmc_ctx* ctx, const vbmc_gp* gp, int Na, const double* Xa, int per_sample_inputs,
                                           const double* lnw, const double* fs2a, const double* Ctmp, vbmc_acq_is** out) {
   if (!ctx) return VBMC_ERR_INVALID;
@@ -1115,25 +1160,16 @@ extern "C" vbmc_status vbmc_acq_is_create(vbmc_ctx* ctx, const vbmc_gp* gp, int 
   if (per_sample_inputs && !fs2a)
     return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_is_create: per-hyper-sample importance points need fs2a from the caller");
   const int N = gp->N, D = gp->D, S = gp->S;
-  const int Nap = ((Na + 15) / 16) * 16;
-  if (Nap > VBMC_LIM_NA) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Na = %d > %d importance points not accelerated", Na, VBMC_LIM_NA);
-  if (trsm_cw_for(N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d too large", N);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  vbmc_acq_is* h = nullptr;
+  VB_TRY(acq_is_new(ctx, gp, Na, per_sample_inputs, lnw != nullptr, &h));
   hipStream_t st = ctx->stream;
-  vbmc_acq_is* h = new vbmc_acq_is();
-  h->Na = Na; h->Nap = Nap; h->per_s = per_sample_inputs ? 1 : 0; h->S = S; h->N = N; h->D = D;
+  const int Nap = h->Nap;
   const size_t nxa = (size_t)Na * D * (per_sample_inputs ? S : 1);
   auto fail = [&](vbmc_status st_) { vbmc_acq_is_free(ctx, h); return st_; };
-#define IS_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(set_err(ctx, VBMC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_))); } while (0)
-  IS_TRY(hipMalloc((void**)&h->Xa, nxa * 8));
-  IS_TRY(hipMalloc((void**)&h->CT, (size_t)S * N * Nap * 8));
-  IS_TRY(hipMalloc((void**)&h->fs2a, (size_t)S * Nap * 8));
   IS_TRY(hipMemcpyAsync(h->Xa, Xa, nxa * 8, hipMemcpyHostToDevice, st));
   // lnw (S x Na, column-major as in MATLAB) -> S x Nap rows, -inf in the padding
   std::vector<double> hb((size_t)S * Nap);
   if (lnw) {
-    h->has_lnw = true;
-    IS_TRY(hipMalloc((void**)&h->lnw, (size_t)S * Nap * 8));
     for (int s = 0; s < S; ++s)
       for (int a = 0; a < Nap; ++a) hb[(size_t)s * Nap + a] = a < Na ? lnw[s + (size_t)S * a] : -INFINITY;
     IS_TRY(hipMemcpyAsync(h->lnw, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
@@ -1152,32 +1188,24 @@ extern "C" vbmc_status vbmc_acq_is_create(vbmc_ctx* ctx, const vbmc_gp* gp, int 
       for (int a = 0; a < Na; ++a) f2[(size_t)s * Nap + a] = tmp[a + (size_t)Na * s];
   }
   IS_TRY(hipMemcpyAsync(h->fs2a, f2.data(), f2.size() * 8, hipMemcpyHostToDevice, st));
-  // Ctmp (N x Na x S): given, or (L\(L'\Kax'))/sn2_eff | L*Kax' computed here (activeimportancesampling_vbmc.m:255-275)
-  TmpBuf dZ, dU;
-  IS_TRY(dZ.alloc(ctx, (size_t)S * N * Na * 8));
-  IS_TRY(dU.alloc(ctx, (size_t)S * N * Na * 8));
   if (Ctmp) {
+    // Ctmp (N x Na x S) given, already scaled: pack with unit scale (flag array of zeros -> sc = 1)
+    TmpBuf dU, dzero;
+    IS_TRY(dU.alloc(ctx, (size_t)S * N * Na * 8));
     IS_TRY(hipMemcpyAsync(dU.p, Ctmp, (size_t)S * N * Na * 8, hipMemcpyHostToDevice, st));
-    // already scaled: pack with unit scale (flag array of zeros -> sc = 1)
-    TmpBuf dzero;
     IS_TRY(dzero.alloc(ctx, S));
     IS_TRY(hipMemsetAsync(dzero.p, 0, S, st));
     hipLaunchKernelGGL(k_ctmp_pack, dim3(64, S), dim3(256), 0, st, N, Na, Nap, dU.as<double>(), gp->d_sn2, dzero.as<unsigned char>(), h->CT);
     IS_TRY(hipGetLastError());
     IS_TRY(hipStreamSynchronize(st));
   } else {
-    hipLaunchKernelGGL(k_cross_kernel, dim3(64, S), dim3(256), 0, st, N, D, gp->Nhyp, Na, h->per_s, gp->X, h->Xa, gp->hyp, dZ.as<double>());
-    hipLaunchKernelGGL(k_symm, dim3(64, S, 1), dim3(256), 0, st, N, Na, S, gp->L, gp->d_lchol, dZ.as<double>(), dU.as<double>());
-    IS_TRY(trsm_fwd_launch(st, N, Na, S, 1, gp->L, gp->d_finv, gp->d_lchol, dZ.as<double>()));
-    IS_TRY(trsm_bwd_launch(st, N, Na, S, 1, gp->L, gp->d_finv, gp->d_lchol, dZ.as<double>(), dU.as<double>()));
-    hipLaunchKernelGGL(k_ctmp_pack, dim3(64, S), dim3(256), 0, st, N, Na, Nap, dU.as<double>(), gp->d_sn2, gp->d_lchol, h->CT);
-    IS_TRY(hipGetLastError());
-    IS_TRY(hipStreamSynchronize(st));
+    vbmc_status cs = acq_is_ctmp_resident(ctx, gp, h);   // (f2 stays alive until its copy has been waited for in there)
+    if (cs != VBMC_OK) return fail(cs);
   }
-#undef IS_TRY
   *out = h;
   return VBMC_OK;
 }
+#undef IS_TRY
 
 extern "C" vbmc_status vbmc_acq_iqr_eval(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, int Nstar, const double* Xs,
                                          const double* gplengthscale, const double* X_rescaled, const double* sn2new,
