@@ -539,6 +539,84 @@ vbmc_status vbmc_acq_is_sample(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_is_s
 vbmc_status vbmc_acq_is_sample_rng_dump(uint64_t seed, int S, int H, int M, double* U);
 
 /*
+ * vbmc_acq_is_setup: the whole set-up of the IMIQR importance sampler in one call, from (vp, gp) to the device-resident
+ * importance-sampling state -- Step 1 (private/activeimportancesampling_vbmc.m:106-151), the resampling of the starting walkers
+ * (:205-215), Step 2 as vbmc_acq_is_sample runs it, the closing prediction and Ctmp.  It serves acqimiqr_vbmc with
+ * importance_sampling_vp = false and vp.delta = 0, the case vbmc_acq_is_sample serves.
+ *
+ * On the device: rect_delta = 2 std(X) and the box LB / UB = data range -/+ half the diameter (:27-31, :112); Nvp points of the
+ * 4K-component smoothed mixture (:116-129, scales 0.05 / 0.2 / 1, weights renormalised) and Nbox points in boxes around training inputs
+ * (:140-141); ONE prediction of the Na1 = Nvp + Nbox points under every hyper-sample; the proposal's log density -- a log-sum-exp over
+ * the 4K components, the number of training inputs whose box holds the point, the two-term log-sum-exp of :335-337 --, lnw = fmu - lpdf
+ * with non-finite values -Inf (:148; a point outside every box and beyond the mixture's range has lpdf = -Inf and weight zero) and the
+ * resampling log weight lnw + u fs + log1p(-exp(-2 u fs)); per hyper-sample W draws without replacement by catrnd's rule
+ * idx = #(cdf < u cdf(end)) + 1 (:208-214, :403-408; weights that ran out are reset to ones), each chosen point clipped into
+ * [LB, UB].  The starting walkers' density comes from the sampler's own first prediction: if any is -Inf the call returns VBMC_OK with
+ * n_bad > 0, the mask `bad` (W x S) and x0, the sampler's outputs untouched and no state -- the caller replaces those walkers and calls
+ * vbmc_acq_is_sample.  Nm = 0 is Step 1 alone (the reference's Nmcmc_samples = 0 branch): no resampling, and `state` is the state of
+ * the Na1 shared points with lnw1.
+ *
+ * All randomness of Step 1 and of the resampling is an INDEXED BLOCK  B  of (D + 1) Na1 + W S doubles:
+ *     point i < Nvp          B[(D + 1) i] a uniform: the mixture component by catrnd;  B[1 + d + (D + 1) i] a standard normal z_d:
+ *                            x_d = mu(d, c mod K) + (lambda_d sigma4_c) z_d
+ *     point Nvp <= i < Na1   B[(D + 1) i] a uniform: the training input j = floor(u N);  B[1 + d + (D + 1) i] a uniform u_d:
+ *                            x_d = X(j, d) + (2 u_d - 1) rect_delta_d
+ *     draw i of ensemble s   B[(D + 1) Na1 + i + W s] a uniform
+ * every operation rounded on its own.  rng_mode 0: the block is generated from `seed` with the Philox uniforms of vbmc_gp_slice_sample
+ * and the normals of vbmc_acq_search, at counters Step 2 never reaches (Step 2 draws from the same seed exactly as vbmc_acq_is_sample
+ * does); vbmc_acq_is_setup_rng_dump -- a pure host function -- writes the block a seed stands for.  rng_mode 1: the caller supplies B
+ * (uniforms strictly inside (0, 1), normals finite; VBMC_ERR_INVALID otherwise) and, optionally, Step 2's block U with Mmax (without
+ * it Step 2 uses `seed`).  A replay of the two dumps is bit-identical in every output.
+ *
+ * Inputs: the variational posterior (K, mu D x K, sigma K, lambda D, w K), Nvp, Nbox >= 0 with 1 <= Nvp + Nbox <= 256, and W, Nm, thin,
+ * burnin, spec, chunk, max_steps, max_shrink as in vbmc_is_sample_args.  Outputs (any may be NULL): Xa1 (Na1 x D), lnw1 (S x Na1),
+ * fs2a1 (Na1 x S), lpdf1 (Na1: the proposal's log density), rect_delta / LB / UB (D each), x0 (W x D x S), idx0 (W x S, 0-based indices
+ * into Xa1), n_bad, bad (W x S), and everything vbmc_is_sample_args returns.  After a bad start funccount and performed count the W S
+ * starting evaluations.
+ *
+ * Errors: those of vbmc_acq_is_sample, and VBMC_ERR_INVALID for Nvp + Nbox outside 1 .. 256, a negative count, a vp that is not finite
+ * (sigma, lambda > 0, w >= 0 with a positive sum), a block value outside its range, fewer than two training inputs; VBMC_ERR_UNSUPPORTED
+ * for K or D beyond the library's limits.  The context stays usable after any error.
+ */
+typedef struct vbmc_is_setup_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_is_setup_args) */
+  int32_t D, S;              /* the dimensions the arrays are laid out for: they must be the GP's */
+  int32_t K;
+  const double* vp_mu;       /* D x K */
+  const double* vp_sigma;    /* K */
+  const double* vp_lambda;   /* D */
+  const double* vp_w;        /* K */
+  int32_t Nvp, Nbox;
+  int32_t W, Nm, thin, burnin, spec, max_steps, max_shrink, chunk;
+  int32_t rng_mode;          /* 0 device generator, 1 parity */
+  int32_t Mmax;              /* rng_mode 1 with U: half-moves in U */
+  uint64_t seed;
+  const double* B;           /* rng_mode 1: (D + 1) Na1 + W S */
+  const double* U;           /* rng_mode 1, optional: 64 x H x S x Mmax */
+  double* Xa1;               /* Na1 x D */
+  double* lnw1;              /* S x Na1 */
+  double* fs2a1;             /* Na1 x S */
+  double* lpdf1;             /* Na1 */
+  double* rect_delta;        /* D */
+  double* LB;                /* D */
+  double* UB;                /* D */
+  double* x0;                /* W x D x S */
+  int32_t* idx0;             /* W x S */
+  int32_t* n_bad;
+  uint8_t* bad;              /* W x S */
+  double* Xa;                /* Nm x D x S */
+  double* lnw;               /* S x Nm */
+  double* fs2a;              /* Nm x S */
+  double* logp;              /* S x Nm */
+  int64_t* funccount;
+  int64_t* performed;
+  int64_t* rounds;           /* 2 */
+  vbmc_acq_is** state;
+} vbmc_is_setup_args;
+vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_is_setup_args* args);
+vbmc_status vbmc_acq_is_setup_rng_dump(uint64_t seed, int D, int S, int W, int Nvp, int Nbox, double* B);
+
+/*
  * The O(N^2) pieces of gplite_post's rank-1 append of one training point x* (gplite/gplite_post.m:173-251),
  * for every hyper-sample: Ks = k(X, x*) (N x S); for Lchol samples v = L' \ Ks and x = L \ v, so that
  * alpha_update = x / sn2_eff (:227) and the new column of L is v / sn2_eff (:228); for low-noise samples

@@ -10,10 +10,17 @@ function [ais,ok] = vbmc_hip_importance_sample(ais_step1,gp,acqfun,options,LB,UB
 % struct comes back with Xa (Nm x D x S), lnw (S x Nm) and fs2a (Nm x S) filled and its device state registered with
 % vbmc_hip_is_handle, so that the acquisition calls of this active-sampling step upload nothing.
 %
+% Given the variational posterior in place of the struct of Step 1 -- vbmc_hip_importance_sample(vp,gp,acqfun,options) -- Step 1 and the
+% resampling run on the device too, in the same call (vbmc_hip_importance_setup, 'is_setup').
+%
 % ok = false (the caller runs its own loop): an acquisition function other than acqimiqr_vbmc, importance_sampling_vp, no MCMC samples
 % requested, an unsupported GP model, or a 'vbmc_hip:unsupported' answer of the library.
 ais = ais_step1;
 ok = false;
+if isfield(ais_step1,'mu') && ~isfield(ais_step1,'Xa')       % the variational posterior: the one-call form
+    [ais,ok] = vbmc_hip_importance_setup(ais_step1,gp,acqfun,options);
+    return;
+end
 nsamples = options.ActiveImportanceSamplingMCMCSamples;
 info = acqfun('info');
 supported = strcmp(func2str(acqfun),'acqimiqr_vbmc') && nsamples > 0 ...

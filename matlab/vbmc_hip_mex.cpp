@@ -36,6 +36,12 @@
 //                                (the MCMC of the IMIQR importance sampler on the device: vbmc_acq_is_sample, matlab/vbmc_hip_importance_sample.m.
 //                                 opts: Thin, Burnin, Spec, MaxSteps, MaxShrink, Seed, Chunk, U (64 x H x S x Mmax: parity mode); out: logp,
 //                                 funccount, performed, rounds, behind; his: the state of those device buffers, freed with 'is_free')
+//     [Xa,lnw,fs2a,his,out] = vbmc_hip_mex('is_setup', h, vp, Nvp, Nbox, Nm, opts)
+//                                (the whole set-up of the IMIQR importance sampler in one call: vbmc_acq_is_setup, matlab/vbmc_hip_importance_setup.m.
+//                                 opts: Thin, Burnin, Spec, MaxSteps, MaxShrink, Seed, Chunk, W (0: 2 (D + 1)), B (the Step 1 block: parity mode),
+//                                 U (64 x H x S x Mmax, with B); out: Xa1, lnw1, fs2a1, lpdf1, rect_delta, LB, UB, x0 (W x D x S), idx0 (W x S,
+//                                 0-based), n_bad, bad (W x S), logp, funccount, performed, rounds, behind; n_bad > 0: Xa, lnw, fs2a are zeros
+//                                 and his is 0; Nm = 0: Step 1 alone, his the state of the Na1 shared points)
 //           vbmc_hip_mex('is_free', his)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
@@ -250,7 +256,7 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr", "acq_is_sample"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr", "acq_is_sample", "is_setup"};
     for (const char* w : with_handle)
       if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || ((!strcmp(cmd, "acq_iqr") || !strcmp(cmd, "acq_search_iqr")) && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
@@ -670,6 +676,82 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     return 0;
   }
   if (!strcmp(cmd, "is_free")) { vbmc_acq_is_free(g_ctx, (vbmc_acq_is*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]))); return 0; }
+
+  if (!strcmp(cmd, "is_setup")) {
+    if (nrhs < 7 || !mxIsStruct(prhs[2]) || !mxIsStruct(prhs[6])) return raise("vbmc_hip:usage", "is_setup: h, vp, Nvp, Nbox, Nm, opts");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    const mxArray *vp = prhs[2], *op = prhs[6];
+    const mxArray *mu = field(vp, "mu"), *sg = field(vp, "sigma"), *lm = field(vp, "lambda"), *ww = field(vp, "w");
+    if (!mu || !sg || !lm || !ww || mxIsEmpty(mu)) return raise("vbmc_hip:usage", "is_setup: vp needs mu, sigma, lambda and w");
+    const int D = (int)mxGetM(mu), K = (int)mxGetN(mu), S = (int)scalar_field(op, "S", 0.0);
+    const int Nvp = (int)mxGetScalar(prhs[3]), Nbox = (int)mxGetScalar(prhs[4]), Nm = (int)mxGetScalar(prhs[5]);
+    if ((int)mxGetNumberOfElements(sg) != K || (int)mxGetNumberOfElements(ww) != K || (int)mxGetNumberOfElements(lm) != D || S < 1 || Nm < 0 || Nvp < 0 ||
+        Nbox < 0 || Nvp + Nbox < 1)
+      return raise("vbmc_hip:usage", "is_setup: vp.mu must be D x K with K sigmas and weights and D lambdas, opts.S = numel(gp.post), the counts non-negative");
+    vbmc_is_setup_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.D = D; a.S = S; a.K = K; a.Nvp = Nvp; a.Nbox = Nbox; a.Nm = Nm;
+    a.vp_mu = mxGetDoubles(mu); a.vp_sigma = mxGetDoubles(sg); a.vp_lambda = mxGetDoubles(lm); a.vp_w = mxGetDoubles(ww);
+    a.W = (int)scalar_field(op, "W", 0.0);
+    if (a.W == 0) a.W = 2 * (D + 1);
+    const int W = a.W, Na1 = Nvp + Nbox;
+    if (W < 0) return raise("vbmc_hip:usage", "is_setup: opts.W must be positive");
+    a.thin = (int)scalar_field(op, "Thin", 1.0); a.burnin = (int)scalar_field(op, "Burnin", -1.0);
+    a.spec = (int)scalar_field(op, "Spec", 0.0); a.max_steps = (int)scalar_field(op, "MaxSteps", 0.0); a.max_shrink = (int)scalar_field(op, "MaxShrink", 0.0);
+    a.chunk = (int)scalar_field(op, "Chunk", 0.0); a.seed = (uint64_t)scalar_field(op, "Seed", 0.0);
+    if (const mxArray* b = field(op, "B")) {
+      if (!mxIsEmpty(b)) {
+        if (mxGetNumberOfElements(b) != (size_t)(D + 1) * Na1 + (Nm > 0 ? (size_t)W * S : 0)) return raise("vbmc_hip:usage", "is_setup: opts.B must hold (D + 1) (Nvp + Nbox) + W S values");
+        a.rng_mode = 1; a.B = mxGetDoubles(b);
+        const mxArray* u = field(op, "U");
+        if (u && !mxIsEmpty(u)) {
+          const size_t nu = mxGetNumberOfElements(u), per = (size_t)64 * (size_t)(W / 2) * (size_t)S;
+          if (per == 0 || nu % per != 0) return raise("vbmc_hip:usage", "is_setup: opts.U must be 64 x H x S x Mmax");
+          a.U = mxGetDoubles(u); a.Mmax = (int)(nu / per);
+        }
+      }
+    }
+    const mwSize dx[3] = {(mwSize)Nm, (mwSize)D, (mwSize)S}, d0[3] = {(mwSize)W, (mwSize)D, (mwSize)S};
+    mxArray* Xa = mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL);
+    mxArray* lnw = mxCreateDoubleMatrix(S, Nm, mxREAL);
+    mxArray* fs2a = mxCreateDoubleMatrix(Nm, S, mxREAL);
+    const char* names[] = {"Xa1", "lnw1", "fs2a1", "lpdf1", "rect_delta", "LB", "UB", "x0", "idx0", "n_bad", "bad", "logp", "funccount", "performed", "rounds", "behind"};
+    enum { oXa1, oLnw1, oFs2a1, oLpdf1, oRd, oLB, oUB, oX0, oIdx0, oNbad, oBad, oLogp, oFc, oPf, oRounds, oBehind, oCount };
+    mxArray* out = mxCreateStructMatrix(1, 1, oCount, names);
+    mxArray* f[oCount];
+    const int rows[oCount] = {Na1, S, Na1, Na1, D, D, D, 0, W, 1, W, S, 1, 1, 1, 1}, cols[oCount] = {D, Na1, S, 1, 1, 1, 1, 0, S, 1, S, Nm, 1, 1, 1, 1};
+    for (int i = 0; i < oCount; ++i) {
+      f[i] = i == oX0 ? mxCreateNumericArray(3, d0, mxDOUBLE_CLASS, mxREAL) : mxCreateDoubleMatrix(rows[i], cols[i], mxREAL);
+      mxSetField(out, 0, names[i], f[i]);
+    }
+    std::vector<int32_t> idx0((size_t)W * S + 1, 0);
+    std::vector<uint8_t> bad((size_t)W * S + 1, 0);
+    int32_t n_bad = 0;
+    int64_t funccount = 0, performed = 0, rounds[2] = {0, 0};
+    vbmc_acq_is* is = nullptr;
+    a.Xa1 = mxGetDoubles(f[oXa1]); a.lnw1 = mxGetDoubles(f[oLnw1]); a.fs2a1 = mxGetDoubles(f[oFs2a1]); a.lpdf1 = mxGetDoubles(f[oLpdf1]);
+    a.rect_delta = mxGetDoubles(f[oRd]); a.LB = mxGetDoubles(f[oLB]); a.UB = mxGetDoubles(f[oUB]); a.x0 = mxGetDoubles(f[oX0]);
+    a.idx0 = idx0.data(); a.n_bad = &n_bad; a.bad = bad.data();
+    if (Nm > 0) { a.Xa = mxGetDoubles(Xa); a.lnw = mxGetDoubles(lnw); a.fs2a = mxGetDoubles(fs2a); a.logp = mxGetDoubles(f[oLogp]); }
+    a.funccount = &funccount; a.performed = &performed; a.rounds = rounds;
+    if (nlhs > 3) a.state = &is;
+    vbmc_status st = vbmc_acq_is_setup(g_ctx, h, &a);
+    for (size_t j = 0; j < (size_t)W * S; ++j) { mxGetDoubles(f[oIdx0])[j] = (double)idx0[j]; mxGetDoubles(f[oBad])[j] = (double)bad[j]; }
+    mxGetDoubles(f[oNbad])[0] = (double)n_bad;
+    mxGetDoubles(f[oFc])[0] = (double)funccount; mxGetDoubles(f[oPf])[0] = (double)performed;
+    mxGetDoubles(f[oRounds])[0] = (double)rounds[0]; mxGetDoubles(f[oBehind])[0] = (double)rounds[1];
+    plhs[0] = Xa;
+    if (nlhs > 1) plhs[1] = lnw; else mxDestroyArray(lnw);
+    if (nlhs > 2) plhs[2] = fs2a; else mxDestroyArray(fs2a);
+    if (nlhs > 3) {
+      plhs[3] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
+      *(uint64_t*)mxGetData(plhs[3]) = (uint64_t)(uintptr_t)is;
+    }
+    if (nlhs > 4) plhs[4] = out; else mxDestroyArray(out);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
 
   if (!strcmp(cmd, "acq_iqr")) {
     vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));

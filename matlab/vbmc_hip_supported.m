@@ -6,6 +6,8 @@ function ok = vbmc_hip_supported(gp,vp,need_var)
 %   vbmc_hip_supported(gp,vp)           ... and the mixture (K; vp.delta where the library carries it)
 %   vbmc_hip_supported(gp,vp,need_var)  ... and, if NEED_VAR, what the variance path needs (N, the factors gp.post(s).L)
 %   lim = vbmc_hip_supported()          the limits themselves
+% The one-call set-up of the IMIQR importance sampler (vbmc_hip_importance_setup, 'is_setup') asks with NEED_VAR: it needs the factors,
+% and its Nvp + Nbox importance points must fit lim.max_Na, which the library checks itself.
 % The numbers are the LIBRARY's: vbmc_hip_mex('limits') returns what its validation enforces (vbmc_get_limits, include/vbmc_hip.h:
 % max_D, max_K, max_N, max_Na, max_T_vargrad, delta_ok, meanfun), asked once per session -- a shim that restates them goes stale
 % (through round 5 this file said K <= 256 and N <= 3872 while the library took 512 and 10208).

@@ -151,6 +151,26 @@ class IsSampleArgs(C.Structure):
     ]
 
 
+class IsSetupArgs(C.Structure):
+    """vbmc_is_setup_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("D", C.c_int32), ("S", C.c_int32), ("K", C.c_int32),
+        ("vp_mu", _dp), ("vp_sigma", _dp), ("vp_lambda", _dp), ("vp_w", _dp),
+        ("Nvp", C.c_int32), ("Nbox", C.c_int32),
+        ("W", C.c_int32), ("Nm", C.c_int32), ("thin", C.c_int32), ("burnin", C.c_int32), ("spec", C.c_int32),
+        ("max_steps", C.c_int32), ("max_shrink", C.c_int32), ("chunk", C.c_int32),
+        ("rng_mode", C.c_int32), ("Mmax", C.c_int32),
+        ("seed", C.c_uint64),
+        ("B", _dp), ("U", _dp),
+        ("Xa1", _dp), ("lnw1", _dp), ("fs2a1", _dp), ("lpdf1", _dp), ("rect_delta", _dp), ("LB", _dp), ("UB", _dp), ("x0", _dp),
+        ("idx0", C.POINTER(C.c_int32)), ("n_bad", C.POINTER(C.c_int32)), ("bad", C.POINTER(C.c_uint8)),
+        ("Xa", _dp), ("lnw", _dp), ("fs2a", _dp), ("logp", _dp),
+        ("funccount", C.POINTER(C.c_int64)), ("performed", C.POINTER(C.c_int64)), ("rounds", C.POINTER(C.c_int64)),
+        ("state", C.POINTER(C.c_void_p)),
+    ]
+
+
 _lib = None
 
 
@@ -221,6 +241,8 @@ def load():
     lib.vbmc_acq_search_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_acq_is_sample.argtypes = [vp, vp, C.POINTER(IsSampleArgs)]
     lib.vbmc_acq_is_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
+    lib.vbmc_acq_is_setup.argtypes = [vp, vp, C.POINTER(IsSetupArgs)]
+    lib.vbmc_acq_is_setup_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)

@@ -477,7 +477,131 @@ def importance_sample_device(gp, x0, LB, UB, Nm, *, thin=1, burnin=None, spec=0,
     return out
 
 
-def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *, rng=None, engine=None, device=False, seed=None):
+def importance_setup_rng_dump(seed, D, S, W, Nvp, Nbox):
+    """The block B ((D + 1) (Nvp + Nbox) + W S doubles) that ``importance_setup_device(..., seed=seed)`` consumes in Step 1 and in the
+    resampling (vbmc_acq_is_setup_rng_dump: a pure host function)."""
+    import ctypes as C
+
+    from ._lib import load
+
+    B = np.zeros((D + 1) * (Nvp + Nbox) + W * S)
+    st = load().vbmc_acq_is_setup_rng_dump(C.c_uint64(seed), int(D), int(S), int(W), int(Nvp), int(Nbox), ptr(B))
+    if st != 0:
+        raise ValueError("vbmc_acq_is_setup_rng_dump: bad arguments")
+    return B
+
+
+def importance_setup_device(vp, gp, Nvp, Nbox, Nm, *, W=None, thin=1, burnin=None, spec=0, seed=0, block=None, uniforms=None, chunk=0,
+                            max_steps=0, max_shrink=0, engine=None, want_state=True):
+    """The thin ctypes call of ``vbmc_acq_is_setup`` (include/vbmc_hip.h): Step 1 of the IMIQR importance sampler, the resampling of
+    the starting walkers, the MCMC, the closing prediction and the importance-sampling state in one call.  ``block``: the caller's
+    Step 1 block (parity mode; ``uniforms``, 64 x H x S x Mmax, is then Step 2's, optional), the library's generator keyed by ``seed``
+    otherwise.  ``Nm = 0``: Step 1 alone.  Returns a dict: Xa1 (Na1 x D), lnw1 (S x Na1), fs2a1 (Na1 x S), lpdf1 (Na1), rect_delta, LB,
+    UB, and with Nm > 0 x0 (S x W x D, as ``importance_sample_device`` takes them), idx0 (W x S), n_bad, bad (W x S) and -- unless
+    n_bad > 0 -- what ``importance_sample_device`` returns."""
+    import ctypes as C
+
+    from ._lib import IsSetupArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    dgp = _device_gp_with_noise(engine, gp)
+    D, K, S = int(vp["D"]), int(vp["K"]), len(gp["post"])
+    Nvp, Nbox, Nm = int(Nvp), int(Nbox), int(Nm)
+    W = 2 * (D + 1) if W is None else int(W)
+    Na1 = max(Nvp + Nbox, 1)
+    keep = {"mu": f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)), "sigma": f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K)),
+            "lambda": f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D)), "w": f64(np.asarray(vp["w"], dtype=np.float64).reshape(K))}
+    a = IsSetupArgs()
+    a.struct_size = C.sizeof(IsSetupArgs)
+    a.D, a.S, a.K, a.Nvp, a.Nbox = D, S, K, Nvp, Nbox
+    a.vp_mu, a.vp_sigma, a.vp_lambda, a.vp_w = ptr(keep["mu"]), ptr(keep["sigma"]), ptr(keep["lambda"]), ptr(keep["w"])
+    a.W, a.Nm, a.thin, a.burnin, a.spec = W, Nm, int(thin), -1 if burnin is None else int(burnin), int(spec)
+    a.max_steps, a.max_shrink, a.chunk, a.seed = int(max_steps), int(max_shrink), int(chunk), int(seed)
+    if block is not None:
+        keep["B"] = f64(np.asarray(block, dtype=np.float64).reshape(-1))
+        if keep["B"].size != (D + 1) * (Nvp + Nbox) + (W * S if Nm > 0 else 0):
+            raise ValueError("importance_setup_device: the block must hold (D + 1) (Nvp + Nbox) + W S values")
+        a.rng_mode, a.B = 1, ptr(keep["B"])
+        if uniforms is not None:
+            keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
+            if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, W // 2, S):
+                raise ValueError("importance_setup_device: uniforms must be 64 x H x S x Mmax = 64 x %d x %d x Mmax" % (W // 2, S))
+            a.Mmax, a.U = keep["U"].shape[3], ptr(keep["U"])
+    elif uniforms is not None:
+        raise ValueError("importance_setup_device: uniforms (Step 2's block) go with a Step 1 block")
+    n, w = max(Nm, 1), max(W, 1)
+    out = {"Xa1": np.zeros((Na1, D), order="F"), "lnw1": np.zeros((S, Na1), order="F"), "fs2a1": np.zeros((Na1, S), order="F"),
+           "lpdf1": np.zeros(Na1), "rect_delta": np.zeros(D), "LB": np.zeros(D), "UB": np.zeros(D)}
+    x0 = np.zeros((w, D, S), order="F")
+    idx0 = np.zeros((w, S), dtype=np.int32, order="F")
+    bad = np.zeros((w, S), dtype=np.uint8, order="F")
+    run = {"Xa": np.zeros((n, D, S), order="F"), "lnw": np.zeros((S, n), order="F"), "fs2a": np.zeros((n, S), order="F"),
+           "logp": np.zeros((S, n), order="F")}
+    nb, fc, pf, rounds = C.c_int32(), C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
+    handle = C.c_void_p()
+    a.Xa1, a.lnw1, a.fs2a1, a.lpdf1 = ptr(out["Xa1"]), ptr(out["lnw1"]), ptr(out["fs2a1"]), ptr(out["lpdf1"])
+    a.rect_delta, a.LB, a.UB, a.x0 = ptr(out["rect_delta"]), ptr(out["LB"]), ptr(out["UB"]), ptr(x0)
+    a.idx0 = idx0.ctypes.data_as(C.POINTER(C.c_int32))
+    a.bad = bad.ctypes.data_as(C.POINTER(C.c_uint8))
+    a.n_bad = C.pointer(nb)
+    a.Xa, a.lnw, a.fs2a, a.logp = ptr(run["Xa"]), ptr(run["lnw"]), ptr(run["fs2a"]), ptr(run["logp"])
+    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
+    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    if want_state:
+        a.state = C.pointer(handle)
+    ctx.check(ctx.lib.vbmc_acq_is_setup(ctx.h, dgp.h, C.byref(a)))
+    out.update(n_bad=int(nb.value), funccount=int(fc.value), performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]), _dgp=dgp,
+               state=ImportanceState.from_handle(engine, handle) if want_state and handle.value else None)
+    if Nm > 0:
+        out.update(x0=np.ascontiguousarray(np.transpose(x0, (2, 0, 1))), idx0=idx0, bad=bad.astype(bool))
+        if out["n_bad"] == 0:
+            out.update(run)
+    return out
+
+
+def _patch_starts(x0, bad, X, LB, UB, logp, rng):
+    """Replace the starting walkers flagged in ``bad`` (S x W) by training inputs inside the box at which the target is finite."""
+    inside = X[np.all((X >= LB) & (X <= UB), axis=1)]
+    for s, i in zip(*np.nonzero(bad)):
+        for cand in inside[rng.permutation(inside.shape[0])[:16]]:
+            if np.isfinite(logp(cand[None, :], np.array([s]))[0]):
+                x0[s, i] = cand
+                break
+
+
+def _importance_setup_one_call(vp, gp, Nvp, Nbox, Nm, thin, rng, seed, engine):
+    """The IMIQR set-up through ``importance_setup_device``; None where the library answers 'unsupported'."""
+    if Nvp + Nbox > 256:                                        # more Step 1 points than an importance-sampling state holds (max_Na)
+        return None
+    sd = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
+    try:
+        r = importance_setup_device(vp, gp, Nvp, Nbox, max(Nm, 0), thin=thin, seed=sd, engine=engine)
+    except VbmcUnsupported:
+        return None
+    if Nm <= 0:
+        return {"Xa": r["Xa1"], "lnw": r["lnw1"], "fs2a": r["fs2a1"], "_device": (r["_dgp"], r["state"])}
+    if r["n_bad"] > 0:
+        X = np.asarray(gp["X"], dtype=np.float64)
+
+        def logp(P, e):
+            fm, f2, _, _ = gplite_pred_device(gp, P, engine)
+            k = np.arange(P.shape[0])
+            v = _islogf("acqimiqr_vbmc", "islogf", None, fm[k, e].reshape(-1, 1), f2[k, e].reshape(-1, 1)).reshape(-1)
+            return np.where(np.isfinite(v), v, -np.inf)
+
+        x0 = r["x0"].copy()
+        _patch_starts(x0, r["bad"].T, X, r["LB"], r["UB"], logp, rng)
+        try:
+            r = importance_sample_device(gp, x0, r["LB"], r["UB"], Nm, thin=thin, seed=sd, engine=engine)
+        except VbmcUnsupported:
+            return None
+    return {"Xa": r["Xa"], "lnw": r["lnw"], "fs2a": r["fs2a"], "logp": r["logp"], "funccount": r["funccount"], "performed": r["performed"],
+            "rounds": r["rounds"], "_device": (r["_dgp"], r["state"])}
+
+
+def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *, rng=None, engine=None, device=False, seed=None,
+                                  one_call=True):
     """ActiveImportanceSampling = activeimportancesampling_vbmc(vp,gp,acqfun,acqinfo,options)
     (private/activeimportancesampling_vbmc.m).
 
@@ -487,7 +611,12 @@ def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *,
     started from a weighted resample of those points (Step 2) -- all hyper-samples' ensembles advance together, every
     log-density evaluation is one batched GP prediction on the device (the reference predicts one point at a time,
     log_isbasefun :343-353), the transition operator is ensemble_slice_sample above.  Xa is then Na x D x S and lnw S x Na.
-    Step 3 (fs2a, Kax, Ctmp) happens on the device inside vbmc_acq_is_create at the first acquisition call."""
+    Step 3 (fs2a, Kax, Ctmp) happens on the device inside vbmc_acq_is_create at the first acquisition call.
+
+    ``device=True`` (acqimiqr_vbmc without importance_sampling_vp): Step 2 runs on the device (``importance_sample_device``), and with
+    ``one_call`` the whole set-up does (``importance_setup_device``: Step 1, the resampling, Step 2 and the state in one call; the
+    random numbers are then the library's, keyed by ``seed`` or by one draw from ``rng``).  Starting walkers of zero density are patched
+    on the host as below and handed to ``importance_sample_device``; an unsupported GP falls back to the path without the one call."""
     info = acqInfo or acq_info(acqFun)
     name = info.get("name") or (acqFun if isinstance(acqFun, str) else acqFun.__name__).lstrip("@")
     engine = engine or default_engine()
@@ -515,6 +644,12 @@ def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *,
     Nbox = evalopt("ActiveImportanceSamplingBoxSamples", 100)
     if Nvp + Nbox <= 0:
         raise ValueError("activeimportancesampling_vbmc: no importance samples requested")
+    on_device = device and name == "acqimiqr_vbmc" and not isamplevp      # (the device target is IMIQR's log base density and nothing else)
+    if on_device and one_call:
+        r = _importance_setup_one_call(vp, gp, Nvp, Nbox, evalopt("ActiveImportanceSamplingMCMCSamples", 100),
+                                       max(1, evalopt("ActiveImportanceSamplingMCMCThin", 1)), rng, seed, engine)
+        if r is not None:
+            return r
     w_vp = Nvp / (Nvp + Nbox)
     rect_delta = 2 * np.std(X, axis=0, ddof=1)
     lnw_l, Xa_l, fs2_l = [], [], []
@@ -573,13 +708,8 @@ def activeimportancesampling_vbmc(vp, gp, acqFun, acqInfo=None, options=None, *,
     # a walker that starts at zero density (a clipped point, a duplicate drawn after the weights ran out) is replaced by a training input
     # inside the box -- the sampler would refuse it, and one degenerate hyper-sample must not abort the acquisition set-up
     lp0 = logp(x0.reshape(S * W, D), np.repeat(np.arange(S), W)).reshape(S, W)
-    inside = X[np.all((X >= LB) & (X <= UB), axis=1)]
-    for s, i in zip(*np.nonzero(~np.isfinite(lp0))):
-        for cand in inside[rng.permutation(inside.shape[0])[:16]]:
-            if np.isfinite(logp(cand[None, :], np.array([s]))[0]):
-                x0[s, i] = cand
-                break
-    if device and name == "acqimiqr_vbmc" and not isamplevp:      # (the device target is IMIQR's log base density and nothing else)
+    _patch_starts(x0, ~np.isfinite(lp0), X, LB, UB, logp, rng)
+    if on_device:
         try:
             sd = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
             r = importance_sample_device(gp, x0, LB, UB, Nm, thin=thin, burnin=burnin, seed=sd, engine=engine)

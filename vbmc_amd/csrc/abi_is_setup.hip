@@ -1,0 +1,178 @@
+// C-ABI entry points of the one-call set-up of the IMIQR importance sampler: vbmc_acq_is_setup and vbmc_acq_is_setup_rng_dump
+// (include/vbmc_hip.h).  Step 1 and the resampling are is_setup_kernels.h; the prediction of the Step 1 points is k_is_pred on the
+// set-up the sampler uses anyway (every ensemble's point buffer holds the same Na1 points); the starting walkers are written where
+// is_core_run (abi_is_sample.hip) expects them, so that Step 2 follows in the same stream.  Included after abi_is_sample.hip.
+#include "is_setup_kernels.h"
+
+namespace {
+inline size_t iss_block_len(int D, int S, int W, int Na1) { return (size_t)(D + 1) * Na1 + (size_t)W * S; }
+}  // namespace
+
+extern "C" vbmc_status vbmc_acq_is_setup_rng_dump(uint64_t seed, int D, int S, int W, int Nvp, int Nbox, double* B) {
+  if (D <= 0 || S <= 0 || W < 0 || Nvp < 0 || Nbox < 0 || Nvp + Nbox < 1 || !B) return VBMC_ERR_INVALID;
+  const int Na1 = Nvp + Nbox;
+  for (int i = 0; i < Na1; ++i) {
+    B[(size_t)(D + 1) * i] = slice_uniform(seed, ISS_CTR_POINT, (unsigned)i, 0u);
+    for (int d = 0; d < D; ++d)
+      B[(size_t)(1 + d) + (size_t)(D + 1) * i] = i < Nvp ? srch_normal(seed, ISS_CTR_POINT, (unsigned)i, (unsigned)d) : slice_uniform(seed, ISS_CTR_POINT, (unsigned)i, (unsigned)(1 + d));
+  }
+  for (int s = 0; s < S; ++s)
+    for (int i = 0; i < W; ++i) B[(size_t)(D + 1) * Na1 + i + (size_t)W * s] = slice_uniform(seed, ISS_CTR_DRAW, (unsigned)s, (unsigned)i);
+  return VBMC_OK;
+}
+
+extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_is_setup_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  const char* who = "vbmc_acq_is_setup";
+  if (args && args->struct_size == sizeof(vbmc_is_setup_args) && args->state) *args->state = nullptr;
+  if (!args || args->struct_size != sizeof(vbmc_is_setup_args)) return set_err(ctx, VBMC_ERR_INVALID, "%s: struct_size mismatch", who);
+  const vbmc_is_setup_args& g = *args;
+  if (g.n_bad) *g.n_bad = 0;
+  if (!gp || !g.vp_mu || !g.vp_sigma || !g.vp_lambda || !g.vp_w) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+  const int D = gp->D, S = gp->S, N = gp->N, K = g.K, Nm = g.Nm;
+  if (g.D != D || g.S != S)
+    return set_err(ctx, VBMC_ERR_INVALID, "%s: the arrays are laid out for D = %d and S = %d, the GP has D = %d and S = %d hyper-samples", who, g.D, g.S, D, S);
+  if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
+  if (K < 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: K = %d", who, K);
+  if (K > VBMC_LIM_K) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "K = %d > %d not accelerated", K, VBMC_LIM_K);
+  if (g.Nvp < 0 || g.Nbox < 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nvp = %d and Nbox = %d must be non-negative", who, g.Nvp, g.Nbox);
+  const long long na_ll = (long long)g.Nvp + g.Nbox;
+  if (na_ll < 1 || na_ll > ISS_MAXNA) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nvp + Nbox = %lld outside 1 .. %d", who, na_ll, ISS_MAXNA);
+  const int Na1 = (int)na_ll, Nap1 = ((Na1 + 15) / 16) * 16, K4 = 4 * K;
+  if (N < 2) return set_err(ctx, VBMC_ERR_INVALID, "%s: rect_delta = 2 std(X) needs at least two training inputs", who);
+  if (g.rng_mode != 0 && g.rng_mode != 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: rng_mode %d (0 device, 1 parity)", who, g.rng_mode);
+  if (Nm < 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nm = %d outside 0 .. %d", who, Nm, VBMC_LIM_NA);
+  const bool step2 = Nm > 0;
+  // Step 1 alone: the sampler's routines still provide the prediction's set-up, for the smallest sampler there is
+  IsParams p{step2 ? g.W : 4, step2 ? Nm : 1, step2 ? g.thin : 1, step2 ? g.burnin : -1, g.spec, g.max_steps, g.max_shrink, g.chunk,
+             (g.rng_mode == 1 && g.U && step2) ? 1 : 0, g.Mmax, g.seed, step2 ? g.U : nullptr};
+  VB_TRY(is_check_params(ctx, who, gp, p));
+  const int W = step2 ? g.W : 0;
+  double wsum = 0.0;
+  bool vp_ok = true;
+  for (int k = 0; k < K; ++k) {
+    vp_ok = vp_ok && std::isfinite(g.vp_sigma[k]) && g.vp_sigma[k] > 0.0 && std::isfinite(g.vp_w[k]) && g.vp_w[k] >= 0.0;
+    wsum += g.vp_w[k];
+    for (int d = 0; d < D; ++d) vp_ok = vp_ok && std::isfinite(g.vp_mu[d + (size_t)D * k]);
+  }
+  for (int d = 0; d < D; ++d) vp_ok = vp_ok && std::isfinite(g.vp_lambda[d]) && g.vp_lambda[d] > 0.0;
+  if (!vp_ok || !(wsum > 0.0) || !std::isfinite(wsum))
+    return set_err(ctx, VBMC_ERR_INVALID, "%s: the variational posterior must be finite with sigma, lambda > 0 and weights >= 0 of positive sum", who);
+  const size_t nB = g.rng_mode == 1 ? iss_block_len(D, S, W, Na1) : 0;
+  if (g.rng_mode == 1) {
+    if (!g.B) return set_err(ctx, VBMC_ERR_INVALID, "%s: parity mode needs the block B", who);
+    for (size_t j = 0; j < nB; ++j) {
+      const size_t i = j / (size_t)(D + 1), slot = j % (size_t)(D + 1);
+      const bool normal = j < (size_t)(D + 1) * Na1 && (int)i < g.Nvp && slot > 0;
+      const double v = g.B[j];
+      if (normal ? !std::isfinite(v) : !(v > 0.0 && v < 1.0))
+        return set_err(ctx, VBMC_ERR_INVALID, "%s: block value %zu: the uniforms must lie strictly inside (0, 1), the normals must be finite", who, j);
+    }
+  }
+
+  IsCore c;
+  VB_TRY(is_core_begin(ctx, gp, who, p, c));
+  hipStream_t st = ctx->stream;
+  // one block of fp64:  mu | sigma | lambda | w | B | geo (D + 1) | comp (12 K) | Xa1 | P1 | logp fmu fs2 ys2 (S x Na1 each) | lpdf |
+  //                     lnw1 fs2a1 (S x Nap1) | lw (S x Na1) | x0
+  const size_t nvp = (size_t)D * K + K + D + K, nX1 = (size_t)Na1 * D, nP1 = (size_t)S * D * Na1, nv1 = (size_t)S * Na1, np1 = (size_t)S * Nap1;
+  const size_t nx0 = (size_t)std::max(W, 1) * D * S;
+  const size_t n1 = nvp + nB + (size_t)(D + 1) + 3 * (size_t)K4 + nX1 + nP1 + 4 * nv1 + Na1 + 2 * np1 + nv1 + nx0;
+  TmpBuf d1, dIdx, dNc1;
+  HIP_TRY(ctx, d1.alloc(ctx, n1 * 8));
+  HIP_TRY(ctx, dIdx.alloc(ctx, (size_t)std::max(W, 1) * S * sizeof(int)));
+  HIP_TRY(ctx, dNc1.alloc(ctx, (size_t)S * sizeof(int)));
+  std::vector<double> hup(nvp + nB);
+  memcpy(hup.data(), g.vp_mu, (size_t)D * K * 8);
+  memcpy(hup.data() + (size_t)D * K, g.vp_sigma, (size_t)K * 8);
+  memcpy(hup.data() + (size_t)D * K + K, g.vp_lambda, (size_t)D * 8);
+  memcpy(hup.data() + (size_t)D * K + K + D, g.vp_w, (size_t)K * 8);
+  if (nB) memcpy(hup.data() + nvp, g.B, nB * 8);
+  const std::vector<int> hnc1(S, Na1);
+  HIP_TRY(ctx, hipMemcpyAsync(d1.p, hup.data(), hup.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(dNc1.p, hnc1.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
+
+  IsSetupKArgs k{};
+  k.D = D; k.N = N; k.S = S; k.K = K; k.Nvp = g.Nvp; k.Nbox = g.Nbox; k.W = W; k.parity = g.rng_mode; k.seed = g.seed;
+  k.w_vp = (double)g.Nvp / (double)Na1;                // :110
+  k.X = gp->X;
+  double* q = d1.as<double>();
+  k.mu = q; q += (size_t)D * K;
+  k.sigma = q; q += K;
+  k.lambda = q; q += D;
+  k.w = q; q += K;
+  k.B = nB ? q : nullptr; q += nB;
+  k.geo = q; q += D + 1;
+  k.comp = q; q += 3 * (size_t)K4;
+  k.Xa1 = q; q += nX1;
+  k.P = q; q += nP1;
+  double* d_pv = q; q += 4 * nv1;
+  k.fmu = d_pv + nv1; k.fs2 = d_pv + 2 * nv1;
+  k.lpdf = q; q += Na1;
+  k.lnw1 = q; q += np1;
+  k.fs2a1 = q; q += np1;
+  k.lw = q; q += nv1;
+  k.x0 = q; q += nx0;
+  k.LB = const_cast<double*>(c.a.LB); k.UB = const_cast<double*>(c.a.UB);
+  k.x = c.a.x; k.idx0 = dIdx.as<int>();
+
+  hipLaunchKernelGGL(k_is_draw, dim3(1), dim3(ISS_DRAW_THREADS), 0, st, k);
+  IsPredArgs pg1 = c.pg;
+  pg1.P = k.P; pg1.mask = nullptr; pg1.ncand = dNc1.as<int>(); pg1.nstride = 1; pg1.C = Na1;
+  pg1.logp = d_pv; pg1.fmu = d_pv + nv1; pg1.fs2 = d_pv + 2 * nv1; pg1.ys2 = d_pv + 3 * nv1;
+  c.pk.launch(st, pg1, (Na1 + 15) / 16);
+  hipLaunchKernelGGL(k_is_proposal, dim3(Nap1), dim3(64), 0, st, k);
+  if (step2) hipLaunchKernelGGL(k_is_resample, dim3(S), dim3(64), 0, st, k);
+  HIP_TRY(ctx, hipGetLastError());
+
+  // ---- Step 2 behind it in the same stream; the Step 1 arrays come back with whatever else the caller asked for
+  IsBadStart bad;
+  const IsOutputs o{g.Xa, g.lnw, g.fs2a, g.logp, g.funccount, g.performed, g.rounds, g.state};
+  if (step2) VB_TRY(is_core_run(ctx, gp, who, p, c, o, &bad));
+  std::vector<double> hl, hf, hg;
+  std::vector<int> hi;
+  if (g.Xa1) HIP_TRY(ctx, hipMemcpyAsync(g.Xa1, k.Xa1, nX1 * 8, hipMemcpyDeviceToHost, st));
+  if (g.lpdf1) HIP_TRY(ctx, hipMemcpyAsync(g.lpdf1, k.lpdf, (size_t)Na1 * 8, hipMemcpyDeviceToHost, st));
+  if (g.lnw1) { hl.resize(np1); HIP_TRY(ctx, hipMemcpyAsync(hl.data(), k.lnw1, np1 * 8, hipMemcpyDeviceToHost, st)); }
+  if (g.fs2a1) { hf.resize(np1); HIP_TRY(ctx, hipMemcpyAsync(hf.data(), k.fs2a1, np1 * 8, hipMemcpyDeviceToHost, st)); }
+  if (g.rect_delta) HIP_TRY(ctx, hipMemcpyAsync(g.rect_delta, k.geo, (size_t)D * 8, hipMemcpyDeviceToHost, st));
+  if (g.LB || g.UB) { hg.resize(2 * (size_t)D); HIP_TRY(ctx, hipMemcpyAsync(hg.data(), k.LB, 2 * (size_t)D * 8, hipMemcpyDeviceToHost, st)); }
+  if (step2 && g.x0) HIP_TRY(ctx, hipMemcpyAsync(g.x0, k.x0, (size_t)W * D * S * 8, hipMemcpyDeviceToHost, st));
+  if (step2 && g.idx0) { hi.resize((size_t)W * S); HIP_TRY(ctx, hipMemcpyAsync(hi.data(), k.idx0, (size_t)W * S * sizeof(int), hipMemcpyDeviceToHost, st)); }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (int s = 0; s < S; ++s)
+    for (int i = 0; i < Na1; ++i) {
+      if (g.lnw1) g.lnw1[s + (size_t)S * i] = hl[(size_t)s * Nap1 + i];
+      if (g.fs2a1) g.fs2a1[i + (size_t)Na1 * s] = hf[(size_t)s * Nap1 + i];
+    }
+  if (g.LB) memcpy(g.LB, hg.data(), (size_t)D * 8);
+  if (g.UB) memcpy(g.UB, hg.data() + D, (size_t)D * 8);
+  if (step2 && g.idx0) for (size_t j = 0; j < hi.size(); ++j) g.idx0[j] = hi[j];
+  if (step2 && bad.n > 0) {
+    if (g.n_bad) *g.n_bad = bad.n;
+    if (g.bad) memcpy(g.bad, bad.mask.data(), (size_t)W * S);
+    if (g.funccount) *g.funccount = (int64_t)W * S;
+    if (g.performed) *g.performed = (int64_t)W * S;
+    if (g.rounds) { g.rounds[0] = 0; g.rounds[1] = 0; }
+    return VBMC_OK;
+  }
+  if (step2 && g.bad) memset(g.bad, 0, (size_t)W * S);
+  if (!step2) {
+    if (g.funccount) *g.funccount = 0;
+    if (g.performed) *g.performed = 0;
+    if (g.rounds) { g.rounds[0] = 0; g.rounds[1] = 0; }
+    if (g.state) {                                     // the state of the Na1 shared points with lnw1 (:148-157 with Nmcmc_samples = 0)
+      vbmc_acq_is* h = nullptr;
+      VB_TRY(acq_is_new(ctx, gp, Na1, 0, true, &h));
+      auto fail = [&](vbmc_status s_) { vbmc_acq_is_free(ctx, h); return s_; };
+      hipError_t e1 = hipMemcpyAsync(h->Xa, k.Xa1, nX1 * 8, hipMemcpyDeviceToDevice, st);
+      hipError_t e2 = hipMemcpyAsync(h->lnw, k.lnw1, np1 * 8, hipMemcpyDeviceToDevice, st);
+      hipError_t e3 = hipMemcpyAsync(h->fs2a, k.fs2a1, np1 * 8, hipMemcpyDeviceToDevice, st);
+      if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(set_err(ctx, VBMC_ERR_HIP, "%s: device copy into the state failed", who));
+      const vbmc_status cs = acq_is_ctmp_resident(ctx, gp, h);
+      if (cs != VBMC_OK) return fail(cs);
+      *g.state = h;
+    }
+  }
+  return VBMC_OK;
+}

@@ -4,4 +4,5 @@
 #include "abi_gp_train.hip"
 #include "abi_acq_search.hip"
 #include "abi_is_sample.hip"
+#include "abi_is_setup.hip"
 #include "abi_comm.hip"
