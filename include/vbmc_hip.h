@@ -912,6 +912,68 @@ vbmc_status vbmc_device_free(vbmc_ctx* ctx, void* dptr);
 vbmc_status vbmc_memcpy_h2d(vbmc_ctx* ctx, void* dst, const void* src, size_t bytes);
 vbmc_status vbmc_memcpy_d2h(vbmc_ctx* ctx, void* dst, const void* src, size_t bytes);
 
+/*
+ * The variational posterior in the caller's own parameter space (additions, backward compatible: VBMC_ABI_VERSION is unchanged):
+ * vbmc_pdf.m, vbmc_rnd.m, vbmc_moments.m:23-28 and vbmc_kldiv.m:70-88 with the variable transform of shared/warpvars_vbmc.m.
+ *
+ * vbmc_vp_desc: one posterior.  Caller-owned host data, column-major fp64; nothing is retained after return.  type == NULL is an
+ * empty trinfo (the identity, warpvars_vbmc.m:47-58).  Per-variable types 0 (unbounded: (x - mu) / delta), 1 (lower bounded:
+ * log(x - lb)), 2 (upper bounded: log(ub - x)) and 3 (logit of (x - lb) / (ub - lb), then (. - mu) / delta) are accelerated; types
+ * 4 .. 13 answer VBMC_ERR_UNSUPPORTED.  scale (NULL or all ones: none) and R (NULL: none; D x D column-major, y = u R) are the
+ * optional scale row and rotation of misc/warp_input_vbmc.m:72-73.  D <= 32, K <= 512, else VBMC_ERR_UNSUPPORTED.
+ *
+ * Randomness (the convention of vbmc_acq_is_setup): sample i owns the slots B[(D + 1) i ..]; slot 0 is a uniform in (0, 1) that
+ * catrnd (vbmc_rnd.m:111-123) uses for an unbalanced draw or for a remainder draw of the balanced split, slots 1 + d are standard
+ * normals.  With block == NULL they come from Philox counters keyed by seed; a non-null block of (D + 1) M doubles replays
+ * vbmc_vp_rnd_rng_dump's, bit-identically in I and in the transformed-space samples.  The balanced split (vbmc_rnd.m:57-77): the
+ * M = sum floor(w N) + ceil(sum w_extra) sample ids below sum floor(w N) take their component from the cumulative counts, the
+ * others from catrnd(w_extra); randperm(numel(I), N) is a bijection pi of [0, M) keyed by seed, built from integer operations alone;
+ * output row r is sample pi(r) (unbalanced: M = N and pi is the identity).  Every entry point below generates "row r -> sample pi(r)",
+ * so that vbmc_vp_moments and vbmc_vp_kldiv equal vbmc_vp_rnd followed by the host's mean / cov resp. by vbmc_vp_pdf on the same seed.
+ *
+ *   vbmc_vp_pdf            y (N) and, where dy != NULL, dy (N x D) = vbmc_pdf(vp, X, origflag, logflag, transflag, df) at the rows of
+ *                          X (N x D).  df = +-Inf or 0: the Gaussian mixture; df > 0 the multivariate t, df < 0 the product of
+ *                          univariate t of |df| degrees of freedom.  Computed in the log domain: where the reference's sum of
+ *                          densities underflows the result is -Inf resp. 0, as there; a value that the reference loses only in the
+ *                          division by the Jacobian stays finite.  The gradient exists for the Gaussian mixture in the transformed
+ *                          space (origflag = 0, or an empty trinfo); the forms the reference stops on (vbmc_pdf.m:82, :100, :117)
+ *                          and the uncorrected plain-density gradient in the original space answer VBMC_ERR_UNSUPPORTED.
+ *   vbmc_vp_rnd            X (N x D) and, where I != NULL, I (N, from 0) = vbmc_rnd(vp, N, origflag, balanceflag, df).  Gaussian
+ *                          components only: a finite non-zero df and balanceflag = 2 (the reference's 'gp') answer
+ *                          VBMC_ERR_UNSUPPORTED.  Original-space samples are clamped into [lb + eps(lb), ub - eps(ub)]
+ *                          (warpvars_vbmc.m:456-459).
+ *   vbmc_vp_moments        mubar (D) and, where Sigma != NULL, Sigma (D x D) of Ns >= 2 balanced draws in the original space
+ *                          (vbmc_moments.m:23-28).  The samples never reach memory: shifted sums about the image of the mixture
+ *                          mean, per-workgroup partials added in index order (no atomics), Sigma = (S2 - S1 S1' / Ns) / (Ns - 1).
+ *   vbmc_vp_kldiv          kls[2] of vbmc_kldiv.m:70-88 (the non-Gaussian branch, the final max(., 0) included).  Direction 1 draws
+ *                          from vp1 with (seed, block1), direction 2 from vp2 with (seed + 1, block2); xx1 / xx2 (Ns x D, NULL: not
+ *                          wanted) are exactly vbmc_vp_rnd's rows for those.  Both densities are evaluated at the original-space
+ *                          point through each posterior's own direct transform, as the reference does.  lb / ub of the two
+ *                          posteriors must be equal, else VBMC_ERR_UNSUPPORTED.
+ *   vbmc_vp_rnd_rng_dump   host function: the block a seed stands for.  B receives (D + 1) M doubles, M <= N + K (size it for
+ *                          N + K samples); perm (N, NULL: not wanted) receives pi(r).  Either may be NULL.
+ */
+typedef struct vbmc_vp_desc {
+  uint32_t struct_size;
+  int32_t D, K;
+  const double* mu;       /* D x K */
+  const double* sigma;    /* K */
+  const double* lambda;   /* D */
+  const double* w;        /* K */
+  const int32_t* type;    /* D, or NULL: empty trinfo */
+  const double* lb;       /* D: trinfo.lb_orig */
+  const double* ub;       /* D: trinfo.ub_orig */
+  const double* tmu;      /* D: trinfo.mu */
+  const double* tdelta;   /* D: trinfo.delta */
+  const double* scale;    /* D, or NULL */
+  const double* R;        /* D x D column-major, or NULL: trinfo.R_mat */
+} vbmc_vp_desc;
+vbmc_status vbmc_vp_pdf(vbmc_ctx* ctx, const vbmc_vp_desc* vp, int64_t N, const double* X, int origflag, int logflag, int transflag, double df, double* y, double* dy);
+vbmc_status vbmc_vp_rnd(vbmc_ctx* ctx, const vbmc_vp_desc* vp, int64_t N, int origflag, int balanceflag, double df, uint64_t seed, const double* block, double* X, int32_t* I);
+vbmc_status vbmc_vp_moments(vbmc_ctx* ctx, const vbmc_vp_desc* vp, int64_t Ns, uint64_t seed, const double* block, double* mubar, double* Sigma);
+vbmc_status vbmc_vp_kldiv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, int64_t Ns, uint64_t seed, const double* block1, const double* block2, double* kls, double* xx1, double* xx2);
+vbmc_status vbmc_vp_rnd_rng_dump(uint64_t seed, int64_t N, int D, int K, int balanceflag, const double* w, double* B, int64_t* perm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,10 @@
 //                                 0-based), n_bad, bad (W x S), logp, funccount, performed, rounds, behind; n_bad > 0: Xa, lnw, fs2a are zeros
 //                                 and his is 0; Nm = 0: Step 1 alone, his the state of the Na1 shared points)
 //           vbmc_hip_mex('is_free', his)
+//     [y,dy] = vbmc_hip_mex('vp_pdf', vp, X, origflag, logflag, transflag, df)        (vbmc_pdf through vp.trinfo: vbmc_vp_pdf, matlab/vbmc_hip_pdf.m)
+//     [X,I] = vbmc_hip_mex('vp_rnd', vp, N, origflag, balanceflag, df, seed)          (vbmc_rnd, I counted from 0: vbmc_vp_rnd, matlab/vbmc_hip_rnd.m)
+//     [mubar,Sigma] = vbmc_hip_mex('vp_moments', vp, Ns, seed)                        (vbmc_moments(vp,1,Ns): vbmc_vp_moments, matlab/vbmc_hip_moments.m)
+//     [kls,xx1,xx2] = vbmc_hip_mex('vp_kldiv', vp1, vp2, Ns, seed)                    (vbmc_kldiv(vp1,vp2,Ns,0): vbmc_vp_kldiv, matlab/vbmc_hip_kldiv.m)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
 //     [samples,logp,widths,counts] = vbmc_hip_mex('slice_sample', X, y, s2, meanfun, noisefun, prior /*struct mu, sigma, df or []*/, LB, UB,
@@ -212,6 +216,34 @@ static void read_gp(const mxArray* gp, GpArrays& g) {
   for (int i = 0; nfa && i < 3 && i < (int)mxGetNumberOfElements(nfa); ++i) g.nf[i] = (int32_t)mxGetDoubles(nfa)[i];
   g.Ncov = (int)scalar_field(gp, "Ncov", g.D + 1); g.Nnoise = (int)scalar_field(gp, "Nnoise", 1);
   g.meanfun = (int)scalar_field(gp, "meanfun", 4);
+}
+
+// vp struct with its trinfo (shared/warpvars_vbmc.m: lb_orig, ub_orig, type, mu, delta, scale, R_mat; empty: the identity) -> vbmc_vp_desc
+// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv').  The arrays stay MATLAB's; only the types are converted to int32.
+static int fill_vp_desc(vbmc_vp_desc& d, const mxArray* vp, std::vector<int32_t>& types) {
+  memset(&d, 0, sizeof d);
+  d.struct_size = sizeof d;
+  if (!vp || !mxIsStruct(vp)) return raise("vbmc_hip:usage", "vp must be a variational-posterior struct");
+  const mxArray *mu = field(vp, "mu"), *sg = field(vp, "sigma"), *lm = field(vp, "lambda"), *ww = field(vp, "w");
+  if (!mu || !sg || !lm || !ww || mxIsEmpty(mu)) return raise("vbmc_hip:usage", "vp needs mu, sigma, lambda and w");
+  d.D = (int32_t)mxGetM(mu); d.K = (int32_t)mxGetN(mu);
+  if (mxGetNumberOfElements(sg) != (size_t)d.K || mxGetNumberOfElements(ww) != (size_t)d.K || mxGetNumberOfElements(lm) != (size_t)d.D)
+    return raise("vbmc_hip:usage", "vp.mu must be D x K with K sigmas and weights and D lambdas");
+  d.mu = mxGetDoubles(mu); d.sigma = mxGetDoubles(sg); d.lambda = mxGetDoubles(lm); d.w = mxGetDoubles(ww);
+  const mxArray* tr = field(vp, "trinfo");
+  if (!tr || mxIsEmpty(tr) || !mxIsStruct(tr)) return 0;
+  const mxArray *ty = field(tr, "type"), *lb = field(tr, "lb_orig"), *ub = field(tr, "ub_orig"), *tm = field(tr, "mu"), *td = field(tr, "delta");
+  const mxArray *sc = field(tr, "scale"), *rm = field(tr, "R_mat");
+  const size_t D = (size_t)d.D;
+  for (const mxArray* a : {ty, lb, ub, tm, td})
+    if (!a || mxGetNumberOfElements(a) != D) return raise("vbmc_hip:usage", "vp.trinfo needs type, lb_orig, ub_orig, mu and delta with D entries each");
+  if ((sc && !mxIsEmpty(sc) && mxGetNumberOfElements(sc) != D) || (rm && !mxIsEmpty(rm) && mxGetNumberOfElements(rm) != D * D))
+    return raise("vbmc_hip:usage", "vp.trinfo.scale must have D entries and vp.trinfo.R_mat D x D");
+  types.resize(D);
+  for (size_t i = 0; i < D; ++i) types[i] = (int32_t)mxGetDoubles(ty)[i];
+  d.type = types.data(); d.lb = mxGetDoubles(lb); d.ub = mxGetDoubles(ub); d.tmu = mxGetDoubles(tm); d.tdelta = mxGetDoubles(td);
+  d.scale = dbl(sc); d.R = dbl(rm);
+  return 0;
 }
 
 // Every command; returns 0 on success, nonzero with g_err_id / g_err_msg set.  All C++ objects live in here.
@@ -749,6 +781,74 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
       *(uint64_t*)mxGetData(plhs[3]) = (uint64_t)(uintptr_t)is;
     }
     if (nlhs > 4) plhs[4] = out; else mxDestroyArray(out);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "vp_pdf")) {      // [y,dy] = vbmc_pdf(vp,X,origflag,logflag,transflag,df): vbmc_vp_pdf
+    if (nrhs < 7) return raise("vbmc_hip:usage", "vp_pdf: vp, X, origflag, logflag, transflag, df");
+    vbmc_vp_desc d;
+    std::vector<int32_t> ty;
+    if (fill_vp_desc(d, prhs[1], ty)) return 1;
+    const mxArray* X = prhs[2];
+    if (!mxIsDouble(X) || (int)mxGetN(X) != d.D) return raise("vbmc_hip:usage", "vp_pdf: X must be N x D");
+    const mwSize N = mxGetM(X);
+    plhs[0] = mxCreateDoubleMatrix(N, 1, mxREAL);
+    mxArray* dy = nlhs > 1 ? mxCreateDoubleMatrix(N, d.D, mxREAL) : nullptr;
+    if (dy) plhs[1] = dy;
+    vbmc_status st = vbmc_vp_pdf(g_ctx, &d, (int64_t)N, dbl(X), mxGetScalar(prhs[3]) != 0, mxGetScalar(prhs[4]) != 0, mxGetScalar(prhs[5]) != 0, mxGetScalar(prhs[6]),
+                                 mxGetDoubles(plhs[0]), dy ? mxGetDoubles(dy) : nullptr);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "vp_rnd")) {      // [X,I] = vbmc_rnd(vp,N,origflag,balanceflag,df) with the library's draws for seed (I from 0): vbmc_vp_rnd
+    if (nrhs < 7) return raise("vbmc_hip:usage", "vp_rnd: vp, N, origflag, balanceflag, df, seed");
+    vbmc_vp_desc d;
+    std::vector<int32_t> ty;
+    if (fill_vp_desc(d, prhs[1], ty)) return 1;
+    const double n = mxGetScalar(prhs[2]);
+    if (!(n >= 0)) return raise("vbmc_hip:usage", "vp_rnd: N must be non-negative");
+    const mwSize N = (mwSize)n;
+    plhs[0] = mxCreateDoubleMatrix(N, d.D, mxREAL);
+    std::vector<int32_t> I(N);
+    vbmc_status st = vbmc_vp_rnd(g_ctx, &d, (int64_t)N, mxGetScalar(prhs[3]) != 0, (int)mxGetScalar(prhs[4]), mxGetScalar(prhs[5]), (uint64_t)mxGetScalar(prhs[6]), nullptr,
+                                 mxGetDoubles(plhs[0]), I.data());
+    if (nlhs > 1) {
+      plhs[1] = mxCreateDoubleMatrix(N, 1, mxREAL);
+      for (mwSize i = 0; i < N; ++i) mxGetDoubles(plhs[1])[i] = (double)I[i];
+    }
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "vp_moments")) {  // [mubar,Sigma] = vbmc_moments(vp,1,Ns) with the library's draws for seed: vbmc_vp_moments
+    if (nrhs < 4) return raise("vbmc_hip:usage", "vp_moments: vp, Ns, seed");
+    vbmc_vp_desc d;
+    std::vector<int32_t> ty;
+    if (fill_vp_desc(d, prhs[1], ty)) return 1;
+    plhs[0] = mxCreateDoubleMatrix(1, d.D, mxREAL);
+    mxArray* S = nlhs > 1 ? mxCreateDoubleMatrix(d.D, d.D, mxREAL) : nullptr;
+    if (S) plhs[1] = S;
+    vbmc_status st = vbmc_vp_moments(g_ctx, &d, (int64_t)mxGetScalar(prhs[2]), (uint64_t)mxGetScalar(prhs[3]), nullptr, mxGetDoubles(plhs[0]), S ? mxGetDoubles(S) : nullptr);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "vp_kldiv")) {    // [kls,xx1,xx2] = vbmc_kldiv(vp1,vp2,Ns,0) with the library's draws for seed: vbmc_vp_kldiv
+    if (nrhs < 5) return raise("vbmc_hip:usage", "vp_kldiv: vp1, vp2, Ns, seed");
+    vbmc_vp_desc d1, d2;
+    std::vector<int32_t> t1, t2;
+    if (fill_vp_desc(d1, prhs[1], t1) || fill_vp_desc(d2, prhs[2], t2)) return 1;
+    const double n = mxGetScalar(prhs[3]);
+    if (!(n >= 1)) return raise("vbmc_hip:usage", "vp_kldiv: Ns must be positive");
+    const mwSize Ns = (mwSize)n;
+    plhs[0] = mxCreateDoubleMatrix(1, 2, mxREAL);
+    mxArray *x1 = nlhs > 1 ? mxCreateDoubleMatrix(Ns, d1.D, mxREAL) : nullptr, *x2 = nlhs > 2 ? mxCreateDoubleMatrix(Ns, d1.D, mxREAL) : nullptr;
+    if (x1) plhs[1] = x1;
+    if (x2) plhs[2] = x2;
+    vbmc_status st = vbmc_vp_kldiv(g_ctx, &d1, &d2, (int64_t)Ns, (uint64_t)mxGetScalar(prhs[4]), nullptr, nullptr, mxGetDoubles(plhs[0]), x1 ? mxGetDoubles(x1) : nullptr,
+                                   x2 ? mxGetDoubles(x2) : nullptr);
     if (st != VBMC_OK) return fail(st);
     return 0;
   }

@@ -1,0 +1,242 @@
+"""GPU: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments and vbmc_vp_kldiv (vbmc_amd.vptools) against the NumPy restatement
+tests/_vptools_ref.py on the cases of that file (A .. F), at 1, 63, 64, 65 and 1003 points and at 70 000 (several workgroups, and more
+tiles than the 512 partials: some workgroups take two).
+
+Tolerances.  They were not fixed in advance: each is ten times the largest deviation of the device from the restatement measured over
+these very cases (DESIGN.md section 6h lists the measurements), and sits below the project's 1e-10 for values and 1e-9 for gradients.
+  log densities          |dev - ref| <= PDF_TOL[family] max(1, |ref|)         plain densities: the same bound relative to ref
+  gradients              |dev - ref| <= GRAD_TOL max_d |ref_row|
+  original-space samples |dev - ref| <= XORIG_TOL max(1, |ref|)
+  moments                |dev - composition| <= MOM_TOL sigma_i sigma_j (mean: sigma_i), the composition being vbmc_vp_rnd on the same seed
+                         followed by the restatement's mean / cov
+  kldiv                  |dev - composition| <= KL_TOL max(1, |composition|), the composition being vbmc_vp_rnd + vbmc_vp_pdf and the
+                         rules and means of vbmc_kldiv.m:75-84
+Identical: I, the transformed-space samples (against mu + lambda (z sigma) formed from the dump), a replay of the dumped block, a
+repeated call, xx1 / xx2 against vbmc_vp_rnd's rows."""
+import numpy as np
+import pytest
+
+from tests import _vptools_ref as T
+
+pytestmark = pytest.mark.gpu
+PDF_TOL = {"gauss": 2.7e-13, "mvt": 3.2e-13, "unit": 2.8e-13}   # measured: 2.66e-14, 3.18e-14, 2.71e-14 (all case E, plain density; logs <= 2.31e-14)
+GRAD_TOL = 1.9e-13         # measured: 1.85e-14 (case E, plain density)
+XORIG_TOL = 8.9e-15        # measured: 8.88e-16 (cases C, D, E)
+MOM_TOL = 1.2e-14          # measured: 1.11e-15 (case B covariance; means <= 6.5e-16)
+KL_TOL = 9.8e-15           # measured: 9.79e-16 (case D, Ns = 70 000; <= 2.1e-16 at Ns = 1003)
+BIG = 70000
+SEED = 20240607
+
+
+@pytest.fixture(scope="module")
+def V():
+    from vbmc_amd import vptools
+
+    return vptools
+
+
+_cache = {}
+
+
+def drawn(V, name, N=65, balanced=True, seed=SEED):
+    """The restatement's draws of a case on the dumped block (computed once, never changed)"""
+    key = (name, N, balanced, seed)
+    if key not in _cache:
+        vp = T.make_case(name)
+        B, perm = V.vp_rnd_rng_dump(seed, N, vp["D"], vp["w"], balanced)
+        X, I, Y = T.rnd(vp, N, True, balanced, B, seed)
+        for a in (B, perm, X, I, Y):
+            a.setflags(write=False)
+        _cache[key] = (vp, B, perm, X, I, Y)
+    return _cache[key]
+
+
+def dev_log(dev, ref, tol, what):
+    fin = np.isfinite(ref)
+    assert np.array_equal(dev[~fin], ref[~fin]), (what, dev[~fin], ref[~fin])
+    err = float(np.max(np.abs(dev[fin] - ref[fin]) / np.maximum(1.0, np.abs(ref[fin])))) if fin.any() else 0.0
+    print("VPT-MEASURE %s %.3e" % (what, err))
+    assert err <= tol, (what, err)
+
+
+def dev_plain(dev, ref, tol, what):
+    nz = ref != 0
+    assert np.array_equal(dev[~nz], ref[~nz]), (what, dev[~nz])
+    err = float(np.max(np.abs(dev[nz] - ref[nz]) / np.abs(ref[nz]))) if nz.any() else 0.0
+    print("VPT-MEASURE %s %.3e" % (what, err))
+    assert err <= tol, (what, err)
+
+
+@pytest.mark.parametrize("name", list(T.CASES))
+def test_pdf_against_the_restatement(V, name):
+    vp, _, _, X, _, Y = drawn(V, name)
+    far = T.far_point(vp)
+    Xo = np.vstack([X, far])
+    Yt = np.vstack([Y, T.warp(far, "d", vp["trinfo"])])
+    for logflag in (True, False):
+        cmp = dev_log if logflag else dev_plain
+        tag = "%s log=%d" % (name, logflag)
+        ref = T.pdf(vp, Xo, True, logflag)
+        assert (np.isinf(ref[-1]) and ref[-1] < 0) if logflag else ref[-1] == 0          # the far point, and only it
+        assert np.all(np.isfinite(ref[:-1])) and (logflag or np.all(ref[:-1] > 0))
+        cmp(V.vbmc_pdf(vp, Xo, True, logflag), ref, PDF_TOL["gauss"], "pdf gauss orig " + tag)
+        cmp(V.vbmc_pdf(vp, Yt, False, logflag), T.pdf(vp, Yt, False, logflag), PDF_TOL["gauss"], "pdf gauss trans " + tag)
+        cmp(V.vbmc_pdf(vp, Yt, True, logflag, True), T.pdf(vp, Yt, True, logflag, True), PDF_TOL["gauss"], "pdf gauss transflag " + tag)
+        for fam, df in (("mvt", 5.0), ("unit", -5.0)):
+            cmp(V.vbmc_pdf(vp, Xo, True, logflag, False, df), T.pdf(vp, Xo, True, logflag, False, df), PDF_TOL[fam], "pdf %s orig %s" % (fam, tag))
+            cmp(V.vbmc_pdf(vp, Yt, False, logflag, False, df), T.pdf(vp, Yt, False, logflag, False, df), PDF_TOL[fam], "pdf %s trans %s" % (fam, tag))
+        # the gradient: transformed space, at the drawn points (at the far point the reference divides 0 by 0)
+        y, dy = V.vbmc_pdf(vp, Y, False, logflag, nargout=2)
+        ry, rdy = T.pdf(vp, Y, False, logflag, grad=True)
+        cmp(y, ry, PDF_TOL["gauss"], "pdf grad-call value " + tag)
+        err = float(np.max(np.abs(dy - rdy) / np.max(np.abs(rdy), axis=1, keepdims=True)))
+        print("VPT-MEASURE pdf gradient %s %.3e" % (tag, err))
+        assert err <= GRAD_TOL, (tag, err)
+
+
+@pytest.mark.parametrize("N", T.POINT_COUNTS + (300,))
+def test_pdf_point_counts(V, N):
+    vp, _, _, X, _, _ = drawn(V, "B", 1003)
+    X = X[:N]
+    dev_log(V.vbmc_pdf(vp, X, True, True), T.pdf(vp, X, True, True), PDF_TOL["gauss"], "pdf counts N=%d" % N)
+
+
+def check_rnd(V, name, N, balanced):
+    vp, B, perm, X, I, Y = drawn(V, name, N, balanced)
+    tag = "%s N=%d bal=%d" % (name, N, balanced)
+    Xd, Id = V.vbmc_rnd(vp, N, True, balanced, seed=SEED)
+    Xr, Ir = V.vbmc_rnd(vp, N, True, balanced, seed=SEED + 99, block=B)                    # the block decides, not the seed's draws ...
+    if not balanced:                                                                       # (... the permutation stays the seed's)
+        assert np.array_equal(Xd, Xr) and np.array_equal(Id, Ir), tag
+    Xr, Ir = V.vbmc_rnd(vp, N, True, balanced, seed=SEED, block=B)
+    assert np.array_equal(Xd, Xr) and np.array_equal(Id, Ir), tag
+    assert np.array_equal(Id, I), tag
+    Yd, Iy = V.vbmc_rnd(vp, N, False, balanced, seed=SEED)
+    assert np.array_equal(Iy, I) and np.array_equal(Yd, Y), tag
+    err = float(np.max(np.abs(Xd - X) / np.maximum(1.0, np.abs(X))))
+    print("VPT-MEASURE rnd orig %s %.3e" % (tag, err))
+    assert err <= XORIG_TOL, (tag, err)
+    if vp["trinfo"]:
+        lo, hi = T.clamp_ends(vp["trinfo"])
+        assert np.all(Xd >= lo) and np.all(Xd <= hi), tag
+    if balanced:
+        w, K = np.ravel(vp["w"]), int(vp["K"])
+        I_all, _ = T.split(w, N, True, B[:, 0])
+        counts, full = np.bincount(Id, minlength=K), np.bincount(I_all, minlength=K)
+        assert len(set(perm.tolist())) == N and perm.min() >= 0 and perm.max() < I_all.size, tag
+        assert np.all(counts <= full) and counts.sum() == N and np.all(full >= np.floor(w * N)), tag
+        if I_all.size == N:
+            assert np.array_equal(counts, full), tag
+
+
+@pytest.mark.parametrize("name", list(T.CASES))
+@pytest.mark.parametrize("balanced", [False, True])
+def test_rnd_cases(V, name, balanced):
+    check_rnd(V, name, 1003, balanced)
+
+
+@pytest.mark.parametrize("N", (1, 63, 64, 65, BIG))
+def test_rnd_point_counts(V, N):
+    check_rnd(V, "B", N, True)
+    check_rnd(V, "C", N, False)
+
+
+def check_moments(V, vp, Ns, tag):
+    mu, S = V.vbmc_moments(vp, True, Ns, seed=SEED)
+    mu2, S2 = V.vbmc_moments(vp, True, Ns, seed=SEED)
+    assert np.array_equal(mu, mu2) and np.array_equal(S, S2), tag                          # determinism
+    X = V.vbmc_rnd(vp, Ns, True, True, seed=SEED, nargout=1)
+    rm, rS = T.moments(X)
+    sd = np.sqrt(np.diag(rS))
+    e1, e2 = float(np.max(np.abs(mu - rm) / sd)), float(np.max(np.abs(S - rS) / np.outer(sd, sd)))
+    print("VPT-MEASURE moments %s mean %.3e cov %.3e" % (tag, e1, e2))
+    assert e1 <= MOM_TOL and e2 <= MOM_TOL, (tag, e1, e2)
+    assert np.array_equal(S, S.T), tag
+
+
+@pytest.mark.parametrize("name", list(T.CASES))
+def test_moments_equal_the_composition(V, name):
+    check_moments(V, T.make_case(name), 1003, name + " Ns=1003")
+
+
+def test_moments_many_partials(V):
+    check_moments(V, T.make_case("D"), BIG, "D Ns=%d" % BIG)
+    check_moments(V, T.make_case("B"), 2, "B Ns=2")
+
+
+def check_kldiv(V, vp1, vp2, Ns, tag, against_ref=True):
+    kls, xx1, xx2 = V.vbmc_kldiv(vp1, vp2, Ns, seed=SEED, nargout=3)
+    again = V.vbmc_kldiv(vp1, vp2, Ns, seed=SEED)
+    assert np.array_equal(kls, again), tag
+    assert np.array_equal(kls, V.vbmc_kldiv(vp1, vp2, Ns, seed=SEED, nargout=2)[0]), tag   # with and without the samples written
+    assert np.array_equal(xx1, V.vbmc_rnd(vp1, Ns, True, True, seed=SEED, nargout=1)), tag
+    assert np.array_equal(xx2, V.vbmc_rnd(vp2, Ns, True, True, seed=SEED + 1, nargout=1)), tag
+    MINP = np.finfo(np.float64).tiny
+    comp, share = [], []
+    for own, oth, xx in ((vp1, vp2, xx1), (vp2, vp1, xx2)):
+        qo, qt = V.vbmc_pdf(own, xx, True), V.vbmc_pdf(oth, xx, True)
+        qo = np.where((qo == 0) | ~np.isfinite(qo), 1.0, qo)
+        fl = (qt == 0) | ~np.isfinite(qt)
+        qt = np.where(fl, MINP, qt)
+        comp.append(max(-np.mean(np.log(qt) - np.log(qo)), 0.0))
+        share.append(float(np.mean(fl)))
+    comp = np.array(comp)
+    err = float(np.max(np.abs(kls - comp) / np.maximum(1.0, np.abs(comp))))
+    print("VPT-MEASURE kldiv %s %.3e kls %s floor shares %s" % (tag, err, kls, share))
+    assert err <= KL_TOL, (tag, err, kls, comp)
+    if against_ref:                                                                       # and the restatement on the same draws
+        ref, _ = T.kldiv_terms(vp1, vp2, xx1, xx2)
+        assert np.allclose(kls, ref, rtol=1e-9, atol=1e-9), (tag, kls, ref)
+    return share
+
+
+@pytest.mark.parametrize("name", list(T.CASES))
+def test_kldiv_equals_the_composition(V, name):
+    vp1 = T.make_case(name)
+    check_kldiv(V, vp1, T.sibling(vp1, 2), 1003, name + " Ns=1003")                        # (B .. F: two different trinfo, equal bounds)
+
+
+def test_kldiv_floor_rule_and_many_partials(V):
+    vp1 = T.make_case(T.NARROW["case"])
+    share = check_kldiv(V, vp1, T.sibling(vp1, 3, T.NARROW["width"], same_mu=True), 1003, "narrow", against_ref=False)   # (densities next to
+    # the smallest double carry a few bits: there the restatement's logarithms are not a reference for the fused sum)
+    assert 0.01 <= share[0] <= 0.20, share
+    vpd = T.make_case("D")
+    check_kldiv(V, vpd, T.sibling(vpd, 2), BIG, "D Ns=%d" % BIG)
+
+
+def test_moments_statistical_sanity(V):
+    """Ns = 65 536 on case D with an identity transform: within 6 standard errors of the analytic vbmc_moments(vp, 0)"""
+    vp = dict(T.make_case("D"), trinfo=None)
+    Ns = 65536
+    mu, S = V.vbmc_moments(vp, True, Ns, seed=SEED)
+    am, aS = V.vbmc_moments(vp, False)
+    rm, rS = T.moments_analytic(vp)
+    assert np.allclose(am, rm) and np.allclose(aS, rS)
+    sd = np.sqrt(np.diag(aS))
+    assert np.all(np.abs(mu - am) <= 6 * sd / np.sqrt(Ns)), np.max(np.abs(mu - am) / (sd / np.sqrt(Ns)))
+    # standard error of a covariance entry from the sample's own fourth moments
+    X = V.vbmc_rnd(vp, Ns, True, True, seed=SEED, nargout=1)
+    Xc = X - X.mean(axis=0)
+    se = np.sqrt(np.maximum(np.einsum("ni,nj->ij", Xc ** 2, Xc ** 2) / Ns - (Xc.T @ Xc / Ns) ** 2, 0.0) / Ns)
+    assert np.all(np.abs(S - aS) <= 6 * se), np.max(np.abs(S - aS) / se)
+
+
+def test_refusals_leave_the_context_usable(V):
+    import vbmc_amd
+
+    vp = T.make_case("B")
+    X = drawn(V, "B")[3]
+    ok = V.vbmc_pdf(vp, X, True, True)
+    bad = dict(vp, trinfo=dict(vp["trinfo"], type=np.array([0, 1, 12, 3])))
+    big = T.make_vp(33, 2, None, False)
+    other = dict(vp, trinfo=dict(vp["trinfo"], ub_orig=np.asarray(vp["trinfo"]["ub_orig"]) + 1.0))
+    calls = [lambda: V.vbmc_pdf(bad, X, True, True), lambda: V.vbmc_rnd(bad, 10), lambda: V.vbmc_moments(bad, True, 100),
+             lambda: V.vbmc_rnd(vp, 10, True, False, 5.0), lambda: V.vbmc_rnd(vp, 10, True, "gp"),
+             lambda: V.vbmc_pdf(vp, X, True, True, nargout=2), lambda: V.vbmc_pdf(vp, X, True, False, nargout=2),
+             lambda: V.vbmc_pdf(vp, X, False, True, False, 5.0, nargout=2),
+             lambda: V.vbmc_kldiv(vp, other, 100), lambda: V.vbmc_pdf(big, np.zeros((3, 33))), lambda: V.vbmc_rnd(big, 10)]
+    for i, f in enumerate(calls):
+        with pytest.raises(vbmc_amd.VbmcUnsupported):
+            f()
+        assert np.array_equal(V.vbmc_pdf(vp, X, True, True), ok), i

@@ -17,3 +17,5 @@ from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, ac
                   ensemble_slice_sample, importance_sample_device, importance_sample_rng_dump, vbmc_moments, vbmc_rnd)
 from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
                        vpsieve_vbmc)
+from . import vptools  # noqa: F401,E402
+from .vptools import vp_rnd_rng_dump, warpvars  # noqa: F401,E402

@@ -171,6 +171,17 @@ class IsSetupArgs(C.Structure):
     ]
 
 
+class VpDesc(C.Structure):
+    """vbmc_vp_desc (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("D", C.c_int32), ("K", C.c_int32),
+        ("mu", _dp), ("sigma", _dp), ("lambda", _dp), ("w", _dp),
+        ("type", C.POINTER(C.c_int32)),
+        ("lb", _dp), ("ub", _dp), ("tmu", _dp), ("tdelta", _dp), ("scale", _dp), ("R", _dp),
+    ]
+
+
 _lib = None
 
 
@@ -243,6 +254,12 @@ def load():
     lib.vbmc_acq_is_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_acq_is_setup.argtypes = [vp, vp, C.POINTER(IsSetupArgs)]
     lib.vbmc_acq_is_setup_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
+    vpd = C.POINTER(VpDesc)
+    lib.vbmc_vp_pdf.argtypes = [vp, vpd, C.c_int64, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp]
+    lib.vbmc_vp_rnd.argtypes = [vp, vpd, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, _dp, _dp, C.POINTER(C.c_int32)]
+    lib.vbmc_vp_moments.argtypes = [vp, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp]
+    lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
+    lib.vbmc_vp_rnd_rng_dump.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)

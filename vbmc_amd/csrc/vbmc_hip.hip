@@ -5,4 +5,5 @@
 #include "abi_acq_search.hip"
 #include "abi_is_sample.hip"
 #include "abi_is_setup.hip"
+#include "abi_vp_tools.hip"
 #include "abi_comm.hip"
