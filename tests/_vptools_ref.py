@@ -274,7 +274,23 @@ CASES = {   # name: (D, K, transform types or None, scale + rotation)
     "D": (10, 50, [0, 3] * 5, False),
     "E": (32, 72, [3] * 16 + [0] * 16, False),
     "F": (2, 512, [0, 3], False),
+    # every padded width DT and, for DT >= 8, a component count past the chunk of 2048 / DT (tests/test_vptools_restatement.py asserts both)
+    "G": (5, 3, [3, 0, 1, 2, 3], True),                       # DT = 8 partly filled, a rotation with padding
+    "H": (8, 257, [0, 3] * 4, False),                         # DT = 8 full, chunks 256 + 1
+    "I": (12, 171, [3] * 6 + [0] * 6, True),                  # DT = 12 full with a rotation, chunks 170 + 1
+    "J": (13, 4, [d % 4 for d in range(13)], True),           # DT = 16 partly filled
+    "K": (16, 129, [0, 3] * 8, True),                         # DT = 16 full with a rotation, chunks 128 + 1
+    "L": (17, 5, [(d + 1) % 4 for d in range(17)], True),     # DT = 24 partly filled
+    "M": (24, 171, [0, 3] * 12, False),                       # DT = 24 full, chunks 85 + 85 + 1
+    "N": (25, 2, [(d + 2) % 4 for d in range(25)], True),     # DT = 32 partly filled: a 25 x 25 rotation in a 32 x 32 block
+    "O": (32, 512, [3] * 16 + [0] * 16, True),                # both limits: eight chunks of 64, the rotation at the largest LDS footprint
 }
+PADDED_WIDTHS = (4, 8, 12, 16, 24, 32)   # vpt_pick_dt (vbmc_amd/csrc/abi_vp_tools.hip): the smallest of these that holds D
+CHUNK_DOUBLES = 2048                     # VPT_CHUNK (vbmc_amd/csrc/vp_tools_kernels.h): 2048 / DT components are staged at a time
+
+
+def padded_width(D):
+    return next(dt for dt in PADDED_WIDTHS if D <= dt)
 POINT_COUNTS = (1, 63, 64, 65, 1003)
 
 
@@ -303,6 +319,100 @@ def make_vp(D, K, types, rot, seed=1, width=1.0):
             tr["scale"] = np.exp(r.normal(0, .2, D))
         vp["trinfo"] = tr
     return vp
+
+
+# ---- small posteriors for the transform's edges (tests/test_gpu_vptools_edges.py): no rotation, so that a row differs from an
+# ordinary one in exactly one transformed coordinate; a wide component (sigma = 8) sits where the edge rows land, so that the density
+# there is finite and depends on the transformed coordinate
+def make_zero_bounds():
+    """D = 3, K = 3: a type-1 variable with lb_orig = 0, a type-2 variable with ub_orig = 0 (only next to a bound at 0 does
+    x - a become subnormal), a type-0 variable; wide components at log(x - a) = -725 and at log(b - x) = -725"""
+    inf = np.inf
+    tr = dict(lb_orig=np.array([0.0, -inf, -inf]), ub_orig=np.array([inf, 0.0, inf]), type=np.array([1, 2, 0]), mu=np.array([0.0, 0.0, 0.3]),
+              delta=np.array([1.0, 1.0, 1.2]), scale=None, R_mat=None)
+    vp = dict(D=3, K=3, mu=np.array([[-0.5, -725.0, 0.0], [0.2, 0.0, -725.0], [0.1, 0.0, 0.0]]), sigma=np.array([0.5, 8.0, 8.0]),
+              w=np.array([0.5, 0.25, 0.25]), trinfo=tr)
+    vp["lambda"] = np.array([1.0, 1.1, 0.9])
+    return vp
+
+
+def make_logit():
+    """D = 2, K = 3: a logit variable on (-1, 3) and a type-0 variable; wide components at logit z = 0.2, 725 and 1e4"""
+    tr = dict(lb_orig=np.array([-1.0, -np.inf]), ub_orig=np.array([3.0, np.inf]), type=np.array([3, 0]), mu=np.array([0.2, -0.1]),
+              delta=np.array([1.3, 0.8]), scale=None, R_mat=None)
+    vp = dict(D=2, K=3, mu=np.array([[0.0, (725.0 - 0.2) / 1.3, (1e4 - 0.2) / 1.3], [-0.2, 0.0, 0.0]]), sigma=np.array([8.0, 8.0, 8.0]),
+              w=np.array([0.5, 0.3, 0.2]), trinfo=tr)
+    vp["lambda"] = np.array([1.0, 1.0])
+    return vp
+
+
+def _rows(base, changes):
+    X = np.repeat(np.asarray(base, dtype=np.float64)[None, :], len(changes) + 1, axis=0)     # row 0 stays ordinary
+    for i, (d, v) in enumerate(changes):
+        X[i + 1, d] = v
+    return X
+
+
+def zero_bounds_rows():
+    """Original-space rows of make_zero_bounds(): (near, huge, on a bound, outside a bound); each differs from the ordinary first
+    row in one coordinate"""
+    base = [np.exp(-0.3), -np.exp(0.4), 0.5]
+    near = _rows(base, [(0, 2.0 ** -1060), (0, 2.0 ** -1030), (1, -2.0 ** -1060), (1, -2.0 ** -1030)])   # x - a resp. b - x subnormal
+    huge = _rows(base, [(2, 1e160), (2, -1e160), (2, 1e200), (2, -1e200)])                                # the squared distance overflows
+    on = _rows(base, [(0, 0.0), (1, 0.0)])
+    out = _rows(base, [(0, -0.5), (1, 0.5), (0, -2.0 ** -1060), (1, 2.0 ** -1060)])
+    return near, huge, on, out
+
+
+def logit_rows():
+    """Original-space rows of make_logit(): (z next to 0 and to 1, huge, on a bound, outside a bound)"""
+    base = [0.7, 0.4]
+    near = _rows(base, [(0, -1.0 + 2.0 ** -38), (0, -1.0 + 2.0 ** -50), (0, 3.0 - 2.0 ** -38), (0, 3.0 - 2.0 ** -50)])   # z = 2^-40, 2^-52, 1 - ...
+    huge = _rows(base, [(1, 1e160), (1, -1e160), (1, 1e200), (1, -1e200)])
+    on = _rows(base, [(0, -1.0), (0, 3.0)])
+    out = _rows(base, [(0, -1.5), (0, 3.5), (0, np.nextafter(-1.0, -2.0)), (0, np.nextafter(3.0, 4.0))])
+    return near, huge, on, out
+
+
+LOGIT_Z = (30.0, 37.0, 40.0, 700.0, 750.0, 1e4)   # 37: 1 + exp(-z) rounds to 1; 745: exp(-z) is 0
+LOGIT_Z_REF_OVERFLOWS = 709.782712893384        # below -log(realmax) the reference's exp(-z) is Inf and its log-Jacobian -Inf
+
+
+def logit_trans_rows(vp, zs):
+    """Transformed-space rows of make_logit() whose logit coordinate is z = y delta + mu for the given z (the first row ordinary)"""
+    tr = vp["trinfo"]
+    return _rows([0.3, -0.2], [(0, (z - tr["mu"][0]) / tr["delta"][0]) for z in zs])
+
+
+def make_clamp():
+    """D = 4, types 0 .. 3, components wide enough that a normal of +-1e3 takes exp() past its range in both directions"""
+    vp = make_vp(4, 3, [0, 1, 2, 3], False)
+    vp["sigma"] = np.array([1.5, 2.0, 2.5])
+    return vp
+
+
+CLAMP_ROWS = ((3, 1e3), (7, -1e3), (20, 1e3), (41, -1e3))   # output rows of vbmc_rnd whose D normals are set to the value
+
+
+def clamp_block(B, perm):
+    """The dumped block with the normals of the samples behind CLAMP_ROWS replaced"""
+    B = np.array(B)
+    for r, v in CLAMP_ROWS:
+        B[perm[r], 1:] = v
+    return B
+
+
+def make_zero_weight(which):
+    """D = 5 with the transform of case G, K = 4; the weights of ``which`` are zero (and the others sum to one)"""
+    D, K, types, rot = CASES["G"]
+    vp = make_vp(D, 4, types, rot)
+    w = np.array(vp["w"])
+    w[list(which)] = 0.0
+    vp["w"] = w / w.sum()
+    return vp
+
+
+ZERO_WEIGHTS = ((0,), (2,), (0, 1, 2))
 
 
 def make_case(name, seed=1, width=1.0):

@@ -1,9 +1,10 @@
 """GPU: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments and vbmc_vp_kldiv (vbmc_amd.vptools) against the NumPy restatement
-tests/_vptools_ref.py on the cases of that file (A .. F), at 1, 63, 64, 65 and 1003 points and at 70 000 (several workgroups, and more
-tiles than the 512 partials: some workgroups take two).
+tests/_vptools_ref.py on the cases of that file (A .. O: every padded width, and from width 8 on a mixture longer than one staged
+chunk), at 1, 63, 64, 65 and 1003 points and at 70 000 (several workgroups, and more tiles than the 512 partials: some workgroups take
+two; cases B, C and D only).  tests/test_gpu_vptools_edges.py holds the numeric edges.
 
 Tolerances.  They were not fixed in advance: each is ten times the largest deviation of the device from the restatement measured over
-these very cases (DESIGN.md section 6h lists the measurements), and sits below the project's 1e-10 for values and 1e-9 for gradients.
+cases A .. F (DESIGN.md section 6h lists the measurements), and sits below the project's 1e-10 for values and 1e-9 for gradients.
   log densities          |dev - ref| <= PDF_TOL[family] max(1, |ref|)         plain densities: the same bound relative to ref
   gradients              |dev - ref| <= GRAD_TOL max_d |ref_row|
   original-space samples |dev - ref| <= XORIG_TOL max(1, |ref|)
@@ -24,6 +25,12 @@ GRAD_TOL = 1.9e-13         # measured: 1.85e-14 (case E, plain density)
 XORIG_TOL = 8.9e-15        # measured: 8.88e-16 (cases C, D, E)
 MOM_TOL = 1.2e-14          # measured: 1.11e-15 (case B covariance; means <= 6.5e-16)
 KL_TOL = 9.8e-15           # measured: 9.79e-16 (case D, Ns = 70 000; <= 2.1e-16 at Ns = 1003)
+# Cases G .. O came after these numbers were set.  Where one exceeds them, the offending points were evaluated at 50 digits
+# (tools/gen_vptools_golden.py's functions): the bound of that case and family, in the plain form, is the larger of the number above and four times the
+# restatement's OWN largest error there (a direct sum against the device's chunked running log-sum-exp: both O(K) roundings).
+# Case N (D = 25, K = 2), the far point, plain density ~1e-80: restatement 8.49e-14 (mvt), 7.28e-14 (unit) from the 50-digit value; device
+# 2.46e-13, 2.10e-13 from it and 3.31e-13, 2.83e-13 from the restatement.
+RESTATEMENT_ERR = {("N", "mvt"): 8.492e-14, ("N", "unit"): 7.282e-14}
 BIG = 70000
 SEED = 20240607
 
@@ -49,6 +56,11 @@ def drawn(V, name, N=65, balanced=True, seed=SEED):
             a.setflags(write=False)
         _cache[key] = (vp, B, perm, X, I, Y)
     return _cache[key]
+
+
+def pdf_tol(name, fam, logflag):
+    """(the excess is in the plain density alone: the log form keeps PDF_TOL)"""
+    return PDF_TOL[fam] if logflag else max(PDF_TOL[fam], 4 * RESTATEMENT_ERR.get((name, fam), 0.0))
 
 
 def dev_log(dev, ref, tol, what):
@@ -83,8 +95,8 @@ def test_pdf_against_the_restatement(V, name):
         cmp(V.vbmc_pdf(vp, Yt, False, logflag), T.pdf(vp, Yt, False, logflag), PDF_TOL["gauss"], "pdf gauss trans " + tag)
         cmp(V.vbmc_pdf(vp, Yt, True, logflag, True), T.pdf(vp, Yt, True, logflag, True), PDF_TOL["gauss"], "pdf gauss transflag " + tag)
         for fam, df in (("mvt", 5.0), ("unit", -5.0)):
-            cmp(V.vbmc_pdf(vp, Xo, True, logflag, False, df), T.pdf(vp, Xo, True, logflag, False, df), PDF_TOL[fam], "pdf %s orig %s" % (fam, tag))
-            cmp(V.vbmc_pdf(vp, Yt, False, logflag, False, df), T.pdf(vp, Yt, False, logflag, False, df), PDF_TOL[fam], "pdf %s trans %s" % (fam, tag))
+            cmp(V.vbmc_pdf(vp, Xo, True, logflag, False, df), T.pdf(vp, Xo, True, logflag, False, df), pdf_tol(name, fam, logflag), "pdf %s orig %s" % (fam, tag))
+            cmp(V.vbmc_pdf(vp, Yt, False, logflag, False, df), T.pdf(vp, Yt, False, logflag, False, df), pdf_tol(name, fam, logflag), "pdf %s trans %s" % (fam, tag))
         # the gradient: transformed space, at the drawn points (at the far point the reference divides 0 by 0)
         y, dy = V.vbmc_pdf(vp, Y, False, logflag, nargout=2)
         ry, rdy = T.pdf(vp, Y, False, logflag, grad=True)

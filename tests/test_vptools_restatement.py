@@ -1,10 +1,11 @@
 """CPU: the NumPy restatement tests/_vptools_ref.py, which the GPU tests of the variational-posterior tools compare against, is itself
-held to 50-digit values (tests/golden/mp_vptools_case{0..3}.json, written by tools/gen_vptools_golden.py) at the golden families'
+held to 50-digit values (tests/golden/mp_vptools_case{0..5}.json, written by tools/gen_vptools_golden.py) at the golden families'
 1e-12, to closed forms (SciPy's multivariate normal, a density that integrates to one over its bounds), and to the properties of the
 balanced split.  The host mirror vbmc_amd.vptools.warpvars is held to the same fixtures.  The randomness of every GPU case keeps the
 margin from the cumulative weights that makes the component choice a matter of exact comparison, not of rounding."""
 import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -14,6 +15,7 @@ from tests import _vptools_ref as T
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-12
 SEED = 20240607      # tests/test_gpu_vptools.py
+NFIX = 6             # mp_vptools_case0 .. 5
 
 
 def load(i):
@@ -30,7 +32,7 @@ def close(a, b, what):
     assert err <= TOL, (what, err)
 
 
-@pytest.mark.parametrize("i", range(4))
+@pytest.mark.parametrize("i", range(NFIX))
 def test_restatement_against_the_fixtures(i):
     g, vp = load(i)
     X, Y, tr = np.array(g["X"]), np.array(g["Y"]), g["trinfo"]
@@ -54,9 +56,9 @@ def test_restatement_against_the_fixtures(i):
 
 def test_fixtures_cover_what_they_should():
     types, rot, dfs, grads = set(), 0, [], 0
-    for i in range(4):
+    for i in range(NFIX):
         g, _ = load(i)
-        assert g["vp"]["D"] <= 3 and g["vp"]["K"] <= 4 and len(g["X"]) <= 8
+        assert g["vp"]["D"] <= 7 and g["vp"]["K"] <= 4 and len(g["X"]) <= 8
         if g["trinfo"]:
             types |= set(g["trinfo"]["type"])
             rot += g["trinfo"]["R_mat"] is not None and g["trinfo"]["scale"] is not None
@@ -65,7 +67,7 @@ def test_fixtures_cover_what_they_should():
     assert types == {0, 1, 2, 3} and rot >= 1 and any(d > 0 for d in dfs) and any(d < 0 for d in dfs) and grads >= 1
 
 
-@pytest.mark.parametrize("i", range(4))
+@pytest.mark.parametrize("i", range(NFIX))
 def test_host_mirror_against_the_fixtures(i):
     from vbmc_amd.vptools import warpvars
 
@@ -145,6 +147,96 @@ def test_catrnd_margins_of_the_gpu_cases():
             smallest = min(smallest, T.catrnd_margin(v["w"], N, bal, B[:, 0]))
     print("smallest margin %.3e" % smallest)
     assert smallest >= 1e-9, smallest
+
+
+def test_cases_reach_every_width_and_a_chunk_seam():
+    """The GPU cases launch all six padded widths of vpt_pick_dt and, at every width from 8 on, a mixture with more components than
+    one staged chunk of 2048 / DT holds (at 4 the chunk is the largest K there is)"""
+    shapes = [(T.padded_width(D), K) for D, K, _, _ in T.CASES.values()]
+    assert {dt for dt, _ in shapes} == set(T.PADDED_WIDTHS), shapes
+    for dt in T.PADDED_WIDTHS:
+        assert dt == 4 or any(d == dt and K > T.CHUNK_DOUBLES // dt for d, K in shapes), (dt, shapes)
+    assert any(d == dt and K == T.CHUNK_DOUBLES // dt + 1 for d, K in shapes for dt in (8, 12, 16))      # a last chunk of one component
+    assert any(K > 2 * (T.CHUNK_DOUBLES // d) for d, K in shapes)                                          # three chunks or more
+    with open(os.path.join(ROOT, "vbmc_amd", "csrc", "abi_vp_tools.hip")) as f:                          # the mirrored constants
+        m = re.search(r"\bdts\s*\[\s*\]\s*=\s*\{([^}]*)\}", f.read())
+        assert m and tuple(int(v) for v in m.group(1).split(",")) == T.PADDED_WIDTHS
+    with open(os.path.join(ROOT, "vbmc_amd", "csrc", "vp_tools_kernels.h")) as f:
+        m = re.search(r"#\s*define\s+VPT_CHUNK\s+(\d+)", f.read())
+        assert m and int(m.group(1)) == T.CHUNK_DOUBLES
+
+
+def test_band_fixture_keeps_clear_of_the_threshold():
+    """tests/golden/mp_vptools_band.json: the log of the transformed-space mixture reaches its targets on both sides of log(realmin) and
+    of log(5e-324), and no stored value lies within 1e-6 of the latter; the restatement agrees where its sum is a normal number"""
+    with open(os.path.join(ROOT, "tests", "golden", "mp_vptools_band.json")) as f:
+        g = json.load(f)
+    thr = g["threshold"]
+    assert thr == -744.4400719213812 and abs(np.exp(thr) / 5e-324 - 1) < 1 and len(g["mixtures"]) == 2
+    targets = [-690, -705, -708.3, -708.5, -720, -740, -744.3, -744.6, -745.2, -760, -1000, -1e5]
+    for m in g["mixtures"]:
+        lm, lo = np.array(m["logmix_trans"]), np.array(m["logpdf_orig"])
+        assert np.max(np.abs(lm[:len(targets)] - targets)) <= 0.05 and len(m["X"]) == len(targets) + 2
+        assert np.min(np.abs(lm - thr)) > 1e-6 and np.min(np.abs(lo - thr)) > 1e-6
+        assert np.sum(lm > thr) >= 9 and np.sum(lm < thr) >= 5 and np.all(np.isfinite(lo))
+        vp = dict(m["vp"], trinfo=m["trinfo"])
+        vp["mu"] = np.array(vp["mu"])
+        normal = lm > -708.0
+        close(T.pdf(vp, np.array(m["X"]), True, True)[normal], lo[normal], "band, log pdf")
+        for df in g["dfs"]:
+            assert np.all(np.isfinite(m["heavy"][str(df)]))
+            close(T.pdf(vp, np.array(m["X"]), True, True, False, df), m["heavy"][str(df)], "band, t family df = %g" % df)
+
+
+def test_edge_rows_are_what_they_claim():
+    """The inputs of tests/test_gpu_vptools_edges.py on the restatement alone: subnormal distances from a bound, logit arguments next to 0
+    and 1, NaN on and beyond a bound; a caller block of +-1e3 normals reaches both clamp ends exactly and +Inf"""
+    from vbmc_amd.vptools import vp_rnd_rng_dump
+
+    vp = T.make_zero_bounds()
+    near, huge, on, out = T.zero_bounds_rows()
+    y = T.warp(near, "d", vp["trinfo"])
+    assert np.all(near[1:3, 0] < 2.3e-308) and np.all(near[1:3, 0] > 0) and np.all(-near[3:5, 1] < 2.3e-308) and np.all(near[3:5, 1] < 0)
+    assert np.allclose([y[1, 0], y[2, 0], y[3, 1], y[4, 1]], np.log(2.0) * np.array([-1060, -1030, -1060, -1030]), rtol=1e-15)
+    assert np.all(np.isfinite(T.pdf(vp, near, True, True)))                        # (a wide component sits there)
+    vl = T.make_logit()
+    lnear, lhuge, lon, lout = T.logit_rows()
+    tr = vl["trinfo"]
+    z = (lnear[1:, 0] - tr["lb_orig"][0]) / (tr["ub_orig"][0] - tr["lb_orig"][0])
+    assert np.array_equal(z, [2.0 ** -40, 2.0 ** -52, 1 - 2.0 ** -40, 1 - 2.0 ** -52])
+    assert np.all(np.isfinite(T.pdf(vl, lnear, True, True)))
+    for v, hg, o, ou in ((vp, huge, on, out), (vl, lhuge, lon, lout)):
+        for logflag in (True, False):
+            r = T.pdf(v, hg, True, logflag)
+            assert np.isfinite(r[0]) and np.all(r[1:] == (-np.inf if logflag else 0.0))
+            for rows in (o, ou):
+                r = T.pdf(v, rows, True, logflag)
+                assert np.isfinite(r[0]) and np.all(np.isnan(r[1:])), (rows, r)
+    Yt = T.logit_trans_rows(vl, [s * z for z in T.LOGIT_Z for s in (1.0, -1.0) if s * z > -T.LOGIT_Z_REF_OVERFLOWS])
+    zz = Yt[1:, 0] * tr["delta"][0] + tr["mu"][0]
+    assert np.sum(1.0 + np.exp(-np.abs(zz)) == 1.0) >= 8 and np.sum(np.exp(-np.abs(zz)) == 0.0) >= 2 and np.sum(np.abs(zz) > 745) >= 2
+    r = T.pdf(vl, Yt, True, True, True)
+    assert not np.any(np.isnan(r)) and np.sum(np.isfinite(r)) >= 9                 # (the wide components again)
+    # the clamp
+    vc = T.make_clamp()
+    lo, hi = T.clamp_ends(vc["trinfo"])
+    for bal in (False, True):
+        B, perm = vp_rnd_rng_dump(SEED, 65, 4, vc["w"], bal)
+        X = T.rnd(vc, 65, True, bal, T.clamp_block(B, perm), SEED)[0]
+        up, down = [r for r, v in T.CLAMP_ROWS if v > 0], [r for r, v in T.CLAMP_ROWS if v < 0]
+        assert np.all(X[up, 1] == np.inf) and np.all(X[up, 2] == -np.inf) and np.all(X[up, 3] == hi[3])
+        assert np.all(X[down, 1] == lo[1]) and np.all(X[down, 2] == hi[2]) and np.all(X[down, 3] == lo[3])
+        assert np.all(np.isfinite(X[:, 0])) and np.all(X >= lo) and np.all(X <= hi)
+        assert T.catrnd_margin(vc["w"], 65, bal, B[:, 0]) >= 1e-9
+    # zero weights: the margin of the component choice
+    for which in T.ZERO_WEIGHTS:
+        vz = T.make_zero_weight(which)
+        assert np.all(vz["w"][list(which)] == 0) and abs(vz["w"].sum() - 1) < 1e-15
+        for v, seed in ((vz, SEED), (vz, SEED + 1), (T.sibling(vz, 2), SEED + 1)):
+            for bal in (False, True):
+                B, _ = vp_rnd_rng_dump(seed, 1003, 5, v["w"], bal)
+                assert T.catrnd_margin(v["w"], 1003, bal, B[:, 0]) >= 1e-9
+                assert not np.isin(T.split(v["w"], 1003, bal, B[:, 0])[0], [k for k in range(4) if v["w"][k] == 0]).any()
 
 
 def test_narrow_case_exercises_the_floor_rule():

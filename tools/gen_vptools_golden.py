@@ -1,6 +1,12 @@
-"""Writes tests/golden/mp_vptools_case{0..3}.json: the variable transform of shared/warpvars_vbmc.m (types 0-3, scale, rotation) and
-vbmc_pdf.m's three density families evaluated with mpmath at 50 digits on tiny shapes (D <= 3, K <= 4, <= 8 points).  A generator
-of its own beside oracle/mp_golden.py; tests/test_vptools_restatement.py holds the NumPy restatement to these values.
+"""Writes tests/golden/mp_vptools_case{0..5}.json: the variable transform of shared/warpvars_vbmc.m (types 0-3, scale, rotation) and
+vbmc_pdf.m's three density families evaluated with mpmath at 50 digits on tiny shapes (D <= 7, K <= 4, <= 8 points).  A generator
+of its own beside oracle/mp_golden.py; tests/test_vptools_restatement.py holds the NumPy restatement to these values and
+tests/test_gpu_vptools_edges.py the device.
+
+And tests/golden/mp_vptools_band.json: two D = 2, K = 2 mixtures (the second with a logit transform of coordinate 2) at points on a
+ray from the heavier component's mean along coordinate 1, placed so that the log of the transformed-space mixture takes chosen values
+on both sides of log(realmin) and of log(5e-324), below which the device returns -Inf resp. 0.  No stored
+value lies within 1e-6 of log(5e-324), so that the side a point is on is never a matter of rounding.
 
     python tools/gen_vptools_golden.py
 """
@@ -17,7 +23,12 @@ CASES = [   # D, K, types, scale + rotation, points, df of the t families (None:
     dict(D=3, K=2, types=[0, 1, 2], rot=False, N=6, dfs=[], grad=True),
     dict(D=3, K=4, types=[3, 0, 3], rot=True, N=8, dfs=[], grad=False),
     dict(D=2, K=4, types=[3, 1], rot=False, N=8, dfs=[4.0, -3.0], grad=False),
+    dict(D=7, K=3, types=[3, 0, 1, 2, 3, 0, 1], rot=True, N=6, dfs=[], grad=True),      # the padded width 8 with a rotation
+    dict(D=6, K=4, types=None, rot=False, N=6, dfs=[4.0, -3.0], grad=True),
 ]
+LOG_DENORM_MIN = -744.4400719213812    # VPT_LOG_DENORM_MIN (vbmc_amd/csrc/vp_tools_kernels.h)
+BAND_TARGETS = [-690.0, -705.0, -708.3, -708.5, -720.0, -740.0, -744.3, -744.6, -745.2, -760.0, -1000.0, -1e5]
+BAND_DFS = [5.0, -5.0]
 
 
 def M(a):
@@ -161,9 +172,56 @@ def build(idx, c):
     return out
 
 
+def build_band():
+    f = lambda v: float(mp.nstr(v, 20))
+    out = dict(threshold=LOG_DENORM_MIN, dfs=BAND_DFS, mixtures=[])
+    for j in range(2):
+        # the lighter component lies behind the ray's origin: the mixture decreases along the ray
+        vp = dict(D=2, K=2, mu=[[0.4, -1.1], [-0.3, 0.6]], sigma=[0.35, 0.5], w=[0.7, 0.3])
+        vp["lambda"] = [1.1, 0.8]
+        tr = None
+        if j == 1:
+            tr = dict(lb_orig=[-np.inf, -1.0], ub_orig=[np.inf, 3.0], type=[0, 3], mu=[0.1, 0.2], delta=[0.9, 1.3], scale=None, R_mat=None)
+
+        def point(t):
+            """the original-space doubles of the ray's point at t, and what they are exactly in the transformed space"""
+            y = [mp.mpf(vp["mu"][0][0]) + t, mp.mpf(vp["mu"][1][0]) + mp.mpf("0.05")]
+            x = [float(v) for v in (y if tr is None else inverse(y, tr))]
+            xm = [mp.mpf(v) for v in x]
+            return x, (xm if tr is None else direct(xm, tr))
+
+        def logmix(t):
+            return mp.log(density(vp, point(t)[1], None)[0])
+
+        ts = [mp.findroot(lambda t: logmix(t) - target, (mp.mpf(1), mp.mpf(200)), solver="anderson", tol=1e-20) for target in BAND_TARGETS]
+        ts += [mp.mpf("0.3"), mp.mpf("-1.7")]                                  # two ordinary points
+        m = dict(vp=vp, trinfo=tr, X=[], logmix_trans=[], logjac=[], logpdf_orig=[], pdf_orig=[], heavy={str(df): [] for df in BAND_DFS})
+        for i, t in enumerate(ts):
+            x, y = point(t)
+            lm = mp.log(density(vp, y, None)[0])
+            lj = mp.mpf(0) if tr is None else logjac(y, tr)
+            if i < len(BAND_TARGETS):
+                assert abs(lm - BAND_TARGETS[i]) <= 0.05, (j, i, lm)
+            for v in (lm, lm - lj):
+                assert abs(v - LOG_DENORM_MIN) > 1e-6, (j, i, v)
+            m["X"].append(x)
+            m["logmix_trans"].append(f(lm))
+            m["logjac"].append(f(lj))
+            m["logpdf_orig"].append(f(lm - lj))
+            m["pdf_orig"].append(f(mp.exp(lm - lj)))
+            for df in BAND_DFS:
+                m["heavy"][str(df)].append(f(mp.log(density(vp, y, df)[0]) - lj))
+        out["mixtures"].append(m)
+    return out
+
+
 if __name__ == "__main__":
     for i, c in enumerate(CASES):
         path = os.path.join(ROOT, "tests", "golden", "mp_vptools_case%d.json" % i)
         with open(path, "w") as fh:
             json.dump(build(i, c), fh, indent=1)
         print("wrote", path)
+    path = os.path.join(ROOT, "tests", "golden", "mp_vptools_band.json")
+    with open(path, "w") as fh:
+        json.dump(build_band(), fh, indent=1)
+    print("wrote", path)

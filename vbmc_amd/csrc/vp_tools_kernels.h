@@ -264,9 +264,16 @@ __global__ void __launch_bounds__(VPT_T) k_vp_pdf(VptPdfArgs a) {
   double x[DT], gn[DT];
 #pragma unroll
   for (int d = 0; d < DT; ++d) x[d] = (d < D && r < N) ? a.X[(size_t)r + (size_t)N * d] : 0.0;
-  const double lo = vpt_eval<DT, GRAD>(x, a.P, S, a.origflag, a.transflag, stg + tid, s_mu, s_cst, s_is2, tab, tid, gn);
+  double lo = vpt_eval<DT, GRAD>(x, a.P, S, a.origflag, a.transflag, stg + tid, s_mu, s_cst, s_is2, tab, tid, gn);
   if (r >= N) return;
-  const double pv = vb_exp_tab<0>(fmin(lo, 800.0), tab);
+  // x now holds the scaled transformed-space point.  A NaN among its D coordinates makes every term NaN, and a NaN term drops out
+  // of the log-sum-exp through the table exponential's lower clamp: the result is NaN, as in the reference.  The padded registers do
+  // not count: an infinite coordinate times the rotation's zero padding is NaN there, and the reference has no such column.
+  bool isnan = false;
+#pragma unroll
+  for (int d = 0; d < DT; ++d) isnan = isnan || (d < D && x[d] != x[d]);
+  if (isnan) lo = __builtin_nan("");
+  const double pv = lo != lo ? lo : vb_exp_tab<0>(fmin(lo, 800.0), tab);   // (fmin drops a NaN: a point on or beyond a bound stays NaN)
   a.y[r] = a.logflag ? lo : pv;
   if (GRAD) {
 #pragma unroll
