@@ -974,6 +974,39 @@ vbmc_status vbmc_vp_moments(vbmc_ctx* ctx, const vbmc_vp_desc* vp, int64_t Ns, u
 vbmc_status vbmc_vp_kldiv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, int64_t Ns, uint64_t seed, const double* block1, const double* block2, double* kls, double* xx1, double* xx2);
 vbmc_status vbmc_vp_rnd_rng_dump(uint64_t seed, int64_t N, int D, int K, int balanceflag, const double* w, double* B, int64_t* perm);
 
+/*
+ * vbmc_vp_mtv: the marginal total variation distances of vbmc_mtv.m between two posteriors (an addition, backward compatible:
+ * VBMC_ABI_VERSION is unchanged).  Ns balanced draws of each posterior in the original space -- vp1 with (seed, block1), vp2 with
+ * (seed + 1, block2), exactly vbmc_vp_rnd's rows, held on the device (more than 1 GiB per posterior: VBMC_ERR_UNSUPPORTED) --; per
+ * posterior and dimension the mesh bounds of vbmc_mtv.m:55-63 (lb / ub of the two posteriors may differ), shared/kde1d.m on nkde mesh
+ * points (binning, cosine transform, the root of fixed_point inside the bracket of root(), inverse transform) and the normalisation of
+ * vbmc_mtv.m:68; per dimension 0.5 qtrapz |s1 - s2| over nquad points of each of the three segments between the four sorted mesh
+ * ends, s1 / s2 the not-a-knot cubic splines through the two densities (0 outside their own mesh).  The unique count of kde1d.m:46
+ * is Ns - max(0, c_lo - 1) - max(0, c_hi - 1), c_lo / c_hi the draws that sit on the column's clamp ends lb + eps(lb), ub - eps(ub).
+ * A column of the draws whose range is zero or not finite gives NaN in that dimension alone.  A column that reaches the reference's
+ * fminbnd branch (no bracket below 0.1, kde1d.m:136-138) answers VBMC_ERR_UNSUPPORTED, as does whatever vbmc_vp_rnd refuses; sample
+ * matrices in place of a posterior (vbmc_mtv.m:35-38) are not part of the ABI.  Column c = p D + d is posterior p (0, 1), dimension d.
+ * Every output pointer may be NULL.  Results are identical from run to run.
+ */
+typedef struct vbmc_mtv_args {
+  uint32_t struct_size;
+  int32_t nkde;           /* 0: 8192; else a power of two in 256 .. 16384 (vbmc_mtv.m:51) */
+  int32_t nquad;          /* 0: 100000; else 2 .. 2^20 (vbmc_mtv.m:76) */
+  int64_t Ns;             /* >= 2 */
+  uint64_t seed;
+  const double* block1;   /* NULL, or vbmc_vp_rnd_rng_dump's block for (seed, vp1) */
+  const double* block2;   /* NULL, or the block for (seed + 1, vp2) */
+  double* mtv;            /* D */
+  double* xx1;            /* Ns x D column-major */
+  double* xx2;            /* Ns x D column-major */
+  double* mesh;           /* 2 x D x 2: MIN, MAX of column c at [2 c], [2 c + 1] */
+  int32_t* counts;        /* 2 x D x nkde: column c at [c nkde ..] */
+  int64_t* nuniq;         /* 2 x D */
+  double* tstar;          /* 2 x D: the root t* of kde1d.m:53 */
+  double* density;        /* 2 x D x nkde: the normalised densities of vbmc_mtv.m:68, :71 */
+} vbmc_mtv_args;
+vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, const vbmc_mtv_args* args);
+
 #ifdef __cplusplus
 }
 #endif

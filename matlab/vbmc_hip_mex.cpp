@@ -47,6 +47,7 @@
 //     [X,I] = vbmc_hip_mex('vp_rnd', vp, N, origflag, balanceflag, df, seed)          (vbmc_rnd, I counted from 0: vbmc_vp_rnd, matlab/vbmc_hip_rnd.m)
 //     [mubar,Sigma] = vbmc_hip_mex('vp_moments', vp, Ns, seed)                        (vbmc_moments(vp,1,Ns): vbmc_vp_moments, matlab/vbmc_hip_moments.m)
 //     [kls,xx1,xx2] = vbmc_hip_mex('vp_kldiv', vp1, vp2, Ns, seed)                    (vbmc_kldiv(vp1,vp2,Ns,0): vbmc_vp_kldiv, matlab/vbmc_hip_kldiv.m)
+//     [mtv,xx1,xx2] = vbmc_hip_mex('vp_mtv', vp1, vp2, Ns, seed)                      (vbmc_mtv(vp1,vp2,Ns): vbmc_vp_mtv, matlab/vbmc_hip_mtv.m)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
 //     [samples,logp,widths,counts] = vbmc_hip_mex('slice_sample', X, y, s2, meanfun, noisefun, prior /*struct mu, sigma, df or []*/, LB, UB,
@@ -219,7 +220,7 @@ static void read_gp(const mxArray* gp, GpArrays& g) {
 }
 
 // vp struct with its trinfo (shared/warpvars_vbmc.m: lb_orig, ub_orig, type, mu, delta, scale, R_mat; empty: the identity) -> vbmc_vp_desc
-// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv').  The arrays stay MATLAB's; only the types are converted to int32.
+// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv', 'vp_mtv').  The arrays stay MATLAB's; only the types are converted to int32.
 static int fill_vp_desc(vbmc_vp_desc& d, const mxArray* vp, std::vector<int32_t>& types) {
   memset(&d, 0, sizeof d);
   d.struct_size = sizeof d;
@@ -849,6 +850,31 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     if (x2) plhs[2] = x2;
     vbmc_status st = vbmc_vp_kldiv(g_ctx, &d1, &d2, (int64_t)Ns, (uint64_t)mxGetScalar(prhs[4]), nullptr, nullptr, mxGetDoubles(plhs[0]), x1 ? mxGetDoubles(x1) : nullptr,
                                    x2 ? mxGetDoubles(x2) : nullptr);
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+
+  if (!strcmp(cmd, "vp_mtv")) {      // [mtv,xx1,xx2] = vbmc_mtv(vp1,vp2,Ns) with the library's draws for seed: vbmc_vp_mtv
+    if (nrhs < 5) return raise("vbmc_hip:usage", "vp_mtv: vp1, vp2, Ns, seed");
+    vbmc_vp_desc d1, d2;
+    std::vector<int32_t> t1, t2;
+    if (fill_vp_desc(d1, prhs[1], t1) || fill_vp_desc(d2, prhs[2], t2)) return 1;
+    const double n = mxGetScalar(prhs[3]);
+    if (!(n >= 1)) return raise("vbmc_hip:usage", "vp_mtv: Ns must be positive");
+    const mwSize Ns = (mwSize)n;
+    plhs[0] = mxCreateDoubleMatrix(1, d1.D, mxREAL);
+    mxArray *x1 = nlhs > 1 ? mxCreateDoubleMatrix(Ns, d1.D, mxREAL) : nullptr, *x2 = nlhs > 2 ? mxCreateDoubleMatrix(Ns, d1.D, mxREAL) : nullptr;
+    if (x1) plhs[1] = x1;
+    if (x2) plhs[2] = x2;
+    vbmc_mtv_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.Ns = (int64_t)Ns;
+    a.seed = (uint64_t)mxGetScalar(prhs[4]);
+    a.mtv = mxGetDoubles(plhs[0]);
+    a.xx1 = x1 ? mxGetDoubles(x1) : nullptr;
+    a.xx2 = x2 ? mxGetDoubles(x2) : nullptr;
+    vbmc_status st = vbmc_vp_mtv(g_ctx, &d1, &d2, &a);
     if (st != VBMC_OK) return fail(st);
     return 0;
   }

@@ -5,6 +5,7 @@ transform types alternating 0 / 3 -- in one process:
     vbmc_rnd      3 10^5 draws    (with the copy to the host) against the restatement
     vbmc_moments  10^6 draws      against the restatement and against this library's own vbmc_rnd + host cov
     vbmc_kldiv    10^5 draws      against the restatement and against this library's own vbmc_rnd + vbmc_pdf
+    vbmc_mtv      10^5 draws      the whole device call against two vbmc_rnd calls + the NumPy restatement (tests/_mtv_ref.py) on the host
     transformed-space pdf / rnd   against the host forms the package had before (acq._vbmc_lnpdf, acq.vbmc_rnd)
 
 The host legs are the NumPy restatement (tests/_vptools_ref.py), not MATLAB.  Every timing is a host clock around a call that ends
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--Nrnd", type=int, default=300000)
     ap.add_argument("--Nmom", type=int, default=1000000)
     ap.add_argument("--Nkl", type=int, default=100000)
+    ap.add_argument("--Nmtv", type=int, default=100000)
+    ap.add_argument("--only-mtv", action="store_true", help="the vbmc_mtv leg alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -64,6 +67,23 @@ def main():
     D, K = vp["D"], vp["K"]
     res = {"shape": {"D": D, "K": K, "types": "alternating 0 / 3"}, "host_label": "NumPy restatement, not MATLAB"}
     seed = 1
+
+    def composed_mtv():
+        from tests import _mtv_ref as M
+
+        x1 = V.vbmc_rnd(vp, a.Nmtv, True, True, seed=seed, nargout=1)
+        x2 = V.vbmc_rnd(vp2, a.Nmtv, True, True, seed=seed + 1, nargout=1)
+        return M.mtv(x1, x2, *M.bounds_of(vp, D), *M.bounds_of(vp2, D))[0]
+
+    res["mtv_device"] = clock(lambda: V.vbmc_mtv(vp, vp2, a.Nmtv, seed=seed), a.reps, a.warmup, sync)
+    res["mtv_rnd_plus_host_restatement"] = clock(composed_mtv, a.host_reps, 0, nosync)
+    res["mtv_max_abs_difference"] = float(np.max(np.abs(V.vbmc_mtv(vp, vp2, a.Nmtv, seed=seed) - composed_mtv())))
+    if a.only_mtv:
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     X = V.vbmc_rnd(vp, a.Npdf, True, True, seed=seed, nargout=1)
     Y = V.vbmc_rnd(vp, a.Npdf, False, True, seed=seed, nargout=1)

@@ -182,6 +182,21 @@ class VpDesc(C.Structure):
     ]
 
 
+class MtvArgs(C.Structure):
+    """vbmc_mtv_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nkde", C.c_int32), ("nquad", C.c_int32),
+        ("Ns", C.c_int64),
+        ("seed", C.c_uint64),
+        ("block1", _dp), ("block2", _dp),
+        ("mtv", _dp), ("xx1", _dp), ("xx2", _dp), ("mesh", _dp),
+        ("counts", C.POINTER(C.c_int32)),
+        ("nuniq", C.POINTER(C.c_int64)),
+        ("tstar", _dp), ("density", _dp),
+    ]
+
+
 _lib = None
 
 
@@ -259,6 +274,7 @@ def load():
     lib.vbmc_vp_rnd.argtypes = [vp, vpd, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, _dp, _dp, C.POINTER(C.c_int32)]
     lib.vbmc_vp_moments.argtypes = [vp, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp]
     lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
+    lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
     lib.vbmc_vp_rnd_rng_dump.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
     lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]

@@ -1,5 +1,6 @@
-"""The variational posterior in the caller's own parameter space: vbmc_pdf, vbmc_rnd, vbmc_moments and vbmc_kldiv with the variable
-transform of shared/warpvars_vbmc.m on the device (include/vbmc_hip.h: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments, vbmc_vp_kldiv).
+"""The variational posterior in the caller's own parameter space: vbmc_pdf, vbmc_rnd, vbmc_moments, vbmc_kldiv and vbmc_mtv with the
+variable transform of shared/warpvars_vbmc.m on the device (include/vbmc_hip.h: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments,
+vbmc_vp_kldiv, vbmc_vp_mtv).
 
 ``vp["trinfo"]`` is a dict with the reference's field names (lb_orig, ub_orig, type, mu, delta and, optionally, scale and R_mat), or
 None / empty for the identity.  Transform types 0 .. 3 are accelerated; anything else raises VbmcUnsupported, on which a caller falls
@@ -256,3 +257,40 @@ def vbmc_kldiv(vp1, vp2, Ns=1e5, gaussflag=False, *, seed=0, block1=None, block2
     B1, B2 = _block(block1), _block(block2)
     ctx.check(ctx.lib.vbmc_vp_kldiv(ctx.h, d1.ref(), d2.ref(), Ns, C.c_uint64(int(seed)), ptr(B1), ptr(B2), ptr(kls), ptr(xx1), ptr(xx2)))
     return (kls, xx1, xx2) if nargout > 1 else kls
+
+
+def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, nquad=None, nargout=1, stages=False, engine=None):
+    """[mtv,xx1,xx2] = vbmc_mtv(vp1,vp2,Ns) on the device in one call: Ns balanced draws of each posterior (vp2 with seed + 1), Botev's
+    kde1d on nkde (default 2^13) mesh points per posterior and dimension, 0.5 * integral |p1 - p2| over nquad (default 1e5) points of
+    each of the three segments.  Sample matrices in place of a posterior are the reference's business (ValueError).  stages=True
+    appends a dict with mesh (2, D, 2: MIN, MAX), counts (2, D, nkde), nuniq (2, D), tstar (2, D) and density (2, D, nkde)."""
+    if not (isinstance(vp1, dict) and isinstance(vp2, dict)):
+        raise ValueError("vbmc_mtv: vp1 and vp2 need to be variational posteriors (sample matrices are not accelerated)")
+    engine = _engine(engine)
+    ctx = engine.ctx
+    d1, d2 = _Desc(vp1), _Desc(vp2)
+    Ns, D = int(Ns), d1.D
+    n = 8192 if not nkde else int(nkde)
+    a = _lib.MtvArgs()
+    a.struct_size = C.sizeof(_lib.MtvArgs)
+    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & (2 ** 64 - 1)
+    B1, B2 = _block(block1), _block(block2)
+    a.block1, a.block2 = ptr(B1), ptr(B2)
+    mtv = np.zeros(D, dtype=np.float64)
+    a.mtv = ptr(mtv)
+    rows = max(Ns, 0)
+    xx1 = np.zeros((rows, D), dtype=np.float64, order="F") if nargout > 1 else None
+    xx2 = np.zeros((rows, D), dtype=np.float64, order="F") if nargout > 2 else None
+    a.xx1, a.xx2 = ptr(xx1), ptr(xx2)
+    st = None
+    if stages and 256 <= n <= 16384:
+        st = {"mesh": np.zeros((2, D, 2)), "counts": np.zeros((2, D, n), dtype=np.int32), "nuniq": np.zeros((2, D), dtype=np.int64),
+              "tstar": np.zeros((2, D)), "density": np.zeros((2, D, n))}
+        a.mesh, a.tstar, a.density = ptr(st["mesh"]), ptr(st["tstar"]), ptr(st["density"])
+        a.counts = st["counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        a.nuniq = st["nuniq"].ctypes.data_as(C.POINTER(C.c_int64))
+    ctx.check(ctx.lib.vbmc_vp_mtv(ctx.h, d1.ref(), d2.ref(), C.byref(a)))
+    out = (mtv, xx1, xx2)[: max(1, min(int(nargout), 3))]
+    if stages:
+        out = out + (st,)
+    return out if len(out) > 1 else out[0]
