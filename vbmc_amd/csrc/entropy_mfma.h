@@ -92,6 +92,34 @@ constexpr bool ent_c2_for(int KT, int QS, int TL, int HV) {
   return QS != 5;
 }
 constexpr bool ent_gp2_for(int KT, int QS, int TL, int HV) { return !(HV == 1 && KT == 1 && TL == 0 && QS <= 3); }
+//  SL   the PV output in the SAMPLE layout -- single-wave gradient kernels at D <= 10 (QS <= 3: D + 2 <= 12, one column block).  The A and B
+//       operand layouts of the 16x16x4 MFMA mirror each other (A: [i = lane & 15][k = lane >> 4], B: [k = lane >> 4][j = lane & 15]), so
+//       the PV MFMAs with their operands swapped deliver Y^T = V^T n^T from the same registers: lane (li = sample, lg) register r holds
+//       slot s = lg + 4 r of sample li -- the row rule of the S-step (ENT_CI).  The slots: s < D: B'_s;  10, 11: A';  12..15: q';  the
+//       others zero.  Register r then holds B' of dimension 4 r + lg, the dimension ev[r] holds in that lane, register 3 holds q'_i in all
+//       four lanes of the sample and register 2 holds A'_i in the lanes lg >= 2 (dimensions 10, 11 do not exist at D <= 10): the
+//       per-sample chain q' -> 1/q' -> gradient pieces is lane-local but for one v_permlane32_swap (A'_i/q'_i from lane + 32 to lane),
+//       where GP2 goes through LDS three times per sign.  The gradient accumulators are per (lane, register) = (sample column, dimension)
+//       and are summed over the sixteen lanes of a row in the wave's epilogue.
+//       Three gradient accumulator pairs per lane instead of one (+8 VGPRs) and the sample fragment ev alive through both signs (+6; the
+//       instantiations at their budget re-read it from the LDS tile instead, ent_sl_evl_for): where that costs an instantiation -- or one of
+//       its log-joint-role / parity / block-sparse / walking siblings, which share the class -- spills or a wave per SIMD against round 6's
+//       build (tools/isa_meta.py over QS = 1..3), the class keeps GP2 or the older epilogue: four k-tiles (at 256 registers before),
+//       D >= 7 with one k-tile and no tail or with two k-tiles and at most a one-value tail.
+//       Not in the walking launch: its headline instantiation ran 2.07 -> 2.17 ms with SL (fewer instructions, SQ_WAIT_ANY 3.9 -> 6.2e8: the two
+//       waves of a SIMD start together there and stay in step), where the chunk grid's went 2.06 -> 1.97 (profiles/r07_sample_layout.md).
+//       The table below is read off the compiler's register figures and has to be re-derived when the compiler changes: make ent_sl_for
+//       return GRAD && HV == 1 && QS <= 3 && !WALK, run `python tools/isa_meta.py QS` for QS = 1, 2, 3 on that tree and on the parent, and take
+//       out every (QS, KT, TL) class in which a line has more vgpr_spill or another waves/SIMD figure than the parent's.
+constexpr bool ent_sl_for(int KT, int QS, int TL, int HV, bool GRAD, bool WALK) {
+  if (!(GRAD && HV == 1 && QS <= 3) || KT == 4 || WALK) return false;
+  if (QS == 3) return !((KT == 1 && TL == 0) || (KT == 2 && TL <= 1));
+  // (D <= 6: the classes where SL's smaller footprint gives an instantiation one more wave per SIMD keep the old form as well -- the launch
+  // plan reads the occupancy, and D = 2, K = 50 ran 1.88 -> 2.10 ms at three waves where the sweeps had set two)
+  if (QS == 2) return KT == 3 || (KT == 2 && TL == 0);
+  return TL == 0 || (KT == 2 && TL == 1) || (KT == 3 && TL == 2);
+}
+constexpr bool ent_sl_evl_for(int KT, int QS, int TL) { return QS == 3 && KT == 3 && TL == 0; }
 
 // Ordering point for LDS words that only ONE wave touches (lanes of a wave exchanging values through LDS): the hardware
 // executes a wave's LDS instructions in order, so no s_barrier and no full s_waitcnt drain is needed -- only the compiler must
@@ -169,8 +197,9 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   constexpr int QL = QS;                   // MFMAs of the linear part of the S-step (inner index c = 4q + lg < D, zero operands beyond D: for
                                            // D mod 4 in {3, 0} the last one multiplies zeros -- a compile-time count keeps the KT chains branch-free)
   __shared__ double Et[16 * DP];   // eps tile [i][d], staged by wave 0 and shared by the HV waves of the workgroup
-  constexpr bool GP2 = GRAD && ent_gp2_for(KT, QS, TL, HV);
-  __shared__ double RQ_all[HV][GP2 ? 32 : 16];   // q'_i then 1/q'_i  (GP2: and A'_i then A'_i/q'_i behind them)
+  constexpr bool SL = NPV == 1 && ent_sl_for(KT, QS, TL, HV, GRAD, WALK);
+  constexpr bool GP2 = GRAD && !SL && ent_gp2_for(KT, QS, TL, HV);
+  __shared__ double RQ_all[HV][SL ? 1 : (GP2 ? 32 : 16)];   // q'_i then 1/q'_i  (GP2: and A'_i then A'_i/q'_i behind them; SL: no exchange)
   __shared__ double BND_all[HV][SPARSE ? KT * 16 * 3 : 1];  // per component: |m'_k|, cK_k - cK_j, h_k  (block-sparse bound)
   // partial PV outputs of the two halves, double-buffered by sign so that one workgroup barrier per sign is enough
   constexpr int YXN = NPV * 4 * WAVE;      // doubles per (sign, wave) slot of the PV exchange (in the dynamic LDS, see PB)
@@ -323,6 +352,13 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         for (int pv = 0; pv < NPV; ++pv) {
           const int col = 16 * pv + li;
           double v = 0.0;
+          if (SL) {      // the slot map of the sample layout (li = slot): B'_s | zero | A' A' | q' q' q' q'
+            if (kv2) {
+              if (li >= 12) v = p2[D + 2];
+              else if (li >= 10) v = p2[D + 3];
+              else if (li < D) v = p2[D + 3] * (p2[li] - pj[li]);
+            }
+          } else
           if (kv2) {
             if (col == 0) v = p2[D + 2];                                        // w_k            -> q'
             else if (col == 1) v = p2[D + 3];                                   // w_k/sigma_k^2  -> A'
@@ -364,6 +400,13 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         for (int pv = 0; pv < NPV; ++pv) {     // PV "B" operand: inner index lg <-> tail component 4u + lg, column 16 pv + li
           const int col = 16 * pv + li;
           double v = 0.0;
+          if (SL) {      // (the slot map, as above)
+            if (kvq) {
+              if (li >= 12) v = pq[D + 2];
+              else if (li >= 10) v = pq[D + 3];
+              else if (li < D) v = pq[D + 3] * (pq[li] - pj[li]);
+            }
+          } else
           if (kvq) {
             if (col == 0) v = pq[D + 2];
             else if (col == 1) v = pq[D + 3];
@@ -395,12 +438,13 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #pragma unroll
   for (int u = 0; u < VBR; ++u) VBreg[u] = VBS[u * WAVE + lane];
 #define VBV(kt_, rr_, pv_) (VBL ? (((kt_) * 4 + (rr_)) * NPV + (pv_) < VBR ? VBreg[(((kt_) * 4 + (rr_)) * NPV + (pv_)) < VBR ? (((kt_) * 4 + (rr_)) * NPV + (pv_)) : 0] : VBS[(((kt_) * 4 + (rr_)) * NPV + (pv_)) * WAVE + lane]) : VB[VBL ? 0 : (kt_)][rr_][pv_])
-  double accH = 0.0, accG[NPV], accLG[NPV];
+  constexpr int NG = SL ? QS : NPV;   // gradient accumulators per lane: one per column block, SL: one per dim-block (dimension 4 r + lg)
+  double accH = 0.0, accG[NG], accLG[NG];
   double pm = 1.0;            // running product of mantissas of q'
   int pe = 0, pcnt = 0;       // running sum of exponents
   double Wacc[KT][4];
 #pragma unroll
-  for (int pv = 0; pv < NPV; ++pv) { accG[pv] = 0.0; accLG[pv] = 0.0; }
+  for (int pv = 0; pv < NG; ++pv) { accG[pv] = 0.0; accLG[pv] = 0.0; }
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -622,11 +666,16 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         for (int u = 0; u < TLN; ++u) t[u] = vb_exp_tab1k<VB_EXP_TAB1K_QUAD>(t[u], TAB);
       }
     };
-    // PV-step: Y[i][col]; lane (col = li, lg) register rr <-> sample lg + 4 rr.  Two accumulator sets halve the dependent chain.
+    // PV-step: Y[i][col]; lane (col = li, lg) register rr <-> sample lg + 4 rr (SL: lane (sample li, lg) register rr <-> slot lg + 4 rr).
+    // Two accumulator sets halve the dependent chain.
     // (NPV >= 2: the column blocks are independent chains already, one set is enough -- 16 VGPRs less.)
     auto pvstep = [&](mf4 (&x)[KT], mf4 (&Y)[NPV], int sg, const double (&tn)[TLN]) {
       constexpr bool TWO = NPV == 1 && KT <= 2;     // (round 5: at three k-tiles and more the second set's eight registers are worth more as PV
                                                     //  operands; the dependent MFMAs of one chain issue back to back anyway: 2.138 vs 2.140 ms)
+      // (SL: operands swapped -- the mixture side as A, the exponentials as B: the transposed product, see ent_sl_for)
+      auto pvm = [&](double xa, double vb, mf4 acc) __attribute__((always_inline)) {
+        return SL ? __builtin_amdgcn_mfma_f64_16x16x4f64(vb, xa, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(xa, vb, acc, 0, 0, 0);
+      };
       mf4 Y2s[TWO ? NPV : 1];
       mf4 (&Y2)[TWO ? NPV : 1] = Y2s;
 #pragma unroll
@@ -637,23 +686,23 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #pragma unroll
         for (int pv = 0; pv < NPV; ++pv) {
           mf4& Yb = TWO ? Y2[TWO ? pv : 0] : Y[pv];
-          Y[pv] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[kt][0], VBV(kt, 0, pv), Y[pv], 0, 0, 0);
-          Yb = __builtin_amdgcn_mfma_f64_16x16x4f64(x[kt][1], VBV(kt, 1, pv), Yb, 0, 0, 0);
-          Y[pv] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[kt][2], VBV(kt, 2, pv), Y[pv], 0, 0, 0);
-          Yb = __builtin_amdgcn_mfma_f64_16x16x4f64(x[kt][3], VBV(kt, 3, pv), Yb, 0, 0, 0);
+          Y[pv] = pvm(x[kt][0], VBV(kt, 0, pv), Y[pv]);
+          Yb = pvm(x[kt][1], VBV(kt, 1, pv), Yb);
+          Y[pv] = pvm(x[kt][2], VBV(kt, 2, pv), Y[pv]);
+          Yb = pvm(x[kt][3], VBV(kt, 3, pv), Yb);
         }
       }
 #pragma unroll
       for (int pv = 0; pv < NPV; ++pv) {
         mf4& Yb = TWO ? Y2[TWO ? pv : 0] : Y[pv];
         if (SP && !((act >> (KT - 1)) & 1u)) { if (TWO) Y[pv] += Yb; continue; }
-        Y[pv] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[KT - 1][0], VBV(KT - 1, 0, pv), Y[pv], 0, 0, 0);
-        if (nr_last > 1) Yb = __builtin_amdgcn_mfma_f64_16x16x4f64(x[KT - 1][1], VBV(KT - 1, 1, pv), Yb, 0, 0, 0);
-        if (nr_last > 2) Y[pv] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[KT - 1][2], VBV(KT - 1, 2, pv), Y[pv], 0, 0, 0);
-        if (nr_last > 3) Yb = __builtin_amdgcn_mfma_f64_16x16x4f64(x[KT - 1][3], VBV(KT - 1, 3, pv), Yb, 0, 0, 0);
+        Y[pv] = pvm(x[KT - 1][0], VBV(KT - 1, 0, pv), Y[pv]);
+        if (nr_last > 1) Yb = pvm(x[KT - 1][1], VBV(KT - 1, 1, pv), Yb);
+        if (nr_last > 2) Y[pv] = pvm(x[KT - 1][2], VBV(KT - 1, 2, pv), Y[pv]);
+        if (nr_last > 3) Yb = pvm(x[KT - 1][3], VBV(KT - 1, 3, pv), Yb);
         if (TL) {   // the tail: inner index lg <-> tail component 4u + lg
 #pragma unroll
-          for (int u = 0; u < TLN; ++u) Y[pv] = __builtin_amdgcn_mfma_f64_16x16x4f64(tn[u], VBt[u][pv], Y[pv], 0, 0, 0);
+          for (int u = 0; u < TLN; ++u) Y[pv] = pvm(tn[u], VBt[u][pv], Y[pv]);
         }
         if (TWO) Y[pv] += Yb;
       }
@@ -677,26 +726,35 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
     };
     // per-sample scalars in the sample layout (lane <-> sample li): q' from column 0, through LDS
+    // (SL: q' is in register 3 of the sample's own lanes -- no exchange, put_q and put_rq are empty)
     auto put_q = [&](mf4 (&Y)[NPV]) {
+      if constexpr (SL) return;
       if (GP2 ? li < 2 : li == 0) {      // column 0: q'_i; GP2: column 1 too, A'_i
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) RQ[(GP2 ? 16 * li : 0) + lg + 4 * rr] = Y[0][rr];
       }
       ent_sync<HV>();   // RQ is private to the wave
     };
-    double arq = 0.0;   // GP2: A'_i / q'_i in the sample layout
+    double arq = 0.0;   // GP2, SL: A'_i / q'_i in the sample layout
     // TQ (round 5): the second sign's gradient epilogue reuses the four u'_id the first sign read (-0.2 %; eight registers across the second
-    // sign's exponentials, so only in the headline class, where they are there).
+    // sign's exponentials, so only in the headline class, where they are there -- with SL: its walking instantiations).
     constexpr bool TQ = GP2 && US && NPV == 1 && HV == 1 && EO && KT == 3 && QS <= 3 && !CO && !EM && VBMC_STAG_FOR(KT, QS, TL);
     double tq[TQ ? 4 : 1];
-    auto get_rq = [&]() -> double {
-      double qs_ = RQ[li];
+    auto get_rq = [&](mf4 (&Y)[NPV]) -> double {
+      double qs_ = SL ? Y[0][3] : RQ[li];
       double rqs = vb_rcp(qs_);
       if (partial) {
         qs_ = svalid ? qs_ : 1.0;
         rqs = svalid ? rqs : 0.0;
       }
       if (GP2) arq = RQ[GP2 ? 16 + li : 0] * rqs;
+      if (SL) {   // A'_i sits in register 2 of the lanes lg >= 2: every lane takes the product of lane | 32 (v_permlane32_swap of the value with
+                  // itself leaves [low half | low half] and [high half | high half], see xor_sum32)
+        const double t = Y[0][2] * rqs;
+        const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(t), (unsigned)__double2loint(t), false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(t), (unsigned)__double2hiint(t), false, false);
+        arq = __hiloint2double((int)hi[1], (int)lo[1]);
+      }
       pm *= __builtin_amdgcn_frexp_mant(qs_);   // sum log q' = ln2 * sum exp + log(prod mant)
       pe += __builtin_amdgcn_frexp_exp(qs_);
       accH += shift;
@@ -715,13 +773,31 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
     };
     auto put_rq = [&](double rqs) {
+      if constexpr (SL) return;
       ent_sync<HV>();
       if (lg == 0) { RQ[li] = rqs; if (GP2) RQ[GP2 ? 16 + li : 0] = arq; }
       ent_sync<HV>();
     };
     // gradient pieces in the PV output layout
-    auto gradpieces = [&](mf4 (&Y)[NPV], double ssig, auto sgc) {   // sgc: the sign as a compile-time +1 / -1 (US: no multiply), or 0: ssig at run time
+    auto gradpieces = [&](mf4 (&Y)[NPV], double rqs, double ssig, auto sgc) {   // sgc: the sign as a compile-time +1 / -1 (US: no multiply), or 0: ssig at run time
       constexpr int SG = decltype(sgc)::value;
+      // (EVL: u'_id from the LDS tile again, not from ev -- six registers less across both signs' chains for three reads per sign that
+      // nothing waits for; the offset is made opaque so that the reads are not merged with the ones ev came from.  No padding mask here:
+      // a padded slot's draw meets B' = 0 and lands in accumulators the epilogue does not store.)
+      constexpr bool EVL = SL && ent_sl_evl_for(KT, QS, TL);
+      int eo = li * DP + lg;
+      if (EVL) asm volatile("" : "+v"(eo));
+      if constexpr (SL) {   // lane-local: register r holds B'_id of the dimension d = 4 r + lg that ev[r] holds (rqs: the sample's 1/q'_i)
+#pragma unroll
+        for (int r = 0; r < QS; ++r) {
+          const double tv = EVL ? Et[eo + 4 * r] : ev[r];
+          const double t = (US && SG > 0) ? tv : ((US && SG < 0) ? -tv : ssig * tv);   // u'_id = +-eps_id sigma_j (zero beyond D)
+          const double gd = fma(t, arq, -(Y[0][r] * rqs));      // (u'_id A'_i - B'_id) / q'_i; the lanes lg >= 2 of register 2 (A' in place of a
+          accG[r] += gd;                                       //  B'; slots 10, 11): finite values in accumulators the epilogue does not store
+          accLG[r] = fma(t, gd, accLG[r]);
+        }
+        return;
+      }
       if constexpr (GP2) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
@@ -788,19 +864,19 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       pvstep(n, Y, 0, ntl);
       put_q(Y);
       exps(nm, I0{}, IH{});
-      const double rqs = get_rq();
+      const double rqs = get_rq(Y);
       put_rq(rqs);
       exps(nm, IH{}, IK{});
       texp(ntm);
       wacc(n, rqs, ntl);
-      gradpieces(Y, sigj, std::integral_constant<int, 1>{});
+      gradpieces(Y, rqs, sigj, std::integral_constant<int, 1>{});
       fold();
       pvstep(nm, Y, 1, ntm);
       put_q(Y);
-      const double rqs2 = get_rq();
+      const double rqs2 = get_rq(Y);
       wacc(nm, rqs2, ntm);
       put_rq(rqs2);
-      gradpieces(Y, -sigj, std::integral_constant<int, -1>{});
+      gradpieces(Y, rqs2, -sigj, std::integral_constant<int, -1>{});
       fold();
     } else {
       // one loop body for both signs; the second sign's exponents are MOVED into n on the back edge -- written as a
@@ -832,10 +908,10 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
           mf4 Y[NPV];
           pvstep(n, Y, sg, ntl);
           put_q(Y);
-          const double rqs = get_rq();
+          const double rqs = get_rq(Y);
           wacc(n, rqs, ntl);
           put_rq(rqs);
-          gradpieces(Y, ssig, std::integral_constant<int, 0>{});
+          gradpieces(Y, rqs, ssig, std::integral_constant<int, 0>{});
         } else {
           double qp = 0.0;
 #pragma unroll
@@ -923,6 +999,20 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   if (lane == 0 && hv == 0) o[0] = accH;
   if (GRAD) {
     double sgsum = 0.0;
+    if constexpr (SL) {   // per (lane, register) = (sample column li, dimension 4 r + lg): the sixteen lanes of a row hold the dimension's terms
+#pragma unroll
+      for (int r = 0; r < QS; ++r) {
+        double g = accG[r], lgd = accLG[r] / sigj;     // accLG carried u' = eps sigma_j in place of eps
+        g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
+        g += __shfl_xor(g, 4, 64); g += __shfl_xor(g, 8, 64);
+        lgd += __shfl_xor(lgd, 1, 64); lgd += __shfl_xor(lgd, 2, 64);
+        lgd += __shfl_xor(lgd, 4, 64); lgd += __shfl_xor(lgd, 8, 64);
+        const int d = 4 * r + lg;
+        const bool dv = li == 0 && d < D;
+        if (dv) { o[1 + d] = g; o[2 + D + d] = lgd; }
+        sgsum += dv ? lgd : 0.0;
+      }
+    } else {
 #pragma unroll
     for (int pv = 0; pv < NPV; ++pv) {
       double g = accG[pv], lgd = accLG[pv] / sigj;   // accLG carried u' = eps sigma_j in place of eps
@@ -933,6 +1023,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       const bool mine = HV == 1 || (pv % HV) == hv;
       if (dv && lg == 0 && mine) { o[1 + d] = g; o[2 + D + d] = lgd; }
       sgsum += (dv && lg == 0 && mine) ? lgd : 0.0;
+    }
     }
     sgsum = wave_sum(sgsum);            // SG = sum_d LG_d  (entmc_vbmc.m:87)
     if (HV > 1) {
