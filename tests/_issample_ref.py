@@ -18,6 +18,12 @@ Cases (D, N, S, W, Nm, thin, meanfun, noisy, low_noise, tight, seed): the smalle
   D  D = 32, H = 33: 198 candidates at spec 3 -- twelve full 16-point tiles and a partial one; QS = 8
   E  H = 2, the degenerate direction pick; bounds so tight that some proposals fall outside them
   F  N = 530: the cross-kernel tile needs more than 64 KB of LDS (the prediction kernel's opted-in dynamic allocation), N no multiple of 16
+
+Edge cases (EDGE_CASES, tests/test_gpu_issetup_edges.py): the seams of k_is_pred's row blocks, walked by the chain
+  G  N = 16: one row block, seven of the eight waves idle, N an exact multiple of 16
+  H  N = 129: nine row blocks, the first turn of the snake order; a Cholesky and a low-noise hyper-sample
+  J  N = 257: seventeen row blocks, the snake's second period
+  T  N = 1136: the top of the range in which inv(L') stays resident, 71 row blocks on both branches
 """
 import math
 
@@ -160,10 +166,18 @@ CASES = {
 }
 
 
+EDGE_CASES = {
+    "G": (2, 16, 1, 6, 6, 1, 0, False, False, False, 1),
+    "H": (3, 129, 2, 8, 8, 1, 1, False, True, False, 1),
+    "J": (3, 257, 2, 8, 8, 1, 4, False, True, False, 1),
+    "T": (3, 1136, 2, 8, 6, 1, 1, False, True, False, 1),
+}
+
+
 def build_case(name):
     from tests._cases import synth_problem
 
-    D, N, S, W, Nm, thin, meanfun, noisy, low_noise, tight, seed = CASES[name]
+    D, N, S, W, Nm, thin, meanfun, noisy, low_noise, tight, seed = CASES[name] if name in CASES else EDGE_CASES[name]
     p = synth_problem(seed, D, N, 3, S, meanfun=meanfun, noisy=noisy)
     hyp = p["hyp"].copy()
     hyp[D + 1, :] = math.log(0.03)

@@ -17,6 +17,20 @@ Cases (D, N, S, K, Nvp, Nbox, Nm, meanfun, seed): the smallest shapes at which e
   P  case A with point 0 planted outside every box and more than 40 sigma from every component
   Z  a hyper-sample whose density is -Inf within reach of the training inputs, and six planted points beyond: one of them is clipped
      onto the face of the box next to a training input -- a start of zero density
+
+Edges (EDGES; the same recipe, the knobs y-scale, "no low-noise hyper-sample", "dead hyper-sample", planted box uniforms):
+  R     case A with y times 3000: hyper-samples keep ONE positive weight -- the weights run out on the second of the W = 6 draws
+  R9    case A with y times 300: weights underflow to exact zeros, at least W stay positive (no run-out)
+  L     Na1 = 256: every lane of the resampling wave holds four weights, 16 point tiles; 4K = 64: one component per lane; N = 130: a
+        third trip of the box count; box points planted on the first and on the last training input
+  RL    case L's shape with y times 1e6: four and one positive weights of 256 -- the reset of all four weights of every lane, draws from
+        the reset weights in lanes 16 and above
+  W     D = 32, W = 66 (the limits), Na1 = 129, 4K = 68, N = 70; no low-noise hyper-sample
+  K     K = 512: 2048 components, 32 per lane
+  O     case A with a hyper-sample under which every point has weight zero (alpha = -1e308, sf2 = e^10, length scales one diameter): the
+        resampling starts from ones, every start has zero density
+  N<n>  N = 7, 16, 128, 129, 256, 257, 1136 (the top of the resident range): the seams of k_is_pred's row blocks and snake order, a Cholesky and a low-noise hyper-sample,
+        Step 1 alone (Nm = 0), 48 points = three point tiles
 """
 import math
 
@@ -108,8 +122,8 @@ def mixture_lpdf(vp4, Xa):
     return np.where(out < LOG_DENORM_MIN, -np.inf, out)
 
 
-def proposal_lpdf(Xa, vp, X, Nvp, Nbox):
-    """the proposal's log density (:301-340), the box terms counted: the two-term log-sum-exp of :335-337"""
+def proposal_lpdf(Xa, vp, X, Nvp, Nbox, terms=False):
+    """the proposal's log density (:301-340), the box terms counted: the two-term log-sum-exp of :335-337; ``terms``: (lpdf, t0, t1)"""
     N, D = X.shape
     w_vp = Nvp / (Nvp + Nbox)
     rd, _, _ = geometry(X)
@@ -126,7 +140,85 @@ def proposal_lpdf(Xa, vp, X, Nvp, Nbox):
             t1 = np.log(cnt / VV / N * (1.0 - w_vp))
     hi, lo = np.maximum(t0, t1), np.minimum(t0, t1)
     with np.errstate(invalid="ignore", divide="ignore"):
-        return np.where(np.isfinite(hi), hi + np.log1p(np.exp(lo - hi)), -np.inf)
+        out = np.where(np.isfinite(hi), hi + np.log1p(np.exp(lo - hi)), -np.inf)
+    return (out, t0, t1) if terms else out
+
+
+def proposal_lpdf_longdouble(Xa, vp, X, Nvp, Nbox):
+    """proposal_lpdf's formula in np.longdouble from the same float64 inputs (points, mixture, rect_delta): what the float64 restatement and
+    the device are both held against where the number of components is beyond the measured range"""
+    ld = np.longdouble
+    N, D = X.shape
+    K = int(vp["K"])
+    w_vp = ld(Nvp) / ld(Nvp + Nbox)
+    rd, _, _ = geometry(X)
+    n = Xa.shape[0]
+    ninf = ld(-np.inf)
+    t0 = np.full(n, ninf, dtype=ld)
+    t1 = np.full(n, ninf, dtype=ld)
+    if Nvp > 0:
+        sig = np.asarray(vp["sigma"], dtype=np.float64).reshape(K).astype(ld)
+        w = np.asarray(vp["w"], dtype=np.float64).reshape(K).astype(ld)
+        lam = np.asarray(vp["lambda"], dtype=np.float64).reshape(D).astype(ld)
+        mu = np.tile(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K), (1, 4)).astype(ld)
+        sig4 = np.concatenate([sig] + [np.sqrt(sig * sig + ld(c) * ld(c)) for c in SCALES])
+        w4 = np.tile(w, 4) / (ld(4) * np.sum(w))
+        cst = np.log(w4) - D * np.log(sig4) - np.sum(np.log(lam)) - ld(0.5) * D * ld("1.8378770664093454835606594728112353")
+        for i in range(n):
+            z = (Xa[i].astype(ld)[None, :] - mu.T) / (sig4[:, None] * lam[None, :])
+            lp = cst - ld(0.5) * np.sum(z * z, axis=1)
+            m = np.max(lp)
+            v = m + np.log(np.sum(np.exp(lp - m)))
+            t0[i] = v + np.log(w_vp) if v >= ld(LOG_DENORM_MIN) else ninf
+    if Nbox > 0:
+        VV = ld(1)
+        for d in range(D):
+            VV = VV * (ld(2) * ld(rd[d]))
+        cnt = np.sum(np.all(np.abs(Xa[:, None, :] - X[None, :, :]) < rd[None, None, :], axis=2), axis=1)
+        for i in range(n):
+            if cnt[i] > 0:
+                t1[i] = np.log(ld(int(cnt[i])) / VV / ld(N) * (ld(1) - w_vp))
+    hi, lo = np.maximum(t0, t1), np.minimum(t0, t1)
+    out = np.full(n, ninf, dtype=ld)
+    for i in range(n):
+        if np.isfinite(hi[i]):
+            out[i] = hi[i] + np.log1p(np.exp(lo[i] - hi[i])) if np.isfinite(lo[i]) else hi[i]
+    return out
+
+
+def gplite_pred_longdouble(gp, P):
+    """(fmu, fs2), n x S each: gplite_pred's formulas (gplite_pred.m:73-104, :120) in np.longdouble from the posterior as it stands in
+    float64 (hyp, alpha, L, sW) -- the value the float64 oracle and the device both approximate.  The mean function is evaluated by the
+    oracle (a constant mean is exact)."""
+    ld = np.longdouble
+    X = np.asarray(gp["X"], dtype=np.float64)
+    N, D = X.shape
+    P = np.asarray(P, dtype=np.float64)
+    n, S = P.shape[0], len(gp["post"])
+    fmu, fs2 = np.zeros((n, S), dtype=ld), np.zeros((n, S), dtype=ld)
+    for s, post in enumerate(gp["post"]):
+        hyp = np.asarray(post["hyp"], dtype=np.float64)
+        ell = np.exp(hyp[:D].astype(ld))
+        sf2 = np.exp(ld(2) * ld(hyp[D]))
+        mstar = R.gplite_meanfun(hyp[gp["Ncov"] + gp["Nnoise"]:gp["Ncov"] + gp["Nnoise"] + gp["Nmean"]], P, gp["meanfun"])
+        d2 = np.zeros((N, n), dtype=ld)
+        for d in range(D):
+            t = X[:, d].astype(ld)[:, None] / ell[d] - P[:, d].astype(ld)[None, :] / ell[d]
+            d2 = d2 + t * t
+        Ks = sf2 * np.exp(-d2 / ld(2))
+        fmu[:, s] = np.asarray(mstar, dtype=np.float64).reshape(-1).astype(ld) + Ks.T @ np.asarray(post["alpha"], dtype=np.float64).astype(ld)
+        L = np.asarray(post["L"], dtype=np.float64).astype(ld)
+        if post["Lchol"]:
+            Bv = np.asarray(post["sW"], dtype=np.float64).astype(ld)[:, None] * Ks
+            Lt = L.T.copy()
+            V = np.zeros((N, n), dtype=ld)
+            for i in range(N):                         # L' \ (sW .* Ks), forward substitution
+                V[i] = (Bv[i] - Lt[i, :i] @ V[:i]) / Lt[i, i]
+            fs2[:, s] = sf2 - np.sum(V * V, axis=0)
+        else:
+            fs2[:, s] = sf2 + np.sum(Ks * (L @ Ks), axis=0)
+        fs2[:, s] = np.maximum(fs2[:, s], ld(0))
+    return fmu, fs2
 
 
 def weights(lpdf, fmu, fs2):
@@ -139,15 +231,25 @@ def weights(lpdf, fmu, fs2):
     return lnw, np.where(np.isfinite(lw), lw, -np.inf)
 
 
-def resample(lw, u, W):
+def resample(lw, u, W, info=None):
     """W draws without replacement from exp(lw - max lw) by catrnd's rule idx = #(cdf < u cdf(end)) (:208-214, :403-408); weights that
-    ran out are reset to ones.  Returns the indices and the smallest |u total - cdf entry| / total over the draws."""
+    ran out are reset to ones.  Returns the indices and the smallest |u total - cdf entry| / total over the draws.  ``info`` (a dict)
+    receives npos, the positive weights at the start, zeros, the finite log weights whose weight is exactly zero, resets, the draws
+    in front of which the weights were reset to ones (a start from ones counts as a reset in front of draw 0), and edge, the smallest
+    distance of a finite lw - max from the underflow edge log(5e-324)."""
     m = np.max(lw)
-    w = np.ones_like(lw) if not np.isfinite(m) else np.exp(lw - m)
+    start_ones = not np.isfinite(m)
+    w = np.ones_like(lw) if start_ones else np.exp(lw - m)
+    if info is not None:
+        fin = np.isfinite(lw)
+        info.update(npos=0 if start_ones else int(np.sum(w > 0)), zeros=0 if start_ones else int(np.sum(fin & (w == 0))),
+                    resets=[0] if start_ones else [], edge=np.inf if start_ones else float(np.min(np.abs((lw[fin] - m) - LOG_DENORM_MIN))))
     idx, margin = [], np.inf
     for i in range(W):
         if not np.sum(w) > 0:
             w = np.ones_like(lw)
+            if info is not None:
+                info["resets"].append(i)
         cdf = np.cumsum(w)
         t = u[i] * cdf[-1]
         margin = min(margin, float(np.min(np.abs(cdf - t))) / cdf[-1])
@@ -155,6 +257,18 @@ def resample(lw, u, W):
         idx.append(k)
         w[k] = 0.0
     return np.array(idx), margin
+
+
+def components(B, vp, Nvp):
+    """the component of the smoothed mixture each of the first Nvp points is drawn from (points' rule)"""
+    D, K = int(vp["D"]), int(vp["K"])
+    cdf = smoothed(vp)[2]
+    return np.array([min(int(np.sum(cdf < B[(D + 1) * i] * cdf[-1])), 4 * K - 1) for i in range(Nvp)], dtype=int)
+
+
+def box_inputs(B, D, N, Nvp, Nbox):
+    """the training input each box point is drawn around (points' rule)"""
+    return np.array([min(int(math.floor(B[(D + 1) * (Nvp + i)] * N)), N - 1) for i in range(Nbox)], dtype=int)
 
 
 def setup(B, vp, gp, Nvp, Nbox, W, pred=None):
@@ -170,17 +284,21 @@ def setup(B, vp, gp, Nvp, Nbox, W, pred=None):
     rd, LB, UB = geometry(X)
     Xa1 = points(B, vp, X, Nvp, Nbox)
     fmu, fs2 = pred(Xa1)
-    lpdf = proposal_lpdf(Xa1, vp, X, Nvp, Nbox)
+    lpdf, t0, t1 = proposal_lpdf(Xa1, vp, X, Nvp, Nbox, terms=True)
     lnw, lw = weights(lpdf, fmu, fs2)
-    out = {"Xa1": Xa1, "lpdf1": lpdf, "lnw1": lnw.T.copy(), "fs2a1": fs2, "fmu1": fmu, "rect_delta": rd, "LB": LB, "UB": UB, "margin": np.inf}
+    out = {"Xa1": Xa1, "lpdf1": lpdf, "lnw1": lnw.T.copy(), "fs2a1": fs2, "fmu1": fmu, "rect_delta": rd, "LB": LB, "UB": UB, "margin": np.inf,
+           "t0": t0, "t1": t1, "lw": lw}
     if W > 0:
         idx0 = np.zeros((W, S), dtype=int)
         x0 = np.zeros((S, W, D))
+        draws = []
         for s in range(S):
-            idx0[:, s], mg = resample(lw[:, s], B[(D + 1) * Na1 + W * s:(D + 1) * Na1 + W * (s + 1)], W)
+            info = {}
+            idx0[:, s], mg = resample(lw[:, s], B[(D + 1) * Na1 + W * s:(D + 1) * Na1 + W * (s + 1)], W, info)
+            draws.append(info)
             out["margin"] = min(out["margin"], mg)
             x0[s] = np.clip(Xa1[idx0[:, s]], LB, UB)
-        out.update(idx0=idx0, x0=x0)
+        out.update(idx0=idx0, x0=x0, draws=draws)
     return out
 
 
@@ -194,32 +312,67 @@ CASES = {
     "Z": (2, 21, 3, 2, 19, 18, 8, 1, 1),
 }
 
+# name: ((D, N, S, K, Nvp, Nbox, Nm, meanfun, seed), knobs).  Knobs: yscale -- y, sf and a constant mean times it; low_noise = False -- no
+# hyper-sample on the Lchol = false branch; dead -- the hyper-sample under which every point has weight zero; plant_box -- the first two
+# box points are drawn around the last and the first training input
+N_SEAMS = (7, 16, 128, 129, 256, 257, 1136)
+N_REFUSED = 1137                                       # the first N whose prediction is the slab form: the sampler answers "unsupported"
+EDGES = {
+    "R": ((2, 21, 3, 2, 19, 18, 8, 0, 1), {"yscale": 3000.0}),
+    "R9": ((2, 21, 3, 2, 19, 18, 8, 0, 1), {"yscale": 300.0}),
+    "L": ((3, 130, 2, 16, 128, 128, 8, 1, 1), {"plant_box": True}),
+    "RL": ((3, 130, 2, 16, 128, 128, 8, 1, 1), {"yscale": 1e6}),
+    "W": ((32, 70, 1, 17, 65, 64, 8, 4, 1), {"low_noise": False}),
+    "K": ((2, 40, 1, 512, 40, 0, 8, 0, 1), {}),
+    "O": ((2, 21, 3, 2, 19, 18, 8, 0, 1), {"dead": 2}),
+}
+EDGES.update({"N%d" % n: ((3, n, 2, 2, 24, 24, 0, 1, 1), {}) for n in N_SEAMS})
+SEAM_NAMES = tuple("N%d" % n for n in N_SEAMS)
+
 
 def build_case(name):
     from tests._cases import synth_problem
     from tests._issample_ref import SLOTS, halfmoves_needed
 
-    D, N, S, K, Nvp, Nbox, Nm, meanfun, seed = CASES[name]
+    (D, N, S, K, Nvp, Nbox, Nm, meanfun, seed), knobs = (CASES[name], {}) if name in CASES else EDGES[name]
     p = synth_problem(seed, D, N, K, S, meanfun=meanfun)
     hyp = p["hyp"].copy()
+    y = p["y"]
     hyp[D + 1, :] = math.log(0.03)
-    hyp[D + 1, S // 2] = math.log(3e-4)                # the middle hyper-sample on the Lchol = false branch (tests/_quad_ref.py::mixed_gp)
-    hyp[:D, S // 2] += math.log(0.25)
+    if knobs.get("low_noise", True):
+        hyp[D + 1, S // 2] = math.log(3e-4)            # the middle hyper-sample on the Lchol = false branch (tests/_quad_ref.py::mixed_gp)
+        hyp[:D, S // 2] += math.log(0.25)
+    if "yscale" in knobs:                              # importance weights spanning yscale times as many nats
+        y = y * knobs["yscale"]
+        hyp[D, :] += math.log(knobs["yscale"])
+        if meanfun >= 1:
+            hyp[D + 2, :] *= knobs["yscale"]
     X = p["X"]
     diam = np.max(X, axis=0) - np.min(X, axis=0)
     if name == "Z":                                    # hyper-sample 1: sf2 = e^10, length scales 0.12 diam -- see below
         hyp[:D, 1] = np.log(0.12 * diam)
         hyp[D, 1] = 5.0
-    gp = R.gplite_post(hyp, X, p["y"], meanfun=meanfun, noisefun=p["noisefun"], s2=p["s2"])
+    if "dead" in knobs:                                # sf2 = e^10 and length scales of one diameter: with alpha = -1e308 (below) the
+        hyp[:D, knobs["dead"]] = np.log(diam)          # prediction is -Inf within 4.3 diameters of a training input -- at every point
+        hyp[D, knobs["dead"]] = 5.0
+    gp = R.gplite_post(hyp, X, y, meanfun=meanfun, noisefun=p["noisefun"], s2=p["s2"])
+    if "dead" in knobs:
+        post = [dict(q) for q in gp["post"]]
+        post[knobs["dead"]] = dict(post[knobs["dead"]], alpha=np.full_like(post[knobs["dead"]]["alpha"], -1e308))
+        gp = dict(gp, post=post)
     rng = np.random.default_rng(seed + 1700)
     best = X[np.argsort(-gp["y"], kind="stable")[: max(K, N // 2)]]
-    vp = {"D": D, "K": K, "mu": best[rng.permutation(best.shape[0])[:K]].T.copy(), "sigma": 0.3 * np.exp(0.3 * rng.standard_normal(K)),
+    pick = rng.permutation(best.shape[0])[np.arange(K) % best.shape[0]]          # (K > N: the component means repeat)
+    vp = {"D": D, "K": K, "mu": best[pick].T.copy(), "sigma": 0.3 * np.exp(0.3 * rng.standard_normal(K)),
           "lambda": np.std(X, axis=0, ddof=1) * np.exp(0.1 * rng.standard_normal(D)), "w": rng.dirichlet(np.ones(K))}
     W = 2 * (D + 1)
     Na1 = Nvp + Nbox
     B = np.minimum(np.maximum(rng.random(block_len(D, S, W, Nvp, Nbox)), 2.0 ** -53), 1.0 - 2.0 ** -53)
     for i in range(Nvp):
         B[(D + 1) * i + 1:(D + 1) * (i + 1)] = rng.standard_normal(D)
+    if knobs.get("plant_box"):                         # floor(u N) = N - 1 at the largest uniform there is, 0 at the smallest
+        B[(D + 1) * Nvp] = 1.0 - 2.0 ** -53
+        B[(D + 1) * (Nvp + 1)] = 2.0 ** -53
     planted = None
     if name == "P":                                    # 300 widths of the widest component away: outside every box, zero density
         B[1:D + 1] = 300.0
@@ -247,6 +400,9 @@ def build_case(name):
     H = W // 2
     M = halfmoves_needed(Nm, H, 1)
     U = np.minimum(np.maximum(rng.random((SLOTS, H, S, M + 1)), 2.0 ** -53), 1.0 - 2.0 ** -53)
+    if Nm == 0:                                        # Step 1 alone: no draws, no walkers
+        B = B[:(D + 1) * Na1].copy()
+        W = 0
     return {"name": name, "gp": gp, "vp": vp, "B": B, "U": U, "D": D, "N": N, "S": S, "K": K, "Nvp": Nvp, "Nbox": Nbox, "Na1": Na1, "W": W,
             "Nm": Nm, "planted": planted}
 

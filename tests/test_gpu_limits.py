@@ -60,7 +60,7 @@ def test_mixtures_whose_finalize_record_exceeds_the_lds(va, cfg):
 
 
 # ---- N beyond the 16-column right-hand-side slab (N > 1136): narrow slabs (8 columns up to N = 2144, 4 up to 3872), the
-# Cholesky panel in global scratch (N > 1232), slab-solve prediction (N > 1248).  VBMC's default MaxFunEvals = 50 (2 + D)
+# Cholesky panel in global scratch (N > 1232), slab-solve prediction (N > 1136).  VBMC's default MaxFunEvals = 50 (2 + D)
 # reaches N = 1150 at D = 21 and 1700 at D = 32.
 def _big_gp(seed, D, N, S, noisy=False, low_noise=False):
     p = synth_problem(seed, D, N, 4, S, noisy=noisy)

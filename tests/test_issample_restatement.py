@@ -22,6 +22,20 @@ def test_every_decision_of_a_case_has_a_margin(name):
         assert ref["outside"] > 0
 
 
+@pytest.mark.parametrize("name", sorted(I.EDGE_CASES))
+def test_every_decision_of_an_edge_case_has_a_margin(name):
+    """the chain cases of tests/test_gpu_issetup_edges.py: N = 16, 129, 257 and 1136, the seams of the prediction's row blocks"""
+    c, ref = I.run_case(name)
+    lchol = [bool(p["Lchol"]) for p in c["gp"]["post"]]
+    print("%s: N %d (%d row blocks) margin %.3e funccount %d half-moves %d outside %d Lchol %s" % (
+        name, c["N"], (c["N"] + 15) // 16, ref["margin"], ref["funccount"], ref["halfmoves"], ref["outside"], lchol))
+    assert ref["margin"] > I.MARGIN
+    assert ref["halfmoves"] == c["M"] <= c["U"].shape[3]
+    assert np.all(ref["Xa"] >= c["LB"][None, :, None]) and np.all(ref["Xa"] <= c["UB"][None, :, None])
+    assert c["N"] == {"G": 16, "H": 129, "J": 257, "T": 1136}[name]
+    assert lchol == ([True] if name == "G" else [True, False])
+
+
 def gauss_target(mu, prec):
     def logp(P, e):
         d = P - mu

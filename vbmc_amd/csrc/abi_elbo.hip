@@ -425,7 +425,8 @@ __global__ void k_pack_sepk(int R, int S, int K, int LJS, int diag_only, const d
 static bool copy_by_kernel(size_t bytes) { return bytes <= COPY_KERNEL_MAX_BYTES; }
 
 // inv(L') of the Lchol samples, once per surrogate (gplite_pred's triangular product and the full-variance path use it); null when
-// a 16-row tile of it does not fit the prediction kernel's LDS (N > 1248: those paths fall back to substitutions)
+// the solves no longer run 16 columns wide (N > 1136) or a 16-row tile of it does not fit the prediction kernel's LDS (N > 1248): those
+// paths fall back to substitutions
 static vbmc_status ensure_tinv(vbmc_ctx* ctx, const vbmc_gp* gp, bool* have) {
   const int N = gp->N, S = gp->S;
   const int Np = ((N + 15) >> 4) << 4, nblk = Np >> 4;

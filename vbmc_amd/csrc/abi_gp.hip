@@ -619,7 +619,8 @@ vbmc_status pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, PredBufs& pb,
   const int N = gp->N, D = gp->D, S = gp->S;
   const bool quad = qsigma != nullptr;
   const int Np = ((N + 15) >> 4) << 4, nblk = Np >> 4;
-  // beyond N = 1248 a 16-row tile of inv(L') no longer fits the LDS: the variance then comes from slab solves (k_pred_slab)
+  // inv(L') stays resident while the solves run 16 columns wide (trsm_cw_for: N <= 1136; the prediction's own 16-row tile would fit the LDS
+  // up to N = 1248): beyond that the variance comes from slab solves (k_pred_slab)
   const bool slab_pred = (size_t)16 * Np * 8 > PRED_LDS_MAX || nblk > PRED_MAXG || trsm_cw_for(N) != 16;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
