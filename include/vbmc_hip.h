@@ -1007,6 +1007,80 @@ typedef struct vbmc_mtv_args {
 } vbmc_mtv_args;
 vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, const vbmc_mtv_args* args);
 
+/*
+ * vbmc_gp_surrogate_sample: samples of the GP surrogate itself (misc/gpsample_vbmc.m -> gplite/gplite_sample.m with method 'parallel';
+ * an addition, backward compatible: VBMC_ABI_VERSION is unchanged).  The whole chain runs on the device.
+ *
+ * THE TARGET is log_gpfun (gplite_sample.m:109-117) on the first two outputs of gplite_pred -- the noisy pair [ymu, ys2] -- averaged
+ * over ALL S hyper-samples as gplite_pred.m:154-164 does: S > 1: ybar = sum ymu_s / S, vy = sum (ymu_s - ybar)^2 / (S - 1),
+ * ys2 = sum ys2_s / S + vy (sums over s in index order); S = 1: that sample's pair.  (VarThresh == 0 or not finite) and beta == 0:
+ * y = ybar.  Otherwise y = ybar - (ys2 - VarThresh) where ys2 >= VarThresh, and everywhere y -= beta sqrt(ys2).  A value that is not
+ * finite is -Inf.
+ *
+ * THE SAMPLER is the ensemble slice sampler of vbmc_acq_is_sample with its indexed uniform block, E INDEPENDENT ensembles of W walkers
+ * (E has nothing to do with S; the block is 64 x H x E x M, vbmc_gp_surrogate_sample_rng_dump writes the one a seed stands for).  Each
+ * ensemble discards `burnin` walker moves (-1: ceil(Ns / 5), the reference's, whatever E is) and records every thin-th move after them
+ * until it has Nm = ceil(Ns / E).  Row r = e + E i of X is record i of ensemble e; rows >= Ns are dropped.  A round is three launches:
+ * the sampler's step, the prediction of every candidate of every ensemble under every hyper-sample, the combination into the target.
+ * spec and chunk change the number of rounds, never a bit of the results.
+ *
+ * THE START: x0 (W x D x E), or, with x0 == NULL, the W E unbalanced transformed-space draws of vbmc_vp_rnd(vp, W E, 0, 0, seed), draw
+ * w + W e being walker w of ensemble e (gpsample_vbmc.m:41).  Either is clipped into [LB, UB] (gplite_sample.m:102).
+ *
+ * THE NOISE ESTIMATE (gpsample_vbmc.m:30-38), with sn2new != NULL: Nnn (0: 20000) draws vbmc_vp_rnd(vp, Nnn, 0, 0, seed + 1) kept on
+ * the device, per draw the nearest row of X_rescaled in units of gplengthscale (first minimum wins), sn2_avg the mean of sn2new there
+ * (a fixed-order reduction) and VarThresh = max(1, sn2_avg), which replaces the argument.  gplengthscale (D), X_rescaled (N x D) and
+ * sn2new (N, the mean over hyper-samples of the training noise) are the caller's O(N D S) set-up, as for vbmc_acq_eval.
+ *
+ * origflag: X is warpvars_vbmc(X, 'inv', vp.trinfo) with its clamp, as vbmc_vp_rnd returns original-space draws; 0: the transformed
+ * space.  vp may be NULL where nothing needs it (x0 given, no noise estimate, origflag = 0).
+ *
+ * Inputs: D, S (the GP's), Ns >= 1, 1 <= E <= 64, W even with 4 <= W <= 2 (D + 1) (0: 2 (D + 1)), thin >= 1, burnin, LB / UB (D,
+ * finite, LB < UB), beta, VarThresh (Inf: none); spec, chunk, max_steps, max_shrink, rng_mode, seed, U, Mmax as in vbmc_is_sample_args.
+ * Outputs (any may be NULL): X (Ns x D), Xt (Nm x D x E, the transformed-space records), logp (E x Nm), x0_out (W x D x E, the clipped
+ * start), varthresh_out, sn2_avg_out (0 without the estimate), sn2_nn (Nnn: sn2new at each draw's nearest row), funccount, performed,
+ * rounds[2].
+ *
+ * VBMC_ERR_UNSUPPORTED: whatever vbmc_gp_pred refuses, N beyond the range in which the prediction keeps inv(L') resident (N <= 1136),
+ * E Nm D doubles above 1 GiB, a vp the vp tools refuse.  VBMC_ERR_INVALID: what vbmc_acq_is_sample answers so (W, the box, thin, spec,
+ * the caps, the uniform block, D / S that are not the GP's, a GP without vbmc_gp_set_noise), Ns < 1, E outside 1 .. 64, vp == NULL
+ * where it is needed, a noise estimate without X_rescaled or gplengthscale, a start of zero density ("a starting point has zero
+ * density").  The context stays usable after any error.
+ */
+typedef struct vbmc_gs_args {
+  uint32_t struct_size;      /* = sizeof(vbmc_gs_args) */
+  int32_t D, S;              /* the GP's */
+  int32_t E, W, thin, burnin, spec, max_steps, max_shrink, chunk;
+  int32_t rng_mode;          /* 0 device generator, 1 parity */
+  int32_t Mmax;              /* rng_mode 1: half-moves in U */
+  int32_t origflag;
+  int32_t Nnn;               /* draws of the noise estimate (0: 20000) */
+  int32_t reserved_;
+  int64_t Ns;
+  uint64_t seed;
+  const double* U;           /* rng_mode 1: 64 x H x E x Mmax */
+  const double* LB;          /* D */
+  const double* UB;          /* D */
+  const double* x0;          /* W x D x E, or NULL */
+  double beta;
+  double VarThresh;
+  const double* X_rescaled;  /* N x D */
+  const double* gplengthscale; /* D */
+  const double* sn2new;      /* N, or NULL: no noise estimate */
+  double* X;                 /* Ns x D */
+  double* Xt;                /* Nm x D x E */
+  double* logp;              /* E x Nm */
+  double* x0_out;            /* W x D x E */
+  double* varthresh_out;
+  double* sn2_avg_out;
+  double* sn2_nn;            /* Nnn */
+  int64_t* funccount;
+  int64_t* performed;
+  int64_t* rounds;           /* 2 */
+} vbmc_gs_args;
+vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_vp_desc* vp, const vbmc_gs_args* args);
+vbmc_status vbmc_gp_surrogate_sample_rng_dump(uint64_t seed, int E, int H, int M, double* U);
+
 #ifdef __cplusplus
 }
 #endif

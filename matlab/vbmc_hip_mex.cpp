@@ -49,6 +49,9 @@
 //     [kls,xx1,xx2] = vbmc_hip_mex('vp_kldiv', vp1, vp2, Ns, seed)                    (vbmc_kldiv(vp1,vp2,Ns,0): vbmc_vp_kldiv, matlab/vbmc_hip_kldiv.m)
 //     [mtv,xx1,xx2] = vbmc_hip_mex('vp_mtv', vp1, vp2, Ns, seed)                      (vbmc_mtv(vp1,vp2,Ns): vbmc_vp_mtv, matlab/vbmc_hip_mtv.m)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
+//     [X,out] = vbmc_hip_mex('gp_surrogate_sample', h, vp, Ns, origflag, LB, UB, noise /*struct X_rescaled, gplengthscale, sn2new or []*/, opts)
+//                                (gpsample_vbmc(vp,gp,Ns,origflag): vbmc_gp_surrogate_sample, matlab/gpsample_vbmc.m.  opts: S, E, W, Seed, Thin,
+//                                 Burnin, Spec, Chunk, Nnn, Beta, VarThresh, x0 (W x D x E); out: VarThresh, sn2_avg, funccount, performed, rounds, behind)
 //     [nlZ,dnlZ] = vbmc_hip_mex('gp_nlz', Hyp /*Nhyp x B*/, X, y, s2, meanfun, noisefun)   (gplite_nlZ for B vectors)
 //     [samples,logp,widths,counts] = vbmc_hip_mex('slice_sample', X, y, s2, meanfun, noisefun, prior /*struct mu, sigma, df or []*/, LB, UB,
 //                                hyp_start, widths, basewidths_or_empty, [Ns Thin Burnin Adaptive W], seed, perms_or_empty, U_or_empty)
@@ -289,7 +292,8 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
   if (ensure_ctx(0)) return 1;
   {  // commands whose first argument is a device handle (the IQR evaluation takes two)
     const char* with_handle[] = {"gp_free", "elbo", "elbo_batch", "elbo_batch_multi", "adam", "gp_rank1", "acq", "is_create", "is_free",
-                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr", "acq_is_sample", "is_setup"};
+                                 "acq_iqr", "gp_pred", "gp_free_all", "acq_delta", "gp_quad", "acq_search", "acq_search_iqr", "acq_is_sample", "is_setup",
+                                 "gp_surrogate_sample"};
     for (const char* w : with_handle)
       if (!strcmp(cmd, w) && (nrhs < 2 || !is_handle(prhs[1]) || ((!strcmp(cmd, "acq_iqr") || !strcmp(cmd, "acq_search_iqr")) && (nrhs < 3 || !is_handle(prhs[2])))))
         return raise("vbmc_hip:usage", "this command takes a uint64 device handle as its first argument");
@@ -891,6 +895,57 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     if (st != VBMC_OK) return fail(st);
     if (nlhs > 1) plhs[1] = fb;
     if (nlhs > 2) plhs[2] = vt;
+    return 0;
+  }
+
+  if (!strcmp(cmd, "gp_surrogate_sample")) {   // X = gpsample_vbmc(vp,gp,Ns,origflag) with the library's draws for opts.Seed: vbmc_gp_surrogate_sample
+    if (nrhs < 9 || !mxIsStruct(prhs[8])) return raise("vbmc_hip:usage", "gp_surrogate_sample: h, vp, Ns, origflag, LB, UB, noise, opts");
+    vbmc_gp* h = (vbmc_gp*)(uintptr_t)(*(uint64_t*)mxGetData(prhs[1]));
+    vbmc_vp_desc d;
+    std::vector<int32_t> ty;
+    const bool have_vp = mxIsStruct(prhs[2]);
+    if (have_vp && fill_vp_desc(d, prhs[2], ty)) return 1;
+    const mxArray *nz = prhs[7], *op = prhs[8];
+    const double n = mxGetScalar(prhs[3]);
+    const int D = (int)mxGetNumberOfElements(prhs[5]);
+    if (!(n >= 1) || D < 1 || (int)mxGetNumberOfElements(prhs[6]) != D || (have_vp && d.D != D))
+      return raise("vbmc_hip:usage", "gp_surrogate_sample: Ns must be positive, LB and UB must hold one value per dimension of vp");
+    vbmc_gs_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.D = D; a.S = (int)scalar_field(op, "S", 1.0); a.Ns = (int64_t)n; a.origflag = mxGetScalar(prhs[4]) != 0;
+    a.E = (int)scalar_field(op, "E", 1.0); a.W = (int)scalar_field(op, "W", 0.0);
+    a.thin = (int)scalar_field(op, "Thin", 1.0); a.burnin = (int)scalar_field(op, "Burnin", -1.0);
+    a.spec = (int)scalar_field(op, "Spec", 0.0); a.max_steps = (int)scalar_field(op, "MaxSteps", 0.0); a.max_shrink = (int)scalar_field(op, "MaxShrink", 0.0);
+    a.chunk = (int)scalar_field(op, "Chunk", 0.0); a.seed = (uint64_t)scalar_field(op, "Seed", 0.0); a.Nnn = (int)scalar_field(op, "Nnn", 0.0);
+    a.beta = scalar_field(op, "Beta", 0.0); a.VarThresh = scalar_field(op, "VarThresh", std::numeric_limits<double>::infinity());
+    a.LB = dbl(prhs[5]); a.UB = dbl(prhs[6]);
+    if (const mxArray* x0 = field(op, "x0")) {
+      if (!mxIsEmpty(x0)) {
+        const mwSize* dm = mxGetDimensions(x0);
+        if ((int)dm[1] != D || mxGetNumberOfElements(x0) != (size_t)dm[0] * D * a.E) return raise("vbmc_hip:usage", "gp_surrogate_sample: opts.x0 must be W x D x E");
+        a.W = (int)dm[0]; a.x0 = mxGetDoubles(x0);
+      }
+    }
+    if (mxIsStruct(nz)) {
+      const mxArray *xr = field(nz, "X_rescaled"), *gl = field(nz, "gplengthscale"), *sn = field(nz, "sn2new");
+      if (!xr || !gl || !sn || (int)mxGetNumberOfElements(gl) != D || mxGetNumberOfElements(xr) != mxGetNumberOfElements(sn) * D)
+        return raise("vbmc_hip:usage", "gp_surrogate_sample: noise needs X_rescaled (N x D), gplengthscale (D) and sn2new (N)");
+      a.X_rescaled = mxGetDoubles(xr); a.gplengthscale = mxGetDoubles(gl); a.sn2new = mxGetDoubles(sn);
+    }
+    plhs[0] = mxCreateDoubleMatrix((mwSize)n, D, mxREAL);
+    const char* names[] = {"VarThresh", "sn2_avg", "funccount", "performed", "rounds", "behind"};
+    mxArray* out = mxCreateStructMatrix(1, 1, 6, names);
+    mxArray* f[6];
+    for (int i = 0; i < 6; ++i) { f[i] = mxCreateDoubleMatrix(1, 1, mxREAL); mxSetField(out, 0, names[i], f[i]); }
+    int64_t funccount = 0, performed = 0, rounds[2] = {0, 0};
+    a.X = mxGetDoubles(plhs[0]); a.varthresh_out = mxGetDoubles(f[0]); a.sn2_avg_out = mxGetDoubles(f[1]);
+    a.funccount = &funccount; a.performed = &performed; a.rounds = rounds;
+    vbmc_status st = vbmc_gp_surrogate_sample(g_ctx, h, have_vp ? &d : nullptr, &a);
+    mxGetDoubles(f[2])[0] = (double)funccount; mxGetDoubles(f[3])[0] = (double)performed;
+    mxGetDoubles(f[4])[0] = (double)rounds[0]; mxGetDoubles(f[5])[0] = (double)rounds[1];
+    if (nlhs > 1) plhs[1] = out; else mxDestroyArray(out);
+    if (st != VBMC_OK) return fail(st);
     return 0;
   }
 

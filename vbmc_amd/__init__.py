@@ -11,11 +11,12 @@ from ._lib import Context, DeviceGP, VbmcHipError, VbmcUnsupported  # noqa: F401
 from .vp import get_vptheta, make_vp, rescale_params, vpbounds  # noqa: F401
 from .elbo import (Engine, PreparedObjective, default_engine, entlb_vbmc, entmc_vbmc, fminadam_device, gplogjoint,  # noqa: F401
                    negelcbo_batch, negelcbo_shard, negelcbo_vbmc)
-from .gplite import (fminfill_design, gplite_hypprior, gplite_nlZ, gplite_post, gplite_post_rank1, gplite_pred, gplite_quad, gplite_train,  # noqa: F401,E402
-                     gplite_train_optimize, gplite_train_sample, slice_rng_dump, slicesamplebnd_gp, sq_dist)
+from .gplite import (fminfill_design, gp_surrogate_sample_rng_dump, gplite_hypprior, gplite_nlZ, gplite_post, gplite_post_rank1, gplite_pred,  # noqa: F401,E402
+                     gplite_quad, gplite_sample, gplite_sample_device, gplite_train, gplite_train_optimize, gplite_train_sample, slice_rng_dump,
+                     slicesamplebnd_gp, sq_dist)
 from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, active_search, activeimportancesampling_vbmc,  # noqa: F401,E402
                   ensemble_slice_sample, importance_sample_device, importance_sample_rng_dump, vbmc_moments, vbmc_rnd)
 from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
                        vpsieve_vbmc)
 from . import vptools  # noqa: F401,E402
-from .vptools import vp_rnd_rng_dump, warpvars  # noqa: F401,E402
+from .vptools import gpsample_vbmc, vp_rnd_rng_dump, warpvars  # noqa: F401,E402

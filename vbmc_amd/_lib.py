@@ -197,6 +197,24 @@ class MtvArgs(C.Structure):
     ]
 
 
+class GsArgs(C.Structure):
+    """vbmc_gs_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("D", C.c_int32), ("S", C.c_int32),
+        ("E", C.c_int32), ("W", C.c_int32), ("thin", C.c_int32), ("burnin", C.c_int32), ("spec", C.c_int32),
+        ("max_steps", C.c_int32), ("max_shrink", C.c_int32), ("chunk", C.c_int32),
+        ("rng_mode", C.c_int32), ("Mmax", C.c_int32), ("origflag", C.c_int32), ("Nnn", C.c_int32), ("reserved_", C.c_int32),
+        ("Ns", C.c_int64),
+        ("seed", C.c_uint64),
+        ("U", _dp), ("LB", _dp), ("UB", _dp), ("x0", _dp),
+        ("beta", C.c_double), ("VarThresh", C.c_double),
+        ("X_rescaled", _dp), ("gplengthscale", _dp), ("sn2new", _dp),
+        ("X", _dp), ("Xt", _dp), ("logp", _dp), ("x0_out", _dp), ("varthresh_out", _dp), ("sn2_avg_out", _dp), ("sn2_nn", _dp),
+        ("funccount", C.POINTER(C.c_int64)), ("performed", C.POINTER(C.c_int64)), ("rounds", C.POINTER(C.c_int64)),
+    ]
+
+
 _lib = None
 
 
@@ -276,7 +294,9 @@ def load():
     lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
     lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
     lib.vbmc_vp_rnd_rng_dump.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
-    lib.vbmc_test_exp.argtypes = [vp, C.c_int, C.c_int, _dp, _dp]
+    lib.vbmc_gp_surrogate_sample.argtypes = [vp, vp, vpd, C.POINTER(GsArgs)]
+    lib.vbmc_gp_surrogate_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
+    lib.vbmc_test_exp.argtypes =[vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)
     vpp = C.POINTER(vp)

@@ -1,0 +1,171 @@
+// C-ABI entry points of the surrogate sampler: vbmc_gp_surrogate_sample and vbmc_gp_surrogate_sample_rng_dump (include/vbmc_hip.h).
+// The kernels are gp_surrogate_kernels.h; the sampler is is_core_begin / is_core_run (abi_is_sample.hip) with the surrogate's target.
+// Host side: validation, the start (the caller's, or draws of k_vp_draw) clipped into the box and written into the sampler's walker
+// buffer, the noise estimate in the same stream in front of the chain, the closing k_gs_finish and the copies back.
+// Included after abi_vp_tools.hip (vpt_pack, vpt_gen_host).
+#include "gp_surrogate_kernels.h"
+
+#define GS_DEFAULT_NNN 20000
+#define GS_MAX_E 64
+#define GS_MAX_BYTES ((size_t)1 << 30)
+
+extern "C" vbmc_status vbmc_gp_surrogate_sample_rng_dump(uint64_t seed, int E, int H, int M, double* U) {
+  return vbmc_acq_is_sample_rng_dump(seed, E, H, M, U);
+}
+
+namespace {
+// N unbalanced transformed-space draws of the posterior into X (N x D column-major, on the device): vbmc_vp_rnd(vp, N, 0, 0, seed)
+vbmc_status gs_draw(vbmc_ctx* ctx, const char* who, const vbmc_vp_desc* vp, const VptPack& pk, long long N, unsigned long long seed, VptGenHost& g, double* X) {
+  VB_TRY(vpt_gen_host(ctx, who, vp->D, vp->K, vp->w, N, 0, seed, g));
+  g.G.origflag = 0;
+  VB_TRY(vpt_gen_upload(ctx, who, vp->D, nullptr, g));
+  VptDrawArgs a{};
+  a.P = pk.P; a.G = g.G; a.X = X; a.I = nullptr;
+  const dim3 grid((unsigned)((N + VPT_T - 1) / VPT_T));
+  VPT_FOR_DT(pk.DT, hipLaunchKernelGGL((k_vp_draw<DT>), grid, dim3(VPT_T), 0, ctx->stream, a))
+  HIP_TRY(ctx, hipGetLastError());
+  return VBMC_OK;
+}
+}  // namespace
+
+extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_vp_desc* vp, const vbmc_gs_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  const char* who = "vbmc_gp_surrogate_sample";
+  if (!args || args->struct_size != sizeof(vbmc_gs_args)) return set_err(ctx, VBMC_ERR_INVALID, "%s: struct_size mismatch", who);
+  const vbmc_gs_args& g = *args;
+  if (!gp || !g.LB || !g.UB) return set_err(ctx, VBMC_ERR_INVALID, "%s: bad arguments", who);
+  const int D = gp->D, S = gp->S, N = gp->N, E = g.E;
+  if (g.D != D || g.S != S)
+    return set_err(ctx, VBMC_ERR_INVALID, "%s: the arrays are laid out for D = %d and S = %d, the GP has D = %d and S = %d hyper-samples", who, g.D, g.S, D, S);
+  if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
+  if (g.rng_mode != 0 && g.rng_mode != 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: rng_mode %d (0 device, 1 parity)", who, g.rng_mode);
+  if (g.Ns < 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: Ns = %lld must be at least 1", who, (long long)g.Ns);
+  if (E < 1 || E > GS_MAX_E) return set_err(ctx, VBMC_ERR_INVALID, "%s: E = %d outside 1 .. %d", who, E, GS_MAX_E);
+  if (g.burnin < -1) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin must be non-negative (-1: ceil(Ns / 5))", who);
+  if (g.beta != g.beta || std::isinf(g.beta)) return set_err(ctx, VBMC_ERR_INVALID, "%s: beta must be finite", who);
+  const int W = g.W ? g.W : 2 * (D + 1);
+  const long long nm_ll = (g.Ns + E - 1) / E;
+  if ((double)nm_ll * E * D * 8.0 > (double)GS_MAX_BYTES)
+    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: E Nm D = %d x %lld x %d doubles of records are more than 1 GiB", who, E, nm_ll, D);
+  const int Nm = (int)nm_ll;
+  const long long burn_ll = g.burnin >= 0 ? g.burnin : (g.Ns + 4) / 5;     // gplite_sample.m:71
+  if (burn_ll > 0x3fffffff) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin = %lld is too large", who, burn_ll);
+  IsParams p{W, Nm, g.thin, (int)burn_ll, g.spec, g.max_steps, g.max_shrink, g.chunk, g.rng_mode, g.Mmax, g.seed, g.U};
+  p.target = IS_TARGET_SURROGATE; p.E = E; p.beta = g.beta;
+  VB_TRY(is_check_params(ctx, who, gp, p));
+  if ((long long)g.thin * Nm + burn_ll > 0x3fffffff) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin + thin Nm is too large", who);
+  for (int d = 0; d < D; ++d) {
+    const double lb = g.LB[d], ub = g.UB[d];
+    if (!std::isfinite(lb) || !std::isfinite(ub) || !(lb < ub))
+      return set_err(ctx, VBMC_ERR_INVALID, "%s: the box needs finite bounds with LB < UB (coordinate %d: [%g, %g])", who, d + 1, lb, ub);
+  }
+  const bool noise = g.sn2new != nullptr;
+  const int Nnn = g.Nnn ? g.Nnn : GS_DEFAULT_NNN;
+  if (noise) {
+    if (!g.X_rescaled || !g.gplengthscale) return set_err(ctx, VBMC_ERR_INVALID, "%s: the noise estimate needs X_rescaled and gplengthscale", who);
+    if (Nnn < 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nnn = %d", who, Nnn);
+    for (int d = 0; d < D; ++d)
+      if (!(std::isfinite(g.gplengthscale[d]) && g.gplengthscale[d] > 0.0)) return set_err(ctx, VBMC_ERR_INVALID, "%s: gplengthscale must be positive", who);
+  }
+  if (!vp && (!g.x0 || noise || g.origflag))
+    return set_err(ctx, VBMC_ERR_INVALID, "%s: the variational posterior is needed (for the start without x0, the noise estimate and origflag)", who);
+  VptPack pk;
+  if (vp) {
+    VB_TRY(vpt_pack(ctx, who, vp, 0.0, pk));
+    if (vp->D != D) return set_err(ctx, VBMC_ERR_INVALID, "%s: the posterior has D = %d, the GP D = %d", who, vp->D, D);
+  }
+  const size_t n0 = (size_t)W * E * D;
+  if (g.x0)
+    for (size_t i = 0; i < n0; ++i)
+      if (!std::isfinite(g.x0[i])) return set_err(ctx, VBMC_ERR_INVALID, "%s: a starting point is not finite", who);
+
+  hipStream_t st = ctx->stream;
+  // vt: VarThresh | sn2_avg | the sum | the partials of k_gs_sum
+  const int nb = noise ? std::min((Nnn + GS_SUM_T - 1) / GS_SUM_T, VPT_MAXBLK) : 0;
+  TmpBuf dV, dX0, dNn;
+  HIP_TRY(ctx, dV.alloc(ctx, (3 + (size_t)VPT_MAXBLK) * 8));
+  double* d_vt = dV.as<double>();
+  p.d_vt = d_vt;
+  IsCore c;
+  VB_TRY(is_core_begin(ctx, gp, who, p, c));
+  std::vector<double> hb(2 * (size_t)D), h0;
+  memcpy(hb.data(), g.LB, (size_t)D * 8);
+  memcpy(hb.data() + D, g.UB, (size_t)D * 8);
+  HIP_TRY(ctx, hipMemcpyAsync(c.dW.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
+  const double hvt[2] = {g.VarThresh, 0.0};
+  HIP_TRY(ctx, hipMemcpyAsync(d_vt, hvt, sizeof hvt, hipMemcpyHostToDevice, st));
+  if (vp) VB_TRY(vpt_upload(ctx, pk));
+
+  // ---- the start: rows r = w + W e of a (W E) x D column-major buffer, clipped into the walker buffer and into x0_out's layout
+  HIP_TRY(ctx, dX0.alloc(ctx, 2 * n0 * 8));
+  double *d_x0 = dX0.as<double>(), *d_x0c = d_x0 + n0;
+  VptGenHost gen0, genn;
+  if (g.x0) {
+    h0.resize(n0);
+    const size_t n = (size_t)W * E;
+    for (int e = 0; e < E; ++e)
+      for (int d = 0; d < D; ++d)
+        for (int w = 0; w < W; ++w) h0[(size_t)w + (size_t)W * e + n * d] = g.x0[w + (size_t)W * (d + (size_t)D * e)];
+    HIP_TRY(ctx, hipMemcpyAsync(d_x0, h0.data(), n0 * 8, hipMemcpyHostToDevice, st));
+  } else {
+    VB_TRY(gs_draw(ctx, who, vp, pk, (long long)W * E, g.seed, gen0, d_x0));
+  }
+  hipLaunchKernelGGL(k_gs_start, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, W, D, E, d_x0, c.a.LB, c.a.UB, c.a.x, d_x0c);
+
+  // ---- the noise estimate: gl | X_rescaled | sn2new | the draws | sn2new at each draw's nearest row
+  double* d_nn = nullptr;
+  if (noise) {
+    const size_t nX = (size_t)N * D, nup = (size_t)D + nX + N;
+    HIP_TRY(ctx, dNn.alloc(ctx, (nup + (size_t)Nnn * D + Nnn) * 8));
+    std::vector<double> hn(nup);
+    memcpy(hn.data(), g.gplengthscale, (size_t)D * 8);
+    memcpy(hn.data() + D, g.X_rescaled, nX * 8);
+    memcpy(hn.data() + D + nX, g.sn2new, (size_t)N * 8);
+    double *d_gl = dNn.as<double>(), *d_xr = d_gl + D, *d_sn = d_xr + nX, *d_xx = d_sn + N;
+    d_nn = d_xx + (size_t)Nnn * D;
+    HIP_TRY(ctx, hipMemcpyAsync(d_gl, hn.data(), nup * 8, hipMemcpyHostToDevice, st));
+    VB_TRY(gs_draw(ctx, who, vp, pk, Nnn, g.seed + 1, genn, d_xx));
+    switch ((D + 3) / 4) {
+#define GS_NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nnn + 15) / 16), dim3(64), 0, st, Nnn, N, D, d_xx, d_gl, d_xr, d_sn, d_nn); break;
+      GS_NN_CASE(1) GS_NN_CASE(2) GS_NN_CASE(3) GS_NN_CASE(4) GS_NN_CASE(5) GS_NN_CASE(6) GS_NN_CASE(7) GS_NN_CASE(8)
+#undef GS_NN_CASE
+      default: return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", D);
+    }
+    hipLaunchKernelGGL(k_gs_sum, dim3(nb), dim3(GS_SUM_T), 0, st, Nnn, d_nn, d_vt + 3);
+    hipLaunchKernelGGL(k_vp_reduce, dim3(1), dim3(VPT_T), 0, st, d_vt + 3, nb, 1, d_vt + 2);
+    hipLaunchKernelGGL(k_gs_thresh, dim3(1), dim3(64), 0, st, d_vt + 2, Nnn, d_vt);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+
+  const IsOutputs o{nullptr, nullptr, nullptr, nullptr, g.funccount, g.performed, g.rounds, nullptr};
+  VB_TRY(is_core_run(ctx, gp, who, p, c, o, nullptr));
+
+  // ---- the recorded walkers into X; the copies back
+  const size_t nXo = (size_t)g.Ns * D, nr = (size_t)E * Nm;
+  TmpBuf dXo;
+  if (g.X) {
+    HIP_TRY(ctx, dXo.alloc(ctx, nXo * 8));
+    GsFinishArgs f{};
+    if (g.origflag) f.P = pk.P;
+    f.P.D = D;
+    f.Ns = (int)g.Ns; f.Nm = Nm; f.E = E; f.origflag = g.origflag ? 1 : 0; f.Xa = c.a.Xa; f.X = dXo.as<double>();
+    const dim3 grid((unsigned)((g.Ns + VPT_T - 1) / VPT_T));
+    VPT_FOR_DT(vpt_pick_dt(D), hipLaunchKernelGGL((k_gs_finish<DT>), grid, dim3(VPT_T), 0, st, f))
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(g.X, f.X, nXo * 8, hipMemcpyDeviceToHost, st));
+  }
+  std::vector<double> hr;
+  double hv[2] = {0.0, 0.0};
+  if (g.Xt) HIP_TRY(ctx, hipMemcpyAsync(g.Xt, c.a.Xa, c.nXa * 8, hipMemcpyDeviceToHost, st));
+  if (g.logp) { hr.resize(nr); HIP_TRY(ctx, hipMemcpyAsync(hr.data(), c.a.rlp, nr * 8, hipMemcpyDeviceToHost, st)); }
+  if (g.x0_out) HIP_TRY(ctx, hipMemcpyAsync(g.x0_out, d_x0c, n0 * 8, hipMemcpyDeviceToHost, st));
+  if (g.sn2_nn && noise) HIP_TRY(ctx, hipMemcpyAsync(g.sn2_nn, d_nn, (size_t)Nnn * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(hv, d_vt, sizeof hv, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (g.logp)
+    for (int e = 0; e < E; ++e)
+      for (int i = 0; i < Nm; ++i) g.logp[e + (size_t)E * i] = hr[(size_t)e * Nm + i];
+  if (g.varthresh_out) *g.varthresh_out = hv[0];
+  if (g.sn2_avg_out) *g.sn2_avg_out = hv[1];
+  return VBMC_OK;
+}

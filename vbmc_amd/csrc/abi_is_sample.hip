@@ -3,11 +3,13 @@
 // evaluates each under its own hyper-sample on the per-hyper-sample set-up of k_pred_prep (abi_gp.hip: pred_plan, run once per call with
 // the centring constant of the training inputs alone).  Rounds are driven in chunks by drive_rounds (abi_gp_train.hip), the S progress
 // words read one chunk behind the one being enqueued.  The importance-sampling state is made of the device buffers where they are
-// (abi_gp.hip: acq_is_new, acq_is_ctmp_resident).  Included after abi_acq_search.hip.
+// (abi_gp.hip: acq_is_new, acq_is_ctmp_resident).  The same two routines run the surrogate sampler (abi_gp_surrogate.hip) by a target
+// kind in IsParams: E ensembles decoupled from the hyper-samples, k_gs_pred and k_gs_target in the round, no limit on Nm, no closing
+// prediction.  Included after abi_acq_search.hip.
 #include <algorithm>
 #include <cmath>
 
-#include "is_sample_kernels.h"
+#include "gp_surrogate_kernels.h"   // is_sample_kernels.h, and the surrogate sampler's kernels (abi_gp_surrogate.hip)
 
 #define IS_DEFAULT_CHUNK 16
 #define IS_DEFAULT_SPEC 3
@@ -27,11 +29,11 @@ namespace {
 struct IsPredKernel {
   void (*fn)(IsPredArgs) = nullptr;
   size_t lds = 0;
-  vbmc_status pick(vbmc_ctx* ctx, int N, int D) {
+  vbmc_status pick(vbmc_ctx* ctx, int N, int D, bool surrogate = false) {
     const int Np = ((N + 15) >> 4) << 4;
     lds = ISP_LDS_BYTES(Np);
     switch ((D + 3) / 4) {
-#define ISP_CASE(QSV) case QSV: fn = k_is_pred<QSV>; break;
+#define ISP_CASE(QSV) case QSV: fn = surrogate ? k_gs_pred<QSV> : k_is_pred<QSV>; break;
       ISP_CASE(1) ISP_CASE(2) ISP_CASE(3) ISP_CASE(4) ISP_CASE(5) ISP_CASE(6) ISP_CASE(7) ISP_CASE(8)
 #undef ISP_CASE
       default: return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", D);
@@ -40,6 +42,7 @@ struct IsPredKernel {
     return VBMC_OK;
   }
   void launch(hipStream_t st, const IsPredArgs& g, int ntile) const { hipLaunchKernelGGL(fn, dim3(ntile, g.pa.S), dim3(ISP_THREADS), lds, st, g); }
+  void launch_surrogate(hipStream_t st, const IsPredArgs& g, int ntile, int E) const { hipLaunchKernelGGL(fn, dim3(ntile, E, g.pa.S), dim3(ISP_THREADS), lds, st, g); }
 };
 
 // What vbmc_acq_is_sample and vbmc_acq_is_setup share: the sampler's parameters with their defaults still unresolved, and the outputs
@@ -47,7 +50,15 @@ struct IsParams {
   int W, Nm, thin, burnin, spec, max_steps, max_shrink, chunk, parity, Mmax;
   unsigned long long seed;
   const double* U;              // parity: IS_SLOTS x H x S x Mmax (host)
+  // the target: IS_TARGET_IMIQR -- one ensemble per hyper-sample, each under its own, at most VBMC_LIM_NA records, the closing
+  // prediction and the importance weights; IS_TARGET_SURROGATE -- E ensembles, every candidate under all hyper-samples (k_gs_pred,
+  // k_gs_target), Nm unbounded, no closing (abi_gp_surrogate.hip finishes)
+  int target = 0, E = 0;
+  double beta = 0.0;
+  const double* d_vt = nullptr; // IS_TARGET_SURROGATE: VarThresh on the device
 };
+enum { IS_TARGET_IMIQR = 0, IS_TARGET_SURROGATE = 1 };
+inline int is_ensembles(const vbmc_gp* gp, const IsParams& g) { return g.target == IS_TARGET_SURROGATE ? g.E : gp->S; }
 struct IsOutputs {
   double *Xa, *lnw, *fs2a, *logp;
   int64_t *funccount, *performed, *rounds;
@@ -64,6 +75,7 @@ struct IsCore {
   IsStepArgs a{};
   IsPredArgs pg{};
   IsPredKernel pk;
+  GsTargetArgs tg{};            // IS_TARGET_SURROGATE
   double *d_val = nullptr, *d_cl = nullptr, *d_lnw = nullptr, *d_fs2a = nullptr;
   size_t nx = 0, nv = 0, nXa = 0, nr = 0, np = 0;
   int C = 0, Nap = 0;
@@ -71,9 +83,9 @@ struct IsCore {
 };
 
 vbmc_status is_check_params(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, const IsParams& g) {
-  const int D = gp->D, S = gp->S, W = g.W, H = W / 2, Nm = g.Nm;
+  const int D = gp->D, S = is_ensembles(gp, g), W = g.W, H = W / 2, Nm = g.Nm;
   if (W < 4 || W % 2 != 0 || W > 2 * (D + 1)) return set_err(ctx, VBMC_ERR_INVALID, "%s: W = %d must be even with 4 <= W <= 2 (D + 1) = %d", who, W, 2 * (D + 1));
-  if (Nm < 1 || Nm > VBMC_LIM_NA) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nm = %d outside 1 .. %d", who, Nm, VBMC_LIM_NA);
+  if (Nm < 1 || (g.target == IS_TARGET_IMIQR && Nm > VBMC_LIM_NA)) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nm = %d outside 1 .. %d", who, Nm, VBMC_LIM_NA);
   if (g.thin < 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: thin must be at least 1", who);
   if (g.burnin < -1) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin must be non-negative (-1: ceil(thin Nm / 2))", who);
   if (g.spec < 0 || g.spec > IS_MAXSPEC) return set_err(ctx, VBMC_ERR_INVALID, "%s: spec = %d outside 1 .. %d (0: %d)", who, g.spec, IS_MAXSPEC, IS_DEFAULT_SPEC);
@@ -95,7 +107,8 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   VB_TRY(pred_check(ctx, who, gp, 16, false));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int N = gp->N, D = gp->D, S = gp->S, W = g.W, H = W / 2, Nm = g.Nm;
+  const bool surr = g.target == IS_TARGET_SURROGATE;
+  const int N = gp->N, D = gp->D, Sg = gp->S, S = is_ensembles(gp, g), W = g.W, H = W / 2, Nm = g.Nm;   // S: the ensembles
   PredBufs& pb = c.pb;
   PredPlan& pl = c.pl;
   // the per-hyper-sample set-up of the prediction (dXc, daa, dmuv; inv(L') on the GP handle), centred on the training inputs alone
@@ -106,7 +119,7 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: N = %d is beyond the range in which the prediction keeps inv(L') resident", who, N);
   pl.pa.mc = 0;
   HIP_TRY(ctx, hipMemsetAsync(pb.dmb.p, 0, (size_t)D * 8, st));
-  hipLaunchKernelGGL(k_pred_prep, dim3(4, S), dim3(256), 0, st, pl.pa, pb.dXc.as<double>(), pb.daa.as<double>(), pb.dmuv.as<double>());
+  hipLaunchKernelGGL(k_pred_prep, dim3(4, Sg), dim3(256), 0, st, pl.pa, pb.dXc.as<double>(), pb.daa.as<double>(), pb.dmuv.as<double>());
 
   IsStepArgs& a = c.a;
   a.D = D; a.S = S; a.W = W; a.H = H; a.Nm = Nm; a.thin = g.thin;
@@ -121,9 +134,11 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   const int Nap = ((Nm + 15) / 16) * 16;
   c.Nap = Nap;
   // one block of fp64 state:  LB | UB | x | lp | P | val fmu fs2 ys2 | Xa | rlp | closing fmu fs2 | lnw fs2a (S x Nap) | U
+  // (the surrogate's target:  ... | val  ymu ys2 (Sg x E x C each) | Xa | rlp | U)
   const size_t nU = g.parity ? (size_t)IS_SLOTS * H * S * g.Mmax : 0;
-  const size_t nx = (size_t)S * W * D, nP = (size_t)S * D * C, nv = (size_t)S * C, nXa = (size_t)Nm * D * S, nr = (size_t)S * Nm, np = (size_t)S * Nap;
-  const size_t n_fixed = 2 * (size_t)D + nx + (size_t)S * W + nP + 4 * nv + nXa + nr + 4 * nr + 2 * np;
+  const size_t nx = (size_t)S * W * D, nP = (size_t)S * D * C, nv = (size_t)S * C, nXa = (size_t)Nm * D * S, nr = (size_t)S * Nm, np = surr ? 0 : (size_t)S * Nap;
+  const size_t nval = surr ? nv + 2 * (size_t)Sg * nv : 4 * nv, ncl = surr ? 0 : 4 * nr;
+  const size_t n_fixed = 2 * (size_t)D + nx + (size_t)S * W + nP + nval + nXa + nr + ncl + 2 * np;
   c.nx = nx; c.nv = nv; c.nXa = nXa; c.nr = nr; c.np = np;
   HIP_TRY(ctx, c.dW.alloc(ctx, (n_fixed + nU) * 8));
   HIP_TRY(ctx, c.dSt.alloc(ctx, (size_t)S * sizeof(IsEnsState)));
@@ -141,11 +156,11 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   a.x = q; q += nx;
   a.lp = q; q += (size_t)S * W;
   a.P = q; q += nP;
-  c.d_val = q; q += 4 * nv;
+  c.d_val = q; q += nval;
   a.val = c.d_val;
   a.Xa = q; q += nXa;
   a.rlp = q; q += nr;
-  c.d_cl = q; q += 4 * nr;                             // closing prediction: logp | fmu | fs2 | ys2, S x Nm each
+  c.d_cl = q; q += ncl;                                // closing prediction: logp | fmu | fs2 | ys2, S x Nm each
   c.d_lnw = q; q += np;
   c.d_fs2a = q; q += np;
   a.U = nU ? q : nullptr;
@@ -159,7 +174,13 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   pg.Xc = pb.dXc.as<double>(); pg.aa = pb.daa.as<double>(); pg.muv = pb.dmuv.as<double>();
   pg.P = a.P; pg.mask = a.mask; pg.ncand = &a.st->ncand; pg.nstride = (int)(sizeof(IsEnsState) / sizeof(int)); pg.C = C;
   pg.logp = c.d_val; pg.fmu = c.d_val + nv; pg.fs2 = c.d_val + 2 * nv; pg.ys2 = c.d_val + 3 * nv;
-  VB_TRY(c.pk.pick(ctx, N, D));
+  if (surr) {                                          // ymu | ys2, Sg x E x C each, behind the E x C values
+    pg.fs2 = nullptr; pg.ys2 = c.d_val + nv + (size_t)Sg * nv;
+    GsTargetArgs& tg = c.tg;
+    tg.S = Sg; tg.E = S; tg.C = C; tg.nstride = pg.nstride; tg.ncand = pg.ncand; tg.mask = a.mask; tg.ymu = pg.fmu; tg.ys2 = pg.ys2;
+    tg.vt = g.d_vt; tg.beta = g.beta; tg.val = c.d_val;
+  }
+  VB_TRY(c.pk.pick(ctx, N, D, surr));
   return VBMC_OK;
 }
 
@@ -170,7 +191,8 @@ vbmc_status is_core_run(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, const
   IsStepArgs& a = c.a;
   IsPredArgs& pg = c.pg;
   IsPredKernel& pk = c.pk;
-  const int S = a.S, W = a.W, H = a.H, Nm = a.Nm, C = c.C, Nap = c.Nap;
+  const bool surr = g.target == IS_TARGET_SURROGATE;
+  const int S = a.S, W = a.W, H = a.H, Nm = a.Nm, C = c.C, Nap = c.Nap;   // S: the ensembles
   const size_t nv = c.nv, nXa = c.nXa, nr = c.nr, np = c.np;
   double *d_cl = c.d_cl, *d_lnw = c.d_lnw, *d_fs2a = c.d_fs2a;
   TmpBuf& dSt = c.dSt;
@@ -185,7 +207,12 @@ vbmc_status is_core_run(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, const
   auto round = [&](int) -> vbmc_status {
     if (++enqueued > round_cap) return set_err(ctx, VBMC_ERR_HIP, "%s: the chain did not finish within %lld rounds", who, round_cap);
     hipLaunchKernelGGL(k_is_step, dim3(S), dim3(64), 0, st, a);
-    pk.launch(st, pg, ntile);
+    if (surr) {
+      pk.launch_surrogate(st, pg, ntile, S);
+      hipLaunchKernelGGL(k_gs_target, dim3((C + 63) / 64, S), dim3(64), 0, st, c.tg);
+    } else {
+      pk.launch(st, pg, ntile);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return VBMC_OK;
   };
@@ -221,6 +248,12 @@ vbmc_status is_core_run(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, const
     funccount += fin[e].funccount; performed += fin[e].performed;
     rounds = std::max<long long>(rounds, fin[e].rounds);
     behind = behind < 0 ? fin[e].behind : std::min<long long>(behind, fin[e].behind);
+  }
+  if (surr) {                                          // the recorded walkers stay on the device: the caller finishes
+    if (o.funccount) *o.funccount = funccount;
+    if (o.performed) *o.performed = performed;
+    if (o.rounds) { o.rounds[0] = rounds; o.rounds[1] = behind; }
+    return VBMC_OK;
   }
   // ---- one closing prediction at the recorded walkers (Xa is the point buffer of Nm slots per ensemble), lnw and fs2a
   IsPredArgs cg = pg;

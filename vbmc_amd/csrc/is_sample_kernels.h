@@ -297,24 +297,26 @@ struct IsPredArgs {
   const double *Xc, *aa, *muv;  // k_pred_prep's per-hyper-sample set-up with mc = 0
   const double* P;              // S x D x C
   const unsigned char* mask;    // S x C or null
-  const int* ncand;             // candidates of ensemble s at ncand[s * nstride]
+  const int* ncand;             // candidates of ensemble e at ncand[e * nstride]  (k_is_pred: e = s)
   int nstride, C;
   double *logp, *fmu, *fs2, *ys2;   // S x C each
 };
 
-template <int QS>
-__global__ void __launch_bounds__(ISP_THREADS) k_is_pred(IsPredArgs g) {
+// The body of k_is_pred and of k_gs_pred (gp_surrogate_kernels.h): the points of ensemble e under hyper-sample s.  SURR = false: e = s,
+// the four outputs at [s][c] and the IMIQR target.  SURR = true: ymu (= fmu) and ys2 at [s][e][c] of E ensembles, no target.
+template <int QS, bool SURR>
+__device__ __forceinline__ void isp_body(const IsPredArgs& g, const int t, const int e, const int s, const int E) {
   constexpr int NWV = ISP_THREADS / 64;
   extern __shared__ double KsL[];              // [n][16], sW-scaled, zero for n >= N and for skipped points
   __shared__ double tab[VB_EXP_TAB_N];
   __shared__ double WS[NWV][16];               // per-wave sums: Ks' alpha first, the variance's sum afterwards
   const PredArgs& a = g.pa;
-  const int t = blockIdx.x, s = blockIdx.y, C = g.C;
-  const int nc = min(g.ncand[(size_t)s * g.nstride], C);
+  const int C = g.C;
+  const int nc = min(g.ncand[(size_t)e * g.nstride], C);
   if (16 * t >= nc) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
   const int jc = 16 * t + li;
-  const bool cv = jc < nc && (!g.mask || g.mask[(size_t)s * C + jc] != 0);
+  const bool cv = jc < nc && (!g.mask || g.mask[(size_t)e * C + jc] != 0);
   if (__ballot(cv) == 0ull) return;            // (every wave sees the same sixteen points)
   const int N = a.N, D = a.D, Np = ((N + 15) >> 4) << 4, nblk = Np >> 4;
   for (int i = tid; i < VB_EXP_TAB_N; i += ISP_THREADS) tab[i] = c_exp2_tab[i];
@@ -328,7 +330,7 @@ __global__ void __launch_bounds__(ISP_THREADS) k_is_pred(IsPredArgs g) {
   const double* xcs = g.Xc + (size_t)s * N * D;
   const double* aas = g.aa + (size_t)s * N;
   const double* al = a.alpha + (size_t)s * N;
-  const double* Ps = g.P + (size_t)s * D * C;
+  const double* Ps = g.P + (size_t)e * D * C;
   // ---- the cross-kernel tile: wave w takes the row blocks w, w + NWV, ...
   double xb[QS], bb = 0.0, fmacc = 0.0;
 #pragma unroll
@@ -411,12 +413,22 @@ __global__ void __launch_bounds__(ISP_THREADS) k_is_pred(IsPredArgs g) {
   const double fs2 = fmax(lc ? sf2 - pv : sf2 + pv, 0.0);
   const double sn2s = a.nf0 ? vb_exp_tab<0>(2.0 * h[a.noff], tab) : 2.220446049250313e-16;
   const double ys2 = fs2 + sn2s * a.sn2_mult[s];
+  if (SURR) {
+    const size_t o = ((size_t)s * E + e) * C + jc;
+    g.fmu[o] = fmu; g.ys2[o] = ys2;
+    return;
+  }
   const double u = 0.6745;
   const double ys = sqrt(fmax(ys2, 2.2250738585072014e-308));
   double lp = fmu + (u * ys + is_log1m(vb_exp_tab<0>(-2.0 * u * ys, tab)));     // (the library's table exponential and logarithm)
   if (!(lp > -__builtin_inf() && lp < __builtin_inf())) lp = -__builtin_inf();
   const size_t o = (size_t)s * C + jc;
   g.logp[o] = lp; g.fmu[o] = fmu; g.fs2[o] = fs2; g.ys2[o] = ys2;
+}
+
+template <int QS>
+__global__ void __launch_bounds__(ISP_THREADS) k_is_pred(IsPredArgs g) {
+  isp_body<QS, false>(g, blockIdx.x, blockIdx.y, blockIdx.y, 0);
 }
 
 // lnw = fmu - logp and fs2a of the recorded walkers in the layout of the importance-sampling state (S x Nap, -inf / 0 in the padding)

@@ -672,3 +672,169 @@ def gplite_train(hyp0, Ns, X, y, covfun=1, meanfun=None, noisefun=None, s2=None,
     new = gplite_post(hyp, X, gp["y"], 1, gp["meanfun"], nfl, s2, need_L=need_L, engine=engine)
     output.update(hyp_prethin=hyp, logp=-opt["nll"][idx], logp_prethin=-opt["nll"])
     return new, hyp, output
+
+
+def gp_surrogate_sample_rng_dump(seed, E, H, M):
+    """U (64 x H x E x M) that ``gplite_sample_device(..., seed=seed)`` consumes (vbmc_gp_surrogate_sample_rng_dump: a pure host function)."""
+    from ._lib import load
+
+    U = np.zeros((64, int(H), int(E), int(M)), order="F")
+    st = load().vbmc_gp_surrogate_sample_rng_dump(C.c_uint64(int(seed)), int(E), int(H), int(M), ptr(U))
+    if st != 0:
+        raise ValueError("vbmc_gp_surrogate_sample_rng_dump: bad arguments")
+    return U
+
+
+def gplite_sample_device(gp, Ns, LB, UB, *, vp=None, x0=None, E=1, W=0, thin=1, burnin=None, beta=0.0, VarThresh=np.inf, noise=None,
+                         origflag=False, spec=0, chunk=0, max_steps=0, max_shrink=0, seed=0, uniforms=None, outputs=("X", "Xt", "logp"),
+                         engine=None):
+    """The thin ctypes call of ``vbmc_gp_surrogate_sample`` (include/vbmc_hip.h): Ns samples of the GP surrogate's log_gpfun target
+    (gplite_sample.m:109-117, the prediction averaged over all hyper-samples) by E ensembles of W walkers, the whole chain on the device.
+
+    ``x0``: E x W x D starting walkers (as ``ensemble_slice_sample`` takes them), or None for draws of ``vp``.  ``noise``: a dict with
+    X_rescaled, gplengthscale, sn2new and, optionally, Nnn -- the noise estimate of gpsample_vbmc.m:30-38, which then sets VarThresh.
+    ``uniforms`` (64 x H x E x Mmax): parity mode; the library's own generator keyed by ``seed`` otherwise.
+    Returns a dict: X (Ns x D), Xt (Nm x D x E), logp (E x Nm), x0 (E x W x D, the clipped start), VarThresh, sn2_avg, sn2_nn (with
+    ``noise``), funccount, performed, rounds, behind."""
+    from ._lib import GsArgs
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    dgp = _device_gp_with_noise(engine, gp)
+    D, S = int(np.asarray(gp["X"]).shape[1]), len(gp["post"])
+    Ns, E = int(Ns), int(E)
+    Wn = int(W) if W else 2 * (D + 1)
+    keep = {"LB": f64(np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (D,)).copy()),
+            "UB": f64(np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (D,)).copy())}
+    a = GsArgs()
+    a.struct_size = C.sizeof(GsArgs)
+    a.D, a.S, a.E, a.W, a.Ns = D, S, E, int(W), Ns
+    a.thin, a.burnin, a.spec, a.chunk = int(thin), -1 if burnin is None else int(burnin), int(spec), int(chunk)
+    a.max_steps, a.max_shrink, a.origflag = int(max_steps), int(max_shrink), int(bool(origflag))
+    a.beta, a.VarThresh = float(beta), float(VarThresh)
+    a.LB, a.UB = ptr(keep["LB"]), ptr(keep["UB"])
+    if x0 is not None:
+        x0 = np.asarray(x0, dtype=np.float64)
+        if x0.ndim == 2:
+            x0 = x0[None]
+        if x0.ndim != 3 or x0.shape[0] != E or x0.shape[2] != D:
+            raise ValueError("gplite_sample_device: x0 must be E x W x D = %d x W x %d" % (E, D))
+        Wn = x0.shape[1]
+        a.W = Wn
+        keep["x0"] = f64(np.transpose(x0, (1, 2, 0)))       # W x D x E
+        a.x0 = ptr(keep["x0"])
+    if uniforms is not None:
+        keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
+        if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, Wn // 2, E):
+            raise ValueError("gplite_sample_device: uniforms must be 64 x H x E x Mmax = 64 x %d x %d x Mmax" % (Wn // 2, E))
+        a.rng_mode, a.Mmax, a.U = 1, keep["U"].shape[3], ptr(keep["U"])
+    a.seed = int(seed) & (2 ** 64 - 1)
+    Nnn = 0
+    if noise is not None:
+        N = np.asarray(gp["X"]).shape[0]
+        keep["xr"] = f64(np.asarray(noise["X_rescaled"], dtype=np.float64).reshape(N, D))
+        keep["gl"] = f64(np.asarray(noise["gplengthscale"], dtype=np.float64).reshape(D))
+        keep["sn"] = f64(np.asarray(noise["sn2new"], dtype=np.float64).reshape(N))
+        a.X_rescaled, a.gplengthscale, a.sn2new = ptr(keep["xr"]), ptr(keep["gl"]), ptr(keep["sn"])
+        a.Nnn = int(noise.get("Nnn", 0) or 0)
+        Nnn = a.Nnn if a.Nnn > 0 else 20000
+    desc = None
+    if vp is not None:
+        from .vptools import _Desc
+
+        desc = _Desc(vp)
+    Nm = max(-(-max(Ns, 1) // max(E, 1)), 1)
+    n, Wp, Ep = max(Ns, 1), max(Wn, 1), max(E, 1)
+    out = {}
+    if "X" in outputs:
+        out["X"] = np.zeros((n, D), order="F")
+        a.X = ptr(out["X"])
+    if "Xt" in outputs:
+        out["Xt"] = np.zeros((Nm, D, Ep), order="F")
+        a.Xt = ptr(out["Xt"])
+    if "logp" in outputs:
+        out["logp"] = np.zeros((Ep, Nm), order="F")
+        a.logp = ptr(out["logp"])
+    x0o = np.zeros((Wp, D, Ep), order="F")
+    a.x0_out = ptr(x0o)
+    vt, sa = np.zeros(1), np.zeros(1)
+    a.varthresh_out, a.sn2_avg_out = ptr(vt), ptr(sa)
+    if noise is not None:
+        out["sn2_nn"] = np.zeros(Nnn)
+        a.sn2_nn = ptr(out["sn2_nn"])
+    fc, pf, rounds = C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
+    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
+    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    ctx.check(ctx.lib.vbmc_gp_surrogate_sample(ctx.h, dgp.h, desc.ref() if desc is not None else None, C.byref(a)))
+    out.update(x0=np.ascontiguousarray(np.transpose(x0o, (2, 0, 1))), VarThresh=float(vt[0]), sn2_avg=float(sa[0]), funccount=int(fc.value),
+               performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]))
+    return out
+
+
+def _log_gpfun_host(gp, beta, VarThresh, engine):
+    """log_gpfun (gplite_sample.m:109-117) over device gplite_pred calls: the target of the host-driven fall-back"""
+    plain = (VarThresh == 0 or not np.isfinite(VarThresh)) and beta == 0
+
+    def logp(P, e):
+        y, s2 = (np.asarray(v, dtype=np.float64).reshape(-1).copy() for v in gplite_pred(gp, P, None, None, False, False, 2, engine=engine))
+        if not plain:
+            over = s2 >= VarThresh
+            y[over] = y[over] - (s2[over] - VarThresh)
+            y = y - beta * np.sqrt(s2)
+        return np.where(np.isfinite(y), y, -np.inf)
+
+    return logp
+
+
+def gplite_sample(gp, Ns, x0=None, method="parallel", logprior=None, beta=0, VarThresh=np.inf, proppdf=None, proprnd=None, bounds=None, *,
+                  E=1, seed=0, uniforms=None, thin=1, burnin=None, spec=0, chunk=0, nargout=1, engine=None):
+    """Xs = gplite_sample(gp,Ns,x0,method,logprior,beta,VarThresh,proppdf,proprnd,bounds), method 'parallel', on the device: the
+    default box (gplite_sample.m:16-20) and the high-posterior-density start of ``x0 = []`` (:88-101, its randperm from a NumPy
+    generator keyed by ``seed``) on the host, the chain in one call of ``gplite_sample_device``.  ``x0``: W x D, or E x W x D.
+    'slicesample', a ``logprior`` and proposal functions raise VbmcUnsupported.  A GP beyond the range in which the prediction keeps
+    inv(L') resident is sampled by the host-driven ``ensemble_slice_sample`` over device ``gplite_pred`` calls.
+    nargout=2 adds the dict of ``gplite_sample_device`` (None on the host-driven path)."""
+    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
+
+    if method is None or method == "":
+        method = "slicesample"                                                   # :5
+    if str(method).lower() != "parallel":
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_sample: method %r is not accelerated ('parallel' is)" % (method,))
+    if logprior is not None or proppdf is not None or proprnd is not None:
+        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_sample: a logprior and Metropolis proposals are not accelerated")
+    X = np.asarray(gp["X"], dtype=np.float64)
+    N, D = X.shape
+    Ns, E = int(Ns), int(E)
+    if bounds is None or np.size(bounds) == 0:                                   # :16-20
+        diam = np.max(X, axis=0) - np.min(X, axis=0)
+        LB, UB = np.min(X, axis=0) - 10 * diam, np.max(X, axis=0) + 10 * diam
+    else:
+        bounds = np.asarray(bounds, dtype=np.float64).reshape(2, D)
+        LB, UB = bounds[0], bounds[1]
+    W = 2 * (D + 1)                                                              # :87
+    if x0 is None or np.size(x0) == 0:                                           # :88-101
+        y = np.asarray(gp["y"], dtype=np.float64).reshape(-1)
+        N_hpd = min(N, max(W, int(np.floor(0.25 * N + 0.5))))
+        X_hpd = X[np.argsort(-y, kind="stable")[:N_hpd]]
+        Wn = min(W, N_hpd) - (min(W, N_hpd) % 2)
+        rng = np.random.default_rng(int(seed))
+        x0 = np.stack([X_hpd[rng.permutation(N_hpd)[:Wn]] for _ in range(E)])
+    else:
+        x0 = np.asarray(x0, dtype=np.float64)
+        x0 = x0[None] if x0.ndim == 2 else x0
+    x0 = np.minimum(np.maximum(x0, LB), UB)                                      # :102
+    try:
+        r = gplite_sample_device(gp, Ns, LB, UB, x0=x0, E=E, thin=thin, burnin=burnin, beta=beta, VarThresh=VarThresh, spec=spec,
+                                 chunk=chunk, seed=seed, uniforms=uniforms, outputs=("X",), engine=engine)
+        Xs = r["X"]
+    except VbmcUnsupported as err:
+        if "resident" not in str(err):
+            raise
+        from .acq import ensemble_slice_sample
+
+        engine = engine or default_engine()
+        Nm = -(-Ns // E)
+        xs, _ = ensemble_slice_sample(_log_gpfun_host(gp, float(beta), float(VarThresh), engine), x0, Nm, LB, UB, thin=int(thin),
+                                      burnin=int(np.ceil(Ns / 5)) if burnin is None else int(burnin), rng=np.random.default_rng(int(seed)))
+        Xs, r = np.transpose(xs, (1, 0, 2)).reshape(Nm * E, D)[:Ns], None        # row e + E i: record i of ensemble e
+    return (Xs, r) if nargout > 1 else Xs

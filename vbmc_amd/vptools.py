@@ -294,3 +294,67 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
     if stages:
         out = out + (st,)
     return out if len(out) > 1 else out[0]
+
+
+def _training_noise(gp):
+    """sn2new of gpsample_vbmc.m:17-28: gplite_noisefun (gplite_noisefun.m:176-210) at the training inputs, the mean over hyper-samples"""
+    X = np.asarray(gp["X"], dtype=np.float64)
+    N, D = X.shape
+    nf = tuple(int(v) for v in gp["noisefun"]) + (0,) * (3 - len(gp["noisefun"]))
+    y = np.asarray(gp["y"], dtype=np.float64).reshape(-1)
+    s2 = np.asarray(gp["s2"], dtype=np.float64).reshape(-1)
+    Ncov = int(gp.get("Ncov", D + 1))
+    acc = np.zeros(N)
+    for post in gp["post"]:
+        hn = np.asarray(post["hyp"], dtype=np.float64).reshape(-1)[Ncov:]
+        idx = 0
+        sn2 = np.full(N, np.finfo(np.float64).eps)
+        if nf[0] == 1:
+            sn2 = np.full(N, np.exp(2 * hn[idx]))
+            idx += 1
+        if nf[1] == 1:
+            sn2 = sn2 + s2
+        elif nf[1] == 2:
+            sn2 = sn2 + np.exp(hn[idx]) * s2
+            idx += 1
+        if nf[2] == 1:
+            sn2 = sn2 + np.exp(2 * hn[idx + 1]) * np.maximum(0.0, hn[idx] - y) ** 2
+        acc = acc + sn2
+    return acc / len(gp["post"])
+
+
+def gpsample_noise_setup(gp):
+    """The host set-up of the noise estimate (gpsample_vbmc.m:8-28): None for a GP without s2, or a dict with gplengthscale (the
+    geometric mean of the length scales over hyper-samples), X_rescaled and sn2new."""
+    s2 = gp.get("s2")
+    if s2 is None or np.size(s2) == 0:
+        return None
+    X = np.asarray(gp["X"], dtype=np.float64)
+    D = X.shape[1]
+    ln_ell = np.stack([np.asarray(p["hyp"], dtype=np.float64).reshape(-1)[:D] for p in gp["post"]], axis=1)
+    gl = np.exp(np.mean(ln_ell, axis=1))
+    return {"gplengthscale": gl, "X_rescaled": X / gl[None, :], "sn2new": _training_noise(gp)}
+
+
+def gpsample_vbmc(vp, gp, Ns, origflag=True, *, E=1, seed=0, Nnn=0, bounds=None, thin=1, burnin=None, spec=0, chunk=0, uniforms=None,
+                  nargout=1, engine=None):
+    """X = gpsample_vbmc(vp,gp,Ns,origflag) on the device in one call: the noise estimate over Nnn (0: 20000) draws of ``vp`` where the
+    GP carries s2 (VarThresh = max(1, sn2_avg), :30-38), W = 2 (D + 1) starting walkers per ensemble drawn from ``vp`` (:41), the
+    'parallel' chain of gplite_sample on its default box, and the way back to the original space (:43-45).  E > 1 runs that many
+    independent ensembles, each with its own burn-in.  nargout=2 adds the dict of ``gplite.gplite_sample_device``."""
+    from .gplite import gplite_sample_device
+
+    X = np.asarray(gp["X"], dtype=np.float64)
+    D = X.shape[1]
+    if bounds is None or np.size(bounds) == 0:                                   # gplite_sample.m:16-20
+        diam = np.max(X, axis=0) - np.min(X, axis=0)
+        LB, UB = np.min(X, axis=0) - 10 * diam, np.max(X, axis=0) + 10 * diam
+    else:
+        bounds = np.asarray(bounds, dtype=np.float64).reshape(2, D)
+        LB, UB = bounds[0], bounds[1]
+    noise = gpsample_noise_setup(gp)
+    if noise is not None:
+        noise["Nnn"] = int(Nnn)
+    r = gplite_sample_device(gp, Ns, LB, UB, vp=vp, E=E, thin=thin, burnin=burnin, VarThresh=1.0, noise=noise, origflag=origflag, spec=spec,
+                             chunk=chunk, seed=seed, uniforms=uniforms, outputs=("X", "Xt", "logp") if nargout > 1 else ("X",), engine=_engine(engine))
+    return (r["X"], r) if nargout > 1 else r["X"]
