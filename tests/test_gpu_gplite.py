@@ -272,7 +272,8 @@ def test_low_noise_posterior_inverse(va, N):
 
 def test_pred_and_acq_chunking_over_many_points(va):
     """Sweeps whose S x N x Nstar cross-kernel matrix would exceed 1 GiB are cut into chunks of test points; the
-    chunked result equals the one-shot result up to the sq_dist centring constant (rounding)."""
+    chunked result equals the one-shot result up to the sq_dist centring constant (rounding) -- through each of the four entry points
+    that sweep in chunks: vbmc_gp_pred, vbmc_acq_eval, vbmc_gp_quad and vbmc_acq_iqr_eval."""
     from tests.test_gpu_elbo import problem
     p, gp, vp, _ = problem(61, 6, 300, 5, 24)          # S*N*8 = 57.6 KB per point -> chunks of 18640 points
     rng = np.random.default_rng(0)
@@ -287,6 +288,17 @@ def test_pred_and_acq_chunking_over_many_points(va):
     acq_s = va.acqwrapper_vbmc(Xs[idx], vp, gp, st, False, "acqflog_vbmc", None)
     far = np.asarray(fs2_s).mean(axis=1) > 1e-6 * sf2
     assert np.max(np.abs(acq[idx][far] - acq_s[far])) < 1e-7
+    # the other two chunked entry points: the quadrature sweep (prediction-like values) and the IQR sweep (acquisition values)
+    sig = np.full(6, 0.3)
+    F, vF = va.gplite_quad(gp, Xs, sig, True)
+    F_s, vF_s = va.gplite_quad(gp, Xs[idx], sig, True)
+    assert relerr(np.asarray(F)[idx], F_s) < 1e-10 and np.max(np.abs(np.asarray(vF)[idx] - np.asarray(vF_s))) < 1e-10 * sf2
+    gl = np.exp(np.mean(np.stack([q["hyp"][:6] for q in gp["post"]], axis=1), axis=1))
+    gp_n = dict(gp, X_rescaled=gp["X"] / gl[None, :], sn2new=np.full(300, 0.05))
+    st_n = dict(st, gplengthscale=gl, ActiveImportanceSampling={"Xa": 1.1 * rng.standard_normal((32, 6))})
+    iqr = va.acqwrapper_vbmc(Xs, vp, gp_n, st_n, False, "acqviqr_vbmc", None)
+    iqr_s = va.acqwrapper_vbmc(Xs[idx], vp, gp_n, st_n, False, "acqviqr_vbmc", None)
+    assert np.max(np.abs(iqr[idx][far] - iqr_s[far])) < 1e-7
 
 
 @pytest.mark.parametrize("cfg", [(4, 60, 3, 3000), (7, 130, 1, 2500), (3, 17, 2, 1111)])

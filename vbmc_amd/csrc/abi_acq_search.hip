@@ -24,23 +24,18 @@ namespace {
 // What the IQR objective reads besides the prediction and the importance-sampling state: the inputs of the nearest-neighbour noise,
 // uploaded once per search.  launch() enqueues k_nn_noise, the tile kernel and the closing kernel on the points a.Xs holds.
 struct IqrTileObjective {
-  TmpBuf dgl, dXr, dsn, dsx, drec, dacqs;
+  NnNoise nn;
+  TmpBuf dsx, drec, dacqs;
   IqrTileArgs a{};
   int NT = 1, W = 1;
   vbmc_status upload(vbmc_ctx* ctx, const vbmc_gp* gp, const vbmc_acq_is* is, int lam, const vbmc_acqsearch_args& g) {
-    hipStream_t st = ctx->stream;
     const int N = gp->N, D = gp->D, S = gp->S;
     NT = is->Nap / 16;
     W = std::max(1, std::min(IQRT_MAXW, (N + 15) / 16));
-    HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
-    HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
-    HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
+    VB_TRY(nn.upload(ctx, gp, g.gplengthscale, g.X_rescaled, g.sn2new));
     HIP_TRY(ctx, dsx.alloc(ctx, (size_t)lam * 8));
     HIP_TRY(ctx, drec.alloc(ctx, (size_t)S * NT * 32 * 8));
     HIP_TRY(ctx, dacqs.alloc(ctx, (size_t)lam * S * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(dgl.p, g.gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dXr.p, g.X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dsn.p, g.sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
     a = IqrTileArgs{};
     a.N = N; a.D = D; a.S = S; a.Nhyp = gp->Nhyp; a.lam = lam; a.Na = is->Na; a.Nap = is->Nap; a.per_s = is->per_s;
     a.reg = g.var_regularized ? 1 : 0; a.TolVar = g.TolGPVar;
@@ -49,13 +44,7 @@ struct IqrTileObjective {
     return VBMC_OK;
   }
   void launch(hipStream_t st) {
-    switch ((a.D + 3) / 4) {
-#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3(1), dim3(64), 0, st, a.lam, a.N, a.D, a.Xs, dgl.as<double>(), \
-                                                 dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
-      NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
-#undef NN_CASE
-      default: break;
-    }
+    nn.launch(st, a.lam, a.Xs, dsx.as<double>());      // lam <= SRCH_MAXLAM = 16 points: one workgroup
     hipLaunchKernelGGL(k_acq_iqr_tile, dim3(NT, a.S), dim3(64 * W), IQRT_LDS_BYTES(W), st, a);
     hipLaunchKernelGGL(k_iqr_tile_final, dim3(1), dim3(64), 0, st, a, NT);
   }
@@ -94,8 +83,7 @@ vbmc_status search_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, const
   double sigma0 = 0.0;
   for (int d = 0; d < D; ++d) {
     const double lb = g.LB[d], ub = g.UB[d], x = g.x0[d], s = g.insigma[d];
-    if (!std::isfinite(lb) || !std::isfinite(ub) || !(lb < ub))
-      return set_err(ctx, VBMC_ERR_INVALID, "%s: the box needs finite bounds with LB < UB (coordinate %d: [%g, %g])", who, d + 1, lb, ub);
+    VB_TRY(check_box(ctx, who, g.LB, g.UB, d, d + 1));
     if (!(x >= lb && x <= ub)) return set_err(ctx, VBMC_ERR_INVALID, "%s: the start x0 is outside the box (coordinate %d: %g not in [%g, %g])", who, d + 1, x, lb, ub);
     if (!(s > 0.0) || !std::isfinite(s)) return set_err(ctx, VBMC_ERR_INVALID, "%s: insigma must be positive and finite", who);
     sigma0 = std::max(sigma0, s);

@@ -8,6 +8,16 @@
 
 #include "gp_kernels.h"
 
+// D -> QS = ceil(D / 4) steps of the MFMA distance blocks, the way DISPATCH_GPDT (gp_kernels.h) pads D; nothing runs for D > 32
+#define DISPATCH_QS_CASE(QSV, ...) case QSV: { constexpr int QS = QSV; __VA_ARGS__; } break;
+#define DISPATCH_QS(D_, ...)                                                                                          \
+  switch (((D_) + 3) / 4) {                                                                                           \
+    DISPATCH_QS_CASE(1, __VA_ARGS__) DISPATCH_QS_CASE(2, __VA_ARGS__) DISPATCH_QS_CASE(3, __VA_ARGS__)                \
+    DISPATCH_QS_CASE(4, __VA_ARGS__) DISPATCH_QS_CASE(5, __VA_ARGS__) DISPATCH_QS_CASE(6, __VA_ARGS__)                \
+    DISPATCH_QS_CASE(7, __VA_ARGS__) DISPATCH_QS_CASE(8, __VA_ARGS__)                                                 \
+    default: break;                                                                                                   \
+  }
+
 namespace {
 
 struct TmpBuf {   // a pooled device block (common.h pool_get/pool_put), returned to the context's pool on scope exit
@@ -611,6 +621,14 @@ vbmc_status pred_check(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Ns
   return VBMC_OK;
 }
 
+// the box of the searches and samplers that run in one: coordinates d0 .. d1 - 1 (host arrays)
+vbmc_status check_box(vbmc_ctx* ctx, const char* who, const double* LB, const double* UB, int d0, int d1) {
+  for (int d = d0; d < d1; ++d)
+    if (!std::isfinite(LB[d]) || !std::isfinite(UB[d]) || !(LB[d] < UB[d]))
+      return set_err(ctx, VBMC_ERR_INVALID, "%s: the box needs finite bounds with LB < UB (coordinate %d: [%g, %g])", who, d + 1, LB[d], UB[d]);
+  return VBMC_OK;
+}
+
 // pb.dXs, pb.dmb (and pb.ds2 / pb.dys where the caller has them) are allocated; their contents are read by pred_launch only
 vbmc_status pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, PredBufs& pb, bool want_ks, const double* qsigma, PredPlan& pl) {
   // output-dependent noise (noisefun(3) = 1) enters ys2 only, and only with a non-empty ystar (gplite_noisefun.m:198-207);
@@ -742,12 +760,8 @@ vbmc_status pred_launch(vbmc_ctx* ctx, PredBufs& pb, const PredPlan& pl) {
     return VBMC_OK;
   }
   // inner dimension of the MFMA distance blocks: QS = ceil(D / 4) steps
-#define PRED_KS_K(KERN, QSV) hipLaunchKernelGGL((KERN<QSV>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(), \
-                                               daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>())
-#define PRED_KS(QSV) case QSV: if (quad) PRED_KS_K(k_quad_ks, QSV); else PRED_KS_K(k_pred_ks, QSV); break;
-  switch ((D + 3) / 4) { PRED_KS(1) PRED_KS(2) PRED_KS(3) PRED_KS(4) PRED_KS(5) PRED_KS(6) PRED_KS(7) PRED_KS(8) default: break; }
-#undef PRED_KS
-#undef PRED_KS_K
+  DISPATCH_QS(D, hipLaunchKernelGGL((quad ? k_quad_ks<QS> : k_pred_ks<QS>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(),
+                                    daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>()))
   if (slab_pred) {
     TRSM_DISPATCH_CW(trsm_cw_for(N), {
       const size_t sl = TRSM_LDS_BYTES_CW(N, CW);
@@ -814,14 +828,30 @@ int pred_chunk_points(const vbmc_gp* gp, int Nstar) {
   const size_t ch = std::max<size_t>(256, (cap / 16) * 16);
   return (size_t)Nstar <= ch ? Nstar : (int)ch;
 }
-// rows [i0, i0 + n) of a column-major Ntot x C matrix -> contiguous n x C
-void gather_rows(const double* src, int Ntot, int C, int i0, int n, std::vector<double>& dst) {
-  dst.resize((size_t)n * C);
-  for (int c = 0; c < C; ++c) memcpy(dst.data() + (size_t)c * n, src + (size_t)c * Ntot + i0, (size_t)n * 8);
-}
-void scatter_rows(const std::vector<double>& src, int Ntot, int C, int i0, int n, double* dst) {
-  if (!dst) return;
-  for (int c = 0; c < C; ++c) memcpy(dst + (size_t)c * Ntot + i0, src.data() + (size_t)c * n, (size_t)n * 8);
+// The sweep over Nstar points in chunks of pred_chunk_points.  in / out: the per-point arrays, column-major Nstar x C each (a null one
+// stays null).  one(n, in, out) is the entry point itself on n points: rows [i0, i0 + n) of every input, contiguous n x C, and n x C
+// of zeros for every output, which go back into rows [i0, i0 + n).
+struct SweepCols { const double* in; double* out; int C; };
+template <class One>
+vbmc_status sweep_chunked(const vbmc_gp* gp, int Nstar, std::vector<SweepCols> cols, One one) {
+  const int CH = pred_chunk_points(gp, Nstar);
+  std::vector<std::vector<double>> buf(cols.size());
+  std::vector<const double*> in(cols.size(), nullptr);
+  std::vector<double*> out(cols.size(), nullptr);
+  for (int i0 = 0; i0 < Nstar; i0 += CH) {
+    const int n = std::min(CH, Nstar - i0);
+    for (size_t k = 0; k < cols.size(); ++k) {
+      if (!cols[k].in && !cols[k].out) continue;
+      buf[k].assign((size_t)n * cols[k].C, 0.0);
+      if (cols[k].in) in[k] = buf[k].data();
+      else out[k] = buf[k].data();
+      for (int c = 0; cols[k].in && c < cols[k].C; ++c) memcpy(buf[k].data() + (size_t)c * n, cols[k].in + (size_t)c * Nstar + i0, (size_t)n * 8);
+    }
+    VB_TRY(one(n, in.data(), out.data()));
+    for (size_t k = 0; k < cols.size(); ++k)
+      for (int c = 0; cols[k].out && c < cols[k].C; ++c) memcpy(cols[k].out + (size_t)c * Nstar + i0, buf[k].data() + (size_t)c * n, (size_t)n * 8);
+  }
+  return VBMC_OK;
 }
 }  // namespace
 
@@ -829,21 +859,11 @@ extern "C" vbmc_status vbmc_gp_pred(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar,
                                     const double* s2star, int ssflag, double* ymu, double* ys2, double* fmu, double* fs2) {
   if (!ctx) return VBMC_ERR_INVALID;
   if (gp && Xstar && Nstar > pred_chunk_points(gp, Nstar)) {
-    const int CH = pred_chunk_points(gp, Nstar), D = gp->D;
     const int nc = (ssflag && gp->S > 1) ? gp->S : 1;
-    std::vector<double> xs, s2c, ysc, o[4];
-    for (int i0 = 0; i0 < Nstar; i0 += CH) {
-      const int n = std::min(CH, Nstar - i0);
-      gather_rows(Xstar, Nstar, D, i0, n, xs);
-      if (s2star) s2c.assign(s2star + i0, s2star + i0 + n);
-      if (ystar) ysc.assign(ystar + i0, ystar + i0 + n);
-      for (auto& v : o) v.assign((size_t)n * nc, 0.0);
-      vbmc_status st_ = vbmc_gp_pred(ctx, gp, n, xs.data(), ystar ? ysc.data() : nullptr, s2star ? s2c.data() : nullptr, ssflag, o[0].data(), o[1].data(), o[2].data(), o[3].data());
-      if (st_ != VBMC_OK) return st_;
-      scatter_rows(o[0], Nstar, nc, i0, n, ymu); scatter_rows(o[1], Nstar, nc, i0, n, ys2);
-      scatter_rows(o[2], Nstar, nc, i0, n, fmu); scatter_rows(o[3], Nstar, nc, i0, n, fs2);
-    }
-    return VBMC_OK;
+    return sweep_chunked(gp, Nstar, {{Xstar, nullptr, gp->D}, {ystar, nullptr, 1}, {s2star, nullptr, 1}, {nullptr, ymu, nc}, {nullptr, ys2, nc},
+                                     {nullptr, fmu, nc}, {nullptr, fs2, nc}}, [&](int n, const double* const* in, double* const* out) {
+      return vbmc_gp_pred(ctx, gp, n, in[0], in[1], in[2], ssflag, out[3], out[4], out[5], out[6]);
+    });
   }
   PredBufs pb;
   VB_TRY(pred_on_device(ctx, "vbmc_gp_pred", gp, Nstar, Xstar, ystar, s2star, pb));
@@ -902,19 +922,10 @@ extern "C" vbmc_status vbmc_gp_quad(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar,
   for (int d = 0; d < D; ++d)
     if (!(sg[d] >= 0.0) || !std::isfinite(sg[d])) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_quad: sigma must be finite and non-negative");
   const int nc = (ssflag && S > 1) ? S : 1;
-  if (Nstar > pred_chunk_points(gp, Nstar)) {
-    const int CH = pred_chunk_points(gp, Nstar);
-    std::vector<double> xs, o[2];
-    for (int i0 = 0; i0 < Nstar; i0 += CH) {
-      const int n = std::min(CH, Nstar - i0);
-      gather_rows(mu, Nstar, D, i0, n, xs);
-      for (auto& v : o) v.assign((size_t)n * nc, 0.0);
-      vbmc_status st_ = vbmc_gp_quad(ctx, gp, n, xs.data(), sg.data(), 1, ssflag, o[0].data(), varF ? o[1].data() : nullptr);
-      if (st_ != VBMC_OK) return st_;
-      scatter_rows(o[0], Nstar, nc, i0, n, F); scatter_rows(o[1], Nstar, nc, i0, n, varF);
-    }
-    return VBMC_OK;
-  }
+  if (Nstar > pred_chunk_points(gp, Nstar))
+    return sweep_chunked(gp, Nstar, {{mu, nullptr, D}, {nullptr, F, nc}, {nullptr, varF, nc}}, [&](int n, const double* const* in, double* const* out) {
+      return vbmc_gp_quad(ctx, gp, n, in[0], sg.data(), 1, ssflag, out[1], out[2]);
+    });
   PredBufs pb;
   VB_TRY(pred_on_device(ctx, "vbmc_gp_quad", gp, Nstar, mu, nullptr, nullptr, pb, false, sg.data()));
   hipStream_t st = ctx->stream;
@@ -986,17 +997,40 @@ struct AcqInputs {
   const double *gplengthscale, *X_rescaled, *sn2new;   // acq_id 3
 };
 
+// The nearest-neighbour noise of acqfsn2, the IQR functions and the surrogate sampler's threshold: sn2new at the training input nearest
+// to each point in the lengthscale-rescaled space.  upload() copies the caller's three arrays as they are, once per call; launch()
+// enqueues k_nn_noise for n points at Xs (n x D, on the device) into out.
+struct NnNoise {
+  TmpBuf dgl, dXr, dsn;
+  int N = 0, D = 0;
+  vbmc_status upload(vbmc_ctx* ctx, const vbmc_gp* gp, const double* gplengthscale, const double* X_rescaled, const double* sn2new) {
+    N = gp->N; D = gp->D;
+    if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", D);
+    HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
+    HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
+    HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
+    HIP_TRY(ctx, hipMemcpyAsync(dgl.p, gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dXr.p, X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dsn.p, sn2new, (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream));
+    return VBMC_OK;
+  }
+  void launch(hipStream_t st, int n, const double* Xs, double* out) {
+    DISPATCH_QS(D, hipLaunchKernelGGL((k_nn_noise<QS>), dim3((n + 15) / 16), dim3(64), 0, st, n, N, D, Xs, dgl.as<double>(), dXr.as<double>(),
+                                      dsn.as<double>(), out))
+  }
+};
+
 // What k_acq reads besides the prediction: the O(K D) constants of the variational posterior's density and, for acqfsn2, the inputs of
 // the nearest-neighbour noise.  upload() fills everything of `a` but Xs / fmu / fs2 and the outputs; launch() enqueues k_nn_noise (acq_id 3)
 // and k_acq on the points a.Xs holds at that moment (shared by the sweep, vbmc_acq_eval, and the search, vbmc_acq_search).
 struct AcqConsts {
-  TmpBuf dmu, dhb, dgl, dXr, dsn, dsx;
+  TmpBuf dmu, dhb, dsx;
+  NnNoise nn;
   std::vector<double> hb;   // staging of the constants: alive until the caller has synchronised
   AcqArgs a{};
   vbmc_status upload(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int Nstar, const AcqInputs& in) {
     const int acq_id = in.acq_id, K = in.K, var_regularized = in.var_regularized;
     const double *vp_mu = in.vp_mu, *vp_sigma = in.vp_sigma, *vp_lambda = in.vp_lambda, *vp_w = in.vp_w;
-    const double *gplengthscale = in.gplengthscale, *X_rescaled = in.X_rescaled, *sn2new = in.sn2new;
     const double ymax = in.ymax, TolGPVar = in.TolGPVar;
     hipStream_t st = ctx->stream;
     const int N = gp->N, D = gp->D, S = gp->S;
@@ -1019,29 +1053,15 @@ struct AcqConsts {
     a.ymax = ymax; a.TolVar = TolGPVar;
     a.mu = dmu.as<double>(); a.isl = dhb.as<double>(); a.coef = dhb.as<double>() + (size_t)K * D;
     if (acq_id == 3) {
-      HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
-      HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
-      HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
-      HIP_TRY(ctx, hipMemcpyAsync(dgl.p, gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(ctx, hipMemcpyAsync(dXr.p, X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(ctx, hipMemcpyAsync(dsn.p, sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
+      VB_TRY(nn.upload(ctx, gp, in.gplengthscale, in.X_rescaled, in.sn2new));
       HIP_TRY(ctx, dsx.alloc(ctx, (size_t)Nstar * 8));
       a.sn2x = dsx.as<double>();
     }
     return VBMC_OK;
   }
   void launch(hipStream_t st) {
-    const int Nstar = a.Nstar, N = a.N, D = a.D, K = a.K;
-    if (a.acq_id == 3) {
-      switch ((D + 3) / 4) {
-#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nstar + 15) / 16), dim3(64), 0, st, Nstar, N, D, a.Xs, \
-                                                 dgl.as<double>(), dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
-        NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
-#undef NN_CASE
-        default: break;
-      }
-    }
-    hipLaunchKernelGGL(k_acq, dim3((Nstar + 255) / 256), dim3(256), (size_t)(2 * K * D + K) * 8, st, a);
+    if (a.acq_id == 3) nn.launch(st, a.Nstar, a.Xs, dsx.as<double>());
+    hipLaunchKernelGGL(k_acq, dim3((a.Nstar + 255) / 256), dim3(256), (size_t)(2 * a.K * a.D + a.K) * 8, st, a);
   }
 };
 }  // namespace
@@ -1055,20 +1075,12 @@ vbmc_status acq_eval_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, int
   if (acq_id < 0 || acq_id > 3) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "acquisition function id %d not accelerated (0 acqf, 1 acqflog, 2 acqus, 3 acqfsn2)", acq_id);
   if (acq_id == 3 && (!gplengthscale || !X_rescaled || !sn2new))
     return set_err(ctx, VBMC_ERR_INVALID, "%s: acqfsn2 needs gplengthscale, X_rescaled and sn2new", who);
-  if (gp && Xs && Nstar > pred_chunk_points(gp, Nstar)) {
-    const int CH = pred_chunk_points(gp, Nstar);
-    std::vector<double> xs, o[3];
-    for (int i0 = 0; i0 < Nstar; i0 += CH) {
-      const int n = std::min(CH, Nstar - i0);
-      gather_rows(Xs, Nstar, gp->D, i0, n, xs);
-      for (auto& v : o) v.assign(n, 0.0);
-      vbmc_status st_ = acq_eval_impl(ctx, who, gp, n, xs.data(), acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
-                                      gplengthscale, X_rescaled, sn2new, delta, o[0].data(), o[1].data(), o[2].data());
-      if (st_ != VBMC_OK) return st_;
-      scatter_rows(o[0], Nstar, 1, i0, n, acq); scatter_rows(o[1], Nstar, 1, i0, n, fbar); scatter_rows(o[2], Nstar, 1, i0, n, vtot);
-    }
-    return VBMC_OK;
-  }
+  if (gp && Xs && Nstar > pred_chunk_points(gp, Nstar))
+    return sweep_chunked(gp, Nstar, {{Xs, nullptr, gp->D}, {nullptr, acq, 1}, {nullptr, fbar, 1}, {nullptr, vtot, 1}},
+                         [&](int n, const double* const* in, double* const* out) {
+      return acq_eval_impl(ctx, who, gp, n, in[0], acq_id, K, vp_mu, vp_sigma, vp_lambda, vp_w, ymax, var_regularized, TolGPVar,
+                           gplengthscale, X_rescaled, sn2new, delta, out[1], out[2], out[3]);
+    });
   PredBufs pb;
   VB_TRY(pred_on_device(ctx, who, gp, Nstar, Xs, nullptr, nullptr, pb, false, delta));
   hipStream_t st = ctx->stream;
@@ -1149,6 +1161,24 @@ vbmc_status acq_is_ctmp_resident(vbmc_ctx* ctx, const vbmc_gp* gp, vbmc_acq_is* 
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return VBMC_OK;
 }
+
+// A state with lnw made of device buffers in the state's own layouts (Xa: Na x D [x S]; lnw, fs2a: S x Nap rows), behind whatever wrote
+// them in the context's stream.
+vbmc_status acq_is_from_device(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, int Na, int per_sample_inputs, const double* Xa,
+                               const double* lnw, const double* fs2a, vbmc_acq_is** out) {
+  vbmc_acq_is* h = nullptr;
+  VB_TRY(acq_is_new(ctx, gp, Na, per_sample_inputs, true, &h));
+  auto fail = [&](vbmc_status s_) { vbmc_acq_is_free(ctx, h); return s_; };
+  const size_t nxa = (size_t)Na * gp->D * (per_sample_inputs ? gp->S : 1), np = (size_t)gp->S * h->Nap;
+  hipError_t e1 = hipMemcpyAsync(h->Xa, Xa, nxa * 8, hipMemcpyDeviceToDevice, ctx->stream);
+  hipError_t e2 = hipMemcpyAsync(h->lnw, lnw, np * 8, hipMemcpyDeviceToDevice, ctx->stream);
+  hipError_t e3 = hipMemcpyAsync(h->fs2a, fs2a, np * 8, hipMemcpyDeviceToDevice, ctx->stream);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(set_err(ctx, VBMC_ERR_HIP, "%s: device copy into the state failed", who));
+  const vbmc_status cs = acq_is_ctmp_resident(ctx, gp, h);
+  if (cs != VBMC_OK) return fail(cs);
+  *out = h;
+  return VBMC_OK;
+}
 }  // namespace
 
 // the host-pointer entry: its uploads, then the device-resident routine (the way pred_on_device / pred_on_device_resident are split)
@@ -1215,41 +1245,22 @@ extern "C" vbmc_status vbmc_acq_iqr_eval(vbmc_ctx* ctx, const vbmc_gp* gp, const
   if (!is || !acq || !gplengthscale || !X_rescaled || !sn2new) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_iqr_eval: bad arguments");
   if (gp && (is->N != gp->N || is->S != gp->S || is->D != gp->D))
     return set_err(ctx, VBMC_ERR_INVALID, "vbmc_acq_iqr_eval: importance-sampling state belongs to a different GP");
-  if (gp && Xs && Nstar > pred_chunk_points(gp, Nstar)) {
-    const int CH = pred_chunk_points(gp, Nstar);
-    std::vector<double> xs, o[3];
-    for (int i0 = 0; i0 < Nstar; i0 += CH) {
-      const int n = std::min(CH, Nstar - i0);
-      gather_rows(Xs, Nstar, gp->D, i0, n, xs);
-      for (auto& v : o) v.assign(n, 0.0);
-      vbmc_status st_ = vbmc_acq_iqr_eval(ctx, gp, is, n, xs.data(), gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar,
-                                          o[0].data(), o[1].data(), o[2].data());
-      if (st_ != VBMC_OK) return st_;
-      scatter_rows(o[0], Nstar, 1, i0, n, acq); scatter_rows(o[1], Nstar, 1, i0, n, fbar); scatter_rows(o[2], Nstar, 1, i0, n, vtot);
-    }
-    return VBMC_OK;
-  }
+  if (gp && Xs && Nstar > pred_chunk_points(gp, Nstar))
+    return sweep_chunked(gp, Nstar, {{Xs, nullptr, gp->D}, {nullptr, acq, 1}, {nullptr, fbar, 1}, {nullptr, vtot, 1}},
+                         [&](int n, const double* const* in, double* const* out) {
+      return vbmc_acq_iqr_eval(ctx, gp, is, n, in[0], gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar, out[1], out[2], out[3]);
+    });
   PredBufs pb;
   VB_TRY(pred_on_device(ctx, "vbmc_acq_iqr_eval", gp, Nstar, Xs, nullptr, nullptr, pb, true));
   hipStream_t st = ctx->stream;
   const int N = gp->N, D = gp->D, S = gp->S;
-  TmpBuf dgl, dXr, dsn, dsx, dacqs, dres;
-  HIP_TRY(ctx, dgl.alloc(ctx, (size_t)D * 8));
-  HIP_TRY(ctx, dXr.alloc(ctx, (size_t)N * D * 8));
-  HIP_TRY(ctx, dsn.alloc(ctx, (size_t)N * 8));
+  NnNoise nn;
+  TmpBuf dsx, dacqs, dres;
+  VB_TRY(nn.upload(ctx, gp, gplengthscale, X_rescaled, sn2new));
   HIP_TRY(ctx, dsx.alloc(ctx, (size_t)Nstar * 8));
   HIP_TRY(ctx, dacqs.alloc(ctx, (size_t)Nstar * S * 8));
   HIP_TRY(ctx, dres.alloc(ctx, (size_t)3 * Nstar * 8));
-  HIP_TRY(ctx, hipMemcpyAsync(dgl.p, gplengthscale, (size_t)D * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dXr.p, X_rescaled, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dsn.p, sn2new, (size_t)N * 8, hipMemcpyHostToDevice, st));
-  switch ((D + 3) / 4) {
-#define NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nstar + 15) / 16), dim3(64), 0, st, Nstar, N, D, pb.dXs.as<double>(), \
-                                                 dgl.as<double>(), dXr.as<double>(), dsn.as<double>(), dsx.as<double>()); break;
-    NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
-#undef NN_CASE
-    default: break;
-  }
+  nn.launch(st, Nstar, pb.dXs.as<double>(), dsx.as<double>());
   IqrArgs a{};
   a.N = N; a.D = D; a.S = S; a.Nhyp = gp->Nhyp; a.Nstar = Nstar; a.Na = is->Na; a.Nap = is->Nap; a.per_s = is->per_s;
   a.Xs = pb.dXs.as<double>(); a.Xa = is->Xa; a.hyp = gp->hyp; a.Xc = pb.dXc.as<double>(); a.muv = pb.dmuv.as<double>();

@@ -1,9 +1,11 @@
 // C-ABI entry points of the surrogate sampler: vbmc_gp_surrogate_sample and vbmc_gp_surrogate_sample_rng_dump (include/vbmc_hip.h).
-// The kernels are gp_surrogate_kernels.h; the sampler is is_core_begin / is_core_run (abi_is_sample.hip) with the surrogate's target.
-// Host side: validation, the start (the caller's, or draws of k_vp_draw) clipped into the box and written into the sampler's walker
-// buffer, the noise estimate in the same stream in front of the chain, the closing k_gs_finish and the copies back.
-// Included after abi_vp_tools.hip (vpt_pack, vpt_gen_host).
+// The kernels are gp_surrogate_kernels.h; the sampler is the ensemble slice sampler of is_core.h with this file's target: E ensembles
+// decoupled from the hyper-samples, every candidate under all of them (k_gs_pred into Sg x E x C means and variances, k_gs_target
+// into the E x C values), no limit on the records.  Host side: validation, the start (the caller's, or draws of k_vp_draw) clipped
+// into the box and written into the sampler's walker buffer, the noise estimate (abi_gp.hip: NnNoise) in the same stream in front of
+// the chain, the closing k_gs_finish and the copies back.  Included after abi_vp_tools.hip (vpt_pack, vpt_gen_host).
 #include "gp_surrogate_kernels.h"
+#include "is_core.h"
 
 #define GS_DEFAULT_NNN 20000
 #define GS_MAX_E 64
@@ -50,15 +52,10 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   const int Nm = (int)nm_ll;
   const long long burn_ll = g.burnin >= 0 ? g.burnin : (g.Ns + 4) / 5;     // gplite_sample.m:71
   if (burn_ll > 0x3fffffff) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin = %lld is too large", who, burn_ll);
-  IsParams p{W, Nm, g.thin, (int)burn_ll, g.spec, g.max_steps, g.max_shrink, g.chunk, g.rng_mode, g.Mmax, g.seed, g.U};
-  p.target = IS_TARGET_SURROGATE; p.E = E; p.beta = g.beta;
-  VB_TRY(is_check_params(ctx, who, gp, p));
+  const IsParams p{W, Nm, g.thin, (int)burn_ll, g.spec, g.max_steps, g.max_shrink, g.chunk, g.rng_mode, g.Mmax, g.seed, g.U};
+  VB_TRY(is_check_params(ctx, who, D, E, 0, p));
   if ((long long)g.thin * Nm + burn_ll > 0x3fffffff) return set_err(ctx, VBMC_ERR_INVALID, "%s: burnin + thin Nm is too large", who);
-  for (int d = 0; d < D; ++d) {
-    const double lb = g.LB[d], ub = g.UB[d];
-    if (!std::isfinite(lb) || !std::isfinite(ub) || !(lb < ub))
-      return set_err(ctx, VBMC_ERR_INVALID, "%s: the box needs finite bounds with LB < UB (coordinate %d: [%g, %g])", who, d + 1, lb, ub);
-  }
+  VB_TRY(check_box(ctx, who, g.LB, g.UB, 0, D));
   const bool noise = g.sn2new != nullptr;
   const int Nnn = g.Nnn ? g.Nnn : GS_DEFAULT_NNN;
   if (noise) {
@@ -83,11 +80,21 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   // vt: VarThresh | sn2_avg | the sum | the partials of k_gs_sum
   const int nb = noise ? std::min((Nnn + GS_SUM_T - 1) / GS_SUM_T, VPT_MAXBLK) : 0;
   TmpBuf dV, dX0, dNn;
+  NnNoise nn;
   HIP_TRY(ctx, dV.alloc(ctx, (3 + (size_t)VPT_MAXBLK) * 8));
   double* d_vt = dV.as<double>();
-  p.d_vt = d_vt;
+  // behind the E x C values:  ymu | ys2, S x E x C each
   IsCore c;
-  VB_TRY(is_core_begin(ctx, gp, who, p, c));
+  const size_t nsv = (size_t)S * E * is_round_candidates(p);
+  VB_TRY(is_core_begin(ctx, gp, who, p, E, 2 * nsv, c));
+  c.pg.fmu = c.d_extra; c.pg.ys2 = c.d_extra + nsv;
+  IsPredKernel pred;
+  void (*gs_pred)(IsPredArgs) = nullptr;
+  DISPATCH_QS(D, gs_pred = k_gs_pred<QS>)
+  VB_TRY(pred.set(ctx, N, D, gs_pred));
+  GsTargetArgs tg{};
+  tg.S = S; tg.E = E; tg.C = c.C; tg.nstride = c.pg.nstride; tg.ncand = c.pg.ncand; tg.mask = c.a.mask; tg.ymu = c.pg.fmu; tg.ys2 = c.pg.ys2;
+  tg.vt = d_vt; tg.beta = g.beta; tg.val = c.d_val;
   std::vector<double> hb(2 * (size_t)D), h0;
   memcpy(hb.data(), g.LB, (size_t)D * 8);
   memcpy(hb.data() + D, g.UB, (size_t)D * 8);
@@ -112,33 +119,29 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   }
   hipLaunchKernelGGL(k_gs_start, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, W, D, E, d_x0, c.a.LB, c.a.UB, c.a.x, d_x0c);
 
-  // ---- the noise estimate: gl | X_rescaled | sn2new | the draws | sn2new at each draw's nearest row
+  // ---- the noise estimate: the draws | sn2new at each draw's nearest row
   double* d_nn = nullptr;
   if (noise) {
-    const size_t nX = (size_t)N * D, nup = (size_t)D + nX + N;
-    HIP_TRY(ctx, dNn.alloc(ctx, (nup + (size_t)Nnn * D + Nnn) * 8));
-    std::vector<double> hn(nup);
-    memcpy(hn.data(), g.gplengthscale, (size_t)D * 8);
-    memcpy(hn.data() + D, g.X_rescaled, nX * 8);
-    memcpy(hn.data() + D + nX, g.sn2new, (size_t)N * 8);
-    double *d_gl = dNn.as<double>(), *d_xr = d_gl + D, *d_sn = d_xr + nX, *d_xx = d_sn + N;
+    HIP_TRY(ctx, dNn.alloc(ctx, ((size_t)Nnn * D + Nnn) * 8));
+    double* d_xx = dNn.as<double>();
     d_nn = d_xx + (size_t)Nnn * D;
-    HIP_TRY(ctx, hipMemcpyAsync(d_gl, hn.data(), nup * 8, hipMemcpyHostToDevice, st));
+    VB_TRY(nn.upload(ctx, gp, g.gplengthscale, g.X_rescaled, g.sn2new));
     VB_TRY(gs_draw(ctx, who, vp, pk, Nnn, g.seed + 1, genn, d_xx));
-    switch ((D + 3) / 4) {
-#define GS_NN_CASE(QSV) case QSV: hipLaunchKernelGGL((k_nn_noise<QSV>), dim3((Nnn + 15) / 16), dim3(64), 0, st, Nnn, N, D, d_xx, d_gl, d_xr, d_sn, d_nn); break;
-      GS_NN_CASE(1) GS_NN_CASE(2) GS_NN_CASE(3) GS_NN_CASE(4) GS_NN_CASE(5) GS_NN_CASE(6) GS_NN_CASE(7) GS_NN_CASE(8)
-#undef GS_NN_CASE
-      default: return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d not accelerated", D);
-    }
+    nn.launch(st, Nnn, d_xx, d_nn);
     hipLaunchKernelGGL(k_gs_sum, dim3(nb), dim3(GS_SUM_T), 0, st, Nnn, d_nn, d_vt + 3);
     hipLaunchKernelGGL(k_vp_reduce, dim3(1), dim3(VPT_T), 0, st, d_vt + 3, nb, 1, d_vt + 2);
     hipLaunchKernelGGL(k_gs_thresh, dim3(1), dim3(64), 0, st, d_vt + 2, Nnn, d_vt);
   }
   HIP_TRY(ctx, hipGetLastError());
 
-  const IsOutputs o{nullptr, nullptr, nullptr, nullptr, g.funccount, g.performed, g.rounds, nullptr};
-  VB_TRY(is_core_run(ctx, gp, who, p, c, o, nullptr));
+  // ---- the chain: a round's candidates under every hyper-sample, then the target
+  IsCounters n;
+  const dim3 pgrid((c.C + 15) / 16, E, S), tgrid((c.C + 63) / 64, E);
+  VB_TRY(is_core_run(ctx, who, p, c, [&] {
+    pred.launch(st, pgrid, c.pg);
+    hipLaunchKernelGGL(k_gs_target, tgrid, dim3(64), 0, st, tg);
+  }, nullptr, n));
+  is_write_counters(n, g.funccount, g.performed, g.rounds);
 
   // ---- the recorded walkers into X; the copies back
   const size_t nXo = (size_t)g.Ns * D, nr = (size_t)E * Nm;
@@ -162,9 +165,7 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   if (g.sn2_nn && noise) HIP_TRY(ctx, hipMemcpyAsync(g.sn2_nn, d_nn, (size_t)Nnn * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(hv, d_vt, sizeof hv, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (g.logp)
-    for (int e = 0; e < E; ++e)
-      for (int i = 0; i < Nm; ++i) g.logp[e + (size_t)E * i] = hr[(size_t)e * Nm + i];
+  if (g.logp) is_unpack_rows(hr, E, Nm, Nm, g.logp, 1, E);
   if (g.varthresh_out) *g.varthresh_out = hv[0];
   if (g.sn2_avg_out) *g.sn2_avg_out = hv[1];
   return VBMC_OK;

@@ -1,7 +1,9 @@
 // C-ABI entry points of the one-call set-up of the IMIQR importance sampler: vbmc_acq_is_setup and vbmc_acq_is_setup_rng_dump
 // (include/vbmc_hip.h).  Step 1 and the resampling are is_setup_kernels.h; the prediction of the Step 1 points is k_is_pred on the
 // set-up the sampler uses anyway (every ensemble's point buffer holds the same Na1 points); the starting walkers are written where
-// is_core_run (abi_is_sample.hip) expects them, so that Step 2 follows in the same stream.  Included after abi_is_sample.hip.
+// the sampler (is_core.h) expects them, so that Step 2 -- the IMIQR target of abi_is_sample.hip: imiqr_begin, imiqr_rounds,
+// imiqr_close -- follows in the same stream.
+#include "is_core.h"
 #include "is_setup_kernels.h"
 
 namespace {
@@ -46,7 +48,7 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   // Step 1 alone: the sampler's routines still provide the prediction's set-up, for the smallest sampler there is
   IsParams p{step2 ? g.W : 4, step2 ? Nm : 1, step2 ? g.thin : 1, step2 ? g.burnin : -1, g.spec, g.max_steps, g.max_shrink, g.chunk,
              (g.rng_mode == 1 && g.U && step2) ? 1 : 0, g.Mmax, g.seed, step2 ? g.U : nullptr};
-  VB_TRY(is_check_params(ctx, who, gp, p));
+  VB_TRY(is_check_params(ctx, who, D, S, VBMC_LIM_NA, p));
   const int W = step2 ? g.W : 0;
   double wsum = 0.0;
   bool vp_ok = true;
@@ -71,7 +73,8 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   }
 
   IsCore c;
-  VB_TRY(is_core_begin(ctx, gp, who, p, c));
+  ImiqrTarget t;
+  VB_TRY(imiqr_begin(ctx, gp, who, p, c, t));
   hipStream_t st = ctx->stream;
   // one block of fp64:  mu | sigma | lambda | w | B | geo (D + 1) | comp (12 K) | Xa1 | P1 | logp fmu fs2 ys2 (S x Na1 each) | lpdf |
   //                     lnw1 fs2a1 (S x Nap1) | lw (S x Na1) | x0
@@ -120,15 +123,16 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   IsPredArgs pg1 = c.pg;
   pg1.P = k.P; pg1.mask = nullptr; pg1.ncand = dNc1.as<int>(); pg1.nstride = 1; pg1.C = Na1;
   pg1.logp = d_pv; pg1.fmu = d_pv + nv1; pg1.fs2 = d_pv + 2 * nv1; pg1.ys2 = d_pv + 3 * nv1;
-  c.pk.launch(st, pg1, (Na1 + 15) / 16);
+  t.pk.launch(st, dim3((Na1 + 15) / 16, S), pg1);
   hipLaunchKernelGGL(k_is_proposal, dim3(Nap1), dim3(64), 0, st, k);
   if (step2) hipLaunchKernelGGL(k_is_resample, dim3(S), dim3(64), 0, st, k);
   HIP_TRY(ctx, hipGetLastError());
 
   // ---- Step 2 behind it in the same stream; the Step 1 arrays come back with whatever else the caller asked for
   IsBadStart bad;
-  const IsOutputs o{g.Xa, g.lnw, g.fs2a, g.logp, g.funccount, g.performed, g.rounds, g.state};
-  if (step2) VB_TRY(is_core_run(ctx, gp, who, p, c, o, &bad));
+  IsCounters n;
+  if (step2) VB_TRY(imiqr_rounds(ctx, who, p, c, t, &bad, n));
+  if (step2 && bad.n == 0) VB_TRY(imiqr_close(ctx, gp, who, c, t, n, {g.Xa, g.lnw, g.fs2a, g.logp, g.funccount, g.performed, g.rounds, g.state}));
   std::vector<double> hl, hf, hg;
   std::vector<int> hi;
   if (g.Xa1) HIP_TRY(ctx, hipMemcpyAsync(g.Xa1, k.Xa1, nX1 * 8, hipMemcpyDeviceToHost, st));
@@ -140,39 +144,22 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   if (step2 && g.x0) HIP_TRY(ctx, hipMemcpyAsync(g.x0, k.x0, (size_t)W * D * S * 8, hipMemcpyDeviceToHost, st));
   if (step2 && g.idx0) { hi.resize((size_t)W * S); HIP_TRY(ctx, hipMemcpyAsync(hi.data(), k.idx0, (size_t)W * S * sizeof(int), hipMemcpyDeviceToHost, st)); }
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  for (int s = 0; s < S; ++s)
-    for (int i = 0; i < Na1; ++i) {
-      if (g.lnw1) g.lnw1[s + (size_t)S * i] = hl[(size_t)s * Nap1 + i];
-      if (g.fs2a1) g.fs2a1[i + (size_t)Na1 * s] = hf[(size_t)s * Nap1 + i];
-    }
+  if (g.lnw1) is_unpack_rows(hl, S, Na1, Nap1, g.lnw1, 1, S);
+  if (g.fs2a1) is_unpack_rows(hf, S, Na1, Nap1, g.fs2a1, Na1, 1);
   if (g.LB) memcpy(g.LB, hg.data(), (size_t)D * 8);
   if (g.UB) memcpy(g.UB, hg.data() + D, (size_t)D * 8);
   if (step2 && g.idx0) for (size_t j = 0; j < hi.size(); ++j) g.idx0[j] = hi[j];
   if (step2 && bad.n > 0) {
     if (g.n_bad) *g.n_bad = bad.n;
     if (g.bad) memcpy(g.bad, bad.mask.data(), (size_t)W * S);
-    if (g.funccount) *g.funccount = (int64_t)W * S;
-    if (g.performed) *g.performed = (int64_t)W * S;
-    if (g.rounds) { g.rounds[0] = 0; g.rounds[1] = 0; }
+    is_write_counters({(long long)W * S, (long long)W * S, 0, 0}, g.funccount, g.performed, g.rounds);
     return VBMC_OK;
   }
   if (step2 && g.bad) memset(g.bad, 0, (size_t)W * S);
   if (!step2) {
-    if (g.funccount) *g.funccount = 0;
-    if (g.performed) *g.performed = 0;
-    if (g.rounds) { g.rounds[0] = 0; g.rounds[1] = 0; }
-    if (g.state) {                                     // the state of the Na1 shared points with lnw1 (:148-157 with Nmcmc_samples = 0)
-      vbmc_acq_is* h = nullptr;
-      VB_TRY(acq_is_new(ctx, gp, Na1, 0, true, &h));
-      auto fail = [&](vbmc_status s_) { vbmc_acq_is_free(ctx, h); return s_; };
-      hipError_t e1 = hipMemcpyAsync(h->Xa, k.Xa1, nX1 * 8, hipMemcpyDeviceToDevice, st);
-      hipError_t e2 = hipMemcpyAsync(h->lnw, k.lnw1, np1 * 8, hipMemcpyDeviceToDevice, st);
-      hipError_t e3 = hipMemcpyAsync(h->fs2a, k.fs2a1, np1 * 8, hipMemcpyDeviceToDevice, st);
-      if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(set_err(ctx, VBMC_ERR_HIP, "%s: device copy into the state failed", who));
-      const vbmc_status cs = acq_is_ctmp_resident(ctx, gp, h);
-      if (cs != VBMC_OK) return fail(cs);
-      *g.state = h;
-    }
+    is_write_counters({0, 0, 0, 0}, g.funccount, g.performed, g.rounds);
+    // the state of the Na1 shared points with lnw1 (:148-157 with Nmcmc_samples = 0)
+    if (g.state) VB_TRY(acq_is_from_device(ctx, gp, who, Na1, 0, k.Xa1, k.lnw1, k.fs2a1, g.state));
   }
   return VBMC_OK;
 }
