@@ -94,7 +94,7 @@ def mc_case(va, seed, D, N, K, S, meanfun, Ns, ent_form, lj_form, **switches):
 
 
 def lane_role_fits(D, K, N, S):
-    """vbmc_amd/csrc/abi_elbo.hip: the role's staged inputs within 48 KB of the lane launch's dynamic LDS"""
+    """vbmc_amd/csrc/elbo_launch_plan.h: the role's staged inputs within 48 KB of the lane launch's dynamic LDS"""
     return (((N + 63) // 64) * 64 * (D + 4) + S * (3 * D + 2) + (D * K + 4 * K + 2 * D + 2) + D) * 8 <= 48 * 1024
 
 

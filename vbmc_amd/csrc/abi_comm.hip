@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "elbo_pass.h"   // the plan, the pass and its read-back; the slot functions used below are abi_elbo_slots.hip's, included before this file
+
 namespace {
 
 struct RcclApi {
@@ -81,7 +83,7 @@ struct vbmc_comm {
   bool local_copy = false;
   std::vector<hipEvent_t> lc_ev;
   // the pipelined form's exchange stream per local device: the collectives of consecutive batches in issue order on ONE stream that
-  // holds nothing else (a pass on a slot stream is ordered after the context's stream, abi_elbo.hip: slot_ctx -- with the exchange on
+  // holds nothing else (a pass on a slot stream is ordered after the context's stream, abi_elbo_slots.hip: slot_ctx -- with the exchange on
   // the context's stream every pass would queue behind the previous batch's exchange)
   std::vector<hipStream_t> xs;
   // pipelined form (vbmc_elbo_multi_submit / _collect): per slot its own exchange blocks, a pinned landing block for the gathered
@@ -530,7 +532,7 @@ static vbmc_status multi_submit_impl(vbmc_comm* c, const vbmc_gp* const* gps, co
       if (th.size() < (size_t)T * n) th.resize((size_t)T * n);
       for (int q = 0; q < n; ++q) memcpy(&th[(size_t)q * T], a->theta + (size_t)(g + (size_t)q * G) * T, T * sizeof(double));
       sub.theta = th.data();
-      // the pass on the slot's own stream (abi_elbo.hip: slot_ctx), the pick after it on the same stream; the exchange on the
+      // the pass on the slot's own stream (abi_elbo_slots.hip: slot_ctx), the pick after it on the same stream; the exchange on the
       // communicator's exchange stream, ordered after the pick by an event: the collectives of one communicator in issue order on one
       // stream, the passes of consecutive batches overlapping
       vbmc_ctx* sc = ctx;
@@ -552,7 +554,7 @@ static vbmc_status multi_submit_impl(vbmc_comm* c, const vbmc_gp* const* gps, co
     // measured equal in round 4)
     hipStream_t xst = ps->stream;
     if (ps != ctx) {
-      if (!c->xs[i]) {     // beside both slot streams (abi_elbo.hip: stream_beside); they exist and, for the first batch, are idle but for this pass
+      if (!c->xs[i]) {     // beside both slot streams (abi_elbo_slots.hip: stream_beside); they exist and, for the first batch, are idle but for this pass
         hipStream_t both[2];
         int nb = 0;
         for (vbmc_ctx* sub : ctx->slot_sub) if (sub) both[nb++] = sub->stream;

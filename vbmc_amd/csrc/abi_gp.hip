@@ -20,16 +20,6 @@
 
 namespace {
 
-struct TmpBuf {   // a pooled device block (common.h pool_get/pool_put), returned to the context's pool on scope exit
-  void* p = nullptr;
-  vbmc_ctx* owner = nullptr;
-  bool is_view = false;   // a window into another block (the packed input block of gp_factorize): nothing to return
-  ~TmpBuf() { if (p && !is_view) pool_put(owner, p); }
-  hipError_t alloc(vbmc_ctx* ctx, size_t bytes) { owner = ctx; return pool_get(ctx, bytes, &p); }
-  void view(void* q) { p = q; is_view = true; }
-  template <typename T> T* as() { return (T*)p; }
-};
-
 // gplite_noisefun.m:176-210 on the host (O(N)): returns per-point sn2 (length N)
 void noise_vector(const int32_t nf[3], const double* hn, int N, const double* y, const double* s2, std::vector<double>& sn2) {
   int idx = 0;
@@ -235,7 +225,7 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, const char* who, int N, int D, int S, in
   f.d_pfd = dal.as<double>() + (size_t)S * N;
   const int moff = Ncov + Nnoise;
   // (small blocks by a kernel that reads the pinned block over the host link instead of the copy engine: the hand-over from a DMA
-  // copy to the first kernel of the stream is 8-9 us on top of the copy's 6.5 -- abi_elbo.hip: copy_by_kernel)
+  // copy to the first kernel of the stream is 8-9 us on top of the copy's 6.5 -- elbo_pass.h: copy_by_kernel)
   if (copy_by_kernel(in_doubles * 8))
     hipLaunchKernelGGL(k_copy_f64, dim3((unsigned)std::min<size_t>((in_doubles + 255) / 256, 1024)), dim3(256), 0, st, in_doubles, (const double*)hin,
                        dIn.as<double>());

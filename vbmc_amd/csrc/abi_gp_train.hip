@@ -1,7 +1,7 @@
 // C-ABI entry points for the two device-resident halves of gplite_train: vbmc_gp_slice_sample, vbmc_gp_train_optimize (and
 // vbmc_slice_rng_dump) (include/vbmc_hip.h).  Both turn candidate hyper-parameter vectors into GP objective values on the device
 // (gpobj_kernels.h) and are driven from the host in chunks of ROUNDS; what they share on the host is in the namespace below.
-// Included after abi_gp.hip, whose TmpBuf, noise_nhyp and gp_launch_* it uses.
+// Included after abi_gp.hip, whose noise_nhyp and gp_launch_* it uses.
 #include <algorithm>
 #include <cmath>
 #include <limits>

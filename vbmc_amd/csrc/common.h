@@ -23,7 +23,7 @@ struct DevBuf {
   size_t cap = 0;
 };
 
-// Pool of device blocks for the per-call temporaries of the GP entry points (abi_gp.hip): hipMalloc/hipFree
+// Pool of device blocks for the per-call temporaries of the entry points (TmpBuf below): hipMalloc/hipFree
 // cost ~0.1 ms each and synchronise the device, which dominated small calls.  Blocks are handed out only
 // between a call's start and its final stream synchronisation, so reuse across calls is safe.
 struct PoolBlk {
@@ -42,8 +42,6 @@ struct vbmc_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool overlap = true;
   bool prof_alone = false;     // vbmc_ctx_set_profiling(ctx, 2): nothing forked beside the dominant kernel while it is timed
-  void* bounce = nullptr;                       // (unused since round 2: see d2h_bounced)
-  hipEvent_t bounce_ev[2] = {nullptr, nullptr};
   std::string err;
   int num_cu = 256;
   // grow-only scratch
@@ -58,12 +56,12 @@ struct vbmc_ctx {
   int last_ent_form = 0, last_lj_form = 0;     // the kernels of the last ELBO pass enqueued here (VBMC_ENTFORM_* / VBMC_LJFORM_*, vbmc_ctx_last_launch)
   std::vector<PoolBlk> pool;
   size_t pool_bytes = 0;
-  // pipelined evaluations (vbmc_elbo_submit / vbmc_elbo_collect, abi_elbo.hip): each of the two slots has its own pinned
+  // pipelined evaluations (vbmc_elbo_submit / vbmc_elbo_collect, abi_elbo_slots.hip): each of the two slots has its own pinned
   // staging block (swapped into `pin` for the duration of a submit), the plan of the pass in flight and its completion event
   void* slot_pin[2] = {nullptr, nullptr};
   size_t slot_pin_cap[2] = {0, 0};
   hipEvent_t slot_ev[2] = {nullptr, nullptr};
-  void* slot_plan[2] = {nullptr, nullptr};     // ElboPlan*
+  void* slot_plan[2] = {nullptr, nullptr};     // SlotPlan* (elbo_pass.h)
   bool slot_busy[2] = {false, false};
   // Round 4: FOUR slots on TWO streams.  Slot s runs on child context s & 1 (own stream, own scratch, created on first use) as that
   // child's slot s >> 1 -- two passes queued per stream, two streams: the small kernels at the head and tail of one pass and the last round
@@ -153,6 +151,18 @@ static inline void pool_put(vbmc_ctx* ctx, void* p) {
   for (auto& b : ctx->pool)
     if (b.p == p) { b.busy = false; return; }
 }
+
+// A pooled device block for the length of a scope: returned to the context's pool on scope exit, on every path
+struct TmpBuf {
+  void* p = nullptr;
+  vbmc_ctx* owner = nullptr;
+  bool is_view = false;   // a window into another block (the packed input block of gp_factorize): nothing to return
+  ~TmpBuf() { if (p && !is_view) pool_put(owner, p); }
+  hipError_t alloc(vbmc_ctx* ctx, size_t bytes) { owner = ctx; return pool_get(ctx, bytes, &p); }
+  void view(void* q) { p = q; is_view = true; }
+  void* release() { void* q = p; p = nullptr; return q; }   // the block outlives the scope: its new owner gives it back
+  template <typename T> T* as() { return (T*)p; }
+};
 
 struct vbmc_gp {
   int N = 0, D = 0, S = 0, Nhyp = 0, Ncov = 0, Nnoise = 0, meanfun = 0;

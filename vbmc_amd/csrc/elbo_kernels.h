@@ -71,8 +71,8 @@ __device__ inline void adam_update_chain(const AdamState& A, int iter, double* _
 }
 
 // ------------------------------------------------------------------------------------------
-// k_prep: unpack theta exactly as misc/negelcbo_vbmc.m:33-48 does.  Inside the on-device optimiser loop the Adam update
-// of the previous iteration (adam_iter > 0) is applied first by the same workgroup, which saves one launch per iteration.
+// k_prep: unpack theta exactly as misc/negelcbo_vbmc.m:33-48 does.  Inside the on-device optimiser loop the finalize kernel of
+// the previous iteration applies the Adam update and unpacks the new theta itself (k_finalize_ws), which saves one launch per iteration.
 // ------------------------------------------------------------------------------------------
 // the body of k_prep for restart r, by whichever workgroup calls it (k_prep, or k_finalize_ws for the NEXT iteration of the
 // on-device optimiser loop); sh: dynamic LDS of D K + 3 K + D doubles + one per wave
@@ -140,16 +140,11 @@ __device__ inline void prep_body(const ElboDims& dm, const double* __restrict__ 
   }
 }
 
-__global__ void __launch_bounds__(256) k_prep(ElboDims dm, double* __restrict__ theta,
+__global__ void __launch_bounds__(256) k_prep(ElboDims dm, const double* __restrict__ theta,
                                               const double* __restrict__ vpfix,  // mu sigma lambda w (fixed vp) packed
-                                              double* __restrict__ vpd, double* __restrict__ entp, AdamState A, int adam_iter,
-                                              const double* __restrict__ prev_out) {
+                                              double* __restrict__ vpd, double* __restrict__ entp) {
   VB_SMALL_PRIO();
   extern __shared__ double sh[];
-  if (adam_iter > 0) {
-    adam_update_chain(A, adam_iter, theta, prev_out, blockIdx.x);
-    __syncthreads();
-  }
   prep_body(dm, theta, vpfix, vpd, entp, blockIdx.x, sh);
 }
 

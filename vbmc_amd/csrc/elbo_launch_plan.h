@@ -1,4 +1,4 @@
-// Which kernels an ELBO pass runs and in what shape: decided ONCE per plan (plan_launch, called by elbo_plan in abi_elbo.hip) from the shape
+// Which kernels an ELBO pass runs and in what shape: decided ONCE per plan (plan_launch, called by elbo_plan in elbo_pass.h) from the shape
 // and call facts, the device facts and the A/B switches.  elbo_enqueue only executes the LaunchChoice it finds in the plan.
 #pragma once
 #include <algorithm>
