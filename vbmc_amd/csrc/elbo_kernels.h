@@ -187,7 +187,11 @@ __global__ void __launch_bounds__(WAVE * LJ_MAXW) k_logjoint(ElboDims dm, const 
 // cores.  Every gradient of gplogjoint.m:206-252 is a combination of the moments of za_n = z_k(n) alpha_n,
 //     M0 = sum_n za_n,   M1_d = sum_n za_n x'_nd,   M2_d = sum_n za_n x'_nd^2        (x' = x - column mean),
 // since delta = (mu' - x') / tau:  sum za delta_d = (mu'_d M0 - M1_d)/tau_d,  sum za delta_d^2 = (mu'_d^2 M0 -
-// 2 mu'_d M1_d + M2_d)/tau_d^2.  A workgroup = one (restart, hyper-sample); wave w owns the 16 components 16w + li.
+// 2 mu'_d M1_d + M2_d)/tau_d^2.  A workgroup = one (hyper-sample s, row group): the rows are the flattened (restart, component) pairs
+// rho = r K + k of the batch, and wave w of group g owns the 16 rows 16 (nw g + w) + li -- the staged feature rows and alpha depend on s
+// alone, so rows of different restarts share a workgroup and only the rows beyond R K are padding (one workgroup per (restart, s) ran
+// 64 rows for K = 50).  Every lane decodes its own (r, k), reads its own restart's parameters and writes its own record; the order of
+// points and chunks within a row is the same wherever the row sits, so a record does not depend on the batch around it.
 // Per k-step (4 training points) a lane evaluates ONE z (its component, point 4q + lg: the MFMA A operand) and the
 // 2D + 1 moment columns are NCT = ceil((2D+1)/16) MFMAs against the feature rows [x', x'^2, 1] of the LDS-staged
 // chunk of X.  The exponent itself stays on the VALU as a sum of squares of (mu' - x')/tau (no cancellation);
@@ -225,12 +229,14 @@ __global__ void __launch_bounds__(1024) k_logjoint_mfma(ElboDims dm, const doubl
   extern __shared__ __attribute__((aligned(16))) double MOM[];         // CH x NFP feature rows; after the loop nw x 16 x NF: moments per wave, [cell][column]
   double (*PHI)[NFP] = reinterpret_cast<double (*)[NFP]>(MOM);
   __shared__ double ALC[CH];
-  const int s = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const int s = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
   const int wv = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
   const int D = dm.D, K = dm.K, N = dm.N;
-  const int kk = 16 * wv + li;
-  const bool kvalid = kk < K;
-  const int k = kvalid ? kk : K - 1;
+  const int rows = dm.R * K;
+  const int rho_ = 16 * ((int)blockIdx.y * (nthr >> 6) + wv) + li;     // the lane's row of the batch
+  const bool kvalid = rho_ < rows;                                     // (a padded row runs the last row's parameters and stores nothing)
+  const int rho = kvalid ? rho_ : rows - 1;
+  const int r = rho / K, k = rho - r * K;
   for (int t = tid; t < VB_EXP_TAB1K_N; t += nthr) TAB[t] = c_exp2_tab1k[t];
   VpLayout L{D, K};
   const double* v = vpd + (size_t)r * L.stride();
@@ -241,7 +247,10 @@ __global__ void __launch_bounds__(1024) k_logjoint_mfma(ElboDims dm, const doubl
   // t_d = sqrt(512/ln2) / tau_d and c_d = mu'_d t_d: two operations per dimension where (mu' - x') / tau, squared and summed, took three, and
   // no scaling of the argument.  (c_d carries one rounding of mu'_d t_d: an absolute error of 1e-16 |mu'_d| / tau_d in delta_d, i.e.
   // 2e-16 |delta_d mu'_d| / tau_d in the exponent -- the reference's own (mu - x) / tau has the rounding of x - mean(x) against it.)
-  const double SQH = 27.17829760922398;      // sqrt(1024 / (2 ln 2))
+  // (the literal read 27.17829760922398 until the row packing: wrong from the eleventh digit on, 2.7e-13 relative -- every exponent was
+  // stretched by 5.4e-13 of itself and every z_k shrunk by that much times its exponent, the same way for all of them: G came out
+  // 9e-13 above the reference and the VALU kernel at D = 4, K = 16, N = 64, where the two now agree to 1e-15)
+  const double SQH = 27.17829760921660937;   // sqrt(1024 / (2 ln 2))
   double tt[DT], cc[DT];
   double sumlogtau = 0.0;
   // (the four point lanes of a component share this set-up: lane group lg takes the dimensions d = lg, lg + 4, .. -- a square root, a
@@ -290,8 +299,7 @@ __global__ void __launch_bounds__(1024) k_logjoint_mfma(ElboDims dm, const doubl
     }
     for (int nl = tid; nl < CH; nl += nthr) ALC[nl] = (c0 + nl < N) ? al[c0 + nl] : 0.0;
     __syncthreads();
-#pragma unroll 2
-    for (int q = 0; q < CH / 4; ++q) {
+    auto kstep = [&](const int q) __attribute__((always_inline)) {
       const int nl = 4 * q + lg;
       const double* xr = &PHI[nl][0];
       double a2 = 0.0;
@@ -305,6 +313,14 @@ __global__ void __launch_bounds__(1024) k_logjoint_mfma(ElboDims dm, const doubl
       } else {
         acc[0][0] += za;
       }
+    };
+    if (c0 + CH <= N) {
+#pragma unroll 2
+      for (int q = 0; q < CH / 4; ++q) kstep(q);
+    } else {     // the last chunk: the k-steps that hold a point -- the others only ever added 0 x (N = 400: 4 of 16)
+      const int nq = (N - c0 + 3) >> 2;
+#pragma unroll 1
+      for (int q = 0; q < nq; ++q) kstep(q);
     }
   }
   if (!GRAD) {      // I_k alone (:169-174): the component's four point lanes, in lane-group order

@@ -513,9 +513,12 @@ inline vbmc_status Pass::logjoint(hipStream_t ls) const {
       const double* al = gp->alpha + (size_t)sl.s0 * dm.N;
       const double* gc = gp->gpc + (size_t)sl.s0 * GPC_STRIDE(D);
       if (lj_mfma) {
+        // rows rho = r K + k of the whole batch, sixteen per wave, nw waves per workgroup (what one restart's K components take): a
+        // workgroup is (hyper-sample, row group) and only the last group can hold padding.  R = 1: one group, the launch as it was.
+        const int ngrp = ((R * K + 15) / 16 + nw - 1) / nw;
         const size_t mom_lds = LJ_MFMA_DYN_LDS(DT, nw);   // feature rows / moment exchange
         const auto kern = P.compute_grad ? k_logjoint_mfma<DT, true> : k_logjoint_mfma<DT, false>;
-        hipLaunchKernelGGL(kern, dim3(sl.ns, R), dim3(WAVE * nw), mom_lds, ls, dml, P.d_vpd, gp->X, gp->d_meanX, al, gc, P.d_delta2, sl.lj_out);
+        hipLaunchKernelGGL(kern, dim3(sl.ns, ngrp), dim3(WAVE * nw), mom_lds, ls, dml, P.d_vpd, gp->X, gp->d_meanX, al, gc, P.d_delta2, sl.lj_out);
         LAUNCH_CHECK(ctx, "k_logjoint_mfma");
       } else {
         hipLaunchKernelGGL((k_logjoint<DT>), dim3((K + 3) / 4, sl.ns, R), dim3(P.lj_split ? WAVE * LJ_MAXW : WAVE), 0, ls, dml, P.d_vpd, gp->X, al, gc,

@@ -842,6 +842,10 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // renormalise the mantissa product before it can underflow (0.5^256 = 8.6e-78): its exponent joins the exponent sum.  (Round 4:
     // this used to take the logarithm here -- two instructions now instead of a library log in the tile loop, whose polynomial
     // constants sat in twelve VGPRs of a kernel that has none to spare.)
+    // (The test is if-converted: six v_cndmask_b32 per tile here, and four more where `ev & mask` is folded into a select -- ten in the
+    // headline kernel's 552-instruction full-tile block.  Measured in place, profiles/r08_logjoint_rows.md: renormalising on every call
+    // and opaque masks take all ten out -- 538 instructions, SQ_INSTS_VALU -1.1 %, SQ_INSTS_SALU -25 %, the same bits -- and the kernel
+    // runs 1.972 -> 1.984 ms.  They stay.)
     auto fold = [&]() {
       if (++pcnt == 256) {
         pe += __builtin_amdgcn_frexp_exp(pm);
