@@ -1008,6 +1008,52 @@ typedef struct vbmc_mtv_args {
 vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, const vbmc_mtv_args* args);
 
 /*
+ * vbmc_vp_diagnostics: the pair loop of vbmc_diagnostics.m:116-127 over R runs in one call (an addition, backward compatible:
+ * VBMC_ABI_VERSION is unchanged).  Run i draws ONCE: the rows of vbmc_vp_rnd(vps[i], Ns, 1, 1, seed + i).  (The reference draws afresh
+ * for every pair; here every pair's estimate is the reference's estimator on Ns balanced draws of each posterior, and only the
+ * estimates of different pairs are correlated.)
+ *   kl_mat[i + R j]      KL(run i || run j) of vbmc_kldiv.m:72-77, :88 on run i's draws, both densities through each posterior's own
+ *                        direct transform: what vbmc_vp_kldiv(vps[i], vps[j], Ns, seed + i) returns in kls[0] (to the bit, unless a
+ *                        density comes within e^40 of the smallest normal double: there it is formed as vbmc_pdf.m:56-60 forms it,
+ *                        exponentials that have lost their bits included, where vbmc_vp_kldiv keeps full precision).  Zero diagonal.  The
+ *                        runs' bounds may differ: a draw outside run j's support has a density that is not a number there, which
+ *                        the rule of :76 replaces by realmin.
+ *   mtv[d + D (i + R j)] vbmc_mtv.m on the two runs' sample matrices: the mesh bounds of :55-63 with lb = -Inf, ub = +Inf (:35-38,
+ *                        :44-47), so that a run's mesh, counts, bandwidth and density depend on that run's draws alone; the unique
+ *                        count by the clamp-end rule of vbmc_vp_mtv with the run's own clamp ends; kde1d, the normalisation and the
+ *                        integral as in vbmc_vp_mtv.  Symmetric in (i, j), zero for i = j.  A run's degenerate column gives NaN in
+ *                        that dimension of every pair the run takes part in.
+ *   maxmtv_mat[i + R j]  the maximum of mtv over the dimensions that are not NaN (MATLAB's max, vbmc_diagnostics.m:124); NaN if all are.
+ * Stage outputs per run, column c = i D + d, as vbmc_mtv_args has them per posterior.  Every output pointer may be NULL.
+ * 2 <= R <= 32; all runs the same D (else VBMC_ERR_INVALID); posteriors, transforms, Ns, nkde and nquad as vbmc_vp_mtv takes them.  A
+ * column that reaches kde1d's fminbnd branch answers VBMC_ERR_UNSUPPORTED and the message names the run and the dimension.  A NULL
+ * context, a wrong struct_size and R < 2 are refused before anything else is read.  Results are identical from call to call, and a
+ * run's stage outputs and draws are identical whichever other runs are in the call.
+ */
+typedef struct vbmc_diag_args {
+  uint32_t struct_size;
+  int32_t nkde;           /* 0: 8192; else a power of two in 256 .. 16384 */
+  int32_t nquad;          /* 0: 100000; else 2 .. 2^20 */
+  int64_t Ns;             /* >= 2 */
+  uint64_t seed;
+  double* kl_mat;         /* R x R column-major */
+  double* mtv;            /* D x R x R */
+  double* maxmtv_mat;     /* R x R */
+  double* mesh;           /* R x D x 2: MIN, MAX of column c at [2 c], [2 c + 1] */
+  int32_t* counts;        /* R x D x nkde: column c at [c nkde ..] */
+  int64_t* nuniq;         /* R x D */
+  double* tstar;          /* R x D */
+  double* density;        /* R x D x nkde */
+  double* xx;             /* Ns x D x R: run i's draws, column-major, at [Ns D i ..] */
+} vbmc_diag_args;
+vbmc_status vbmc_vp_diagnostics(vbmc_ctx* ctx, int32_t R, const vbmc_vp_desc* const* vps, const vbmc_diag_args* args);
+
+/* Test hook: one cosine transform of kde1d (forward: dct1d with a2 = (a_k / 2)^2, a2 may be NULL; inverse: idct1d) of C columns of n
+ * values (n a power of two in 256 .. 16384, column c at [c n ..]) by the kernel of vbmc_vp_mtv (kernel 0) or of vbmc_vp_diagnostics
+ * (kernel 1), launched reps times; out / a2 are the last launch's, ms[reps] (may be NULL) each launch's HIP-event duration. */
+vbmc_status vbmc_test_dct(vbmc_ctx* ctx, int n, int C, int inverse, int kernel, int reps, const double* in, double* out, double* a2, double* ms);
+
+/*
  * vbmc_gp_surrogate_sample: samples of the GP surrogate itself (misc/gpsample_vbmc.m -> gplite/gplite_sample.m with method 'parallel';
  * an addition, backward compatible: VBMC_ABI_VERSION is unchanged).  The whole chain runs on the device.
  *

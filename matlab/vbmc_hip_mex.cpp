@@ -48,6 +48,7 @@
 //     [mubar,Sigma] = vbmc_hip_mex('vp_moments', vp, Ns, seed)                        (vbmc_moments(vp,1,Ns): vbmc_vp_moments, matlab/vbmc_hip_moments.m)
 //     [kls,xx1,xx2] = vbmc_hip_mex('vp_kldiv', vp1, vp2, Ns, seed)                    (vbmc_kldiv(vp1,vp2,Ns,0): vbmc_vp_kldiv, matlab/vbmc_hip_kldiv.m)
 //     [mtv,xx1,xx2] = vbmc_hip_mex('vp_mtv', vp1, vp2, Ns, seed)                      (vbmc_mtv(vp1,vp2,Ns): vbmc_vp_mtv, matlab/vbmc_hip_mtv.m)
+//     [kl_mat,maxmtv_mat,mtv,xx] = vbmc_hip_mex('vp_diag', Ns, seed, vp1, vp2, ...)   (the pair loop of vbmc_diagnostics: vbmc_vp_diagnostics, matlab/vbmc_hip_diagnostics.m)
 //     [acq,fbar,vtot] = vbmc_hip_mex('acq_iqr', h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar)
 //     [X,out] = vbmc_hip_mex('gp_surrogate_sample', h, vp, Ns, origflag, LB, UB, noise /*struct X_rescaled, gplengthscale, sn2new or []*/, opts)
 //                                (gpsample_vbmc(vp,gp,Ns,origflag): vbmc_gp_surrogate_sample, matlab/gpsample_vbmc.m.  opts: S, E, W, Seed, Thin,
@@ -223,7 +224,7 @@ static void read_gp(const mxArray* gp, GpArrays& g) {
 }
 
 // vp struct with its trinfo (shared/warpvars_vbmc.m: lb_orig, ub_orig, type, mu, delta, scale, R_mat; empty: the identity) -> vbmc_vp_desc
-// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv', 'vp_mtv').  The arrays stay MATLAB's; only the types are converted to int32.
+// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv', 'vp_mtv', 'vp_diag').  The arrays stay MATLAB's; only the types are converted to int32.
 static int fill_vp_desc(vbmc_vp_desc& d, const mxArray* vp, std::vector<int32_t>& types) {
   memset(&d, 0, sizeof d);
   d.struct_size = sizeof d;
@@ -1101,6 +1102,36 @@ static int dispatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) 
     if (b && (int)mxGetM(b) != D) return raise("vbmc_hip:sq_dist", "Error: column lengths must agree.");
     plhs[0] = mxCreateDoubleMatrix(n, m, mxREAL);
     vbmc_status st = vbmc_sq_dist(g_ctx, D, n, m, mxGetDoubles(a), b ? mxGetDoubles(b) : nullptr, mxGetDoubles(plhs[0]));
+    if (st != VBMC_OK) return fail(st);
+    return 0;
+  }
+  if (!strcmp(cmd, "vp_diag")) {     // [kl_mat,maxmtv_mat,mtv,xx] of vbmc_diagnostics.m:116-127 over the runs vp1, vp2, ... with the library's draws for seed: vbmc_vp_diagnostics
+    if (nrhs < 4) return raise("vbmc_hip:usage", "vp_diag: Ns, seed, vp1, vp2, ...");
+    const int R = nrhs - 3;
+    std::vector<vbmc_vp_desc> d(R);
+    std::vector<std::vector<int32_t>> t(R);
+    std::vector<const vbmc_vp_desc*> p(R);
+    for (int i = 0; i < R; ++i) {
+      if (fill_vp_desc(d[i], prhs[3 + i], t[i])) return 1;
+      p[i] = &d[i];
+    }
+    const double n = mxGetScalar(prhs[1]);
+    if (!(n >= 1)) return raise("vbmc_hip:usage", "vp_diag: Ns must be positive");
+    const mwSize Ns = (mwSize)n, dm[3] = {(mwSize)d[0].D, (mwSize)R, (mwSize)R}, dx[3] = {Ns, (mwSize)d[0].D, (mwSize)R};
+    plhs[0] = mxCreateDoubleMatrix(R, R, mxREAL);
+    if (nlhs > 1) plhs[1] = mxCreateDoubleMatrix(R, R, mxREAL);
+    if (nlhs > 2) plhs[2] = mxCreateNumericArray(3, dm, mxDOUBLE_CLASS, mxREAL);
+    if (nlhs > 3) plhs[3] = mxCreateNumericArray(3, dx, mxDOUBLE_CLASS, mxREAL);
+    vbmc_diag_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_size = sizeof a;
+    a.Ns = (int64_t)Ns;
+    a.seed = (uint64_t)mxGetScalar(prhs[2]);
+    a.kl_mat = mxGetDoubles(plhs[0]);
+    a.maxmtv_mat = nlhs > 1 ? mxGetDoubles(plhs[1]) : nullptr;
+    a.mtv = nlhs > 2 ? mxGetDoubles(plhs[2]) : nullptr;
+    a.xx = nlhs > 3 ? mxGetDoubles(plhs[3]) : nullptr;
+    vbmc_status st = vbmc_vp_diagnostics(g_ctx, R, p.data(), &a);
     if (st != VBMC_OK) return fail(st);
     return 0;
   }

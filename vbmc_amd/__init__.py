@@ -19,4 +19,4 @@ from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, ac
 from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
                        vpsieve_vbmc)
 from . import vptools  # noqa: F401,E402
-from .vptools import gpsample_vbmc, vp_rnd_rng_dump, warpvars  # noqa: F401,E402
+from .vptools import gpsample_vbmc, vbmc_diagnostics, vp_rnd_rng_dump, warpvars  # noqa: F401,E402

@@ -197,6 +197,20 @@ class MtvArgs(C.Structure):
     ]
 
 
+class DiagArgs(C.Structure):
+    """vbmc_diag_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nkde", C.c_int32), ("nquad", C.c_int32),
+        ("Ns", C.c_int64),
+        ("seed", C.c_uint64),
+        ("kl_mat", _dp), ("mtv", _dp), ("maxmtv_mat", _dp), ("mesh", _dp),
+        ("counts", C.POINTER(C.c_int32)),
+        ("nuniq", C.POINTER(C.c_int64)),
+        ("tstar", _dp), ("density", _dp), ("xx", _dp),
+    ]
+
+
 class GsArgs(C.Structure):
     """vbmc_gs_args (include/vbmc_hip.h)"""
     _fields_ = [
@@ -293,6 +307,8 @@ def load():
     lib.vbmc_vp_moments.argtypes = [vp, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp]
     lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
     lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
+    lib.vbmc_vp_diagnostics.argtypes = [vp, C.c_int32, C.POINTER(vpd), C.POINTER(DiagArgs)]
+    lib.vbmc_test_dct.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     lib.vbmc_vp_rnd_rng_dump.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
     lib.vbmc_gp_surrogate_sample.argtypes = [vp, vp, vpd, C.POINTER(GsArgs)]
     lib.vbmc_gp_surrogate_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]

@@ -24,6 +24,50 @@ void mtv_spline_host(const double* y, int n, double* m, std::vector<double>& cp)
   m[0] = 2.0 * m[1] - m[2];
   m[n - 1] = 2.0 * m[n - 2] - m[n - 3];
 }
+
+// tab[m] = cos(pi m / (2 n)), m = 0 .. n: the quarter wave k_mtv_dct folds every cosine into
+void mtv_cos_table(int n, std::vector<double>& htab) {
+  htab.resize((size_t)n + 1);
+  for (int m = 0; m <= n; ++m) htab[m] = (double)cosl(3.14159265358979323846264338327950288L * (long double)m / (long double)(2 * n));
+  htab[n] = 0.0;
+}
+
+// the constants of fixed_point (kde1d.m:84)
+void mtv_root_consts(MtvRootArgs& a) {
+  const double pi = 3.14159265358979323846;
+  for (int l = 2; l <= 7; ++l) a.pi2l[l] = std::pow(pi, 2.0 * l);
+  for (int s = 2; s <= 6; ++s) {
+    double prod = 1.0;
+    for (int j = 1; j <= 2 * s - 1; j += 2) prod *= j;
+    const double K0 = prod / std::sqrt(2.0 * pi), cst = (1.0 + std::pow(0.5, s + 0.5)) / 3.0;
+    a.ck[s] = 2.0 * cst * K0;
+  }
+  a.sqrtpi = std::sqrt(pi);
+}
+
+// kde1d.m:58, :62 and vbmc_mtv.m:68, :71 on one column of the inverse transform (y, overwritten by the normalised density), then its
+// spline (m) and its mesh row msh[4]: MIN, dx, the last mesh point, bad
+void mtv_finish_column(const MtvCol& q, int n, double* y, double* m, double* msh, std::vector<double>& cp) {
+  if (q.bad) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int j = 0; j < n; ++j) { y[j] = nan; m[j] = 0.0; }
+    msh[0] = q.MIN; msh[1] = 0.0; msh[2] = q.MIN; msh[3] = 1.0;
+    return;
+  }
+  const double R = q.MAX - q.MIN, dx = R / (double)(n - 1);
+  double sum = 0.0;
+  for (int j = 0; j < n; ++j) {
+    double v = y[j] / R;                                                               // kde1d.m:58
+    if (v < 0.0) v = MTV_EPS;                                                           // :62
+    y[j] = v;
+    sum += v;
+  }
+  const double qt = sum - 0.5 * (y[0] + y[n - 1]), h = (q.MIN + dx) - q.MIN;            // qtrapz; xmesh(2) - xmesh(1)
+  const double nrm = qt * h;
+  for (int j = 0; j < n; ++j) y[j] = y[j] / nrm;                                        // vbmc_mtv.m:68, :71
+  mtv_spline_host(y, n, m, cp);
+  msh[0] = q.MIN; msh[1] = dx; msh[2] = q.MIN + (double)(n - 1) * dx; msh[3] = 0.0;
+}
 }  // namespace
 
 extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, const vbmc_mtv_args* args) {
@@ -75,9 +119,8 @@ extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const
 
   // ---- mesh, counts, cosine coefficients, bandwidth, inverse transform
   const size_t nC = (size_t)C2 * n;
-  std::vector<double> htab((size_t)n + 1);
-  for (int m = 0; m <= n; ++m) htab[m] = (double)cosl(3.14159265358979323846264338327950288L * (long double)m / (long double)(2 * n));
-  htab[n] = 0.0;
+  std::vector<double> htab;
+  mtv_cos_table(n, htab);
   TmpBuf dEnds, dCol, dNu, dCnt, dW, dTab, dT, dStat;
   HIP_TRY(ctx, dEnds.alloc(ctx, ends.size() * 8));
   HIP_TRY(ctx, dCol.alloc(ctx, (size_t)C2 * sizeof(MtvCol)));
@@ -112,15 +155,7 @@ extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const
   {
     MtvRootArgs a{};
     a.n = n; a.D = D; a.col = dCol.as<MtvCol>(); a.a = d_a; a.a2 = d_a2; a.at = d_at; a.tstar = dT.as<double>(); a.status = dStat.as<int>();
-    const double pi = 3.14159265358979323846;
-    for (int l = 2; l <= 7; ++l) a.pi2l[l] = std::pow(pi, 2.0 * l);
-    for (int s = 2; s <= 6; ++s) {                                                        // kde1d.m:84
-      double prod = 1.0;
-      for (int j = 1; j <= 2 * s - 1; j += 2) prod *= j;
-      const double K0 = prod / std::sqrt(2.0 * pi), cst = (1.0 + std::pow(0.5, s + 0.5)) / 3.0;
-      a.ck[s] = 2.0 * cst * K0;
-    }
-    a.sqrtpi = std::sqrt(pi);
+    mtv_root_consts(a);
     hipLaunchKernelGGL(k_mtv_root, dim3(C2), dim3(MTV_T), 0, st, a);
   }
   MtvDctArgs bw{};
@@ -150,29 +185,7 @@ extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const
   // ---- kde1d.m:58, :62 and vbmc_mtv.m:68, :71 on the host, then the splines
   const double nan = std::numeric_limits<double>::quiet_NaN();
   std::vector<double> msh(4 * (size_t)C2), geo(4 * (size_t)D), cp;
-  for (int c = 0; c < C2; ++c) {
-    double* y = yy.data() + (size_t)c * n;
-    double* m = mm.data() + (size_t)c * n;
-    const MtvCol& q = hcol[c];
-    if (q.bad) {
-      for (int j = 0; j < n; ++j) { y[j] = nan; m[j] = 0.0; }
-      msh[4 * c] = q.MIN; msh[4 * c + 1] = 0.0; msh[4 * c + 2] = q.MIN; msh[4 * c + 3] = 1.0;
-      continue;
-    }
-    const double R = q.MAX - q.MIN, dx = R / (double)(n - 1);
-    double sum = 0.0;
-    for (int j = 0; j < n; ++j) {
-      double v = y[j] / R;                                                               // kde1d.m:58
-      if (v < 0.0) v = MTV_EPS;                                                           // :62
-      y[j] = v;
-      sum += v;
-    }
-    const double qt = sum - 0.5 * (y[0] + y[n - 1]), h = (q.MIN + dx) - q.MIN;            // qtrapz; xmesh(2) - xmesh(1)
-    const double nrm = qt * h;
-    for (int j = 0; j < n; ++j) y[j] = y[j] / nrm;                                        // vbmc_mtv.m:68, :71
-    mtv_spline_host(y, n, m, cp);
-    msh[4 * c] = q.MIN; msh[4 * c + 1] = dx; msh[4 * c + 2] = q.MIN + (double)(n - 1) * dx; msh[4 * c + 3] = 0.0;
-  }
+  for (int c = 0; c < C2; ++c) mtv_finish_column(hcol[c], n, yy.data() + (size_t)c * n, mm.data() + (size_t)c * n, &msh[4 * (size_t)c], cp);
   for (int d = 0; d < D; ++d) {                                                           // vbmc_mtv.m:74
     double* bb = &geo[4 * (size_t)d];
     bb[0] = msh[4 * d]; bb[1] = msh[4 * d + 2]; bb[2] = msh[4 * (D + d)]; bb[3] = msh[4 * (D + d) + 2];

@@ -1,6 +1,6 @@
 """The variational posterior in the caller's own parameter space: vbmc_pdf, vbmc_rnd, vbmc_moments, vbmc_kldiv and vbmc_mtv with the
 variable transform of shared/warpvars_vbmc.m on the device (include/vbmc_hip.h: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments,
-vbmc_vp_kldiv, vbmc_vp_mtv).
+vbmc_vp_kldiv, vbmc_vp_mtv), and vbmc_diagnostics over several runs (vbmc_vp_diagnostics: every pair's divergences in one call).
 
 ``vp["trinfo"]`` is a dict with the reference's field names (lb_orig, ub_orig, type, mu, delta and, optionally, scale and R_mat), or
 None / empty for the identity.  Transform types 0 .. 3 are accelerated; anything else raises VbmcUnsupported, on which a caller falls
@@ -10,6 +10,8 @@ replays a block written by ``vp_rnd_rng_dump``.  Component indices count from 0.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import warnings
 
 import numpy as np
 
@@ -294,6 +296,165 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
     if stages:
         out = out + (st,)
     return out if len(out) > 1 else out[0]
+
+
+def vp_diagnostics(vp_array, Ns=1e5, *, seed=0, nkde=None, nquad=None, stages=False, draws=False, outputs=("kl_mat", "mtv", "maxmtv_mat"),
+                   engine=None):
+    """The pair loop of vbmc_diagnostics.m:116-127 on the device in one call (vbmc_vp_diagnostics).  Run i draws once, with seed + i.
+    Returns a dict: kl_mat (R, R) with kl_mat[i, j] = KL(run i || run j), mtv (R, R, D), maxmtv_mat (R, R) (the maximum over the
+    dimensions that are not NaN); stages=True adds mesh (R, D, 2), counts (R, D, nkde), nuniq (R, D), tstar (R, D) and density
+    (R, D, nkde); draws=True adds xx (R, Ns, D).  ``outputs`` names the matrices wanted: the library skips the cross densities
+    without kl_mat and the integrals without mtv and maxmtv_mat."""
+    engine = _engine(engine)
+    ctx = engine.ctx
+    descs = [_Desc(v) for v in vp_array]
+    R, D, Ns = len(descs), descs[0].D if descs else 0, int(Ns)
+    n = 8192 if not nkde else int(nkde)
+    a = _lib.DiagArgs()
+    a.struct_size = C.sizeof(_lib.DiagArgs)
+    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & (2 ** 64 - 1)
+    out = {"kl_mat": np.zeros((R, R), order="F"), "mtv": np.zeros((R, R, D)), "maxmtv_mat": np.zeros((R, R), order="F")}
+    for k in ("kl_mat", "mtv", "maxmtv_mat"):
+        if k in outputs:
+            setattr(a, k, ptr(out[k]))
+        else:
+            del out[k]
+    if stages and 256 <= n <= 16384:
+        out.update(mesh=np.zeros((R, D, 2)), counts=np.zeros((R, D, n), dtype=np.int32), nuniq=np.zeros((R, D), dtype=np.int64),
+                   tstar=np.zeros((R, D)), density=np.zeros((R, D, n)))
+        a.mesh, a.tstar, a.density = ptr(out["mesh"]), ptr(out["tstar"]), ptr(out["density"])
+        a.counts = out["counts"].ctypes.data_as(C.POINTER(C.c_int32))
+        a.nuniq = out["nuniq"].ctypes.data_as(C.POINTER(C.c_int64))
+    if draws:
+        xx = np.zeros((R, D, max(Ns, 0)))                       # run i, column d, row r: the ABI's Ns x D x R column-major
+        a.xx = ptr(xx)
+    arr = (C.POINTER(_lib.VpDesc) * max(R, 1))(*[C.pointer(d.d) for d in descs])
+    ctx.check(ctx.lib.vbmc_vp_diagnostics(ctx.h, R, arr, C.byref(a)))
+    for k in ("kl_mat", "maxmtv_mat"):
+        if k in out:
+            out[k] = np.ascontiguousarray(out[k])
+    if draws:
+        out["xx"] = np.ascontiguousarray(xx.transpose(0, 2, 1))
+    return out
+
+
+_DIAG_MSG = {1: "Diagnostic test PASSED.",
+             0: "Diagnostic test FAILED: only one run has converged, so there is nothing to compare it with.",
+             -1: "Diagnostic test FAILED: too few runs agree with the best posterior (symmetrized KL divergence or largest marginal total variation).",
+             -2: "Diagnostic test FAILED: too few runs agree with the best ELBO.",
+             -3: "Diagnostic test FAILED: no run has converged."}
+
+
+def diagnostics_decision(elbo, elbo_sd, stable, kl_mat, maxmtv_mat, beta_lcb=3, elbo_thresh=1, sKL_thresh=1, maxmtv_thresh=0.2):
+    """The decision of vbmc_diagnostics.m:58-114, :129-222 as a function of the runs' statistics and the two distance matrices (host
+    only, no device).  Returns a dict with exitflag, idx_best (from 0; None when the best run is not stable), the index best_run the
+    comparisons used, elcbo, sKL_best, maxmtv_best, the three boolean rows elbo_ok / sKL_ok / maxmtv_ok (None for one run), msg and
+    the list of warnings.
+
+    The best run is the first maximum of elbo - beta_lcb elbo_sd among the converged runs (among all runs when none has converged); a
+    NaN there is skipped as MATLAB's max skips it.  A run agrees when |elbo - elbo_best| < elbo_thresh, resp. its symmetrized KL
+    divergence to the best run < sKL_thresh, resp. its largest marginal total variation to it < maxmtv_thresh (a NaN never agrees;
+    the best run always agrees with itself); each of the three counts has to reach max(Nruns / 3, 2)."""
+    elbo = np.asarray(elbo, dtype=np.float64).reshape(-1)
+    elbo_sd = np.asarray(elbo_sd, dtype=np.float64).reshape(-1)
+    stable = np.asarray(stable).reshape(-1).astype(bool)
+    R = elbo.size
+    kl_mat = np.asarray(kl_mat, dtype=np.float64).reshape(R, R)
+    maxmtv_mat = np.asarray(maxmtv_mat, dtype=np.float64).reshape(R, R)
+    notes = []
+    exitflag = math.inf
+    if R == 1:
+        notes.append("vbmc_diagnostics needs the posteriors of several runs; a single run cannot be compared with anything.")
+    active = stable.copy()
+    nok = int(np.sum(stable))
+    if nok == 0:
+        notes.append("No run has converged; the comparisons use a solution that may be unstable.")
+        active[:] = True
+        exitflag = -3
+    elif nok == 1:
+        notes.append("Only one run has converged; perform more runs.")
+        exitflag = 0
+    elcbo = elbo - beta_lcb * elbo_sd
+    eff = np.where(active, elcbo, -np.inf)
+    cand = np.flatnonzero(~np.isnan(eff))
+    best = int(cand[np.argmax(eff[cand])]) if cand.size else 0        # the first maximum; NaN skipped; all NaN: the first run
+    sKL_best = 0.5 * (kl_mat[:, best] + kl_mat[best, :])
+    maxmtv_best = maxmtv_mat[best, :].copy()
+    oks = {"elbo_ok": None, "sKL_ok": None, "maxmtv_ok": None}
+    if R > 1:
+        need = max(R * (1.0 / 3.0), 2)
+        with np.errstate(invalid="ignore"):
+            oks["elbo_ok"] = np.abs(elbo[best] - elbo) < elbo_thresh
+            oks["sKL_ok"] = sKL_best < sKL_thresh
+            oks["maxmtv_ok"] = maxmtv_best < maxmtv_thresh
+        for key, flag, what in (("elbo_ok", -2, "the best ELBO"), ("sKL_ok", -1, "the best posterior (symmetrized KL divergence)"),
+                                ("maxmtv_ok", -1, "the best posterior (largest marginal total variation)")):
+            if np.sum(oks[key]) < need:
+                notes.append("Too few runs agree with %s." % what)
+                exitflag = min(exitflag, flag)
+    if math.isinf(exitflag):
+        exitflag = 1
+    exitflag = int(exitflag)
+    return dict(exitflag=exitflag, idx_best=best if stable[best] else None, best_run=best, elcbo=elcbo, sKL_best=sKL_best,
+                maxmtv_best=maxmtv_best, msg=_DIAG_MSG[exitflag], warnings=notes, **oks)
+
+
+def vbmc_diagnostics(vp_array, beta_lcb=3, elbo_thresh=1, sKL_thresh=1, maxmtv_thresh=0.2, *, Ns=1e5, seed=0, nkde=None, nquad=None,
+                     stages=False, verbose=True, engine=None):
+    """[exitflag,best,idx_best,stats] = vbmc_diagnostics(vp_array,beta_lcb,elbo_thresh,sKL_thresh,maxmtv_thresh): the convergence
+    diagnostics over several VBMC runs, every pair's KL divergences and marginal total variations in ONE device call.  Each vp dict
+    carries ``stats = {elbo, elbo_sd, stable}``.  Exit flags: 1 passed; 0 only one run converged; -1 too few runs agree with the best
+    posterior; -2 too few agree with the best ELBO; -3 no run converged.  ``best`` = {vp, elbo, elbo_sd} and ``idx_best`` (from 0) are
+    None when the best run is not stable.  ``stats`` has the reference's fields (vbmc_diagnostics.m:226-239); stages=True adds the
+    device call's stage outputs under ``stats["stages"]``.  One run needs no device call: the matrices are zero and a warning is given.
+
+    Intentional divergences from the reference:
+      * run i draws once (seed + i) and meets every other run on those draws; the reference draws afresh for every pair.
+      * vbmc_diagnostics.m:53-56 test ``nargin`` one too high, so there the last argument a caller gives is overwritten by its default.
+        Here, as the help text (:30-49) says, an argument that is given is used.
+    Kept from the reference: maxmtv_mat is the maximum over the dimensions that are not NaN (MATLAB's max at :124 skips NaN)."""
+    vps = list(vp_array)
+    R = len(vps)
+    if R < 1:
+        raise ValueError("vbmc_diagnostics: vp_array is empty")
+    D = int(vps[0]["D"])
+    elbo = np.array([float(v["stats"]["elbo"]) for v in vps])
+    elbo_sd = np.array([float(v["stats"]["elbo_sd"]) for v in vps])
+    stable = np.array([bool(v["stats"]["stable"]) for v in vps])
+    dev = None
+    if R > 1:
+        dev = vp_diagnostics(vps, Ns, seed=seed, nkde=nkde, nquad=nquad, stages=stages, engine=engine)
+        kl_mat, maxmtv_mat = dev["kl_mat"], dev["maxmtv_mat"]
+    else:
+        kl_mat, maxmtv_mat = np.zeros((1, 1)), np.zeros((1, 1))
+    dec = diagnostics_decision(elbo, elbo_sd, stable, kl_mat, maxmtv_mat, beta_lcb, elbo_thresh, sKL_thresh, maxmtv_thresh)
+    notes = list(dec["warnings"])
+    rec = max(2, int(math.ceil(math.log2(D)))) if D > 1 else 2
+    if R < rec:
+        notes.append("For a problem in D = %d dimensions at least %d runs are recommended." % (D, rec))
+    for m in notes:
+        warnings.warn(m, stacklevel=2)
+    if verbose:
+        print("%d of %d runs have converged." % (int(np.sum(stable)), R))
+        print(" run         elbo     elbo_sd        elcbo  converged    sKL[best]  maxMTV[best]")
+        for i in range(R):
+            print("%4d %12.2f %11.2f %12.2f %10s %12.2f %13.2f %s" % (i, elbo[i], elbo_sd[i], dec["elcbo"][i], "yes" if stable[i] else "no",
+                                                                     dec["sKL_best"][i], dec["maxmtv_best"][i], "best" if i == dec["best_run"] else ""))
+        for key, what, thr in (("elbo_ok", "the best ELBO", elbo_thresh), ("sKL_ok", "the best posterior in symmetrized KL", sKL_thresh),
+                               ("maxmtv_ok", "the best posterior in largest marginal total variation", maxmtv_thresh)):
+            if dec[key] is not None:
+                print("%d of %d runs agree with %s (below %g)." % (int(np.sum(dec[key])), R, what, thr))
+        print(dec["msg"])
+    idx_best = dec["idx_best"]
+    best = None if idx_best is None else {"vp": vps[idx_best], "elbo": float(elbo[idx_best]), "elbo_sd": float(elbo_sd[idx_best])}
+    stats = dict(beta_lcb=beta_lcb, elbo_thresh=elbo_thresh, sKL_thresh=sKL_thresh, maxmtv_thresh=maxmtv_thresh, elbo=elbo, elbo_sd=elbo_sd,
+                 elcbo=dec["elcbo"], idx_best=idx_best, sKL_best=dec["sKL_best"], maxmtv_best=dec["maxmtv_best"], kl_mat=kl_mat,
+                 maxmtv_mat=maxmtv_mat, exitflag=dec["exitflag"], msg=dec["msg"])
+    if dev is not None:
+        stats["mtv"] = dev["mtv"]
+        if stages:
+            stats["stages"] = {k: dev[k] for k in ("mesh", "counts", "nuniq", "tstar", "density") if k in dev}
+    return dec["exitflag"], best, idx_best, stats
 
 
 def _training_noise(gp):
