@@ -2,7 +2,7 @@
 // The kernels are gp_surrogate_kernels.h; the sampler is the ensemble slice sampler of is_core.h with this file's target: E ensembles
 // decoupled from the hyper-samples, every candidate under all of them (k_gs_pred into Sg x E x C means and variances, k_gs_target
 // into the E x C values), no limit on the records.  Host side: validation, the start (the caller's, or draws of k_vp_draw) clipped
-// into the box and written into the sampler's walker buffer, the noise estimate (abi_gp.hip: NnNoise) in the same stream in front of
+// into the box and written into the sampler's walker buffer, the noise estimate (gp_pred.h: NnNoise) in the same stream in front of
 // the chain, the closing k_gs_finish and the copies back.  Included after abi_vp_tools.hip (vpt_pack, vpt_gen_host).
 #include "gp_surrogate_kernels.h"
 #include "is_core.h"

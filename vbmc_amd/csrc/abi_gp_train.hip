@@ -1,12 +1,12 @@
 // C-ABI entry points for the two device-resident halves of gplite_train: vbmc_gp_slice_sample, vbmc_gp_train_optimize (and
 // vbmc_slice_rng_dump) (include/vbmc_hip.h).  Both turn candidate hyper-parameter vectors into GP objective values on the device
-// (gpobj_kernels.h) and are driven from the host in chunks of ROUNDS; what they share on the host is in the namespace below.
-// Included after abi_gp.hip, whose noise_nhyp and gp_launch_* it uses.
+// (gpobj_kernels.h) and are driven from the host in chunks of ROUNDS; what they share on the host is in the namespace below, over
+// the factorisation core of gp_factor.h.
 #include <algorithm>
 #include <cmath>
 #include <limits>
 
-#include "gp_kernels.h"
+#include "gp_factor.h"
 #include "slice_kernels.h"
 #include "trainopt_kernels.h"
 
@@ -15,23 +15,6 @@ namespace {
 double host_eps(double x) {   // MATLAB's eps(x): NaN for an infinite x
   const double ax = std::fabs(x);
   return std::nextafter(ax, std::numeric_limits<double>::infinity()) - ax;
-}
-
-// The GP models both entry points accelerate.  *Ncov: on entry the caller's own count of covariance hyper-parameters if it states
-// one (0: it does not), held against the model's with the identity; on return Ncov, Nnoise, Nmean are the model's.
-vbmc_status gp_model_check(vbmc_ctx* ctx, int N, int D, int Nhyp, int meanfun, const int32_t noisefun[3], int* Ncov, int* Nnoise, int* Nmean) {
-  if (D > VBMC_LIM_D) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "D = %d > %d not accelerated", D, VBMC_LIM_D);
-  if (!(meanfun == 0 || meanfun == 1 || meanfun == 4))
-    return set_err(ctx, VBMC_ERR_UNSUPPORTED, "gplite mean function %d not accelerated (0,1,4 are)", meanfun);
-  for (int i = 0; i < 3; ++i)
-    if (noisefun[i] < 0 || noisefun[i] > (i == 1 ? 2 : 1))
-      return set_err(ctx, VBMC_ERR_UNSUPPORTED, "gplite noise function [%d %d %d] not accelerated", noisefun[0], noisefun[1], noisefun[2]);
-  const int given = *Ncov;
-  *Ncov = D + 1; *Nnoise = noise_nhyp(noisefun); *Nmean = meanfun == 0 ? 0 : (meanfun == 1 ? 1 : 2 * D + 1);
-  if (Nhyp != *Ncov + *Nnoise + *Nmean || (given != 0 && given != *Ncov))
-    return set_err(ctx, VBMC_ERR_INVALID, "gplite_nlZ:dimmismatch Number of hyperparameters mismatched with GP model specification.");
-  if (trsm_cw_for(N) == 0) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "N = %d > %d not accelerated", N, trsm_max_n());
-  return VBMC_OK;
 }
 
 // hyper-prior classes and normalising terms (gplite_hypprior.m:34-36,49-58)
@@ -53,8 +36,7 @@ struct HyperPrior {
 
 // The factorisation workspace of B candidates at (N, D), and the value path of gplite_nlZ over it.
 struct GpObjWork {
-  TmpBuf dXc, daa, dA, dpf, dr, dz, dal, dfinv, dPg;
-  double* pfd = nullptr;          // the failure indices as doubles, behind alpha
+  GpWork w;
   // what the value path reads besides the workspace: set by the caller once its kernel arguments are laid out
   vbmc_ctx* ctx = nullptr;
   int N = 0, D = 0, Nhyp = 0, moff = 0, meanfun = 0;
@@ -64,27 +46,16 @@ struct GpObjWork {
 
   vbmc_status alloc(vbmc_ctx* c, int N_, int D_, int B) {
     ctx = c; N = N_; D = D_;
-    HIP_TRY(ctx, dXc.alloc(ctx, (size_t)B * N * D * 8));
-    HIP_TRY(ctx, daa.alloc(ctx, (size_t)B * N * 8));
-    HIP_TRY(ctx, dA.alloc(ctx, (size_t)B * N * N * 8));
-    HIP_TRY(ctx, dpf.alloc(ctx, (size_t)B * sizeof(int)));
-    HIP_TRY(ctx, dr.alloc(ctx, (size_t)B * N * 8));
-    HIP_TRY(ctx, dz.alloc(ctx, (size_t)B * N * 8));
-    HIP_TRY(ctx, dal.alloc(ctx, ((size_t)B * N + B) * 8));
-    HIP_TRY(ctx, dfinv.alloc(ctx, (size_t)B * TRSM_NBLK(N) * 256 * 8));
-    if (chol2_needs_gpanel(N, true)) HIP_TRY(ctx, dPg.alloc(ctx, (size_t)B * 16 * (size_t)(((N + 15) >> 4) << 4) * 8));
-    pfd = dal.as<double>() + (size_t)B * N;
-    return VBMC_OK;
+    return w.alloc(ctx, N, D, B);
   }
   // value path of n candidates whose inputs a propose launch has written; checked: with the nine x10 noise-inflation retries
   vbmc_status value_path(hipStream_t st, int n, int checked) {
-    gp_launch_scale(st, N, D, n, Nhyp, moff, meanfun, X, hyp, dXc.as<double>(), daa.as<double>(), y, dr.as<double>());
+    gp_launch_scale(st, N, D, n, Nhyp, moff, meanfun, X, hyp, w.dXc.as<double>(), w.daa.as<double>(), y, w.dr.as<double>());
     for (int t = 0; t < (checked ? 10 : 1); ++t) {
-      if (t > 0) hipLaunchKernelGGL(k_gpobj_retry, dim3((n + 63) / 64), dim3(64), 0, st, n, dpf.as<int>(), scal, act);
-      HIP_TRY(ctx, gp_launch_try(st, N, D, n, Nhyp, hyp, dXc.as<double>(), daa.as<double>(), sn2, scal, act, dA.as<double>(), dpf.as<int>(),
-                                 dPg.p ? dPg.as<double>() : nullptr, dfinv.as<double>(), pfd, dr.as<double>(), dz.as<double>()));
+      if (t > 0) hipLaunchKernelGGL(k_gpobj_retry, dim3((n + 63) / 64), dim3(64), 0, st, n, w.dpf.as<int>(), scal, act);
+      HIP_TRY(ctx, gp_launch_try(st, N, D, n, Nhyp, hyp, sn2, scal, act, w));
     }
-    gp_launch_alpha(st, N, n, dA.as<double>(), dfinv.as<double>(), on, dz.as<double>(), dal.as<double>(), scal);
+    gp_launch_alpha(st, N, n, w.dA.as<double>(), w.dfinv.as<double>(), on, w.dz.as<double>(), w.dal.as<double>(), scal);
     return VBMC_OK;
   }
 };
@@ -168,8 +139,10 @@ extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args
   const int N = g.N, D = g.D, Nhyp = g.Nhyp, meanfun = g.meanfun;
   if (N <= 0 || D <= 0 || !g.X || !g.y || !g.LB || !g.UB || !g.hyp_start || !g.widths)
     return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_slice_sample: bad arguments");
-  int Ncov = 0, Nnoise = 0, Nmean = 0;
-  VB_TRY(gp_model_check(ctx, N, D, Nhyp, meanfun, g.noisefun, &Ncov, &Nnoise, &Nmean));
+  GpModel gm;
+  VB_TRY(gp_noise_range_check(ctx, g.noisefun));
+  VB_TRY(gp_model_check(ctx, "gplite_nlZ", N, D, Nhyp, meanfun, g.noisefun, 0, gm));
+  const int Ncov = gm.Ncov, Nnoise = gm.Nnoise, Nmean = gm.Nmean;
   if (Nhyp > SLICE_MAXHYP) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Nhyp = %d > %d not accelerated", Nhyp, SLICE_MAXHYP);
   if (g.Ns < 1 || g.Thin < 1 || g.Burnin < 0)
     return set_err(ctx, VBMC_ERR_INVALID, "slicesamplebnd:options Ns and the thinning factor need to be positive integers, the burn-in non-negative.");
@@ -279,8 +252,8 @@ extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args
       ++enqueued;
       hipLaunchKernelGGL(k_slice_propose, dim3(W), dim3(256), 0, st, a, checked);
       VB_TRY(wk.value_path(st, W, checked));
-      gp_launch_nlz_final(st, N, D, W, Nhyp, Nnoise, Nmean, meanfun, 0, 0, dX, a.y, a.hyp, wk.dA.as<double>(), wk.dal.as<double>(), a.scal, nullptr,
-                          wk.pfd, dOut.as<double>());
+      gp_launch_nlz_final(st, N, D, W, Nhyp, Nnoise, Nmean, meanfun, 0, 0, dX, a.y, a.hyp, wk.w.dA.as<double>(), wk.w.dal.as<double>(), a.scal, nullptr,
+                          wk.w.pfd, dOut.as<double>());
       hipLaunchKernelGGL(k_slice_decide, dim3(1), dim3(64), 0, st, a, checked);
       HIP_TRY(ctx, hipGetLastError());
       return VBMC_OK;
@@ -335,8 +308,10 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
   const vbmc_gptrain_args& g = *args;
   const int N = g.N, D = g.D, Nhyp = g.Nhyp, meanfun = g.meanfun, Nopts = g.Nopts;
   if (N <= 0 || D <= 0 || !g.X || !g.y || !g.LB || !g.UB || !g.design) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_train_optimize: bad arguments");
-  int Ncov = g.Ncov, Nnoise = 0, Nmean = 0;
-  VB_TRY(gp_model_check(ctx, N, D, Nhyp, meanfun, g.noisefun, &Ncov, &Nnoise, &Nmean));
+  GpModel gm;
+  VB_TRY(gp_noise_range_check(ctx, g.noisefun));
+  VB_TRY(gp_model_check(ctx, "gplite_nlZ", N, D, Nhyp, meanfun, g.noisefun, g.Ncov, gm));
+  const int Ncov = gm.Ncov, Nnoise = gm.Nnoise, Nmean = gm.Nmean;
   if (Nhyp > TOPT_MAXHYP) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Nhyp = %d > %d not accelerated", Nhyp, TOPT_MAXHYP);
   if (Nopts < 1 || Nopts > TOPT_MAXOPTS) return set_err(ctx, VBMC_ERR_UNSUPPORTED, "Nopts = %d outside 1 .. %d", Nopts, TOPT_MAXOPTS);
   if (g.W < 0 || g.W > TOPT_MAXW) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_gp_train_optimize: speculation width W = %d outside 0 .. %d", g.W, TOPT_MAXW);
@@ -416,7 +391,7 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
   HIP_TRY(ctx, hipMemsetAsync(dHyp.p, 0, (size_t)BB * Nhyp * 8, st));       // k_gp_scale / k_nlz_grad / k_nlz_final are not gated: they read every row
   HIP_TRY(ctx, hipMemsetAsync(dScal.p, 0, (size_t)BB * 4 * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dDs.p, 0, (size_t)BB * std::max(Nnoise, 1) * N * 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(wk.dal.p, 0, ((size_t)BB * N + BB) * 8, st));
+  HIP_TRY(ctx, hipMemsetAsync(wk.w.dal.p, 0, ((size_t)BB * N + BB) * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dKi.p, 0, (size_t)B * N * N * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dHist.p, 0, std::max<size_t>(1, (size_t)Nopts * hist_cap * (Nhyp + 1)) * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dInt.as<int>() + Nhyp, 0, ((size_t)Nrows + 1 + (size_t)Nopts * hist_cap + 1) * sizeof(int), st));
@@ -449,8 +424,8 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
     const int n = std::min(CH, Nrows - c0);
     hipLaunchKernelGGL(k_topt_propose, dim3(n), dim3(256), 0, st, a, 1, c0, 1);
     VB_TRY(wk.value_path(st, n, 1));
-    gp_launch_nlz_final(st, N, D, n, Nhyp, Nnoise, Nmean, meanfun, 0, 0, dX, a.y, a.hyp, wk.dA.as<double>(), wk.dal.as<double>(), a.scal, nullptr,
-                        wk.pfd, dOut.as<double>());
+    gp_launch_nlz_final(st, N, D, n, Nhyp, Nnoise, Nmean, meanfun, 0, 0, dX, a.y, a.hyp, wk.w.dA.as<double>(), wk.w.dal.as<double>(), a.scal, nullptr,
+                        wk.w.pfd, dOut.as<double>());
     hipLaunchKernelGGL(k_topt_fill_collect, dim3((n + 255) / 256), dim3(256), 0, st, a, n, c0);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -465,12 +440,10 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
   auto round = [&](int checked) -> vbmc_status {
     hipLaunchKernelGGL(k_topt_propose, dim3(B), dim3(256), 0, st, a, 0, 0, checked);
     VB_TRY(wk.value_path(st, B, checked));
-    HIP_TRY(ctx, tri_inverse_launch(st, N, B, wk.dA.as<double>(), wk.dfinv.as<double>(), a.on, dTT.as<double>(), 1));
-    syrk_tt_launch(st, N, B, dTT.as<double>(), a.on, dKi.as<double>(), false, syrk_form);
-    DISPATCH_GPDT(D, hipLaunchKernelGGL((k_nlz_grad<DT>), dim3(nt1, nt1, B), dim3(256), 0, st, N, D, Nhyp, Nnoise, a.hyp, wk.dXc.as<double>(),
-                                        wk.daa.as<double>(), dKi.as<double>(), wk.dal.as<double>(), a.scal, a.dsn2, dPart.as<double>()));
-    gp_launch_nlz_final(st, N, D, B, Nhyp, Nnoise, Nmean, meanfun, ntile, 1, dX, a.y, a.hyp, wk.dA.as<double>(), wk.dal.as<double>(), a.scal,
-                        dPart.as<double>(), wk.pfd, dOut.as<double>());
+    VB_TRY(gp_launch_grad(ctx, st, N, D, B, Nhyp, Nnoise, a.hyp, a.scal, a.on, a.dsn2, wk.w, dTT.as<double>(), dKi.as<double>(), dPart.as<double>(), false,
+                          syrk_form, nullptr));
+    gp_launch_nlz_final(st, N, D, B, Nhyp, Nnoise, Nmean, meanfun, ntile, 1, dX, a.y, a.hyp, wk.w.dA.as<double>(), wk.w.dal.as<double>(), a.scal,
+                        dPart.as<double>(), wk.w.pfd, dOut.as<double>());
     hipLaunchKernelGGL(k_topt_decide, dim3(Nopts), dim3(64), 0, st, a, checked);
     HIP_TRY(ctx, hipGetLastError());
     return VBMC_OK;

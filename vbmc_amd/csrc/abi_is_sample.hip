@@ -3,7 +3,7 @@
 // too: one ensemble per hyper-sample, k_is_pred evaluating each ensemble's candidates under its own hyper-sample, at most VBMC_LIM_NA
 // records.  imiqr_begin sets the sampler up with the target's buffers, imiqr_rounds runs it, imiqr_close is what follows the chain: one
 // closing prediction at the recorded walkers, lnw and fs2a (k_is_finish), the outputs and the importance-sampling state
-// (abi_gp.hip: acq_is_from_device).
+// (gp_pred.h: acq_is_from_device).
 #include "is_core.h"
 
 extern "C" vbmc_status vbmc_acq_is_sample_rng_dump(uint64_t seed, int S, int H, int M, double* U) {

@@ -124,6 +124,14 @@ __global__ void k_pack_sepk(int R, int S, int K, int LJS, int diag_only, const d
 }
 
 static bool copy_by_kernel(size_t bytes) { return bytes <= COPY_KERNEL_MAX_BYTES; }
+// n doubles between the pinned block and device memory in stream st: k_copy_f64 while they are few (a failed launch shows at the
+// caller's next hipGetLastError), the copy engine (`kind`) beyond
+static hipError_t copy_f64_small(vbmc_ctx* ctx, hipStream_t st, double* dst, const double* src, size_t n, hipMemcpyKind kind) {
+  (void)ctx;
+  if (!copy_by_kernel(n * 8)) return hipMemcpyAsync(dst, src, n * 8, kind, st);
+  hipLaunchKernelGGL(k_copy_f64, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, st, n, src, dst);
+  return hipSuccess;
+}
 
 // gathered blocks of a sharded evaluation (ShardSpec below) -> the unsharded record layouts lj[r][s][k][LJS] and part[r][j][c][ncol]
 __global__ void __launch_bounds__(256) k_shard_scatter(int R, int S, int K, int LJS, int C, int ncol, int world, int perS, int perC,

@@ -2,16 +2,16 @@
 // knowing none of their targets.  A target brings: the number of ensembles E, a limit on the records per ensemble if it has one, the
 // doubles it wants behind the E x C values k_is_step reads, a kernel of k_is_pred's shape picked for the GP's D (IsPredKernel), and a
 // callable that enqueues the evaluation of a round's candidates into those values.  The core owns the parameters and their checks,
-// the prediction's per-hyper-sample set-up (k_pred_prep of abi_gp.hip's pred_plan, centred on the training inputs alone), the state
+// the prediction's per-hyper-sample set-up (k_pred_prep of gp_pred.h's pred_plan, centred on the training inputs alone), the state
 // block, the uniforms, the rounds (drive_rounds of abi_gp_train.hip, the E progress words read one chunk behind the one being
 // enqueued) under their cap, the ensembles' final states with their errors, and the report of starts of zero density.  It returns the
-// run's counters and leaves the recorded walkers c.a.Xa and their values c.a.rlp on the device.  Included by the unity translation
-// unit behind abi_gp.hip and abi_gp_train.hip.
+// run's counters and leaves the recorded walkers c.a.Xa and their values c.a.rlp on the device.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "gp_pred.h"
 #include "is_sample_kernels.h"
 
 #define IS_DEFAULT_CHUNK 16
@@ -100,7 +100,7 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   HIP_TRY(ctx, pb.dXs.alloc(ctx, (size_t)16 * D * 8));
   HIP_TRY(ctx, pb.dmb.alloc(ctx, (size_t)D * 8));
   VB_TRY(pred_plan(ctx, gp, 16, pb, false, nullptr, pl));
-  if (pl.slab_pred)
+  if (pl.f.slab_pred)
     return set_err(ctx, VBMC_ERR_UNSUPPORTED, "%s: N = %d is beyond the range in which the prediction keeps inv(L') resident", who, N);
   pl.pa.mc = 0;
   HIP_TRY(ctx, hipMemsetAsync(pb.dmb.p, 0, (size_t)D * 8, st));
