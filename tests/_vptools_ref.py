@@ -285,7 +285,7 @@ CASES = {   # name: (D, K, transform types or None, scale + rotation)
     "N": (25, 2, [(d + 2) % 4 for d in range(25)], True),     # DT = 32 partly filled: a 25 x 25 rotation in a 32 x 32 block
     "O": (32, 512, [3] * 16 + [0] * 16, True),                # both limits: eight chunks of 64, the rotation at the largest LDS footprint
 }
-PADDED_WIDTHS = (4, 8, 12, 16, 24, 32)   # vpt_pick_dt (vbmc_amd/csrc/abi_vp_tools.hip): the smallest of these that holds D
+PADDED_WIDTHS = (4, 8, 12, 16, 24, 32)   # vpt_pick_dt (vbmc_amd/csrc/vp_tools_host.h): the smallest of these that holds D
 CHUNK_DOUBLES = 2048                     # VPT_CHUNK (vbmc_amd/csrc/vp_tools_kernels.h): 2048 / DT components are staged at a time
 
 

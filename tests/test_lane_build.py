@@ -38,12 +38,12 @@ def test_no_lane_kernel_spills(tmp_path):
 
 
 def test_fused_prediction_kernel_does_not_spill(tmp_path):
-    """k_pred_fused<QS, PT> (vbmc_amd/csrc/gp_kernels.h) for every (QS, PT) the host may launch -- PT <= PREDF_PT_FOR_QS(QS) -- compiles
+    """k_pred_fused<QS, PT> (vbmc_amd/csrc/gp_pred_kernels.h) for every (QS, PT) the host may launch -- PT <= PREDF_PT_FOR_QS(QS) -- compiles
     without spilled registers: the resident-tile count is chosen so (three tiles at D <= 12, two up to 20, one beyond)."""
     src = os.path.join(str(tmp_path), "pf.hip")
     combos = [(q, p) for q in range(1, 9) for p in range(1, (3 if q <= 3 else (2 if q <= 5 else 1)) + 1)]
     with open(src, "w") as f:
-        f.write('#include "%s/common.h"\n#include "%s/device_math.h"\n#include "%s/trsm_mfma.h"\n#include "%s/gp_kernels.h"\n' % ((CSRC,) * 4))
+        f.write('#include "%s/gp_pred_kernels.h"\n' % CSRC)
         for q, p in combos:
             f.write("template __global__ void k_pred_fused<%d, %d>(PredArgs, const double*, const double*, const double*, double*, double*, int);\n" % (q, p))
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-I" + os.path.join(ROOT, "include"),

@@ -1,4 +1,4 @@
-"""CPU check beside tests/test_lane_build.py: the quadrature forms of the prediction kernels (vbmc_amd/csrc/gp_kernels.h) -- k_quad_fused<QS, PT>
+"""CPU check beside tests/test_lane_build.py: the quadrature forms of the prediction kernels (vbmc_amd/csrc/gp_pred_kernels.h) -- k_quad_fused<QS, PT>
 for every (QS, PT) the host may launch, PT <= PREDF_PT_FOR_QS(QS), and k_quad_ks<QS> -- compile for gfx950 with no spilled vector registers and
 no private segment (the criterion of tests/test_lane_build.py), within the register budget of the prediction forms they share a body with."""
 import os
@@ -14,7 +14,7 @@ def test_quadrature_kernels_do_not_spill(tmp_path):
     src = os.path.join(str(tmp_path), "qf.hip")
     combos = [(q, p) for q in range(1, 9) for p in range(1, (3 if q <= 3 else (2 if q <= 5 else 1)) + 1)]
     with open(src, "w") as f:
-        f.write('#include "%s/common.h"\n#include "%s/device_math.h"\n#include "%s/trsm_mfma.h"\n#include "%s/gp_kernels.h"\n' % ((CSRC,) * 4))
+        f.write('#include "%s/gp_pred_kernels.h"\n' % CSRC)
         for q, p in combos:
             f.write("template __global__ void k_quad_fused<%d, %d>(PredArgs, const double*, const double*, const double*, double*, double*, int);\n" % (q, p))
         for q in range(1, 9):

@@ -158,7 +158,7 @@ def test_cases_reach_every_width_and_a_chunk_seam():
         assert dt == 4 or any(d == dt and K > T.CHUNK_DOUBLES // dt for d, K in shapes), (dt, shapes)
     assert any(d == dt and K == T.CHUNK_DOUBLES // dt + 1 for d, K in shapes for dt in (8, 12, 16))      # a last chunk of one component
     assert any(K > 2 * (T.CHUNK_DOUBLES // d) for d, K in shapes)                                          # three chunks or more
-    with open(os.path.join(ROOT, "vbmc_amd", "csrc", "abi_vp_tools.hip")) as f:                          # the mirrored constants
+    with open(os.path.join(ROOT, "vbmc_amd", "csrc", "vp_tools_host.h")) as f:                         # the mirrored constants
         m = re.search(r"\bdts\s*\[\s*\]\s*=\s*\{([^}]*)\}", f.read())
         assert m and tuple(int(v) for v in m.group(1).split(",")) == T.PADDED_WIDTHS
     with open(os.path.join(ROOT, "vbmc_amd", "csrc", "vp_tools_kernels.h")) as f:

@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../vbmc_amd/csrc/gp_kernels.h"
+#include "../vbmc_amd/csrc/chol_mfma.h"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 

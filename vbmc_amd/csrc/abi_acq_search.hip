@@ -2,13 +2,15 @@
 // (include/vbmc_hip.h).  The optimiser is search_kernels.h; the objective is the prediction (gp_pred.h: pred_plan once, pred_launch
 // per generation, on points and column means the optimiser's kernel writes into the prediction's own buffers) followed by k_acq
 // (AcqConsts: the density-based functions) or by the tile form of the IQR functions (IqrTileObjective, iqr_tile_kernels.h).  Both entry
-// points are search_impl; generations are driven in chunks by drive_rounds (abi_gp_train.hip), the progress word read one chunk behind
+// points are search_impl; generations are driven in chunks by drive_rounds (round_driver.h), the progress word read one chunk behind
 // the one being enqueued.
 #include <algorithm>
 #include <cmath>
 
 #include "gp_pred.h"
 #include "iqr_tile_kernels.h"
+#include "parity_rng.h"
+#include "round_driver.h"
 #include "search_kernels.h"
 
 #define SEARCH_DEFAULT_CHUNK 16

@@ -16,7 +16,8 @@
 #include <string>
 #include <vector>
 
-#include "elbo_pass.h"   // the plan, the pass and its read-back; the slot functions used below are abi_elbo_slots.hip's, included before this file
+#include "elbo_pass.h"    // the plan, the pass and its read-back
+#include "elbo_slots.h"   // the slot core the multi-GPU submit / collect are built on
 
 namespace {
 

@@ -1,6 +1,6 @@
 // C-ABI entry points of libvbmc_hip.so for the ELBO objective (include/vbmc_hip.h): the blocking batch, the sharded evaluation and the
-// on-device Adam loop.  The pass itself -- plan, stages, read-back -- is elbo_pass.h; the pipelined form is abi_elbo_slots.hip.  Included
-// after abi_ctx.hip, whose null_gp_for the entropy-only call uses.
+// on-device Adam loop.  The pass itself -- plan, stages, read-back -- is elbo_pass.h; the pipelined form is abi_elbo_slots.hip.
+#include "ctx_core.h"    // null_gp_for: the entropy-only call
 #include "elbo_pass.h"
 
 // ------------------------------------------------------------------------------------------

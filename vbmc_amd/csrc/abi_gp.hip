@@ -5,14 +5,9 @@
 #include <cmath>
 #include <limits>
 
+#include "ctx_core.h"    // gp_constants, gp_upload_impl
 #include "gp_factor.h"
 #include "gp_pred.h"
-
-// abi_ctx.hip's: the per-sample constants of a surrogate, and a surrogate assembled from host or device blocks
-static void gp_constants(int D, int S, int Nhyp, int Ncov, int Nnoise, int meanfun, const double* hyp, double* gpc);
-static vbmc_status gp_upload_impl(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, int Ncov, int Nnoise, int meanfun, const double* X,
-                                  const double* hyp, const double* alpha, const double* L, const double* dL_chol, const double* dL_inv,
-                                  const double* sW1, const uint8_t* Lchol, vbmc_gp** out);
 
 // ------------------------------------------------------------------------------------------
 extern "C" vbmc_status vbmc_sq_dist(vbmc_ctx* ctx, int D, int n, int m, const double* a, const double* b, double* C) {

@@ -3,9 +3,10 @@
 // decoupled from the hyper-samples, every candidate under all of them (k_gs_pred into Sg x E x C means and variances, k_gs_target
 // into the E x C values), no limit on the records.  Host side: validation, the start (the caller's, or draws of k_vp_draw) clipped
 // into the box and written into the sampler's walker buffer, the noise estimate (gp_pred.h: NnNoise) in the same stream in front of
-// the chain, the closing k_gs_finish and the copies back.  Included after abi_vp_tools.hip (vpt_pack, vpt_gen_host).
+// the chain, the closing k_gs_finish and the copies back.  The packing of a posterior and the split of a draw are vp_tools_host.h's.
 #include "gp_surrogate_kernels.h"
 #include "is_core.h"
+#include "vp_tools_host.h"
 
 #define GS_DEFAULT_NNN 20000
 #define GS_MAX_E 64

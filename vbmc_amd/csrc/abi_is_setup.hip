@@ -1,10 +1,12 @@
 // C-ABI entry points of the one-call set-up of the IMIQR importance sampler: vbmc_acq_is_setup and vbmc_acq_is_setup_rng_dump
 // (include/vbmc_hip.h).  Step 1 and the resampling are is_setup_kernels.h; the prediction of the Step 1 points is k_is_pred on the
 // set-up the sampler uses anyway (every ensemble's point buffer holds the same Na1 points); the starting walkers are written where
-// the sampler (is_core.h) expects them, so that Step 2 -- the IMIQR target of abi_is_sample.hip: imiqr_begin, imiqr_rounds,
+// the sampler (is_core.h) expects them, so that Step 2 -- the IMIQR target of imiqr_target.h: imiqr_begin, imiqr_rounds,
 // imiqr_close -- follows in the same stream.
+#include "imiqr_target.h"
 #include "is_core.h"
 #include "is_setup_kernels.h"
+#include "parity_rng.h"
 
 namespace {
 inline size_t iss_block_len(int D, int S, int W, int Na1) { return (size_t)(D + 1) * Na1 + (size_t)W * S; }

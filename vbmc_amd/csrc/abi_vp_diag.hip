@@ -1,10 +1,11 @@
 // C-ABI entry point of the multi-run diagnostics: vbmc_vp_diagnostics (include/vbmc_hip.h).  The kernels are diag_kernels.h and, for
-// what is per run, mtv_kernels.h and k_vp_draw; packing and the split of a draw are abi_vp_tools.hip's, the cosine table, the constants
-// of fixed_point and the host tail of a column (normalisation, spline) abi_vp_mtv.hip's.  Per run: one draw into the single sample
+// what is per run, mtv_kernels.h and k_vp_draw; packing and the split of a draw are vp_tools_host.h's, the cosine table, the constants
+// of fixed_point and the host tail of a column (normalisation, spline) mtv_host.h's.  Per run: one draw into the single sample
 // buffer, its mesh and counts, its own density and the R - 1 cross densities; then over all R D columns at once the cosine transform,
 // the bandwidth and the inverse transform; R D splines on the host; one integral launch over every pair and dimension.
-// Included after abi_vp_mtv.hip.
 #include "diag_kernels.h"
+#include "mtv_host.h"
+#include "vp_tools_host.h"
 
 extern "C" vbmc_status vbmc_vp_diagnostics(vbmc_ctx* ctx, int32_t R, const vbmc_vp_desc* const* vps, const vbmc_diag_args* args) {
   if (!ctx) return VBMC_ERR_INVALID;

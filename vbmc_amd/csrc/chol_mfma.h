@@ -20,6 +20,9 @@
 // GP = true: the 16 x Np panel does not fit the LDS (N > 1200) and lives in a global scratch block.
 // Measured (tools/chol_bench.hip, MI355X): N = 400: 0.29 ms for one matrix, 0.38 ms for 256 (first generation: 0.52 / 0.66).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_math.h"   // vb_d4
 
 #ifndef CH2_THREADS
 #define CH2_THREADS 512
@@ -48,6 +51,21 @@
 // tile factorisation + the panel
 #define CH2_LDS_FIXED (5 * 16 * 17 + 64)
 #define CHOL2_LDS_BYTES(N) ((size_t)(CH2_LDS_FIXED + 16 * (size_t)((((N) + 15) >> 4) << 4)) * sizeof(double))
+
+#ifdef CHOL_TS   // tools/chol_bench.hip only: per-step phase stamps of matrix 0 (wall_clock64, 100 MHz)
+__device__ long long g_chol_ts[4 * 512];
+__device__ long long g_chol_clk[2 * 512];   // shader-clock readings next to slot 0 / slot 3: cycles per microsecond = the clock the CU really ran at
+#define CHOL_STAMP(slot, step) do { if (blockIdx.x == 0 && (step) < 512) { g_chol_ts[4 * (step) + (slot)] = wall_clock64(); if ((slot) == 0) g_chol_clk[2 * (step)] = clock64(); if ((slot) == 3) g_chol_clk[2 * (step) + 1] = clock64(); } } while (0)
+#else
+#define CHOL_STAMP(slot, step) do { } while (0)
+#endif
+
+__device__ __forceinline__ double chol_readlane(double v, int l) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_readlane(lo, l);
+  hi = __builtin_amdgcn_readlane(hi, l);
+  return __hiloint2double(hi, lo);
+}
 
 // sqrt(p) and 1/sqrt(p) from the v_rsq_f64 seed with two Goldschmidt steps and a final residual correction (the sequence of
 // the compiler's own sqrt expansion, which also yields the reciprocal root): ~12 dependent operations instead of an IEEE sqrt
@@ -120,7 +138,7 @@ __device__ __forceinline__ void chol_diag_tile3(double (&X)[4], double* __restri
     }
     X[b] = lg == 0 ? w[0] : (lg == 1 ? w[1] : (lg == 2 ? w[2] : w[3]));
     if (b < 3) {
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[b], X[b], acc, 0, 0, 0);
 #pragma unroll
       for (int r = b + 1; r < 4; ++r) X[r] -= acc[r];
@@ -263,7 +281,7 @@ __device__ __forceinline__ bool chol_diag_tile_fast(double (&X)[4], double* __re
     const double lsel = lg == 0 ? l0 : (lg == 1 ? l1 : (lg == 2 ? l2 : l3));
     const double usel = lg == 0 ? u0 : (lg == 1 ? u1 : (lg == 2 ? u2 : u3));
     if (b < 3) {
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lsel, usel, acc, 0, 0, 0);
 #pragma unroll
       for (int r = b + 1; r < 4; ++r) X[r] -= acc[r];
@@ -508,17 +526,17 @@ __global__ void __launch_bounds__(CH2_THREADS) k_chol2(int N, double* __restrict
         for (int p = 0; p < PT; ++p) {
           const int tj = tb + p * CH2_W, j = (tj << 4) + li;
           if (tj < nt) {                                                   // wave-uniform
-            d4_t acc = {0.0, 0.0, 0.0, 0.0};
+            vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], bv[p][q], acc, 0, 0, 0);
             // One step of iterative refinement: the product with the explicit inverse is only accurate to cond(Rkk) eps (2e-8 in
             // alpha on a kernel matrix of condition 1e7, found by the random-shape sweep), the substitution it replaces was
             // backward stable.  res = A - Rkk' P (register q of the accumulator layout IS k-slice q of a B operand), P += W res.
-            d4_t res = {bv[p][0], bv[p][1], bv[p][2], bv[p][3]};
+            vb_d4 res = {bv[p][0], bv[p][1], bv[p][2], bv[p][3]};
 #pragma unroll
             for (int q = 0; q < 4; ++q) res = __builtin_amdgcn_mfma_f64_16x16x4f64(-rv[q], acc[q], res, 0, 0, 0);
             {
-              const d4_t rr = res;
+              const vb_d4 rr = res;
 #pragma unroll
               for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], rr[q], acc, 0, 0, 0);
             }
@@ -561,7 +579,7 @@ __global__ void __launch_bounds__(CH2_THREADS) k_chol2(int N, double* __restrict
         for (int r = 0; r < 4; ++r) X[r] = Xn[r];
       } else load_diag(At, nb2, X);
       CH2_LSTAMP(1);
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
       const d4v pa = ldP4(pbuf, lg, li);
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[q], pa[q], acc, 0, 0, 0);
@@ -616,7 +634,7 @@ __global__ void __launch_bounds__(CH2_THREADS) k_chol2(int N, double* __restrict
           const bool ok = i < ntr && j < ntr;
           c[r] = At[ok ? j * N + i : 0];
         }
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
+        vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
         {
           const d4v pj = ldP4(pbuf, lg, j0 + li), pi = ldP4(pbuf, lg, i0 + li);
 #pragma unroll
@@ -691,9 +709,9 @@ __global__ void __launch_bounds__(CH2_THREADS) k_chol2(int N, double* __restrict
           }
         }
         CH2_GSTAMP(1);
-        d4_t ae[2], ao[2];
+        vb_d4 ae[2], ao[2];
 #pragma unroll
-        for (int g = 0; g < 2; ++g) { ae[g] = (d4_t){0.0, 0.0, 0.0, 0.0}; ao[g] = (d4_t){0.0, 0.0, 0.0, 0.0}; }
+        for (int g = 0; g < 2; ++g) { ae[g] = (vb_d4){0.0, 0.0, 0.0, 0.0}; ao[g] = (vb_d4){0.0, 0.0, 0.0, 0.0}; }
 #pragma unroll
         for (int pn = 0; pn < (TWO ? 2 : 1); ++pn) {
           const int buf = TWO ? 1 - pn : 0, sh = (TWO && pn == 1) ? 16 : 0;   // panel B first (its columns start at this step's t0)
@@ -792,9 +810,9 @@ __global__ void __launch_bounds__(CH2_THREADS) k_chol2(int N, double* __restrict
           }
         }
         CH2_GSTAMP(1);
-        d4_t acc[CH2_G];
+        vb_d4 acc[CH2_G];
 #pragma unroll
-        for (int g = 0; g < CH2_G; ++g) acc[g] = (d4_t){0.0, 0.0, 0.0, 0.0};
+        for (int g = 0; g < CH2_G; ++g) acc[g] = (vb_d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int pn = 0; pn < (TWO ? 2 : 1); ++pn) {
           const int buf = TWO ? 1 - pn : 0, sh = (TWO && pn == 1) ? 16 : 0;   // panel B first (its columns start at this step's t0)

@@ -8,7 +8,7 @@
 
 #include "elbo_kernels.h"
 #include "var_kernels.h"
-#include "gp_kernels.h"
+#include "gp_pred_kernels.h"   // PRED_LDS_MAX, PRED_MAXG: what ensure_tinv's product has to fit
 #include "elbo_launch_plan.h"
 
 // ------------------------------------------------------------------------------------------

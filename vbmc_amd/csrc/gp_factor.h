@@ -9,7 +9,9 @@
 #include <functional>
 #include <limits>
 
-#include "elbo_pass.h"   // copy_f64_small; gp_kernels.h
+#include "elbo_pass.h"   // copy_f64_small
+#include "gp_factor_kernels.h"
+#include "gp_nlz_kernels.h"
 
 namespace {
 

@@ -6,9 +6,12 @@
 #include <algorithm>
 #include <cmath>
 
-#include "gp_factor.h"   // HandleGuard; elbo_pass.h: ensure_tinv; gp_kernels.h
+#include "elbo_pass.h"   // ensure_tinv
+#include "gp_acq_kernels.h"
+#include "gp_factor.h"   // HandleGuard
+#include "gp_pred_kernels.h"
 
-// D -> QS = ceil(D / 4) steps of the MFMA distance blocks, the way DISPATCH_GPDT (gp_kernels.h) pads D; nothing runs for D > 32
+// D -> QS = ceil(D / 4) steps of the MFMA distance blocks, the way DISPATCH_GPDT (gp_factor_kernels.h) pads D; nothing runs for D > 32
 #define DISPATCH_QS_CASE(QSV, ...) case QSV: { constexpr int QS = QSV; __VA_ARGS__; } break;
 #define DISPATCH_QS(D_, ...)                                                                                          \
   switch (((D_) + 3) / 4) {                                                                                           \

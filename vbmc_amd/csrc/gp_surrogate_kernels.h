@@ -17,6 +17,7 @@
 // k_gs_start clips W E points -- draws of k_vp_draw or the caller's -- into [LB, UB] (gplite_sample.m:102) and writes them into the
 // sampler's walker buffer.  Nothing is atomic, no transcendental is the device library's.
 #pragma once
+#include "is_sample_kernels.h"   // isp_body, IsPredArgs
 #include "vp_tools_kernels.h"
 
 template <int QS>

@@ -1,6 +1,6 @@
 // The device half of the GP objective that the slice sampler (slice_kernels.h) and the train optimiser (trainopt_kernels.h) share:
 // what turns one candidate hyper-parameter vector into the inputs of the batched gplite_nlZ path (k_gp_scale .. k_nlz_final,
-// abi_gp.hip: gp_launch_*), and the noise inflation between two tries of a checked factorisation.  Both callers promise their
+// gp_factor.h: gp_launch_*), and the noise inflation between two tries of a checked factorisation.  Both callers promise their
 // results bit for bit (W-invariance, parity with the NumPy restatements), so there is one copy of this arithmetic.
 #pragma once
 #include "common.h"

@@ -1,5 +1,5 @@
 // The IQR acquisition functions (acq/acqviqr_vbmc.m:36-109, acq/acqimiqr_vbmc.m:30-95) for ONE tile of at most 16 points: the
-// objective of the device-resident acquisition search on noisy targets (vbmc_acq_search_iqr).  k_acq_iqr (gp_kernels.h) is shaped for
+// objective of the device-resident acquisition search on noisy targets (vbmc_acq_search_iqr).  k_acq_iqr (gp_acq_kernels.h) is shaped for
 // sweeps of thousands of points -- eight waves of 16 points each, every wave walking all ceil(N / 16) chunks of Ctmp behind a workgroup
 // barrier; with the search's lambda <= 16 points seven of its waves are idle and the grid is S workgroups.  Here the work of the one
 // tile is split the other way:
@@ -17,7 +17,9 @@
 // depends neither on its slot nor on the other slots (an MFMA output element is a function of its own row and column).
 // Slots lam .. 15 are padding: their indices are clamped, their A operands are zero and their records are not written.
 #pragma once
-#include "gp_kernels.h"
+#include "common.h"
+#include "device_math.h"
+#include "gp_acq_kernels.h"   // IqrArgs, iqr_final_point
 
 #define IQRT_MAXW 8
 #define IQRT_LDS_BYTES(W) ((size_t)(W) * 256 * sizeof(double))
@@ -68,7 +70,7 @@ __global__ void __launch_bounds__(64 * IQRT_MAXW) k_acq_iqr_tile(IqrTileArgs a) 
   const bool pvalid = li < lam;
   const double isw = a.lchol[s] ? sqrt(a.sn2_eff[s]) : 1.0;      // undo sW = 1/sqrt(sn2_eff)
   const int nch = (N + 15) >> 4;
-  d4_t acc = {0.0, 0.0, 0.0, 0.0};
+  vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
   double kv[4], bv[4], kvn[4], bvn[4];                           // this wave's chunk and its next one, loaded one step ahead
   auto fetch = [&](int c, double* k, double* b) {
 #pragma unroll

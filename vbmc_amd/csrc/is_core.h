@@ -3,7 +3,7 @@
 // doubles it wants behind the E x C values k_is_step reads, a kernel of k_is_pred's shape picked for the GP's D (IsPredKernel), and a
 // callable that enqueues the evaluation of a round's candidates into those values.  The core owns the parameters and their checks,
 // the prediction's per-hyper-sample set-up (k_pred_prep of gp_pred.h's pred_plan, centred on the training inputs alone), the state
-// block, the uniforms, the rounds (drive_rounds of abi_gp_train.hip, the E progress words read one chunk behind the one being
+// block, the uniforms, the rounds (drive_rounds of round_driver.h, the E progress words read one chunk behind the one being
 // enqueued) under their cap, the ensembles' final states with their errors, and the report of starts of zero density.  It returns the
 // run's counters and leaves the recorded walkers c.a.Xa and their values c.a.rlp on the device.
 #pragma once
@@ -13,6 +13,7 @@
 
 #include "gp_pred.h"
 #include "is_sample_kernels.h"
+#include "round_driver.h"
 
 #define IS_DEFAULT_CHUNK 16
 #define IS_DEFAULT_SPEC 3

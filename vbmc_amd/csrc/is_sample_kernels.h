@@ -17,8 +17,11 @@
 // for every spec; a point's value depends neither on its slot nor on its companions (an MFMA output element is a function of its own row
 // and column, every sum runs in a fixed order, nothing is atomic).
 #pragma once
-#include "gp_kernels.h"
-#include "search_kernels.h"   // srch_log, slice_uniform, slice_prop
+#include "common.h"
+#include "device_math.h"
+#include "gp_factor_kernels.h"   // gp_meanfun
+#include "gp_pred_kernels.h"     // PredArgs
+#include "parity_rng.h"          // srch_log, slice_uniform, slice_prop
 
 #define IS_MAXH 33              // W = 2 H <= 2 (VBMC_LIM_D + 1)
 #define IS_MAXSPEC 4
@@ -343,7 +346,7 @@ __device__ __forceinline__ void isp_body(const IsPredArgs& g, const int t, const
   bb = xor_sum32(bb);
   for (int nb = wave; nb < nblk; nb += NWV) {
     const int n0 = nb * 16, na = min(n0 + li, N - 1);
-    d4_t acc = {0.0, 0.0, 0.0, 0.0};
+    vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < QS; ++q) {
       const int d = 4 * q + lg;
@@ -378,7 +381,7 @@ __device__ __forceinline__ void isp_body(const IsPredArgs& g, const int t, const
     const int rt = nblk - 1 - k;
     const int ncol = lc ? (rt + 1) * 16 : Np;
     const int row = rt * 16 + li;
-    d4_t acc = {0.0, 0.0, 0.0, 0.0};
+    vb_d4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int c0 = 0; c0 < ncol; c0 += 16) {      // (ncol is a multiple of 16: four k-steps, their loads ahead of the MFMAs)
       double av[4], bv[4];
 #pragma unroll

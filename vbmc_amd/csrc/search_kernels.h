@@ -4,12 +4,13 @@
 //   k_search_step   consume the previous generation's lambda acquisition values (rank, update xmean / ps / pc / C / sigma, the bests,
 //                   the history ring, the stopping rules, the progress word), factorise C, draw or read Z, write the lambda clamped
 //                   points and their column means straight into the prediction's device buffers
-//   the prediction of <= 16 points x S hyper-samples (abi_gp.hip: pred_launch) and k_acq, which leave the lambda values on the device.
+//   the prediction of <= 16 points x S hyper-samples (gp_pred.h: pred_launch) and k_acq, which leave the lambda values on the device.
 // One workgroup of one wave: D <= 32, lambda <= 16.  The optimiser's own arithmetic is written with plain operators in scopes with
 // contraction off and every sum runs in index order, so that a trajectory is a function of (Z, F) alone -- not of the chunking, not of
 // the launch that happens to run it.
 #pragma once
-#include "slice_kernels.h"   // slice_philox
+#include "common.h"
+#include "parity_rng.h"
 
 #define SRCH_MAXD 32
 #define SRCH_MAXLAM 16
@@ -45,64 +46,6 @@ struct SearchArgs {
   int* tr_order;                      // trace_cap x lam   (all four may be null)
   double *tr_F, *tr_xmean, *tr_sigma; // trace_cap x lam sorted values, trace_cap x D, trace_cap
 };
-
-// ---- the library's own normals: Philox4x32-10 keyed by the seed, counter (generation, point, d); 52 bits -> u in (0, 1) -> the
-// inverse normal CDF by Wichura's AS 241 (PPND16).  Only +, -, *, /, sqrt and integer operations, each rounded on its own (contraction
-// off) -- the logarithm of the tail branch included (srch_log) --, so that the host (vbmc_acq_search_rng_dump) and the device compute
-// the same bits.
-__host__ __device__ inline double srch_log(double x) {   // ln x for a positive normal x, |error| ~ 1e-16 relative
-#pragma clang fp contract(off)
-  unsigned long long b;
-  memcpy(&b, &x, 8);
-  int e = (int)((b >> 52) & 0x7ff) - 1023;
-  b = (b & 0x000fffffffffffffull) | 0x3ff0000000000000ull;
-  double m;
-  memcpy(&m, &b, 8);                                     // [1, 2)
-  if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }   // [sqrt(1/2), sqrt(2)]
-  const double t = (m - 1.0) / (m + 1.0), t2 = t * t;    // ln m = 2 atanh t, t^2 <= 0.0295
-  double s = 1.0 / 27.0;
-  s = s * t2 + 1.0 / 25.0; s = s * t2 + 1.0 / 23.0; s = s * t2 + 1.0 / 21.0; s = s * t2 + 1.0 / 19.0; s = s * t2 + 1.0 / 17.0;
-  s = s * t2 + 1.0 / 15.0; s = s * t2 + 1.0 / 13.0; s = s * t2 + 1.0 / 11.0; s = s * t2 + 1.0 / 9.0; s = s * t2 + 1.0 / 7.0;
-  s = s * t2 + 1.0 / 5.0; s = s * t2 + 1.0 / 3.0; s = s * t2 + 1.0;
-  return (double)e * 0.6931471805599453 + 2.0 * t * s;
-}
-__host__ __device__ inline double srch_ndtri(double p) {
-#pragma clang fp contract(off)
-  const double q = p - 0.5;
-  if (q >= -0.425 && q <= 0.425) {
-    const double r = 0.180625 - q * q;
-    const double num = (((((((2.5090809287301226727e+3 * r + 3.3430575583588128105e+4) * r + 6.7265770927008700853e+4) * r + 4.5921953931549871457e+4) * r +
-                           1.3731693765509461125e+4) * r + 1.9715909503065514427e+3) * r + 1.3314166789178437745e+2) * r + 3.3871328727963666080e+0) * q;
-    const double den = ((((((5.2264952788528545610e+3 * r + 2.8729085735721942674e+4) * r + 3.9307895800092710610e+4) * r + 2.1213794301586595867e+4) * r +
-                          5.3941960214247511077e+3) * r + 6.8718700749205790830e+2) * r + 4.2313330701600911252e+1) * r + 1.0;
-    return num / den;
-  }
-  double r = q < 0.0 ? p : 1.0 - p;
-  r = sqrt(-srch_log(r));
-  double x;
-  if (r <= 5.0) {
-    r = r - 1.6;
-    const double num = ((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r + 1.27045825245236838258e+0) * r +
-                          3.64784832476320460504e+0) * r + 5.76949722146069140550e+0) * r + 4.63033784615654529590e+0) * r + 1.42343711074968357734e+0;
-    const double den = ((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r + 1.48103976427480074590e-1) * r +
-                          6.89767334985100004550e-1) * r + 1.67638483018380384940e+0) * r + 2.05319162663775882187e+0) * r + 1.0;
-    x = num / den;
-  } else {
-    r = r - 5.0;
-    const double num = ((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r + 2.65321895265761230930e-2) * r +
-                          2.96560571828504891230e-1) * r + 1.78482653991729133580e+0) * r + 5.46378491116411436990e+0) * r + 6.65790464350110377720e+0;
-    const double den = ((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r + 7.86869131145613259100e-4) * r +
-                          1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r + 5.99832206555887937690e-1) * r + 1.0;
-    x = num / den;
-  }
-  return q < 0.0 ? -x : x;
-}
-__host__ __device__ inline double srch_normal(unsigned long long seed, unsigned gen, unsigned point, unsigned d) {
-  unsigned c[4] = {gen, point, d, 2u};
-  slice_philox(c, (unsigned)seed, (unsigned)(seed >> 32));
-  const double v = (double)(c[0] >> 6) * 67108864.0 + (double)(c[1] >> 6);   // < 2^52: exact
-  return srch_ndtri((v + 0.5) * 2.220446049250313e-16);
-}
 
 // lower Cholesky factor of the D x D matrix sC (leading dimension SRCH_MAXD + 1) into sA, column by column, lane i owning row i; every
 // inner product in index order.  False: a pivot that is not positive (or not a number).  All 64 lanes call it.

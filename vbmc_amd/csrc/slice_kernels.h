@@ -1,7 +1,7 @@
 // Device-resident slice sampler for the GP hyper-parameter posterior (utils/slicesamplebnd.m:229-358 with StepOut = false, target
 // gp_objfun with swapsign, gplite_train.m:318): the chain's state lives on the device and one ROUND of the chain is
 //   k_slice_propose  W speculative shrink proposals of the open coordinate -> the hyper-parameter block, noise vectors, jitter scalars
-//                    and hyper-prior of the batched gplite_nlZ value path (k_gp_scale .. k_nlz_final, abi_gp.hip: gp_launch_*)
+//                    and hyper-prior of the batched gplite_nlZ value path (k_gp_scale .. k_nlz_final, gp_factor.h: gp_launch_*)
 //   k_slice_decide   first accepted proposal (in order), chain update, bookkeeping of a finished sweep, set-up of the next coordinate
 // Speculation: with StepOut = false the k-th proposal UNDER THE HYPOTHESIS that proposals 1 .. k-1 were rejected is a function of the
 // current point, the interval and the uniforms alone (:283-304: a rejection moves the interval's end on the proposal's side).  Both
@@ -9,6 +9,7 @@
 // so the chain is the sequential one for every W, bit for bit.
 #pragma once
 #include "gpobj_kernels.h"
+#include "parity_rng.h"
 
 struct SliceChainState {
   int phase;            // 0: the evaluation at hyp_start is pending, 1: running, 2: finished, 3: stopped with an error
@@ -40,44 +41,11 @@ struct SliceKernelArgs : GpObjArgs {           // (hyp, sn2, scal, lp: one row p
   double *samples, *logp;                     // Ns x Nhyp (column-major), Ns
 };
 
-// ---- the library's own uniforms: Philox4x32-10 keyed by the seed, counter (sweep, idd, slot, stream); 52 bits -> (0, 1).
-// Integer arithmetic and exactly representable fp64 steps: the host (vbmc_slice_rng_dump) and the device compute the same bits.
-__host__ __device__ inline void slice_philox(unsigned c[4], unsigned k0, unsigned k1) {
-  for (int i = 0; i < 10; ++i) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-__host__ __device__ inline double slice_uniform(unsigned long long seed, unsigned sweep, unsigned idd, unsigned slot) {
-  unsigned c[4] = {sweep, idd, slot, 0u};
-  slice_philox(c, (unsigned)seed, (unsigned)(seed >> 32));
-  const double v = (double)(c[0] >> 6) * 67108864.0 + (double)(c[1] >> 6);   // < 2^52: exact
-  return (v + 0.5) * 2.220446049250313e-16;                                  // (v + 1/2) 2^-52
-}
-__host__ __device__ inline unsigned slice_perm_word(unsigned long long seed, unsigned sweep, unsigned j) {
-  unsigned c[4] = {sweep, j, 0u, 1u};
-  slice_philox(c, (unsigned)seed, (unsigned)(seed >> 32));
-  return c[0];
-}
-
 // slot 0: slice level (:245), 1: interval placement (:252), 2 + k: k-th shrink proposal (:286).  NaN: the parity block has no such slot.
 __device__ __forceinline__ double slice_u(const SliceKernelArgs& a, int sweep, int idd, int slot) {
   if (!a.parity) return slice_uniform(a.seed, (unsigned)sweep, (unsigned)idd, (unsigned)slot);
   if (slot >= 2 + a.Kmax) return __builtin_nan("");
   return a.U[((size_t)sweep * a.Nhyp + idd) * (size_t)(2 + a.Kmax) + slot];
-}
-
-// xprime(dd) = rand()*(x_r(dd) - x_l(dd)) + x_l(dd)   (:286), every operation rounded on its own.  The compiler contracts a multiply
-// and an add into an fma unless told otherwise -- inside the __d*_rn intrinsics too, whose bodies are plain operators compiled with the
-// default setting, so they are no protection: the chain's own arithmetic is written with plain operators in a scope with contraction off --
-// this recursion, the interval placement, the burn-in sums whose variance of a FIXED coordinate is zero or a rounding error of either
-// sign (:347-349) --, so that it is MATLAB's arithmetic operation for operation.
-__device__ __forceinline__ double slice_prop(double u, double xl, double xr) {
-#pragma clang fp contract(off)
-  return u * (xr - xl) + xl;
 }
 
 // One workgroup per candidate w: the candidate's hyper-parameter vector, its noise vector / Cholesky branch (gplite_core.m:33-40,67,

@@ -14,7 +14,9 @@
 // Feistel network on 2 hb bits with cycle walking), so that the host dump reproduces it.
 // Kernels are templated on the padded dimension DT (4, 8, 12, 16, 24, 32): every per-dimension loop over registers is unrolled.
 #pragma once
-#include "is_sample_kernels.h"   // srch_log, srch_normal, slice_uniform, slice_philox, vb_exp_tab
+#include "common.h"
+#include "device_math.h"   // vb_exp_tab
+#include "parity_rng.h"    // srch_log, srch_normal, slice_uniform, slice_philox
 
 #define VPT_T 128                 // threads per workgroup
 #define VPT_TS (VPT_T + 1)        // stride of the per-thread stage columns (bank spread for the moments' row reads)
