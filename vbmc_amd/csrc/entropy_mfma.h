@@ -120,6 +120,22 @@ constexpr bool ent_sl_for(int KT, int QS, int TL, int HV, bool GRAD, bool WALK) 
   return TL == 0 || (KT == 2 && TL == 1) || (KT == 3 && TL == 2);
 }
 constexpr bool ent_sl_evl_for(int KT, int QS, int TL) { return QS == 3 && KT == 3 && TL == 0; }
+//  PM   ONE PV product per antithetic pair (dense SL kernels).  With r+-_ik = n+-_ik / q'+-_i, p = r+ + r-, m = r+ - r-, a_k = w_k/sigma_k^2 and
+//       V_kd = a_k m'_kd the two signs' gradient pieces (gd = (t A' - B'_d)/q', t = +-u'_id; G += gd, LG += t gd, W_k += n_ik/q'_i) add up to
+//         W_k  = sum_i p_ik
+//         G_d  = sum_i u'_id Am_i - sum_k V_kd W_k          Am_i = sum_k a_k m_ik
+//         LG_d = sum_i u'_id (u'_id Ap_i - Bm_id)           Ap_i = sum_k a_k p_ik,  Bm_id = sum_k V_kd m_ik
+//       so the PV step runs once per tile, on m (same operand table, same slot map: Bm_d in slot d, Am in 10, 11; the q' slots go unused), and
+//       the B' part of G is a K x D contraction of the finished W record in the wave's epilogue.  q'+- and Ap come from the VALU: lane-local
+//       FMAs against [w_k, a_k] (a pair table in LDS, broadcast reads) and two cross-lane adds over the lane groups each.  r+- are
+//       responsibilities in [0, 1]: no new cancellation (tests/test_gpu_entropy_sign_pair.py restates the regrouping in numpy).
+//       Per tile of the headline class 13 MFMAs fewer (35 -> 22) for about 60 fp64 VALU instructions more.  A subset of SL, gated the same
+//       way (tools/isa_meta.py against the parent: no more vgpr_spill, the same waves/SIMD in every line of the class): three k-tiles with
+//       a one-value tail at D = 7..10 (K = 49..52).  Without the tail (K = 41..48) both signs' exponentials alive at once spill 36-58 VGPRs
+//       in all three lines of the class (256 before): it keeps SL.
+constexpr bool ent_pm_for(int KT, int QS, int TL, int HV, bool GRAD, bool WALK) {
+  return ent_sl_for(KT, QS, TL, HV, GRAD, WALK) && QS == 3 && KT == 3 && TL == 1;
+}
 
 // Ordering point for LDS words that only ONE wave touches (lanes of a wave exchanging values through LDS): the hardware
 // executes a wave's LDS instructions in order, so no s_barrier and no full s_waitcnt drain is needed -- only the compiler must
@@ -199,6 +215,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   __shared__ double Et[16 * DP];   // eps tile [i][d], staged by wave 0 and shared by the HV waves of the workgroup
   constexpr bool SL = NPV == 1 && ent_sl_for(KT, QS, TL, HV, GRAD, WALK);
   constexpr bool GP2 = GRAD && !SL && ent_gp2_for(KT, QS, TL, HV);
+  constexpr bool PM = SL && !SPARSE && ent_pm_for(KT, QS, TL, HV, GRAD, WALK);   // one PV product per antithetic pair (see ent_pm_for)
   __shared__ double RQ_all[HV][SL ? 1 : (GP2 ? 32 : 16)];   // q'_i then 1/q'_i  (GP2: and A'_i then A'_i/q'_i behind them; SL: no exchange)
   __shared__ double BND_all[HV][SPARSE ? KT * 16 * 3 : 1];  // per component: |m'_k|, cK_k - cK_j, h_k  (block-sparse bound)
   // partial PV outputs of the two halves, double-buffered by sign so that one workgroup barrier per sign is enough
@@ -221,6 +238,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #define ENT_CI(kt_, rr_) (16 * (kt_) + 4 * (rr_) + lg)
   __shared__ __attribute__((aligned(16))) double SCP_all[HV][C2 ? KT * 16 * 2 : 2];   // C2: [component 16 kt + c][2 c0, 2 c1] of the even part
   __shared__ double BTL_all[HV][TL ? 4 * TL * DP : 1];  // tail: linear S-step coefficients [t][d] (x 1024/ln2), zero beyond D and for absent components
+  __shared__ __attribute__((aligned(16))) double WAP[PM ? KT * 16 * 2 : 2];   // PM: [component 16 kt + c][w_k, a_k = w_k/sigma_k^2], zero for padded components
   constexpr bool NML = HV > 1 && EO;   // multi-wave workgroups park the second sign's exponents in LDS: their registers are spoken for
   __shared__ double NMS_all[HV][NML ? KT * 4 * WAVE : 1];
 #ifdef VBMC_INSTRUMENT
@@ -342,6 +360,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     SC[kt] = ESC * (!kv ? (lg == 1 ? -1.0e6 : 0.0)                          // padded component: exp -> 0
                         : (lg == 0 ? h + hj_neg : (lg == 1 ? fma(h, m2, pk[D + 1]) - cKj : 0.0)));
     if (C2 && lg < 2) SCP[(16 * kt + li) * 2 + lg] = 2.0 * SC[kt];
+    if (PM && lg < 2) WAP[(16 * kt + li) * 2 + lg] = kv ? pk[D + 2 + lg] : 0.0;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int k2 = ENT_CI(kt, rr);
@@ -376,9 +395,10 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   // ---- tail components 16 KT + lg (TL): even-part coefficients, PV operand and weight in registers (one component per lane
   // group), the linear coefficients as a row of BTL
   double tC0[TLN], tC1[TLN], VBt[TLN][NPV], WFt[TLN], Wt[TLN];
+  double tA[TLN];   // PM: a_k of the lane's tail component (its w_k is WFt)
 #pragma unroll
   for (int u = 0; u < TLN; ++u) {
-    tC0[u] = 0.0; tC1[u] = 0.0; WFt[u] = 0.0; Wt[u] = 0.0;
+    tC0[u] = 0.0; tC1[u] = 0.0; WFt[u] = 0.0; Wt[u] = 0.0; tA[u] = 0.0;
 #pragma unroll
     for (int pv = 0; pv < NPV; ++pv) VBt[u][pv] = 0.0;
   }
@@ -414,6 +434,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
           }
           VBt[u][pv] = v;
         }
+        if (PM) { WFt[u] = kvq ? pq[D + 2] : 0.0; tA[u] = kvq ? pq[D + 3] : 0.0; }
       } else {
         WFt[u] = kvq ? pq[D + 2] : 0.0;
       }
@@ -760,6 +781,19 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       accH += shift;
       return rqs;
     };
+    // (PM: the same per-sample bookkeeping on a q' that came from the VALU.  Kept apart from get_rq: with the two folded into one helper the
+    // compiler schedules nineteen instantiations of the QS = 3 unit differently, multi-wave ones among them -- code no measurement here covers.)
+    auto rq_pm = [&](double qs_) -> double {
+      double rqs = vb_rcp(qs_);
+      if (partial) {
+        qs_ = svalid ? qs_ : 1.0;
+        rqs = svalid ? rqs : 0.0;
+      }
+      pm *= __builtin_amdgcn_frexp_mant(qs_);
+      pe += __builtin_amdgcn_frexp_exp(qs_);
+      accH += shift;
+      return rqs;
+    };
     auto wacc = [&](mf4 (&x)[KT], double rqs, const double (&tn)[TLN]) {
       if (TL) {
 #pragma unroll
@@ -857,6 +891,77 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     using IH = std::integral_constant<int, (KT + 1) / 2>;
     using IK = std::integral_constant<int, KT>;
 
+    if constexpr (PM) {
+      // Both signs' exponentials first, q'+- and the pair's p = r+ + r-, m = r+ - r- on the VALU, then ONE PV chain on m (ent_pm_for).
+      // m overwrites n, p overwrites nm (the tail pair alike); samples beyond Mh have rqs = 0 and vanish from p, m and everything after.
+      exps(n, I0{}, IK{});
+      texp(ntl);
+      double qp = 0.0, qm = 0.0;
+      if (TL) {
+#pragma unroll
+        for (int u = 0; u < TLN; ++u) qp = fma(WFt[u], ntl[u], qp);
+      }
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) qp = fma(WAP[ENT_CI(kt, rr) * 2], n[kt][rr], qp);
+      // the first sign's cross-lane sum and reciprocal chain go under the second sign's exponentials (behind them: 1.929 against 1.923 ms per
+      // step, seven of eight alternating pairs, profiles/r09_sign_pair.md)
+      qp = xor_sum16(qp);
+      qp = xor_sum32(qp);
+      const double rqp = rq_pm(qp);
+      fold();
+      exps(nm, I0{}, IK{});
+      texp(ntm);
+      if (TL) {
+#pragma unroll
+        for (int u = 0; u < TLN; ++u) qm = fma(WFt[u], ntm[u], qm);
+      }
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) qm = fma(WAP[ENT_CI(kt, rr) * 2], nm[kt][rr], qm);
+      qm = xor_sum16(qm);
+      qm = xor_sum32(qm);
+      const double rqm = rq_pm(qm);
+      fold();
+      const double nrqm = -rqm;
+      double ap = 0.0;
+      if (TL) {
+#pragma unroll
+        for (int u = 0; u < TLN; ++u) {
+          const double rp = ntl[u] * rqp, x = ntm[u];
+          ntm[u] = fma(x, rqm, rp);
+          ntl[u] = fma(x, nrqm, rp);
+          Wt[u] += ntm[u];
+          ap = fma(tA[u], ntm[u], ap);
+        }
+      }
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const double rp = n[kt][rr] * rqp, x = nm[kt][rr];
+          nm[kt][rr] = fma(x, rqm, rp);
+          n[kt][rr] = fma(x, nrqm, rp);
+          Wacc[kt][rr] += nm[kt][rr];                                   // (:100, both signs)
+          ap = fma(WAP[ENT_CI(kt, rr) * 2 + 1], nm[kt][rr], ap);
+        }
+      mf4 Y[NPV];
+      pvstep(n, Y, 0, ntl);
+      ap = xor_sum16(ap);
+      ap = xor_sum32(ap);
+      // Am_i sits in register 2 of the lanes lg >= 2: every lane takes the value of lane | 32 (as get_rq does for A'_i / q'_i)
+      const double t2 = Y[0][2];
+      const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(t2), (unsigned)__double2loint(t2), false, false);
+      const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(t2), (unsigned)__double2hiint(t2), false, false);
+      const double am = __hiloint2double((int)hi[1], (int)lo[1]);
+#pragma unroll
+      for (int r = 0; r < QS; ++r) {     // register r: dimension 4 r + lg (the lanes lg >= 2 of register 2: accumulators nobody stores)
+        accG[r] = fma(ev[r], am, accG[r]);
+        accLG[r] = fma(ev[r], fma(ev[r], ap, -Y[0][r]), accLG[r]);
+      }
+    } else
     if constexpr (EO && GRAD && HV == 1 && VBMC_STAG_FOR(KT, QS, TL)) {
       // Both signs in straight-line code, staggered: the second sign's exponentials (independent of everything the first
       // sign's per-sample chain waits for -- the q' exchange through LDS, the reciprocal, the 1/q' exchange) are issued
@@ -1013,7 +1118,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         lgd += __shfl_xor(lgd, 4, 64); lgd += __shfl_xor(lgd, 8, 64);
         const int d = 4 * r + lg;
         const bool dv = li == 0 && d < D;
-        if (dv) { o[1 + d] = g; o[2 + D + d] = lgd; }
+        if (dv) { if (!PM) o[1 + d] = g; o[2 + D + d] = lgd; }      // (PM: G_d still lacks its W part, below)
         sgsum += dv ? lgd : 0.0;
       }
     } else {
@@ -1039,6 +1144,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       for (int w = 1; w < HV; ++w) sgsum += YX[w * YXN];
     }
     if (lane == 0 && hv == 0) o[1 + D] = sgsum;
+    double corr = 0.0;   // PM: this lane group's part of sum_k V[k][slot li] W_k (the PV operand of lane (li, lg) IS V[k][li] of its components)
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -1048,6 +1154,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         wv += __shfl_xor(wv, 4, 64); wv += __shfl_xor(wv, 8, 64);
         const int k = ENT_CI(kt, rr);
         if (li == 0 && k < Kw) o[2 + 2 * D + kbase + k] = wv;
+        if (PM) corr = fma(VBV(kt, rr, 0), wv, corr);
       }
     if (TL) {
 #pragma unroll
@@ -1057,6 +1164,20 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         wv += __shfl_xor(wv, 4, 64); wv += __shfl_xor(wv, 8, 64);
         const int k = 16 * KT + 4 * u + lg;
         if (li == 0 && k < Kw) o[2 + 2 * D + kbase + k] = wv;
+        if (PM) corr = fma(VBt[u][0], wv, corr);
+      }
+    }
+    if constexpr (PM) {   // G_d = sum_i u'_id Am_i - sum_k V_kd W_k: after the sum over the lane groups every lane of slot li = d holds the
+                          // second term, and the lane with li = 4 r + lg holds the row sum of register r for that very d -- no exchange
+      corr = xor_sum16(corr);
+      corr = xor_sum32(corr);
+#pragma unroll
+      for (int r = 0; r < QS; ++r) {
+        double g = accG[r];
+        g += __shfl_xor(g, 1, 64); g += __shfl_xor(g, 2, 64);
+        g += __shfl_xor(g, 4, 64); g += __shfl_xor(g, 8, 64);
+        const int d = 4 * r + lg;
+        if (li == d && d < D) o[1 + d] = g - corr;
       }
     }
   }
