@@ -96,7 +96,7 @@ CONFIGS = [
     ("K57-D10", 10, 40, 57, 2, 40, "lumpy"),
     # round 3: K = 57..64 at D >= 31 run on TWO waves with two k-tiles each (ent_hv_small, elbo_launch_plan.h), the last wave possibly short
     # (K = 59: 30 + 29); one-wave kernels with four k-tiles from D = 15 on, and with three from D = 27 on, are built for ONE wave per
-    # SIMD (VBMC_ENT_ONE_WAVE, entropy_mfma.h)
+    # SIMD (ent_one_wave_for, entropy_mfma.h)
     ("hv2-K64-D32", 32, 36, 64, 1, 32, "lumpy"),
     ("hv2-K59-D31", 31, 36, 59, 1, 32, "lumpy"),
     ("w1-K54-D32", 32, 36, 54, 1, 32, "lumpy"),

@@ -1,5 +1,5 @@
 """Builds variants of the library with extra -D flags on the entropy-kernel translation units (all nine QS) into
-vbmc_amd/lib/tune/lib_<name>.so.   usage: python tools/tune_build.py base: stag:-DVBMC_STAG pv2:-DVBMC_TUNE_PV2=1,-DVBMC_TUNE_EVREG=0
+vbmc_amd/lib/tune/lib_<name>.so.   usage: python tools/tune_build.py base: inst:-DVBMC_INSTRUMENT
 For tools/tune_sweep.py."""
 import os
 import subprocess

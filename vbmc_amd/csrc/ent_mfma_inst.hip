@@ -14,11 +14,9 @@
 template <int KT, int HV, int TL = 0>
 static int launch_kt(int mode, int grad, dim3 grid, hipStream_t st, const EntArgs& ea) {
   // dynamic LDS: the parameter block (<= 74 KB at K = 256, D = 32), reused by the exp table (8 KB) and the PV exchange of
-  // multi-wave workgroups (2 signs x HV waves x NPV x 4 x 64 doubles)
-  constexpr int NPV_ = (4 * QS_VALUE + 15) / 16;
+  // multi-wave workgroups (EntForm::DYN_LDS: it depends on QS and HV alone, so every variant of the class launched below has this one)
   size_t lds = (size_t)ea.K * (ea.D + ENTP_EXTRA) * sizeof(double);
-  size_t after = (size_t)VB_EXP_TAB1K_N * sizeof(double);          // the exp table takes the block's place once the operands are built
-  if (HV > 1) after += (size_t)(VBMC_ENT_EO(HV) ? 1 : 2) * HV * NPV_ * 4 * WAVE * sizeof(double);   // PV exchange: per sign, or one for both (entropy_mfma.h: YXSB)
+  constexpr size_t after = EntForm<QS_VALUE, KT, false, false, HV, TL, false, true, false>::DYN_LDS;
   if (after > lds) lds = after;
   const void* fn = nullptr;
   if constexpr (ent_mfma_role_inst(QS_VALUE, HV)) {

@@ -13,20 +13,28 @@
 // layout of the PV MFMA, so n never leaves registers and the weight gradient
 // W_l = sum_i n_il / q_i (entmc_vbmc.m:100) is one lane-local FMA per pair.
 //
-// One wave (= one 64-thread workgroup) per (sample chunk, source component j, restart r).  A tile is
-// 16 base samples, processed twice (+eps, -eps: antithetic, entmc_vbmc.m:53-54).  The pair shares the even part of the
-// exponent: E+ = C + L, E- = 2C - E+ with ONE even product C and ONE linear product L per tile (see the S-step below).
+// One workgroup of HV waves (HV = 1: K <= 64; 2, 4, 8: the components split over the waves) per (sample chunk, source component j,
+// restart r), or -- the walking launch -- per range of the launch's tile sequence.  A tile is 16 base samples, processed twice
+// (+eps, -eps: antithetic, entmc_vbmc.m:53-54).  The pair shares the even part of the exponent in every instantiation: E+ = C + L,
+// E- = 2C - E+ with ONE even product C and ONE linear product L per tile (see the S-step below); the second sign's exponents wait in
+// registers (single-wave workgroups) or parked in LDS (multi-wave ones).  The LDS tile holds u' = eps sigma_j, the product every reader wants.
 // The S-step operands are built once per wave and stay in registers, the PV operands of larger mixtures in LDS; LDS also
-// holds the 16 x D eps tile (read in two layouts), the 1024-entry exp table (in the space of the parameter block, which is
-// dead once the operands are built; the table's factor 1024/ln2 rides in the S-step operands) and 16 scalars.  The number of
-// k-tiles per wave KT <= 4 is a template parameter (K > 64: HV = 2 or 4 waves per workgroup share the components, see below);
+// holds the 16 x D tile of u' (read in two layouts), the 1024-entry exp table (in the space of the parameter block, which is
+// dead once the operands are built; the table's factor 1024/ln2 rides in the S-step operands), behind the table the one PV exchange buffer of
+// the multi-wave workgroups, and 16 scalars.  The number of k-tiles per wave KT <= 4 is a template parameter;
 // the last (components per wave) mod 16 <= 8 components can run as a lane-layout TAIL instead of a k-tile (TL, see below).
-// The tile body is straight-line code: the sign loop, or -- where its registers allow -- both signs staggered (VBMC_STAG_FOR).
+// The tile body is straight-line code in one of three schedules: one PV product for the pair (PM), both signs staggered (STAG), or the sign loop.
+// Which form an instantiation takes -- layouts, schedule, register budget, LDS -- is decided in ONE place, EntForm below, from the measured
+// policy tables (the ent_*_for functions) in front of it; tests/test_entropy_forms.py prints the table on the host and checks its invariants.
 // Padded components carry the constant -1e6 and vanish in the exp.
 // sum_i log q'_i is accumulated as a mantissa product + exponent sum (one log per 256 samples).
 // Partials have the same layout as k_entropy (sum log q | G[D] | SG | LG[D] | W[K]) and are reduced
 // by k_ent_reduce / k_finalize in a fixed order.
+// (The code is sensitive to how it is cut: a lambda of the body moved into a free function, or two of the per-sample helpers folded into
+// one, changes the address arithmetic and the schedule of many instantiations.  The lambdas stay lambdas.  Forms that were measured and
+// dropped -- the plain per-sign S-step, per-sign exchange buffers among them -- are in docs/history.md.)
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 #include "device_math.h"
@@ -35,26 +43,26 @@
 #include "logjoint_body.h"
 
 typedef double mf4 __attribute__((ext_vector_type(4)));
-// how the tile body learns whether its tile can hold samples beyond Mh: a run-time test, or compiled in (see VBMC_ENT_SPLIT)
-struct EntTileAny { static constexpr bool rt = false, val = true; };     // one body for every tile: the selects are always there (a run-time test of
-                                                                          // the tile gets if-converted into twice as many)
-struct EntTileFull { static constexpr bool rt = false, val = false; };
-struct EntTilePartial { static constexpr bool rt = false, val = true; };
-#define VBMC_ENT_SPLIT(KT_, QS_, TL_, HV_) ((HV_) == 1)
+// how the tile body learns, at compile time, whether its tile can hold samples beyond Mh
+struct EntTileFull { static constexpr bool val = false; };
+struct EntTilePartial { static constexpr bool val = true; };
 
-#ifdef VBMC_INSTRUMENT   // timeline experiment (tools/archive/r4_timeline.py): per wave [entry, loop start, loop end, exit] on the 100 MHz counter + HW_ID + XCC_ID
+#ifdef VBMC_INSTRUMENT   // timeline experiment (tools/ent_timeline.py): per wave [entry, loop start, loop end, exit] on the 100 MHz counter + HW_ID + XCC_ID
 #define VBMC_DBG_WAVES 32768
 __device__ unsigned long long g_ent_dbg[6 * VBMC_DBG_WAVES];
 #endif
 
-// The staggered schedule: both signs in straight-line code, the second sign's exponentials issued inside the first sign's
-// per-sample latency chain.  It pays where the registers are there: one and three k-tiles per wave (K <= 16, 33..48: no spills,
-// 0-6 % faster, tools/tune_sweep.py small); with two k-tiles (168-VGPR budget of three waves per SIMD) and with four (256) it
-// spills and loses 2-12 %, so those keep the sign loop.
+// ---- The policy tables: which (k-tiles KT, QS = ceil((D + 2) / 4), tail TL, waves per workgroup HV) class takes which form.  Each was set by
+// a sweep; the comments say which.
+//
+// STAG, the staggered schedule: both signs in straight-line code, the second sign's exponentials issued inside the first sign's
+// per-sample latency chain (single-wave gradient kernels).  It pays where the registers are there: one and three k-tiles per wave (K <= 16,
+// 33..48: no spills, 0-6 % faster, tools/tune_sweep.py small); with two k-tiles (168-VGPR budget of three waves per SIMD) and with four (256)
+// it spilled and lost 2-12 %, so those kept the sign loop.
 // At three k-tiles with a component tail and D >= 19 (QS >= 6), and without a tail at D >= 31, the staggered code spills too
 // (37-90 VGPRs) and the loop is 2-10 % faster again.
 // Round 4 (the in-loop log's twelve constant registers are gone): four k-tiles (-0.6..-2.5 %) and two k-tiles from D = 19 on (-1.8..-3.7 %) too.
-#define VBMC_STAG_FOR(KT_, QS_, TL_) ((KT_) == 1 || (KT_) == 4 || ((KT_) == 2 && (QS_) >= 6) || ((KT_) == 3 && (QS_) <= ((TL_) ? 5 : 8)))
+constexpr bool ent_stag_for(int KT, int QS, int TL) { return KT == 1 || KT == 4 || (KT == 2 && QS >= 6) || (KT == 3 && QS <= (TL ? 5 : 8)); }
 
 
 // Round 5 (profiles/r05_experiments.md; the measured alternatives -- round 4's forms, the and-mask zeroing EVX, the fp32 S-step F32S -- are in
@@ -133,33 +141,108 @@ constexpr bool ent_sl_evl_for(int KT, int QS, int TL) { return QS == 3 && KT == 
 //       way (tools/isa_meta.py against the parent: no more vgpr_spill, the same waves/SIMD in every line of the class): three k-tiles with
 //       a one-value tail at D = 7..10 (K = 49..52).  Without the tail (K = 41..48) both signs' exponentials alive at once spill 36-58 VGPRs
 //       in all three lines of the class (256 before): it keeps SL.
-constexpr bool ent_pm_for(int KT, int QS, int TL, int HV, bool GRAD, bool WALK) {
-  return ent_sl_for(KT, QS, TL, HV, GRAD, WALK) && QS == 3 && KT == 3 && TL == 1;
+constexpr bool ent_pm_for(int KT, int QS, int TL) { return QS == 3 && KT == 3 && TL == 1; }   // (within SL and dense: EntForm::PM)
+// Waves per SIMD the register budget is set for: three (168 VGPRs) for the small kernels, two (256) from three k-tiles on.
+// Two k-tiles + a tail of ONE value per lane (K = 33..36) spills 14 VGPRs at 168 and is still 5-9 % faster than the spill-free
+// two-wave build; with TWO tail values per lane (K = 37..40: 24 spilled) the two-wave build wins by 2-4 % (round 3,
+// tools/ent_experiments.py x_w2 at D = 10), so that one instantiation moved (single-wave workgroups only: the multi-wave ones
+// were not re-measured).
+// ONE wave per SIMD (512 registers: nothing spills) where the two-wave build spills so much that losing the second wave's latency
+// hiding is the smaller evil (round 3, tools/tune_build.py w1:-DVBMC_ENT_WAVES_ALL=1 against the policy over 112 shapes,
+// profiles/r03_shape_sweep.md): four k-tiles on one wave from D = 15 on (K = 53..64: 11-23 % faster), three k-tiles from D = 27 on
+// (7-23 %), four-wave workgroups with four k-tiles from D = 23 on (round 4: from D = 19 on -- K = 256, D = 20: 16.9 ms
+// at two waves, 13.8 at one, with the shared even part in these kernels; D = 18: 12.3 against 13.1 the other way) and with three at D >= 31 (K = 193..256: 27-49 %).  Everywhere
+// else one wave per SIMD costs 2-49 %.
+constexpr bool ent_one_wave_for(int KT, int QS, int HV) {
+  return (HV == 1 && KT == 4 && QS >= 5) || (HV == 1 && KT == 3 && QS >= 8) || (HV == 4 && KT == 4 && QS >= 6) || (HV == 4 && KT == 3 && QS >= 9);
 }
+constexpr int ent_waves_for(int KT, int QS, int TL, int HV) {
+  return ent_one_wave_for(KT, QS, HV) ? 1 : (((KT <= 2 && QS <= 4) && !(KT == 2 && TL == 2 && HV == 1)) ? 3 : 2);
+}
+// The device-RNG path calls the generator instead of inlining it (inlined since round 4: -2.5 % at the headline shape -- no call, no wait for
+// every outstanding memory operation at its entry, scalar key schedule) in the two instantiations where the inlined body costs registers the
+// kernel does not have (tools/tune_sweep.py: D = 18, K = 80: +6 %, D = 24, K = 96: +11 %).
+constexpr bool ent_rng_call_for(int KT, int QS, int TL, int HV) { return HV == 2 && ((KT == 2 && TL == 2 && QS == 5) || (KT == 3 && TL == 0 && QS == 7)); }
+
+// ---- The form of one instantiation: every compile-time decision the kernel, its launch bound and its launcher take, in one table.
+// (HV, TL, CO, EM, WALK: see the comment in front of ent_mfma_segment.)
+template <int QS, int KT, bool GRAD, bool SPARSE, int HV, int TL, bool CO, bool EM, bool WALK>
+struct EntForm {
+  static_assert(!CO || (HV == 1 && QS <= 8 && !SPARSE), "the log-joint role exists for single-wave dense kernels at D <= 30");
+  static_assert(!WALK || (HV == 1 && !CO), "the walk exists for single-wave workgroups without the log-joint role");
+  static_assert(KT <= 4 && (HV == 1 || HV == 2 || HV == 4 || HV == 8), "larger mixtures are split over the waves of a workgroup (HV = 2, 4; round 5: 8, K <= 512)");
+  static_assert(TL == 0 || ((TL == 1 || TL == 2) && !SPARSE), "the component tail (one or two values per lane) exists for the dense kernels only");
+  static constexpr int DP = 4 * QS;               // padded row length of the u' tile
+  static constexpr int NPV = (4 * QS + 15) / 16;  // 16-column blocks of the PV output (D + 2 columns)
+  // layouts of the PV output and the gradient epilogue (see ent_sl_for, ent_pm_for, ent_gp2_for)
+  static constexpr bool SL = NPV == 1 && ent_sl_for(KT, QS, TL, HV, GRAD, WALK);
+  static constexpr bool EVL = SL && ent_sl_evl_for(KT, QS, TL);
+  static constexpr bool PM = SL && !SPARSE && ent_pm_for(KT, QS, TL);
+  static constexpr bool GP2 = GRAD && !SL && ent_gp2_for(KT, QS, TL, HV);
+  static constexpr int NG = SL ? QS : NPV;        // gradient accumulator pairs per lane: one per column block, SL: one per dim-block
+  // the even part of the exponent in the linear product (the block-sparse kernels skip k-tiles and keep the separate even product)
+  static constexpr bool C2 = !SPARSE && ent_c2_for(KT, QS, TL, HV);
+  // PV "B" operands in LDS: single-wave gradient kernels from three k-tiles or two column blocks on -- the 32 VGPRs hold the second sign's exponents
+  static constexpr bool VBL = GRAD && HV == 1 && (KT >= 3 || NPV >= 2);
+  // VBR (round 5): with the registers the gradient epilogue gave back (GP2) and one PV accumulator set (TWO), PV operands of the
+  // three-k-tile kernels stay in registers again -- the LDS reads of the PV step were worth 2-3 % (profiles/r05_experiments.md: all
+  // twelve in registers -3.4 %, ten -2.5 %, with the parity-mode prefetch holding its QS registers): all of them in the device-RNG
+  // instantiation (EM = false), ten in the one that prefetches its draws.
+  static constexpr int VBR = (VBL && NPV == 1 && KT == 3 && !CO) ? ((EM && QS <= 4) ? (TL == 2 ? 4 : 10) : 12) : 0;
+  // the parity mode's tile of draws, loaded one tile ahead into QS registers per lane -- where the registers are there
+  static constexpr bool EPF = EM && HV == 1 && QS <= 4 && KT <= 3 && !SPARSE;
+  // the schedule of the tile body: PM, else STAG, else the sign loop
+  static constexpr bool STAG = GRAD && HV == 1 && !PM && ent_stag_for(KT, QS, TL);
+  // TQ (round 5): the second sign's gradient epilogue reuses the four u'_id the first sign read (-0.2 %; eight registers across the second
+  // sign's exponentials, so only in the headline class, where they are there -- with SL: its walking instantiations).
+  static constexpr bool TQ = GP2 && NPV == 1 && KT == 3 && QS <= 3 && !CO && !EM && STAG;
+  // two PV accumulator sets halve the dependent chain.  (NPV >= 2: the column blocks are independent chains already, one set is enough -- 16
+  // VGPRs less.  Round 5: at three k-tiles and more the second set's eight registers are worth more as PV operands; the dependent MFMAs of one
+  // chain issue back to back anyway: 2.138 vs 2.140 ms.)
+  static constexpr bool TWO = NPV == 1 && KT <= 2;
+  static constexpr bool RNG_CALL = ent_rng_call_for(KT, QS, TL, HV);
+  // Launch bound, waves per SIMD.  The kernels that carry the log-joint role (CO) are built for two waves per SIMD whatever the entropy body
+  // needs (ONE from D = 15 on): see CO in front of ent_mfma_segment.
+  static constexpr int WAVES = CO ? (QS <= 4 ? 2 : 1) : ent_waves_for(KT, QS, TL, HV);
+  // the falling issue priority (s_setprio 3 -> 0, see the tile loop): single-wave workgroups that share their SIMD with another wave
+  static constexpr bool PRIO = HV == 1 && WAVES > 1;
+  // Dynamic LDS once the parameter block is dead: the exp table and, behind it, the PV exchange of a multi-wave workgroup -- YXN doubles
+  // per wave, ONE buffer for both signs (a barrier more per tile; the LDS that saves holds the parked exponents).  The launcher takes the
+  // larger of this and the parameter block.
+  static constexpr int YXN = NPV * 4 * WAVE;
+  static constexpr size_t DYN_LDS = (size_t)(VB_EXP_TAB1K_N + (HV > 1 ? HV * YXN : 0)) * sizeof(double);
+  static_assert(!SL || NPV == 1, "the sample layout has one column block");
+  static_assert(!(GP2 && SL) && (!TQ || GP2) && (!EVL || SL), "one gradient epilogue per instantiation");
+  static_assert(!PM || (SL && !STAG), "the sign pair's one PV product is a schedule of the sample layout");
+  static_assert(VBR <= KT * 4 * NPV && (VBR == 0 || VBL), "VBreg holds a prefix of the PV operands in VBS");
+  static_assert(WAVES >= 1 && WAVES <= 3, "waves per SIMD the registers are budgeted for");
+};
 
 // Ordering point for LDS words that only ONE wave touches (lanes of a wave exchanging values through LDS): the hardware
 // executes a wave's LDS instructions in order, so no s_barrier and no full s_waitcnt drain is needed -- only the compiler must
 // keep the accesses in program order (wave-level fence).  The waves of a two-wave workgroup meet only at the eps staging and
 // at the PV exchange (__syncthreads there).
-template <int HV>
 __device__ __forceinline__ void ent_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// the eps tile is shared by the waves of a workgroup: a real barrier when there are two, the wave-level fence when there is one
+// the eps tile is shared by the waves of a workgroup: a real barrier when there are several, the wave-level fence when there is one
 template <int HV>
 __device__ __forceinline__ void ent_sync_wg() {
-  if (HV == 1) ent_sync<1>();
+  if (HV == 1) ent_sync();
   else __syncthreads();
 }
 
-// HV = 2 or 4 (K > 64): the components are split between the HV waves of a workgroup, each running the KT <= 4
+// The template parameters beside QS, KT, GRAD and SPARSE (block-sparse variant: uniform per-k-tile branches; the dense variant is branch-free):
+// HV = 2, 4 or 8 (K > 64): the components are split between the HV waves of a workgroup, each running the KT <= 4
 // register-resident body on its share; per sign the waves exchange their partial PV outputs (16 x 16 NPV doubles per wave
-// through LDS, one workgroup barrier) and all continue with the full q', A', B' -- the partials are added in wave order on
-// every wave, so all hold identical bits.  Wave 0 owns the entropy accumulator, the column blocks of the gradient are dealt
-// to the waves, each wave owns the weight gradient of its components.  The exchange buffers reuse the parameter block's LDS
-// (needed only while the operand fragments are built).
+// through LDS, two workgroup barriers for the second sign: the buffer is shared) and all continue with the full q', A', B' -- the
+// partials are added in wave order on every wave, so all hold identical bits.  Wave 0 owns the entropy accumulator, the column blocks of
+// the gradient are dealt to the waves, each wave owns the weight gradient of its components.  The exchange buffer reuses the parameter
+// block's LDS (needed only while the operand fragments are built).  These kernels share the even part of the exponent like the single-wave
+// ones (round 4: up to -35 % at D >= 20, tools/tune_sweep.py, BASELINE configs[4] 9.75 -> 8.5 ms), with the second sign's exponents
+// parked in LDS (NMS): their registers are spoken for, and the single exchange buffer pays for that LDS.
 //
 // TL = 1, 2: the last (components of the wave) mod 16 <= 4 TL components do not get a k-tile of their own.  A 16-wide k-tile for two
 // components (K = 50) costs four S-step MFMAs, 26 VGPRs of operands / exponents / accumulators and an exp register per sign; as a
@@ -173,74 +256,37 @@ __device__ __forceinline__ void ent_sync_wg() {
 // (ONE from D = 15 on): the grids they serve do not fill the chip anyway, and the log-joint body keeps 6 x 4 QS values per lane in
 // registers (185 VGPRs at QS = 3, beyond 256 from QS = 6 on, where the accumulation registers take the overflow).
 // EM (round 5): the instantiation reads its draws from memory (parity mode / eps_mode 2) -- it spends QS registers per lane on the tile
-// loaded one tile ahead (EPF below).  EM = false: the device-RNG launch of the same shape; those registers hold PV operands instead
+// loaded one tile ahead (EPF).  EM = false: the device-RNG launch of the same shape; those registers hold PV operands instead
 // (VBR).  Only the instantiations that prefetch exist twice (ent_mfma_inst.hip); everywhere else EM = true is the one kernel for both.
-template <int QS, int KT, bool GRAD, bool SPARSE, int HV = 1, int TL = 0, bool CO = false, bool EM = true, bool WALK = false>
-// Waves per SIMD the register budget is set for: three (168 VGPRs) for the small kernels, two (256) from three k-tiles on.
-// Two k-tiles + a tail of ONE value per lane (K = 33..36) spills 14 VGPRs at 168 and is still 5-9 % faster than the spill-free
-// two-wave build; with TWO tail values per lane (K = 37..40: 24 spilled) the two-wave build wins by 2-4 % (round 3,
-// tools/ent_experiments.py x_w2 at D = 10), so that one instantiation moved (single-wave workgroups only: the multi-wave ones
-// were not re-measured).
-// Which workgroup shapes share the even part of the exponent between the antithetic pair (EO: 4 instead of 2 QS S-step MFMAs per k-tile and
-// tile).  Single-wave workgroups since round 2; round 4: two- and four-wave workgroups (64 < K <= 256) too -- the second sign's exponents are
-// parked in LDS (NML) and the PV exchange is single-buffered to pay for that LDS: up to -35 % at D >= 20 (tools/tune_sweep.py, r04_experiments.md
-// section 10), BASELINE configs[4] 9.75 -> 8.5 ms.  (The plain per-sign S-step, !EO, remains as the general form of the sign loop.)
-#define VBMC_ENT_EO(HV_) true
-// ONE wave per SIMD (512 registers: nothing spills) where the two-wave build spills so much that losing the second wave's latency
-// hiding is the smaller evil (round 3, tools/tune_build.py w1:-DVBMC_ENT_WAVES_ALL=1 against the policy over 112 shapes,
-// profiles/r03_shape_sweep.md): four k-tiles on one wave from D = 15 on (K = 53..64: 11-23 % faster), three k-tiles from D = 27 on
-// (7-23 %), four-wave workgroups with four k-tiles from D = 23 on (round 4: from D = 19 on -- K = 256, D = 20: 16.9 ms
-// at two waves, 13.8 at one, with the shared even part in these kernels; D = 18: 12.3 against 13.1 the other way) and with three at D >= 31 (K = 193..256: 27-49 %).  Everywhere
-// else one wave per SIMD costs 2-49 %.
-#define VBMC_ENT_ONE_WAVE(KT_, QS_, TL_, HV_) \
-  (((HV_) == 1 && (KT_) == 4 && (QS_) >= 5) || ((HV_) == 1 && (KT_) == 3 && (QS_) >= 8) || ((HV_) == 4 && (KT_) == 4 && (QS_) >= 6) || \
-   ((HV_) == 4 && (KT_) == 3 && (QS_) >= 9))
-#define VBMC_ENT_WAVES(KT_, QS_, TL_, HV_) \
-  (VBMC_ENT_ONE_WAVE(KT_, QS_, TL_, HV_) ? 1 : ((((KT_) <= 2 && (QS_) <= 4) && !((KT_) == 2 && (TL_) == 2 && (HV_) == 1)) ? 3 : 2))
+//
 // ent_mfma_segment: the work of one wave (workgroup) on ONE (component j, restart r): tiles [t0, t1) of the component's samples, partial
 // record into slot c.  The kernel below calls it once (the chunk grid) or once per segment of the wave's tile range (the walk, see there);
 // pdone / ptot: the tiles the wave had behind it when it entered the segment / has in all (the progress its issue priority follows).
+template <int QS, int KT, bool GRAD, bool SPARSE, int HV = 1, int TL = 0, bool CO = false, bool EM = true, bool WALK = false>
 __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, const int j, const int r, const int t0, const int t1,
                                                  const int pdone, const int ptot) {
-  static_assert(!CO || (HV == 1 && QS <= 8 && !SPARSE), "the log-joint role exists for single-wave dense kernels at D <= 30");
-  static_assert(!WALK || (HV == 1 && !CO), "the walk exists for single-wave workgroups without the log-joint role");
-  static_assert(KT <= 4 && (HV == 1 || HV == 2 || HV == 4 || HV == 8), "larger mixtures are split over the waves of a workgroup (HV = 2, 4; round 5: 8, K <= 512)");
-  static_assert(TL == 0 || ((TL == 1 || TL == 2) && !SPARSE), "the component tail (one or two values per lane) exists for the dense kernels only");
+  using F = EntForm<QS, KT, GRAD, SPARSE, HV, TL, CO, EM, WALK>;
   constexpr int TLN = TL > 0 ? TL : 1;     // tail values per lane: tail component 4u + lg, u < TL (the layout of a k-tile's register u)
-  constexpr bool SP = SPARSE;  // block-sparse variant: uniform per-k-tile branches; the dense variant is branch-free
-  constexpr int DP = 4 * QS;               // padded eps row length
-  constexpr int NPV = (4 * QS + 15) / 16;  // 16-column blocks of the PV output (D + 2 columns)
-  constexpr int QL = QS;                   // MFMAs of the linear part of the S-step (inner index c = 4q + lg < D, zero operands beyond D: for
-                                           // D mod 4 in {3, 0} the last one multiplies zeros -- a compile-time count keeps the KT chains branch-free)
-  __shared__ double Et[16 * DP];   // eps tile [i][d], staged by wave 0 and shared by the HV waves of the workgroup
-  constexpr bool SL = NPV == 1 && ent_sl_for(KT, QS, TL, HV, GRAD, WALK);
-  constexpr bool GP2 = GRAD && !SL && ent_gp2_for(KT, QS, TL, HV);
-  constexpr bool PM = SL && !SPARSE && ent_pm_for(KT, QS, TL, HV, GRAD, WALK);   // one PV product per antithetic pair (see ent_pm_for)
-  __shared__ double RQ_all[HV][SL ? 1 : (GP2 ? 32 : 16)];   // q'_i then 1/q'_i  (GP2: and A'_i then A'_i/q'_i behind them; SL: no exchange)
+  // (Eight locals stay beside F, each at the place it always had, because the generated code depends on them, profiles/ent_forms_cleanup.md:
+  // DP, NPV, VBL, VBR and the constant US are captured by the generic lambdas below -- without them the closures are laid out differently and
+  // most kernels of a unit are scheduled differently; US has no other purpose, the `US &&` in gradpieces folds away.  NG, EPF and PRIO
+  // are not captured (the lambdas read F::EPF), but without their stack slots two instructions of the tail kernels' set-up change places.)
+  constexpr int DP = F::DP, NPV = F::NPV;
+  __shared__ double Et[16 * DP];   // tile of u' = eps sigma_j [i][d] (every reader wants the product), staged by wave 0 and shared by the HV waves
+  __shared__ double RQ_all[HV][F::SL ? 1 : (F::GP2 ? 32 : 16)];   // q'_i then 1/q'_i  (GP2: and A'_i then A'_i/q'_i behind them; SL: no exchange)
   __shared__ double BND_all[HV][SPARSE ? KT * 16 * 3 : 1];  // per component: |m'_k|, cK_k - cK_j, h_k  (block-sparse bound)
-  // partial PV outputs of the two halves, double-buffered by sign so that one workgroup barrier per sign is enough
-  constexpr int YXN = NPV * 4 * WAVE;      // doubles per (sign, wave) slot of the PV exchange (in the dynamic LDS, see PB)
-  // PV "B" operands of large mixtures live in LDS (lane-contiguous: conflict-free ds_read_b64 right before the MFMA that
-  // consumes them) -- the 32 VGPRs they would occupy hold the second sign's exponents instead (see the S-step)
-  // EO: the even / odd split of the S-step below (needs 32 more VGPRs for the second sign's exponents, paid for by VBL).
-  // Multi-wave workgroups (K > 64) kept the plain per-sign S-step through round 3 (their LDS already holds the PV exchange buffers and a
-  // larger parameter block, and 32 KB of PV operands more would halve the resident waves); since round 4 they share the even part as
-  // well, with the second sign's exponents parked in LDS (NML) and the PV exchange single-buffered (YXSB) -- see VBMC_ENT_EO.
-  constexpr bool EO = VBMC_ENT_EO(HV);
-  constexpr bool YXSB = HV > 1 && EO;   // one PV exchange buffer for both signs (a barrier more per tile): the LDS it frees holds the parked exponents
-  // US (round 4): the LDS tile holds u' = eps sigma_j, not eps -- every reader wanted the product (S-step operand, tail, gradient
-  // epilogue: a multiply per use), the own exponent comes from |u'|^2 as well
-  constexpr bool US = EO;
-  constexpr bool VBL = GRAD && HV == 1 && (KT >= 3 || NPV >= 2);
+  constexpr bool US = true;   // the LDS tile holds u' = eps sigma_j (kept for its capture alone, see above)
+  constexpr bool VBL = F::VBL;
+  // VBL: PV "B" operands in LDS (lane-contiguous: conflict-free ds_read_b64 right before the MFMA that consumes them) -- the 32 VGPRs they
+  // would occupy hold the second sign's exponents instead (see the S-step)
   __shared__ double VBS_all[HV][VBL ? KT * 4 * NPV * WAVE : 1];
-  constexpr bool C2 = EO && !SPARSE && ent_c2_for(KT, QS, TL, HV);
   // component (within the wave's share) held by accumulator register rr of this lane group in k-tile kt
 #define ENT_CI(kt_, rr_) (16 * (kt_) + 4 * (rr_) + lg)
-  __shared__ __attribute__((aligned(16))) double SCP_all[HV][C2 ? KT * 16 * 2 : 2];   // C2: [component 16 kt + c][2 c0, 2 c1] of the even part
+  __shared__ __attribute__((aligned(16))) double SCP_all[HV][F::C2 ? KT * 16 * 2 : 2];   // C2: [component 16 kt + c][2 c0, 2 c1] of the even part
   __shared__ double BTL_all[HV][TL ? 4 * TL * DP : 1];  // tail: linear S-step coefficients [t][d] (x 1024/ln2), zero beyond D and for absent components
-  __shared__ __attribute__((aligned(16))) double WAP[PM ? KT * 16 * 2 : 2];   // PM: [component 16 kt + c][w_k, a_k = w_k/sigma_k^2], zero for padded components
-  constexpr bool NML = HV > 1 && EO;   // multi-wave workgroups park the second sign's exponents in LDS: their registers are spoken for
-  __shared__ double NMS_all[HV][NML ? KT * 4 * WAVE : 1];
+  __shared__ __attribute__((aligned(16))) double WAP[F::PM ? KT * 16 * 2 : 2];   // PM: [component 16 kt + c][w_k, a_k = w_k/sigma_k^2], zero for padded components
+  // multi-wave workgroups park the second sign's exponents in LDS: their registers are spoken for
+  __shared__ double NMS_all[HV][HV > 1 ? KT * 4 * WAVE : 1];
 #ifdef VBMC_INSTRUMENT
   const unsigned long long wckE = wall_clock64();
 #endif
@@ -270,8 +316,8 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   // the per-lane operand fragments below are gathered from LDS, not from global memory
   extern __shared__ double PB[];
   // The parameter block is needed only while the operand fragments are built; afterwards its LDS holds the exp table
-  // 2^(j/1024) (8 KB) and, behind it, the PV exchange buffers of multi-wave workgroups [sign][wave][YXN] (the launcher sizes the
-  // dynamic LDS for the larger of the two uses)
+  // 2^(j/1024) (8 KB) and, behind it, the PV exchange buffer of multi-wave workgroups [wave][YXN], one for both signs (the launcher
+  // sizes the dynamic LDS for the larger of the two uses: EntForm::DYN_LDS)
   double* const TAB = PB;
   double* const YX = PB + VB_EXP_TAB1K_N;
   // (round 5) the exp table's global loads and sigma_j leave at the kernel's entry, beside the parameter block's: three round trips to
@@ -286,22 +332,21 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // eight loads in flight per lane: the plain copy loop waits for every load in turn, and with few tiles per wave (a
     // single chain) this setup is a quarter of the kernel
     const double* gsrc = entp_ + (size_t)r * K * PSg;
-    constexpr int NT = WAVE * HV;
     const int n = K * PSg;
     int idx = tid;
-    for (; idx + 7 * NT < n; idx += 8 * NT) {
+    for (; idx + 7 * NTH0 < n; idx += 8 * NTH0) {
       double t8[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) t8[u] = gsrc[idx + u * NT];
+      for (int u = 0; u < 8; ++u) t8[u] = gsrc[idx + u * NTH0];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) PB[idx + u * NT] = t8[u];
+      for (int u = 0; u < 8; ++u) PB[idx + u * NTH0] = t8[u];
     }
     {
       double t8[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) t8[u] = (idx + u * NT < n) ? gsrc[idx + u * NT] : 0.0;
+      for (int u = 0; u < 8; ++u) t8[u] = (idx + u * NTH0 < n) ? gsrc[idx + u * NTH0] : 0.0;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) if (idx + u * NT < n) PB[idx + u * NT] = t8[u];
+      for (int u = 0; u < 8; ++u) if (idx + u * NTH0 < n) PB[idx + u * NTH0] = t8[u];
     }
   }
   __syncthreads();
@@ -315,8 +360,8 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 
   // ---- mixture-side operand fragments (registers, built once).  The S-step operands carry the factor 1024/ln2 of the exp's
   // range reduction (device_math.h: vb_exp_tab1k): the MFMAs deliver E * 1024/ln2
-  constexpr double ESC = VB_EXP_TAB1K_SCALE;
-  double SA[KT][QL];  // S-step "A" operand, linear part: comp 16kt + li, inner c = 4q + lg < D
+  double SA[KT][QS];  // S-step "A" operand, linear part: comp 16kt + li, inner c = 4q + lg < D (zero operands beyond D: for D mod 4 in {3, 0} the
+                      // last of the QS MFMAs multiplies zeros -- a compile-time count keeps the KT chains branch-free)
   double SC[KT];              // S-step "A" operand, even part: inner index lg = 0 (coefficient of |u'|^2), 1 (constant), 2, 3 (zero)
   double VB[VBL ? 1 : KT][4][NPV];   // PV "B" operand: comp 16kt + 4r + lg, column 16pv + li      (GRAD; in LDS when VBL)
   double WF[KT][4];           // w_k for comp 16kt + 4r + lg                                  (!GRAD)
@@ -337,30 +382,20 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // per tile the S-step is ONE even product C (inner dimension 4: |u'|^2, 1, 0, 0) and ONE linear product L (inner
     // dimension D) for both signs: E+ = C + L accumulates L on top of C, E- = 2C - E+
 #pragma unroll
-    for (int q = 0; q < QL; ++q) {
+    for (int q = 0; q < QS; ++q) {
       const int cc = 4 * q + lg;
-      if (EO) {
-        double sav = (kv && cc < D) ? ESC * (-2.0 * h * (pk[cc] - pj[cc])) : 0.0;   // m'_ck / sigma_k^2   (h = -1/(2 sigma^2))
-        if (C2) {   // the even part in the free inner slots D (coefficient of |u'|^2) and D + 1 (constant; padded component: exp -> 0)
-          if (cc == D) sav = kv ? ESC * (h + hj_neg) : 0.0;
-          if (cc == D + 1) sav = ESC * (kv ? fma(h, m2, pk[D + 1]) - cKj : -1.0e6);
-        }
-        SA[kt][q] = sav;
-      } else {   // plain S-step: linear and even columns in one (D + 2)-column operand, QS MFMAs per sign
-        double v;
-        if (!kv) v = (cc == D + 1) ? -1.0e6 : 0.0;
-        else if (cc < D) v = -2.0 * h * (pk[cc] - pj[cc]);
-        else if (cc == D) v = h + hj_neg;
-        else if (cc == D + 1) v = fma(h, m2, pk[D + 1]) - cKj;
-        else v = 0.0;
-        SA[kt][q] = ESC * v;
+      double sav = (kv && cc < D) ? VB_EXP_TAB1K_SCALE * (-2.0 * h * (pk[cc] - pj[cc])) : 0.0;   // m'_ck / sigma_k^2   (h = -1/(2 sigma^2))
+      if (F::C2) {   // the even part in the free inner slots D (coefficient of |u'|^2) and D + 1 (constant; padded component: exp -> 0)
+        if (cc == D) sav = kv ? VB_EXP_TAB1K_SCALE * (h + hj_neg) : 0.0;
+        if (cc == D + 1) sav = VB_EXP_TAB1K_SCALE * (kv ? fma(h, m2, pk[D + 1]) - cKj : -1.0e6);
       }
+      SA[kt][q] = sav;
     }
     // the sample's own exponent -shift_i = -cK_j + |u'_i|^2/(2 sigma_j^2) is folded into the two even columns: accumulators start at 0
-    SC[kt] = ESC * (!kv ? (lg == 1 ? -1.0e6 : 0.0)                          // padded component: exp -> 0
+    SC[kt] = VB_EXP_TAB1K_SCALE * (!kv ? (lg == 1 ? -1.0e6 : 0.0)                          // padded component: exp -> 0
                         : (lg == 0 ? h + hj_neg : (lg == 1 ? fma(h, m2, pk[D + 1]) - cKj : 0.0)));
-    if (C2 && lg < 2) SCP[(16 * kt + li) * 2 + lg] = 2.0 * SC[kt];
-    if (PM && lg < 2) WAP[(16 * kt + li) * 2 + lg] = kv ? pk[D + 2 + lg] : 0.0;
+    if (F::C2 && lg < 2) SCP[(16 * kt + li) * 2 + lg] = 2.0 * SC[kt];
+    if (F::PM && lg < 2) WAP[(16 * kt + li) * 2 + lg] = kv ? pk[D + 2 + lg] : 0.0;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int k2 = ENT_CI(kt, rr);
@@ -371,7 +406,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         for (int pv = 0; pv < NPV; ++pv) {
           const int col = 16 * pv + li;
           double v = 0.0;
-          if (SL) {      // the slot map of the sample layout (li = slot): B'_s | zero | A' A' | q' q' q' q'
+          if (F::SL) {      // the slot map of the sample layout (li = slot): B'_s | zero | A' A' | q' q' q' q'
             if (kv2) {
               if (li >= 12) v = p2[D + 2];
               else if (li >= 10) v = p2[D + 3];
@@ -412,15 +447,15 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       const double h = pq[D];
       double m2 = 0.0;
       for (int d = 0; d < D; ++d) { double t = pq[d] - pj[d]; m2 = fma(t, t, m2); }
-      tC0[u] = kvq ? ESC * (h + hj_neg) : 0.0;
-      tC1[u] = ESC * (kvq ? fma(h, m2, pq[D + 1]) - cKj : -1.0e6);            // absent component: exp -> 0
-      for (int d = li; d < DP; d += 16) BTL[tq * DP + d] = (kvq && d < D) ? ESC * (-2.0 * h * (pq[d] - pj[d])) : 0.0;
+      tC0[u] = kvq ? VB_EXP_TAB1K_SCALE * (h + hj_neg) : 0.0;
+      tC1[u] = VB_EXP_TAB1K_SCALE * (kvq ? fma(h, m2, pq[D + 1]) - cKj : -1.0e6);            // absent component: exp -> 0
+      for (int d = li; d < DP; d += 16) BTL[tq * DP + d] = (kvq && d < D) ? VB_EXP_TAB1K_SCALE * (-2.0 * h * (pq[d] - pj[d])) : 0.0;
       if (GRAD) {
 #pragma unroll
         for (int pv = 0; pv < NPV; ++pv) {     // PV "B" operand: inner index lg <-> tail component 4u + lg, column 16 pv + li
           const int col = 16 * pv + li;
           double v = 0.0;
-          if (SL) {      // (the slot map, as above)
+          if (F::SL) {      // (the slot map, as above)
             if (kvq) {
               if (li >= 12) v = pq[D + 2];
               else if (li >= 10) v = pq[D + 3];
@@ -434,7 +469,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
           }
           VBt[u][pv] = v;
         }
-        if (PM) { WFt[u] = kvq ? pq[D + 2] : 0.0; tA[u] = kvq ? pq[D + 3] : 0.0; }
+        if (F::PM) { WFt[u] = kvq ? pq[D + 2] : 0.0; tA[u] = kvq ? pq[D + 3] : 0.0; }
       } else {
         WFt[u] = kvq ? pq[D + 2] : 0.0;
       }
@@ -449,18 +484,14 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   }
   __syncthreads();
 
-#define SAV(kt_, q_) SA[kt_][q_]
-  // VBR (round 5): with the registers the gradient epilogue gave back (GP2) and one PV accumulator set (TWO below), PV operands of the
-  // three-k-tile kernels stay in registers again -- the LDS reads of the PV step were worth 2-3 % (profiles/r05_experiments.md: all
-  // twelve in registers -3.4 %, ten -2.5 %, with the parity-mode prefetch holding its QS registers): all of them in the device-RNG
-  // instantiation (EM = false), ten in the one that prefetches its draws.
-  constexpr int VBR = (VBL && NPV == 1 && HV == 1 && KT == 3 && !CO) ? ((EM && QS <= 4) ? (TL == 2 ? 4 : 10) : 12) : 0;
+  // (VBR: the first VBR PV operands of VBS come back into registers)
+  constexpr int VBR = F::VBR;
   double VBreg[VBR > 0 ? VBR : 1];
 #pragma unroll
   for (int u = 0; u < VBR; ++u) VBreg[u] = VBS[u * WAVE + lane];
 #define VBV(kt_, rr_, pv_) (VBL ? (((kt_) * 4 + (rr_)) * NPV + (pv_) < VBR ? VBreg[(((kt_) * 4 + (rr_)) * NPV + (pv_)) < VBR ? (((kt_) * 4 + (rr_)) * NPV + (pv_)) : 0] : VBS[(((kt_) * 4 + (rr_)) * NPV + (pv_)) * WAVE + lane]) : VB[VBL ? 0 : (kt_)][rr_][pv_])
-  constexpr int NG = SL ? QS : NPV;   // gradient accumulators per lane: one per column block, SL: one per dim-block (dimension 4 r + lg)
-  double accH = 0.0, accG[NG], accLG[NG];
+  constexpr int NG = F::NG;
+  double accH = 0.0, accG[NG], accLG[NG];   // NG gradient accumulators per lane: one per column block, SL: one per dim-block (dimension 4 r + lg)
   double pm = 1.0;            // running product of mantissas of q'
   int pe = 0, pcnt = 0;       // running sum of exponents
   double Wacc[KT][4];
@@ -475,7 +506,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   const unsigned long long wck0 = wall_clock64();
 #endif
   const int ntile = (a.Mh + 15) >> 4;
-  const double sfm0 = lg == 0 ? 1.0 : 0.0, sfm1 = lg == 1 ? 1.0 : 0.0;   // sample-side operand of the even S-step product (EO)
+  const double sfm0 = lg == 0 ? 1.0 : 0.0, sfm1 = lg == 1 ? 1.0 : 0.0;   // sample-side operand of the even S-step product
   const int emask = (4 * (QS - 1) + lg < D) ? -1 : 0;   // this lane's slot of the last dim-block: a dimension (all ones) or padding (zero)
   const int emask2 = (QS >= 2 && 4 * (QS - 2) + lg < D) ? -1 : 0;   // ... and of the one before
   const double* epsr = a.eps ? a.eps + (size_t)r * a.eps_stride_r + (size_t)j * a.Mh * D : nullptr;
@@ -483,11 +514,11 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   // into QS registers per lane (round 4) -- issued right after the current tile went to LDS, waited for at the next tile's start, a whole
   // tile of arithmetic later -- instead of a load-and-wait at the head of every tile.  Where the registers are there (EPF); the same
   // kernel serves the device-RNG mode, so the registers are spent in both.
-  constexpr bool EPF = EM && HV == 1 && QS <= 4 && KT <= 3 && !SPARSE;
+  constexpr bool EPF = F::EPF;
   double epre[EPF ? QS : 1];
   auto eps_fetch = [&](const int tile) {
 #pragma unroll
-    for (int u = 0; u < (EPF ? QS : 0); ++u) {
+    for (int u = 0; u < (F::EPF ? QS : 0); ++u) {
       const int idx = lane + u * WAVE, i = idx / DP, d = idx - i * DP;     // (16 DP = 64 QS slots: every lane has exactly QS)
       double v = 0.0;
       if (tile < t1 && d < D && tile * 16 + i < a.Mh) v = epsr[(size_t)(tile * 16 + i) * D + d];
@@ -505,25 +536,25 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   const double c2u1 = (4 * (QS - 1) + lg == D) ? 1.0 : 0.0, c2o1 = (4 * (QS - 1) + lg == D + 1) ? 1.0 : 0.0;
   const double c2u2 = (QS >= 2 && 4 * (QS - 2) + lg == D) ? 1.0 : 0.0;
 
-  // The tile body, compiled twice where it pays (VBMC_ENT_SPLIT): once for the full tiles -- no sample-validity selects at all: a
+  // The tile body, compiled twice in the single-wave kernels: once for the full tiles (EntTileFull) -- no sample-validity selects at all: a
   // v_cndmask_b32 costs four fp64 operations on this chip (tools/valu_rate.hip), and written as rare uniform branches inside one body
   // they cost registers the staggered schedule does not have -- and once for the single tile of a component that can hold samples
-  // beyond Mh (its last).  Elsewhere one body with the run-time test.
+  // beyond Mh (its last; EntTilePartial).  The multi-wave kernels run the body with the selects on every tile.
   auto tile_body = [&](const int tile, auto pkind) __attribute__((always_inline)) {
-    using PK = decltype(pkind);
+    using PK = decltype(pkind);   // PK::val: can this tile hold samples beyond Mh?
     const int b0 = tile * 16;
     // ---- stage the 16 x D eps tile in LDS (zeros for padded dims / samples beyond Mh)
     ent_sync_wg<HV>();
     if (HV > 1 && hv != 0) {
       // wave 0 stages (and, in device-RNG mode, draws) the tile for both
-    } else if (EPF && epsr) {
+    } else if (F::EPF && epsr) {
 #pragma unroll
-      for (int u = 0; u < (EPF ? QS : 0); ++u) Et[lane + u * WAVE] = US ? sigj * epre[u] : epre[u];
+      for (int u = 0; u < (F::EPF ? QS : 0); ++u) Et[lane + u * WAVE] = sigj * epre[u];
       eps_fetch(tile + 1);
     } else if (epsr) {
       for (int idx = lane; idx < 16 * DP; idx += WAVE) {
         const int i = idx / DP, d = idx - i * DP;
-        Et[idx] = (d < D && b0 + i < a.Mh) ? (US ? sigj * epsr[(size_t)(b0 + i) * D + d] : epsr[(size_t)(b0 + i) * D + d]) : 0.0;
+        Et[idx] = (d < D && b0 + i < a.Mh) ? sigj * epsr[(size_t)(b0 + i) * D + d] : 0.0;
       }
     } else {
       // no select on the way into the tile (v_cndmask_b32 costs four fp64 operations on this chip: tools/valu_rate.hip): draws
@@ -537,19 +568,15 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #pragma unroll
       for (int q = lg; q < QS; q += 4) {
         double z4[4] = {0.0, 0.0, 0.0, 0.0};
-        // inlined (round 4: -2.5 % at the headline shape -- no call, no wait for every outstanding memory operation at its entry, scalar key
-        // schedule) except in the two instantiations where the inlined body costs registers the kernel does not have (tools/tune_sweep.py:
-        // D = 18, K = 80: +6 %, D = 24, K = 96: +11 %)
-#define VBMC_RNG_CALL_FOR(KT_, QS_, TL_, HV_) ((HV_) == 2 && (((KT_) == 2 && (TL_) == 2 && (QS_) == 5) || ((KT_) == 3 && (TL_) == 0 && (QS_) == 7)))
-        if constexpr (!VBMC_RNG_CALL_FOR(KT, QS, TL, HV)) {
+        // the generator inlined, except where that costs registers the kernel does not have (RNG_CALL: ent_rng_call_for)
+        if constexpr (!F::RNG_CALL) {
         if (q < (D + 3) / 4) { const vb_d4 zz = vb_normal4i(seed_t, (unsigned)(b0 + li), (unsigned)j, (unsigned)(a.r0 + r * a.rstride), (unsigned)q); z4[0] = zz[0]; z4[1] = zz[1]; z4[2] = zz[2]; z4[3] = zz[3]; }
         } else {
         if (q < (D + 3) / 4) vb_normal4(seed_t, (unsigned)(b0 + li), (unsigned)j, (unsigned)(a.r0 + r * a.rstride), (unsigned)q, z4);
         }
-#undef VBMC_RNG_CALL_FOR
         if (q < (D + 3) / 4) {     // (ETZ: an all-padding dim-block has been zero since the start of the wave)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) Et[li * DP + 4 * q + t] = US ? sigj * z4[t] : z4[t];
+        for (int t = 0; t < 4; ++t) Et[li * DP + 4 * q + t] = sigj * z4[t];
         }
       }
     }
@@ -568,13 +595,11 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     }
     e2 = xor_sum16(e2);     // (PLS, round 5: on the VALU -- |u'|^2 heads the last MFMA group of the S-step and the second sign's exponents)
     e2 = xor_sum32(e2);
-    // US: the sum above is |u'_i|^2 already
-    double shift = US ? fma(-e2, hj_neg, cKj) : cKj - 0.5 * e2;              // exponent of the sample's own component: cK_j - |eps_i|^2 / 2
-    const double u2 = US ? e2 : sigj * sigj * e2;                            // |u'_i|^2
-    if (US && SPARSE) e2 *= 2.0 * hj_neg;                                    // |eps_i|^2 for the bound below
-    constexpr bool partial = PK::val;   // can this tile hold samples beyond Mh?  (only the last tile of a component can)
-    const bool svalid = b0 + li < a.Mh;
-    if (partial) shift = svalid ? shift : 0.0;
+    double shift = fma(-e2, hj_neg, cKj);                                    // exponent of the sample's own component: cK_j - |eps_i|^2 / 2
+    const double u2 = e2;                                                    // |u'_i|^2 (the tile holds u')
+    if (SPARSE) e2 *= 2.0 * hj_neg;                                          // |eps_i|^2 for the bound below
+    const bool svalid = b0 + li < a.Mh;                                      // (only the last tile of a component can hold samples beyond Mh)
+    if (PK::val) shift = svalid ? shift : 0.0;
     // ---- block-sparse mode: which k-tiles can contribute more than exp(-cutoff) * q to any sample of this tile?
     // n_ik / q'_i <= exp(cK_k - cK_j - (max(0, |m'_k| - |u'_i|))^2 / (2 sigma_k^2) + |u'_i|^2 / (2 sigma_j^2)) / w_j
     unsigned act = FULL_MASK;
@@ -595,50 +620,49 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     }
 
     // ---- S-step, once per tile for both signs
-    mf4 n[KT], nm[(EO && !NML) ? KT : 1];
-    if (EO) {
-      const double sfc = fma(u2, sfm0, sfm1);   // [|u'|^2, 1, 0, 0] over the lane groups, exactly, without the two selects
-      double sfl[QL];
+    // (n: the first sign's exponents; nm: the second sign's, in registers in the single-wave kernels, parked in NMS otherwise)
+    mf4 n[KT], nm[HV == 1 ? KT : 1];
+    const double sfc = fma(u2, sfm0, sfm1);   // [|u'|^2, 1, 0, 0] over the lane groups, exactly, without the two selects
+    double sfl[QS];
 #pragma unroll
-      for (int q = 0; q < QL; ++q) sfl[q] = US ? ev[q] : ev[q] * sigj;       // u'_ic (zero beyond D)
-      if (C2) {
-        sfl[QL - 1] = fma(u2, c2u1, sfl[QL - 1] + c2o1);      // (the dimensions' lanes: + 0)
-        if (QS >= 2) sfl[QL >= 2 ? QL - 2 : 0] = fma(u2, c2u2, sfl[QL >= 2 ? QL - 2 : 0]);   // (c2u2 = 0 unless D = 4 QS - 5; unconditional: the
-                                                                                               //  compiler if-converts the test into two selects)
-      }
+    for (int q = 0; q < QS; ++q) sfl[q] = ev[q];       // u'_ic (zero beyond D)
+    if (F::C2) {
+      sfl[QS - 1] = fma(u2, c2u1, sfl[QS - 1] + c2o1);      // (the dimensions' lanes: + 0)
+      if (QS >= 2) sfl[QS >= 2 ? QS - 2 : 0] = fma(u2, c2u2, sfl[QS >= 2 ? QS - 2 : 0]);   // (c2u2 = 0 unless D = 4 QS - 5; unconditional: the
+                                                                                             //  compiler if-converts the test into two selects)
+    }
 #pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        n[kt] = (mf4){0.0, 0.0, 0.0, 0.0};
-        if (!NML) nm[(EO && !NML) ? kt : 0] = (mf4){0.0, 0.0, 0.0, 0.0};
-        if (C2) {
+    for (int kt = 0; kt < KT; ++kt) {
+      n[kt] = (mf4){0.0, 0.0, 0.0, 0.0};
+      if (HV == 1) nm[HV == 1 ? kt : 0] = (mf4){0.0, 0.0, 0.0, 0.0};
+      if (F::C2) {
 #pragma unroll
-          for (int q = 0; q < QL; ++q) n[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(SAV(kt, q), sfl[q], n[kt], 0, 0, 0);
-          mf4 e2nd;
+        for (int q = 0; q < QS; ++q) n[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(SA[kt][q], sfl[q], n[kt], 0, 0, 0);
+        mf4 e2nd;
 #pragma unroll
-          for (int rr = 0; rr < 4; ++rr) {
-            const double2 pr = *reinterpret_cast<const double2*>(SCP + ENT_CI(kt, rr) * 2);
-            e2nd[rr] = fma(pr.x, u2, pr.y) - n[kt][rr];
-          }
-          if (NML) {
+        for (int rr = 0; rr < 4; ++rr) {
+          const double2 pr = *reinterpret_cast<const double2*>(SCP + ENT_CI(kt, rr) * 2);
+          e2nd[rr] = fma(pr.x, u2, pr.y) - n[kt][rr];
+        }
+        if (HV > 1) {
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) NMS[(kt * 4 + rr) * WAVE + lane] = e2nd[rr];
-          } else {
-            nm[(EO && !NML) ? kt : 0] = e2nd;
-          }
-        } else
-        if (!SP || ((act >> kt) & 1u)) {
-          const mf4 cacc = __builtin_amdgcn_mfma_f64_16x16x4f64(SC[kt], sfc, n[kt], 0, 0, 0);
-          n[kt] = cacc;
+          for (int rr = 0; rr < 4; ++rr) NMS[(kt * 4 + rr) * WAVE + lane] = e2nd[rr];
+        } else {
+          nm[HV == 1 ? kt : 0] = e2nd;
+        }
+      } else
+      if (!SPARSE || ((act >> kt) & 1u)) {
+        const mf4 cacc = __builtin_amdgcn_mfma_f64_16x16x4f64(SC[kt], sfc, n[kt], 0, 0, 0);
+        n[kt] = cacc;
 #pragma unroll
-          for (int q = 0; q < QL; ++q)
-            n[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(SAV(kt, q), sfl[q], n[kt], 0, 0, 0);
-          if (NML) {
-            const mf4 e2nd = 2.0 * cacc - n[kt];
+        for (int q = 0; q < QS; ++q)
+          n[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(SA[kt][q], sfl[q], n[kt], 0, 0, 0);
+        if (HV > 1) {
+          const mf4 e2nd = 2.0 * cacc - n[kt];
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) NMS[(kt * 4 + rr) * WAVE + lane] = e2nd[rr];
-          } else {
-            nm[(EO && !NML) ? kt : 0] = 2.0 * cacc - n[kt];
-          }
+          for (int rr = 0; rr < 4; ++rr) NMS[(kt * 4 + rr) * WAVE + lane] = e2nd[rr];
+        } else {
+          nm[HV == 1 ? kt : 0] = 2.0 * cacc - n[kt];
         }
       }
     }
@@ -653,7 +677,6 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         double lt = 0.0;
 #pragma unroll
         for (int d = 0; d < DP; ++d) lt = fma(BTL[(4 * u + lg) * DP + d], Et[li * DP + d], lt);    // zero beyond D on both sides
-        if (!US) lt *= sigj;
         const double ct = fma(tC0[u], u2, tC1[u]);
         ntl[u] = ct + lt;
         ntm[u] = ct - lt;
@@ -666,9 +689,9 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #pragma unroll
       for (int kt = k0; kt < k1; ++kt) {
         if (kt < KT - 1) {
-          if (!SP || ((act >> kt) & 1u)) x[kt] = vb_exp_tab1k4<VB_EXP_TAB1K_QUAD>(x[kt], TAB);
+          if (!SPARSE || ((act >> kt) & 1u)) x[kt] = vb_exp_tab1k4<VB_EXP_TAB1K_QUAD>(x[kt], TAB);
           else x[kt] = (mf4){0.0, 0.0, 0.0, 0.0};
-        } else if (SP && !((act >> (KT - 1)) & 1u)) {
+        } else if (SPARSE && !((act >> (KT - 1)) & 1u)) {
           x[KT - 1] = (mf4){0.0, 0.0, 0.0, 0.0};
         } else if (nr_last == 4) {
           x[KT - 1] = vb_exp_tab1k4<VB_EXP_TAB1K_QUAD>(x[KT - 1], TAB);
@@ -688,25 +711,22 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
     };
     // PV-step: Y[i][col]; lane (col = li, lg) register rr <-> sample lg + 4 rr (SL: lane (sample li, lg) register rr <-> slot lg + 4 rr).
-    // Two accumulator sets halve the dependent chain.
-    // (NPV >= 2: the column blocks are independent chains already, one set is enough -- 16 VGPRs less.)
+    // Two accumulator sets halve the dependent chain (TWO).
     auto pvstep = [&](mf4 (&x)[KT], mf4 (&Y)[NPV], int sg, const double (&tn)[TLN]) {
-      constexpr bool TWO = NPV == 1 && KT <= 2;     // (round 5: at three k-tiles and more the second set's eight registers are worth more as PV
-                                                    //  operands; the dependent MFMAs of one chain issue back to back anyway: 2.138 vs 2.140 ms)
       // (SL: operands swapped -- the mixture side as A, the exponentials as B: the transposed product, see ent_sl_for)
       auto pvm = [&](double xa, double vb, mf4 acc) __attribute__((always_inline)) {
-        return SL ? __builtin_amdgcn_mfma_f64_16x16x4f64(vb, xa, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(xa, vb, acc, 0, 0, 0);
+        return F::SL ? __builtin_amdgcn_mfma_f64_16x16x4f64(vb, xa, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(xa, vb, acc, 0, 0, 0);
       };
-      mf4 Y2s[TWO ? NPV : 1];
-      mf4 (&Y2)[TWO ? NPV : 1] = Y2s;
+      mf4 Y2s[F::TWO ? NPV : 1];
+      mf4 (&Y2)[F::TWO ? NPV : 1] = Y2s;
 #pragma unroll
-      for (int pv = 0; pv < NPV; ++pv) { Y[pv] = (mf4){0.0, 0.0, 0.0, 0.0}; if (TWO) Y2[pv] = (mf4){0.0, 0.0, 0.0, 0.0}; }
+      for (int pv = 0; pv < NPV; ++pv) { Y[pv] = (mf4){0.0, 0.0, 0.0, 0.0}; if (F::TWO) Y2[pv] = (mf4){0.0, 0.0, 0.0, 0.0}; }
 #pragma unroll
       for (int kt = 0; kt < KT - 1; ++kt) {
-        if (SP && !((act >> kt) & 1u)) continue;
+        if (SPARSE && !((act >> kt) & 1u)) continue;
 #pragma unroll
         for (int pv = 0; pv < NPV; ++pv) {
-          mf4& Yb = TWO ? Y2[TWO ? pv : 0] : Y[pv];
+          mf4& Yb = F::TWO ? Y2[F::TWO ? pv : 0] : Y[pv];
           Y[pv] = pvm(x[kt][0], VBV(kt, 0, pv), Y[pv]);
           Yb = pvm(x[kt][1], VBV(kt, 1, pv), Yb);
           Y[pv] = pvm(x[kt][2], VBV(kt, 2, pv), Y[pv]);
@@ -715,8 +735,8 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
 #pragma unroll
       for (int pv = 0; pv < NPV; ++pv) {
-        mf4& Yb = TWO ? Y2[TWO ? pv : 0] : Y[pv];
-        if (SP && !((act >> (KT - 1)) & 1u)) { if (TWO) Y[pv] += Yb; continue; }
+        mf4& Yb = F::TWO ? Y2[F::TWO ? pv : 0] : Y[pv];
+        if (SPARSE && !((act >> (KT - 1)) & 1u)) { if (F::TWO) Y[pv] += Yb; continue; }
         Y[pv] = pvm(x[KT - 1][0], VBV(KT - 1, 0, pv), Y[pv]);
         if (nr_last > 1) Yb = pvm(x[KT - 1][1], VBV(KT - 1, 1, pv), Yb);
         if (nr_last > 2) Y[pv] = pvm(x[KT - 1][2], VBV(KT - 1, 2, pv), Y[pv]);
@@ -725,23 +745,23 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 #pragma unroll
           for (int u = 0; u < TLN; ++u) Y[pv] = pvm(tn[u], VBt[u][pv], Y[pv]);
         }
-        if (TWO) Y[pv] += Yb;
+        if (F::TWO) Y[pv] += Yb;
       }
       if (HV > 1) {
-        if (YXSB && sg == 1) __syncthreads();     // every wave has read the first sign's partials
+        if (sg == 1) __syncthreads();     // one exchange buffer for both signs: every wave has read the first sign's partials
         // all shares of the mixture: the partial q', A', B' of every wave, added in wave order
 #pragma unroll
         for (int pv = 0; pv < NPV; ++pv)
 #pragma unroll
-          for (int rr = 0; rr < 4; ++rr) YX[((YXSB ? 0 : sg) * HV + hv) * YXN + (pv * 4 + rr) * WAVE + lane] = Y[pv][rr];
+          for (int rr = 0; rr < 4; ++rr) YX[hv * F::YXN + (pv * 4 + rr) * WAVE + lane] = Y[pv][rr];
         __syncthreads();
 #pragma unroll
         for (int pv = 0; pv < NPV; ++pv)
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
-            double t = YX[((YXSB ? 0 : sg) * HV + 0) * YXN + (pv * 4 + rr) * WAVE + lane];
+            double t = YX[(pv * 4 + rr) * WAVE + lane];
 #pragma unroll
-            for (int w = 1; w < HV; ++w) t += YX[((YXSB ? 0 : sg) * HV + w) * YXN + (pv * 4 + rr) * WAVE + lane];
+            for (int w = 1; w < HV; ++w) t += YX[w * F::YXN + (pv * 4 + rr) * WAVE + lane];
             Y[pv][rr] = t;
           }
       }
@@ -749,27 +769,24 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // per-sample scalars in the sample layout (lane <-> sample li): q' from column 0, through LDS
     // (SL: q' is in register 3 of the sample's own lanes -- no exchange, put_q and put_rq are empty)
     auto put_q = [&](mf4 (&Y)[NPV]) {
-      if constexpr (SL) return;
-      if (GP2 ? li < 2 : li == 0) {      // column 0: q'_i; GP2: column 1 too, A'_i
+      if constexpr (F::SL) return;
+      if (F::GP2 ? li < 2 : li == 0) {      // column 0: q'_i; GP2: column 1 too, A'_i
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) RQ[(GP2 ? 16 * li : 0) + lg + 4 * rr] = Y[0][rr];
+        for (int rr = 0; rr < 4; ++rr) RQ[(F::GP2 ? 16 * li : 0) + lg + 4 * rr] = Y[0][rr];
       }
-      ent_sync<HV>();   // RQ is private to the wave
+      ent_sync();   // RQ is private to the wave
     };
     double arq = 0.0;   // GP2, SL: A'_i / q'_i in the sample layout
-    // TQ (round 5): the second sign's gradient epilogue reuses the four u'_id the first sign read (-0.2 %; eight registers across the second
-    // sign's exponentials, so only in the headline class, where they are there -- with SL: its walking instantiations).
-    constexpr bool TQ = GP2 && US && NPV == 1 && HV == 1 && EO && KT == 3 && QS <= 3 && !CO && !EM && VBMC_STAG_FOR(KT, QS, TL);
-    double tq[TQ ? 4 : 1];
+    double tq[F::TQ ? 4 : 1];   // TQ: the second sign's gradient epilogue reuses the four u'_id the first sign read
     auto get_rq = [&](mf4 (&Y)[NPV]) -> double {
-      double qs_ = SL ? Y[0][3] : RQ[li];
+      double qs_ = F::SL ? Y[0][3] : RQ[li];
       double rqs = vb_rcp(qs_);
-      if (partial) {
+      if (PK::val) {
         qs_ = svalid ? qs_ : 1.0;
         rqs = svalid ? rqs : 0.0;
       }
-      if (GP2) arq = RQ[GP2 ? 16 + li : 0] * rqs;
-      if (SL) {   // A'_i sits in register 2 of the lanes lg >= 2: every lane takes the product of lane | 32 (v_permlane32_swap of the value with
+      if (F::GP2) arq = RQ[F::GP2 ? 16 + li : 0] * rqs;
+      if (F::SL) {   // A'_i sits in register 2 of the lanes lg >= 2: every lane takes the product of lane | 32 (v_permlane32_swap of the value with
                   // itself leaves [low half | low half] and [high half | high half], see xor_sum32)
         const double t = Y[0][2] * rqs;
         const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(t), (unsigned)__double2loint(t), false, false);
@@ -785,7 +802,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // compiler schedules nineteen instantiations of the QS = 3 unit differently, multi-wave ones among them -- code no measurement here covers.)
     auto rq_pm = [&](double qs_) -> double {
       double rqs = vb_rcp(qs_);
-      if (partial) {
+      if (PK::val) {
         qs_ = svalid ? qs_ : 1.0;
         rqs = svalid ? rqs : 0.0;
       }
@@ -801,30 +818,29 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
-        if (SP && !((act >> kt) & 1u)) continue;
+        if (SPARSE && !((act >> kt) & 1u)) continue;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) Wacc[kt][rr] = fma(x[kt][rr], rqs, Wacc[kt][rr]);  // (:100)
       }
     };
     auto put_rq = [&](double rqs) {
-      if constexpr (SL) return;
-      ent_sync<HV>();
-      if (lg == 0) { RQ[li] = rqs; if (GP2) RQ[GP2 ? 16 + li : 0] = arq; }
-      ent_sync<HV>();
+      if constexpr (F::SL) return;
+      ent_sync();
+      if (lg == 0) { RQ[li] = rqs; if (F::GP2) RQ[F::GP2 ? 16 + li : 0] = arq; }
+      ent_sync();
     };
     // gradient pieces in the PV output layout
-    auto gradpieces = [&](mf4 (&Y)[NPV], double rqs, double ssig, auto sgc) {   // sgc: the sign as a compile-time +1 / -1 (US: no multiply), or 0: ssig at run time
+    auto gradpieces = [&](mf4 (&Y)[NPV], double rqs, double ssig, auto sgc) {   // sgc: the sign as a compile-time +1 / -1 (no multiply), or 0: ssig = +-1 at run time
       constexpr int SG = decltype(sgc)::value;
       // (EVL: u'_id from the LDS tile again, not from ev -- six registers less across both signs' chains for three reads per sign that
       // nothing waits for; the offset is made opaque so that the reads are not merged with the ones ev came from.  No padding mask here:
       // a padded slot's draw meets B' = 0 and lands in accumulators the epilogue does not store.)
-      constexpr bool EVL = SL && ent_sl_evl_for(KT, QS, TL);
       int eo = li * DP + lg;
-      if (EVL) asm volatile("" : "+v"(eo));
-      if constexpr (SL) {   // lane-local: register r holds B'_id of the dimension d = 4 r + lg that ev[r] holds (rqs: the sample's 1/q'_i)
+      if (F::EVL) asm volatile("" : "+v"(eo));
+      if constexpr (F::SL) {   // lane-local: register r holds B'_id of the dimension d = 4 r + lg that ev[r] holds (rqs: the sample's 1/q'_i)
 #pragma unroll
         for (int r = 0; r < QS; ++r) {
-          const double tv = EVL ? Et[eo + 4 * r] : ev[r];
+          const double tv = F::EVL ? Et[eo + 4 * r] : ev[r];
           const double t = (US && SG > 0) ? tv : ((US && SG < 0) ? -tv : ssig * tv);   // u'_id = +-eps_id sigma_j (zero beyond D)
           const double gd = fma(t, arq, -(Y[0][r] * rqs));      // (u'_id A'_i - B'_id) / q'_i; the lanes lg >= 2 of register 2 (A' in place of a
           accG[r] += gd;                                       //  B'; slots 10, 11): finite values in accumulators the epilogue does not store
@@ -832,17 +848,17 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         }
         return;
       }
-      if constexpr (GP2) {
+      if constexpr (F::GP2) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const int i = lg + 4 * rr;
-          const double rq = RQ[i], ar = RQ[GP2 ? 16 + i : 0];     // one broadcast read of the pair
+          const double rq = RQ[i], ar = RQ[F::GP2 ? 16 + i : 0];     // one broadcast read of the pair
 #pragma unroll
           for (int pv = 0; pv < NPV; ++pv) {
             if (HV > 1 && (pv % HV) != hv) continue;      // the waves share the column blocks of the gradient
             const int d = min(max(16 * pv + li - 2, 0), DP - 1);   // columns that are no dimension read a valid slot and are never stored
             double tv;
-            if (TQ) { if (SG >= 0) tq[TQ ? rr : 0] = Et[i * DP + d]; tv = tq[TQ ? rr : 0]; }    // (TQ: the second sign reuses the first sign's reads)
+            if (F::TQ) { if (SG >= 0) tq[F::TQ ? rr : 0] = Et[i * DP + d]; tv = tq[F::TQ ? rr : 0]; }    // (TQ: the second sign reuses the first sign's reads)
             else tv = Et[i * DP + d];
             const double t = (US && SG > 0) ? tv : ((US && SG < 0) ? -tv : ssig * tv);   // u'_id = +-eps_id sigma_j
             const double gd = fma(t, ar, -(Y[pv][rr] * rq));     // lambda_d lsum_d / q = (u'_id A'_i - B'_id) / q'_i  (:77-79)
@@ -850,7 +866,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
             accLG[pv] = fma(t, gd, accLG[pv]);                   // -> sigma/lambda grads (:87-93), times sigma_j (divided out at the end)
           }
         }
-        ent_sync<HV>();
+        ent_sync();
         return;
       }
       const int base = lane & 48;
@@ -871,7 +887,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
           }
         }
       }
-      ent_sync<HV>();
+      ent_sync();
     };
     // renormalise the mantissa product before it can underflow (0.5^256 = 8.6e-78): its exponent joins the exponent sum.  (Round 4:
     // this used to take the logarithm here -- two instructions now instead of a library log in the tile loop, whose polynomial
@@ -891,7 +907,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     using IH = std::integral_constant<int, (KT + 1) / 2>;
     using IK = std::integral_constant<int, KT>;
 
-    if constexpr (PM) {
+    if constexpr (F::PM) {
       // Both signs' exponentials first, q'+- and the pair's p = r+ + r-, m = r+ - r- on the VALU, then ONE PV chain on m (ent_pm_for).
       // m overwrites n, p overwrites nm (the tail pair alike); samples beyond Mh have rqs = 0 and vanish from p, m and everything after.
       exps(n, I0{}, IK{});
@@ -962,7 +978,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         accLG[r] = fma(ev[r], fma(ev[r], ap, -Y[0][r]), accLG[r]);
       }
     } else
-    if constexpr (EO && GRAD && HV == 1 && VBMC_STAG_FOR(KT, QS, TL)) {
+    if constexpr (F::STAG) {
       // Both signs in straight-line code, staggered: the second sign's exponentials (independent of everything the first
       // sign's per-sample chain waits for -- the q' exchange through LDS, the reciprocal, the 1/q' exchange) are issued
       // inside that chain, so this wave keeps the pipe busy across its own latencies instead of leaving them to the one
@@ -991,26 +1007,9 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       // one loop body for both signs; the second sign's exponents are MOVED into n on the back edge -- written as a
       // conditional at the loop head the compiler turns them into 32 selects per sign
       int sg = 0;
-      double ssig = US ? 1.0 : sigj;          // +-sigma_j (US: +-1, the tile holds the product)
+      double ssig = 1.0;          // the sign (the tile holds u' = eps sigma_j)
 #pragma unroll 1
       for (;;) {
-        if (!EO) {   // plain S-step of this sign: KT independent accumulator chains
-          double sf[QS];
-#pragma unroll
-          for (int q = 0; q < QS; ++q) {
-            const int cc = 4 * q + lg;
-            // the sample-side fragment: kept in registers across the sign loop, or re-read from the LDS tile (2 QS registers
-            // less) where the kernel is short of them -- tools/tune_sweep.py: four k-tiles per wave or D >= 27
-            constexpr bool EVREG = KT <= 3 && QS <= 7;
-            sf[q] = (cc < D) ? ssig * (EVREG ? ev[q] : Et[li * DP + 4 * q + lg]) : ((cc == D) ? u2 : ((cc == D + 1) ? 1.0 : 0.0));
-          }
-#pragma unroll
-          for (int kt = 0; kt < KT; ++kt) {
-            n[kt] = (mf4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int q = 0; q < QS; ++q) n[kt] = __builtin_amdgcn_mfma_f64_16x16x4f64(SA[kt][q], sf[q], n[kt], 0, 0, 0);
-          }
-        }
         exps(n, I0{}, IK{});
         texp(ntl);
         if (GRAD) {
@@ -1034,15 +1033,15 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
           qp += __shfl_xor(qp, 16, 64);
           qp += __shfl_xor(qp, 32, 64);
           if (HV > 1) {
-            if (YXSB && sg == 1) __syncthreads();
-            YX[((YXSB ? 0 : sg) * HV + hv) * YXN + lane] = qp;
+            if (sg == 1) __syncthreads();
+            YX[hv * F::YXN + lane] = qp;
             __syncthreads();
-            qp = YX[((YXSB ? 0 : sg) * HV + 0) * YXN + lane];
+            qp = YX[lane];
 #pragma unroll
-            for (int w = 1; w < HV; ++w) qp += YX[((YXSB ? 0 : sg) * HV + w) * YXN + lane];
+            for (int w = 1; w < HV; ++w) qp += YX[w * F::YXN + lane];
           }
           double qs_ = qp;
-          if (partial) qs_ = svalid ? qp : 1.0;
+          if (PK::val) qs_ = svalid ? qp : 1.0;
           pm *= __builtin_amdgcn_frexp_mant(qs_);
           pe += __builtin_amdgcn_frexp_exp(qs_);
           accH += shift;
@@ -1050,16 +1049,14 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         fold();
         if (sg) break;
         sg = 1;
-        ssig = US ? -1.0 : -sigj;
-        if (EO) {
+        ssig = -1.0;
 #pragma unroll
-          for (int kt = 0; kt < KT; ++kt) {
-            if (NML) {
+        for (int kt = 0; kt < KT; ++kt) {
+          if (HV > 1) {
 #pragma unroll
-              for (int rr = 0; rr < 4; ++rr) n[kt][rr] = NMS[(kt * 4 + rr) * WAVE + lane];
-            } else {
-              n[kt] = nm[(EO && !NML) ? kt : 0];
-            }
+            for (int rr = 0; rr < 4; ++rr) n[kt][rr] = NMS[(kt * 4 + rr) * WAVE + lane];
+          } else {
+            n[kt] = nm[HV == 1 ? kt : 0];
           }
         }
 #pragma unroll
@@ -1067,7 +1064,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
       }
     }
   };
-  if constexpr (VBMC_ENT_SPLIT(KT, QS, TL, HV)) {
+  if constexpr (HV == 1) {
     const int tf = min(t1, a.Mh >> 4);        // tiles [t0, tf) hold 16 samples each
     // A wave's issue priority falls as it progresses (s_setprio 3 -> 0 at the quarter points of its tiles): of two waves that share a
     // SIMD the one BEHIND is served first.  At equal priority the arbiter keeps serving the older wave: with a single round of waves
@@ -1077,7 +1074,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     // Halves instead of quarters: a third of the gain.  EntArgs::prio = 0 (VBMC_ENT_PRIO=0): without (A/B).
     // Not in the instantiations built for ONE wave per SIMD (nothing to arbitrate; the thresholds only cost scalar registers there: +0.5-1.1 %
     // at D >= 20, K = 56..64 over the 112-shape sweep, against -3.2 % on average for the shapes of 8..64 components).
-    constexpr bool PRIO = CO ? QS <= 4 : VBMC_ENT_WAVES(KT, QS, TL, HV) > 1;
+    constexpr bool PRIO = F::PRIO;
     const bool pr = PRIO && a.prio != 0;
     // (the quarter points of the WAVE's tiles, as tile indices of this segment: one that lies in an earlier segment was passed there, one at
     // this segment's first tile fires there)
@@ -1093,7 +1090,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   } else {
     // (no priorities here: in the multi-wave kernels the three thresholds cost scalar registers these instantiations do not have --
     // BASELINE configs[4]: kernel alone 8.31 -> 8.64 ms with the code in place and switched off, 8.50 switched on)
-    for (int tile = t0; tile < t1; ++tile) tile_body(tile, EntTileAny{});
+    for (int tile = t0; tile < t1; ++tile) tile_body(tile, EntTilePartial{});   // (a run-time test of the tile gets if-converted into twice the selects)
   }
 #ifdef VBMC_INSTRUMENT
   const unsigned long long wck1 = wall_clock64();
@@ -1108,7 +1105,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   if (lane == 0 && hv == 0) o[0] = accH;
   if (GRAD) {
     double sgsum = 0.0;
-    if constexpr (SL) {   // per (lane, register) = (sample column li, dimension 4 r + lg): the sixteen lanes of a row hold the dimension's terms
+    if constexpr (F::SL) {   // per (lane, register) = (sample column li, dimension 4 r + lg): the sixteen lanes of a row hold the dimension's terms
 #pragma unroll
       for (int r = 0; r < QS; ++r) {
         double g = accG[r], lgd = accLG[r] / sigj;     // accLG carried u' = eps sigma_j in place of eps
@@ -1118,7 +1115,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         lgd += __shfl_xor(lgd, 4, 64); lgd += __shfl_xor(lgd, 8, 64);
         const int d = 4 * r + lg;
         const bool dv = li == 0 && d < D;
-        if (dv) { if (!PM) o[1 + d] = g; o[2 + D + d] = lgd; }      // (PM: G_d still lacks its W part, below)
+        if (dv) { if (!F::PM) o[1 + d] = g; o[2 + D + d] = lgd; }      // (PM: G_d still lacks its W part, below)
         sgsum += dv ? lgd : 0.0;
       }
     } else {
@@ -1137,11 +1134,11 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
     sgsum = wave_sum(sgsum);            // SG = sum_d LG_d  (entmc_vbmc.m:87)
     if (HV > 1) {
       __syncthreads();
-      if (lane == 0) YX[hv * YXN] = sgsum;
+      if (lane == 0) YX[hv * F::YXN] = sgsum;
       __syncthreads();
       sgsum = YX[0];
 #pragma unroll
-      for (int w = 1; w < HV; ++w) sgsum += YX[w * YXN];
+      for (int w = 1; w < HV; ++w) sgsum += YX[w * F::YXN];
     }
     if (lane == 0 && hv == 0) o[1 + D] = sgsum;
     double corr = 0.0;   // PM: this lane group's part of sum_k V[k][slot li] W_k (the PV operand of lane (li, lg) IS V[k][li] of its components)
@@ -1154,7 +1151,7 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         wv += __shfl_xor(wv, 4, 64); wv += __shfl_xor(wv, 8, 64);
         const int k = ENT_CI(kt, rr);
         if (li == 0 && k < Kw) o[2 + 2 * D + kbase + k] = wv;
-        if (PM) corr = fma(VBV(kt, rr, 0), wv, corr);
+        if (F::PM) corr = fma(VBV(kt, rr, 0), wv, corr);
       }
     if (TL) {
 #pragma unroll
@@ -1164,10 +1161,10 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
         wv += __shfl_xor(wv, 4, 64); wv += __shfl_xor(wv, 8, 64);
         const int k = 16 * KT + 4 * u + lg;
         if (li == 0 && k < Kw) o[2 + 2 * D + kbase + k] = wv;
-        if (PM) corr = fma(VBt[u][0], wv, corr);
+        if (F::PM) corr = fma(VBt[u][0], wv, corr);
       }
     }
-    if constexpr (PM) {   // G_d = sum_i u'_id Am_i - sum_k V_kd W_k: after the sum over the lane groups every lane of slot li = d holds the
+    if constexpr (F::PM) {   // G_d = sum_i u'_id Am_i - sum_k V_kd W_k: after the sum over the lane groups every lane of slot li = d holds the
                           // second term, and the lane with li = 4 r + lg holds the row sum of register r for that very d -- no exchange
       corr = xor_sum16(corr);
       corr = xor_sum32(corr);
@@ -1192,7 +1189,6 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
   }
 #endif
 #undef VBV
-#undef SAV
 #undef ENT_CI
 }
 
@@ -1204,10 +1200,9 @@ __device__ __forceinline__ void ent_mfma_segment(const EntArgs& a, const int c, 
 // the operand fragments, the exp table: 8-11 us during which the SIMD's other wave issues alone, at 2/3 of the pair's rate) and an epilogue --
 // every chunk; the walk pays them once per (wave, pair): 2.6 instead of 11 per slot at the headline shape, and 4x fewer partial records.
 template <int QS, int KT, bool GRAD, bool SPARSE, int HV = 1, int TL = 0, bool CO = false, bool EM = true, bool WALK = false>
-__global__ void __launch_bounds__(WAVE * HV, CO ? (QS <= 4 ? 2 : 1) : VBMC_ENT_WAVES(KT, QS, TL, HV)) k_entropy_mfma(EntArgs a) {
+__global__ void __launch_bounds__(WAVE * HV, (EntForm<QS, KT, GRAD, SPARSE, HV, TL, CO, EM, WALK>::WAVES)) k_entropy_mfma(EntArgs a) {
   const int ntile = (a.Mh + 15) >> 4;
   // ONE call site for all forms (the body is ~5000 instructions): the chunk grid is a walk of one segment
-  constexpr bool walk = WALK;
   int c = (int)blockIdx.x, j = CO ? (int)blockIdx.y - a.lj.rows : (int)blockIdx.y, r = (int)blockIdx.z;
   int tlo = ((int)blockIdx.x + a.c0) * a.tiles_per_chunk, thi = min(tlo + a.tiles_per_chunk, ntile), pdone = 0, rem = 0;
   if (!WALK && a.co_c2 > 0 && c >= a.co_c1) {      // a chunk of the second class (launched without the role: the grid spans both classes)
@@ -1231,7 +1226,7 @@ __global__ void __launch_bounds__(WAVE * HV, CO ? (QS <= 4 ? 2 : 1) : VBMC_ENT_W
       __syncthreads();      // the role's table and rows: the entropy set-up overwrites them
     }
   }
-  if (walk) {   // (the host keeps K R ntile below 2^31)
+  if (WALK) {   // (the host keeps K R ntile below 2^31)
     const int g = (int)blockIdx.x * a.walk_tpw;
     rem = min(a.walk_tpw, a.K * a.walk_R * ntile - g);
     const int p = g / ntile;
@@ -1240,11 +1235,11 @@ __global__ void __launch_bounds__(WAVE * HV, CO ? (QS <= 4 ? 2 : 1) : VBMC_ENT_W
     j = p - r * a.K;
     c = (int)blockIdx.x - (g - tlo) / a.walk_tpw;     // = w - ent_walk_first(p): a pair that begins inside this wave's range has it as its first
   }
-  const int ptot = walk ? rem : thi - tlo;
+  const int ptot = WALK ? rem : thi - tlo;
   for (;;) {
-    if (walk) thi = min(ntile, tlo + rem);
+    if (WALK) thi = min(ntile, tlo + rem);
     ent_mfma_segment<QS, KT, GRAD, SPARSE, HV, TL, CO, EM, WALK>(a, c, j, r, tlo, thi, pdone, ptot);
-    if (!walk) break;
+    if (!WALK) break;
     pdone += thi - tlo;
     rem -= thi - tlo;
     if (rem <= 0) break;
