@@ -1,7 +1,8 @@
 """Harness that EXECUTES the MEX gateway (matlab/vbmc_hip_mex.cpp) without MATLAB: the gateway is compiled against the
 functional mock of the mx* / mex* API under tests/mock_mex/ and linked with libvbmc_hip.so into one shared object;
 ``Mex.call(nlhs, cmd, *args)`` builds the prhs array from Python values the way MATLAB would hand them over, calls
-mexFunction and converts plhs back.  Test infrastructure only.
+mexFunction and converts plhs back.  ``gateway_commands()``, ``gateway_block(name)`` and ``gateway_function(name)`` read the
+gateway's command table, its handlers and its helpers out of the source, for the static tests.  Test infrastructure only.
 
 Python -> MATLAB value mapping: float / int -> 1x1 double; numpy float64 array -> double array of the same shape
 (column-major; 1-D arrays become columns); numpy uint64 scalar -> uint64 scalar (device handles); bool -> logical scalar;
@@ -10,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -23,6 +25,45 @@ LIBDIR = os.path.join(ROOT, "vbmc_amd", "lib")
 
 mxDOUBLE, mxLOGICAL, mxCHAR, mxSTRUCT, mxUINT8, mxINT32, mxUINT64 = 6, 3, 4, 2, 9, 12, 15
 _NP = {mxDOUBLE: np.float64, mxUINT8: np.uint8, mxINT32: np.int32, mxUINT64: np.uint64, mxLOGICAL: np.bool_}
+
+
+# ---- readers of the gateway's source: its command table and the handlers the rows point at (what the static tests go by)
+_ROW = re.compile(r'^\s*\{"(\w+)", (\d+), (\d), "([^"]*)", (cmd_\w+), (?:0|NO_CTX)\},$', re.M)
+
+
+def gateway_rows():
+    """The rows of commands[] in the order of the source, as (name, min_nrhs, handles, usage, handler).  Every line between the
+    braces of the table must be a row of that one shape."""
+    src = open(SRCS[0]).read()
+    table = src[src.index("static const Command commands[] = {\n") + len("static const Command commands[] = {\n"):]
+    table = table[: table.index("\n};")]
+    rows = [(n, int(a), int(h), u, f) for n, a, h, u, f in _ROW.findall(table)]
+    assert rows and len(rows) == len(table.split("\n")), "a line of commands[] is not a row"
+    return rows
+
+
+def gateway_commands():
+    """{name: (min_nrhs, handles, usage, handler)}: min_nrhs counts the command string, handles the leading uint64 arguments."""
+    return {r[0]: r[1:] for r in gateway_rows()}
+
+
+def gateway_function(name, src=None):
+    """Text of the file-scope function `static <type> name(...)` (a template too) with the comment lines directly above it."""
+    src = src if src is not None else open(SRCS[0]).read()
+    m = re.search(r"(?:^//[^\n]*\n)*^(?:template <[^>]*> )?static \w+ %s\([^\n]*$" % re.escape(name), src, re.M)
+    assert m, name
+    if m.group(0).rstrip().endswith("}"):             # a one-line function
+        return m.group(0)
+    return src[m.start(): src.index("\n}\n", m.end()) + 2]
+
+
+def gateway_block(name):
+    """Text of the handler of command `name` (its doc comment included); where the handler is a wrapper that passes a flag to
+    a body shared with another command, the wrapper and that body."""
+    src = open(SRCS[0]).read()
+    blk = gateway_function(gateway_commands()[name][3], src)
+    m = re.search(r"\{ return (\w+_body)\(nlhs, plhs, (?:nrhs, )?prhs, (?:true|false)\); \}", blk)
+    return blk + "\n" + gateway_function(m.group(1), src) if m else blk
 
 
 class MexError(RuntimeError):

@@ -5,6 +5,7 @@ with the same arguments, and the documented replacement line for noisy targets."
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,18 +36,17 @@ def test_signature_and_fall_through():
 
 def test_gateway_command_and_argument_counts():
     src = open(MFILE).read()
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
-    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_search_iqr"} and '!strcmp(cmd, "acq_search_iqr")' in gateway
-    assert "vbmc_acq_search_iqr(g_ctx" in gateway
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("acq_search_iqr")
+    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_search_iqr"} and "acq_search_iqr" in cmds
+    min_nrhs, handles, usage, _ = cmds["acq_search_iqr"]
+    assert "vbmc_acq_search_iqr(g_ctx" in blk
     code = re.sub(r"\.\.\.\s*\n", "", src)
     counts = [len(c.split(",")) for c in re.findall(r"vbmc_hip_mex\('acq_search_iqr',([^;]*)\);", code)]
     assert counts == [14], counts
-    usage = re.search(r'"acq_search_iqr: (h, his, acq_id[^"]*)"', gateway).group(1)
-    assert len([t for t in usage.split(",") if t.strip()]) == 14
-    assert re.search(r"search_iqr && \(nrhs < 15", gateway)                      # the command's name + 14 arguments
-    hc = gateway[gateway.index("const char* with_handle[]"):]
-    hc = hc[: hc.index("return raise")]
-    assert '"acq_search_iqr"' in hc and re.search(r'!strcmp\(cmd, "acq_search_iqr"\)\) && \(nrhs < 3 \|\| !is_handle\(prhs\[2\]\)', hc)
+    assert usage.startswith("h, his, acq_id") and "[" not in usage and len([t for t in usage.split(",") if t.strip()]) == 14
+    assert min_nrhs == 15                                                        # the command's name + 14 arguments
+    assert handles == 2                                                          # h and his are both checked before the handler runs
+    assert "handle_in<vbmc_gp>(prhs[1])" in blk and "handle_in<vbmc_acq_is>(prhs[2])" in blk
     for f in ("TolX", "TolFun", "TolHistFun", "MaxFunEvals", "MaxIter", "PopSize", "Seed", "Chunk"):
         assert "'%s'" % f in src, f
     for f in ("xbest", "fbest", "xmean", "sigma", "C", "evals", "generations", "stop", "behind"):

@@ -5,6 +5,7 @@ to cmaes_modded for everything the device search refuses, and the documented one
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, calls, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,17 +37,20 @@ def test_signature_is_the_call_it_replaces():
 
 def test_gateway_command_and_argument_counts():
     src = open(MFILE).read()
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
-    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_search"} and '!strcmp(cmd, "acq_search")' in gateway
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("acq_search")
+    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_search"} and "acq_search" in cmds
+    min_nrhs, handles, usage, _ = cmds["acq_search"]
+    assert "vbmc_acq_search(g_ctx" in blk and handles == 1
     code = re.sub(r"\.\.\.\s*\n", "", src)
     counts = sorted(len(c.split(",")) for c in re.findall(r"vbmc_hip_mex\('acq_search',([^;]*)\);", code))
     assert counts == [11, 14], counts                  # h .. opts, and + gplengthscale, X_rescaled, sn2new for acqfsn2
-    usage = re.search(r'"acq_search: (h, acq_id[^"\[]*)\[', gateway).group(1)
-    assert len([t for t in usage.split(",") if t.strip()]) == 11
+    assert min_nrhs == 12                                # the command's name + the 11 arguments every call passes
+    assert usage.startswith("h, acq_id") and len([t for t in usage.split("[")[0].split(",") if t.strip()]) == 11
+    assert len([t for t in re.sub(r"[\[\]]", "", usage).split(",") if t.strip()]) == 14
     for f in ("TolX", "TolFun", "TolHistFun", "MaxFunEvals", "MaxIter", "PopSize", "Seed", "Chunk"):
-        assert "'%s'" % f in src and 'scalar_field(op, "%s"' % f in gateway, f
+        assert "'%s'" % f in src and 'scalar_field(op, "%s"' % f in blk, f
     for f in ("xbest", "fbest", "xmean", "sigma", "C", "evals", "generations", "stop", "behind"):
-        assert "res.%s" % f in src and '"%s"' % f in gateway, f
+        assert "res.%s" % f in src and '"%s"' % f in blk, f
 
 
 def test_integration_documents_the_replacement():

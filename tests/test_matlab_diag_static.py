@@ -3,10 +3,11 @@ to run it): it calls only the gateway's 'vp_diag' command, with the arguments th
 reference function's in the reference's order followed by one options struct, its outputs the reference's; it falls through to
 vbmc_diagnostics on 'vbmc_hip:unsupported'; it takes its seed from one randi; every default tests nargin against the argument's own
 position (the reference's are one too high); it contains no arithmetic of the estimators; no same-named vbmc_diagnostics.m exists;
-and the gateway's block is logic-free and stands after every other command."""
+and the gateway's handler is logic-free."""
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,18 +30,16 @@ def test_signature_is_the_reference_plus_options():
 
 
 def test_gateway_command_and_argument_count():
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("vp_diag")
     src = open(SHIM).read()
     assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"vp_diag"}
-    assert '!strcmp(cmd, "vp_diag")' in gateway and "vbmc_vp_diagnostics(g_ctx" in gateway
+    assert "vp_diag" in cmds and "vbmc_vp_diagnostics(g_ctx" in blk
+    min_nrhs, handles, usage, _ = cmds["vp_diag"]
     calls = re.findall(r"vbmc_hip_mex\('vp_diag',([^;]*)\);", src)
     assert calls == ["Ns,seed,vp_array{:}"], calls                                                # Ns, seed, then one argument per run
-    assert re.search(r'"vp_diag"\)\) \{[^\n]*\n\s*if \(nrhs < 4\)', gateway)                      # the command, Ns, seed and at least one run
-    usage = re.search(r'"vp_diag: ([^"]*)"', gateway).group(1)
-    assert [t.strip() for t in usage.split(",")] == ["Ns", "seed", "vp1", "vp2", "..."]
-    start = gateway.index('if (!strcmp(cmd, "vp_diag")) {')
-    assert start > max(m.start() for m in re.finditer(r'!strcmp\(cmd, "(?!vp_diag)\w+"\)', gateway))   # after the last command
-    blk = gateway[start:gateway.index('return raise("vbmc_hip:usage", "unknown command");')]
+    assert min_nrhs == 4 and handles == 0                                                         # the command, Ns, seed and at least one run
+    assert [t.strip() for t in re.sub(r"[\[\]]", "", usage).split(",")] == ["Ns", "seed", "vp1", "vp2", "..."]
+    assert [t.strip() for t in usage.split("[")[0].split(",")] == ["Ns", "seed", "vp1"]          # the further runs are optional
     for word in ("8192", "100000", "1e5", "exp(", "log(", "cos(", "fmax(", "std::max", "isnan"):   # logic-free: no default, no reduction
         assert word not in blk, word
     assert "R = nrhs - 3" in blk and blk.count("fill_vp_desc(") == 1

@@ -7,6 +7,7 @@ import json
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, calls, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,23 +30,19 @@ def test_signature_equals_the_reference():
 
 
 def test_gateway_command_and_argument_count():
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("gp_surrogate_sample")
     src = open(SHIM).read()
     assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"gp_surrogate_sample"}
-    assert '!strcmp(cmd, "gp_surrogate_sample")' in gateway and "vbmc_gp_surrogate_sample(g_ctx" in gateway
+    assert "gp_surrogate_sample" in cmds and "vbmc_gp_surrogate_sample(g_ctx" in blk
+    min_nrhs, handles, usage, _ = cmds["gp_surrogate_sample"]
     (call,) = re.findall(r"vbmc_hip_mex\('gp_surrogate_sample',([^;]*)\);", src)
     args = re.sub(r"\([^()]*\)", "", call).split(",")                                             # (nested parentheses dropped)
     assert len(args) == 8 and args[0] == "vbmc_hip_gp_handle" and args[1:3] == ["vp", "Ns"] and args[-2:] == ["noise", "opts"], args
-    assert re.search(r'"gp_surrogate_sample"\)\) \{[^\n]*\n\s*if \(nrhs < 9 ', gateway)
-    usage = re.search(r'"gp_surrogate_sample: (h, [^"]*)"', gateway).group(1)
+    assert min_nrhs == 9                                                                          # the command's name + 8 arguments
     assert [t.strip() for t in usage.split(",")] == ["h", "vp", "Ns", "origflag", "LB", "UB", "noise", "opts"]
-    hc = gateway[gateway.index("const char* with_handle[]"):]
-    assert '"gp_surrogate_sample"' in hc[: hc.index("return raise")]
-    blk = gateway[gateway.index('if (!strcmp(cmd, "gp_surrogate_sample")) {'):gateway.index('if (!strcmp(cmd, "gp_nlz")) {')]
+    assert handles == 1
     for word in ("20000", "2e4", "exp(", "log(", "sqrt(", "ceil("):                                # logic-free: no default of the library is restated
         assert word not in blk, word
-    # no existing static test slices across the new block: they all end at the block in front of it
-    assert gateway.index('if (!strcmp(cmd, "acq_iqr")) {') < gateway.index('if (!strcmp(cmd, "gp_surrogate_sample")) {')
 
 
 def test_fall_through_and_draws():

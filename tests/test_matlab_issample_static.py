@@ -5,6 +5,7 @@ vbmc_hip_is_handle, and no limit of the library restated in a .m file."""
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,21 +53,20 @@ def test_state_handle_is_registered_where_the_search_looks_for_it():
 def test_gateway_command_and_argument_counts():
     src = open(MFILE).read()
     gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
-    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_is_sample"} and '!strcmp(cmd, "acq_is_sample")' in gateway
-    assert "vbmc_acq_is_sample(g_ctx" in gateway
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("acq_is_sample")
+    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"acq_is_sample"} and "acq_is_sample" in cmds
+    min_nrhs, handles, usage, _ = cmds["acq_is_sample"]
+    assert "vbmc_acq_is_sample(g_ctx" in blk
     code = re.sub(r"\.\.\.\s*\n", "", src)
     counts = [len(c.split(",")) for c in re.findall(r"vbmc_hip_mex\('acq_is_sample',([^;]*)\);", code)]
     assert counts == [6], counts
-    usage = re.search(r'"acq_is_sample: (h, x0[^"]*)"', gateway).group(1)
-    assert len([t for t in usage.split(",") if t.strip()]) == 6
-    assert re.search(r'"acq_is_sample"\)\) \{\s*if \(nrhs < 7', gateway)                      # the command's name + 6 arguments
-    hc = gateway[gateway.index("const char* with_handle[]"):]
-    hc = hc[: hc.index("return raise")]
-    assert '"acq_is_sample"' in hc
+    assert usage.startswith("h, x0") and len([t for t in usage.split(",") if t.strip()]) == 6
+    assert min_nrhs == 7 and handles == 1                                                     # the command's name + 6 arguments
+    reader = _mex.gateway_function("read_sampler_opts")                                       # the one reader of the sampler's options
+    assert "read_sampler_opts(a, op)" in blk                                                  # the sampler's options: one reader for every command
     for f in ("Thin", "Burnin", "Spec", "Seed", "Chunk"):
-        assert "'%s'" % f in src and '"%s"' % f in gateway, f
+        assert "'%s'" % f in src and 'scalar_field(op, "%s"' % f in blk + reader, f
     # the command is logic-free: limits and defaults are the library's
-    blk = gateway[gateway.index('if (!strcmp(cmd, "acq_is_sample")) {'):gateway.index('if (!strcmp(cmd, "is_create")) {')]
     for lim in ("256", "66", " 20", " 60"):
         assert lim not in blk, lim
 

@@ -6,6 +6,7 @@ file."""
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,21 +56,20 @@ def test_the_step_two_shim_takes_the_one_call_form_when_given_vp():
 def test_gateway_command_and_argument_counts():
     src = open(MFILE).read()
     gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
-    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"is_setup"} and '!strcmp(cmd, "is_setup")' in gateway
-    assert "vbmc_acq_is_setup(g_ctx" in gateway
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("is_setup")
+    assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"is_setup"} and "is_setup" in cmds
+    min_nrhs, handles, usage, _ = cmds["is_setup"]
+    assert "vbmc_acq_is_setup(g_ctx" in blk
     code = re.sub(r"\.\.\.\s*\n", "", src)
     counts = [len(c.split(",")) for c in re.findall(r"vbmc_hip_mex\('is_setup',([^;]*)\);", code)]
     assert counts == [6], counts
-    usage = re.search(r'"is_setup: (h, vp[^"]*)"', gateway).group(1)
-    assert len([t for t in usage.split(",") if t.strip()]) == 6
-    assert re.search(r'"is_setup"\)\) \{\s*if \(nrhs < 7', gateway)                             # the command's name + 6 arguments
-    hc = gateway[gateway.index("const char* with_handle[]"):]
-    hc = hc[: hc.index("return raise")]
-    assert '"is_setup"' in hc
+    assert usage.startswith("h, vp") and len([t for t in usage.split(",") if t.strip()]) == 6
+    assert min_nrhs == 7 and handles == 1                                                       # the command's name + 6 arguments
+    reader = _mex.gateway_function("read_sampler_opts")                                       # the one reader of the sampler's options
+    assert "read_sampler_opts(a, op)" in blk and 'scalar_field(op, "S"' in blk
     for f in ("Thin", "Burnin", "Spec", "Seed", "Chunk", "S"):
-        assert "'%s'" % f in src and '"%s"' % f in gateway, f
+        assert "'%s'" % f in src and 'scalar_field(op, "%s"' % f in blk + reader, f
     # the command is logic-free: limits and defaults of the sampler are the library's
-    blk = gateway[gateway.index('if (!strcmp(cmd, "is_setup")) {'):gateway.index('if (!strcmp(cmd, "acq_iqr")) {')]
     for lim in ("256", "512", " 66", " 20", " 60", "0.05", "0.6745"):
         assert lim not in blk, lim
     for name in ("Xa1", "lnw1", "fs2a1", "lpdf1", "rect_delta", "x0", "idx0", "n_bad", "bad"):

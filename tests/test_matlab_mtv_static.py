@@ -7,6 +7,7 @@ import json
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,17 +31,16 @@ def test_signature_equals_the_reference():
 
 
 def test_gateway_command_and_argument_count():
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
+    cmds, blk = _mex.gateway_commands(), _mex.gateway_block("vp_mtv")
     src = open(SHIM).read()
     assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {"vp_mtv"}
-    assert '!strcmp(cmd, "vp_mtv")' in gateway and "vbmc_vp_mtv(g_ctx" in gateway
+    assert "vp_mtv" in cmds and "vbmc_vp_mtv(g_ctx" in blk
+    min_nrhs, handles, usage, _ = cmds["vp_mtv"]
     calls = re.findall(r"vbmc_hip_mex\('vp_mtv',([^;]*)\);", src)
     assert len(calls) == 3 and {len(c.split(",")) for c in calls} == {4}, calls               # nargout 3, 2, 1: vp1, vp2, Ns, seed
     assert all(c.startswith("vp1,vp2,Ns,") for c in calls), calls                              # the reference's order, then the seed
-    assert re.search(r'"vp_mtv"\)\) \{[^\n]*\n\s*if \(nrhs < 5\)', gateway)
-    usage = re.search(r'"vp_mtv: ([^"]*)"', gateway).group(1)
+    assert min_nrhs == 5 and handles == 0                                                      # the command's name + 4 arguments
     assert [t.strip() for t in usage.split(",")] == ["vp1", "vp2", "Ns", "seed"]
-    blk = gateway[gateway.index('if (!strcmp(cmd, "vp_mtv")) {'):gateway.index('if (!strcmp(cmd, "acq_iqr")) {')]
     for word in ("8192", "100000", "1e5", "exp(", "log(", "cos("):                           # logic-free: no default of the library is restated
         assert word not in blk, word
 

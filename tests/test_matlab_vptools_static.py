@@ -7,6 +7,7 @@ import json
 import os
 import re
 
+from tests import _mex
 from tests.test_matlab_static import _block, _signature, strip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,18 +39,18 @@ def test_signatures_equal_the_reference():
 
 
 def test_gateway_commands_and_argument_counts():
-    gateway = open(os.path.join(ROOT, "matlab", "vbmc_hip_mex.cpp")).read()
+    cmds = _mex.gateway_commands()
     for name, (ref, cmd, nargs) in SHIMS.items():
         src = re.sub(r"\.\.\.\s*\n", "", open(path(name)).read())
         assert set(re.findall(r"vbmc_hip_mex\(\s*'(\w+)'", src)) == {cmd}, name
-        assert '!strcmp(cmd, "%s")' % cmd in gateway and "vbmc_%s(g_ctx" % cmd in gateway
+        assert cmd in cmds and "vbmc_%s(g_ctx" % cmd in _mex.gateway_block(cmd)
+        min_nrhs, handles, usage, _ = cmds[cmd]
         counts = {len(c.split(",")) for c in re.findall(r"vbmc_hip_mex\('%s',([^;]*)\);" % cmd, strip(src).replace("''", "'%s'" % cmd))}
         assert counts == {nargs}, (name, counts)
-        assert re.search(r'"%s"\)\) \{[^\n]*\n\s*if \(nrhs < %d\)' % (cmd, nargs + 1), gateway), cmd      # the command's name + its arguments
-        usage = re.search(r'"%s: ([^"]*)"' % cmd, gateway).group(1)
-        assert len([t for t in usage.split(",") if t.strip()]) == nargs, (cmd, usage)
+        assert min_nrhs == nargs + 1 and handles == 0, cmd                                              # the command's name + its arguments
+        assert "[" not in usage and len([t for t in usage.split(",") if t.strip()]) == nargs, (cmd, usage)
     # the commands are logic-free: no limit, default or constant of the library is restated
-    blk = gateway[gateway.index('if (!strcmp(cmd, "vp_pdf")) {'):gateway.index('if (!strcmp(cmd, "acq_iqr")) {')]
+    blk = "\n".join(_mex.gateway_block(cmd) for _, cmd, _ in SHIMS.values())
     for word in ("512", " 32", "exp(", "log(", "1e5", "1e6"):
         assert word not in blk, word
 
