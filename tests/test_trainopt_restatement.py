@@ -11,7 +11,7 @@ import pytest
 from scipy.optimize import minimize
 
 from tests import _trainopt_ref as T
-from tests._trainopt_cases import PARITY_CASES, PARITY_NINIT, PARITY_NOPTS, gp_case, parity_case
+from tests._trainopt_cases import PARITY_CASES, WIDE_CASES, gp_case, parity_case, parity_sizes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
@@ -104,7 +104,8 @@ def test_oracle_objective_not_worse_than_lbfgsb(meanfun, noisefun, prior):
 def test_parity_cases_are_decidable_and_well_conditioned(ci):
     """The two conditions under which the GPU parity cases were chosen (tests/_trainopt_cases.py), with the oracle's objective:
     every Armijo / stopping decision and every gap between fill values at least 1e-6 relative from flipping, and iterates that a
-    1e-13 relative perturbation of the gradient (two draws) moves by at most 1e-10."""
+    1e-13 relative perturbation of the gradient (two draws) moves by at most 1e-10.  The wide cases (8 on) also meet the third, that
+    the oracle's value at every iterate is settled to 1e-11, and those with Nhyp > 64 reach the full H product."""
     import vbmc_amd as va
     from oracle import vbmc_ref as R
 
@@ -124,8 +125,9 @@ def test_parity_cases_are_decidable_and_well_conditioned(ci):
             return f, g * (1.0 + eps * rng.standard_normal(g.size))
         return fun
 
-    design = va.fminfill_design(c["h0"][None], c["LB"], c["UB"], c["PLB"], c["PUB"], c["hprior"], PARITY_NINIT, seed=3)
-    run = lambda fun, m=None: T.train_optimize(fun, design, PARITY_NOPTS, c["gp"]["Ncov"], c["gp"]["Nnoise"], c["LB"], c["UB"], tol, MaxIter=maxit, margin=m)
+    Ninit, Nopts = parity_sizes(ci)
+    design = va.fminfill_design(c["h0"][None], c["LB"], c["UB"], c["PLB"], c["PUB"], c["hprior"], Ninit, seed=3)
+    run = lambda fun, m=None: T.train_optimize(fun, design, Nopts, c["gp"]["Ncov"], c["gp"]["Nnoise"], c["LB"], c["UB"], tol, MaxIter=maxit, margin=m)
     margin = []
     base = run(make(0.0, 0), margin)
     fin = base["fill_fvals"][np.isfinite(base["fill_fvals"])]
@@ -140,6 +142,28 @@ def test_parity_cases_are_decidable_and_well_conditioned(ci):
                 worst = max(worst, float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b)))))
     print("case %d: margin %.2e, moved %.2e, %r" % (ci, min(margin), worst, [(r["iterations"], r["exitflag"]) for r in base["runs"]]))
     assert worst <= 1e-10, worst
+    if ci in WIDE_CASES:
+        # condition 3: the oracle's own value at every iterate is settled far below the 1e-10 it is the yardstick for
+        X, pts = c["gp"]["X"], [x for r in base["runs"] for x in r["hist_x"]]
+        val = lambda gp: np.array([float(R.gplite_nlZ(x, gp, c["hprior"], False)[0]) for x in pts])
+        v0, settled = val(c["gp"]), 0.0
+        for seed in (1, 2):
+            v1 = val(dict(c["gp"], X=X * (1.0 + 2.0 ** -52 * np.random.default_rng(seed).standard_normal(X.shape))))
+            settled = max(settled, float(np.max(np.abs(v1 - v0) / np.maximum(1.0, np.abs(v0)))))
+        print("case %d: one unit in the last place of X moves the oracle's values by %.2e" % (ci, settled))
+        assert settled <= 1e-11, settled
+    if c["h0"].size > 64:
+        # the cases that are there for the H products beyond lane 63 reach them: every start moves at least three times, and from the
+        # third step on the step is not along the gradient (a step with the identity in H's place is, exactly: cosine 1; the cosines
+        # here were at most 0.99972 when the cases were chosen)
+        exact = make(0.0, 0)
+        for r in base["runs"]:
+            assert r["iterations"] >= 3
+            hx = np.array(r["hist_x"])
+            for k in range(2, r["iterations"]):
+                m = np.all((hx[k - 1:k + 1] > c["LB"]) & (hx[k - 1:k + 1] < c["UB"]), axis=0)    # (the coordinates no bound cuts short)
+                s, g = (hx[k] - hx[k - 1])[m], exact(hx[k - 1])[1][m]
+                assert np.sum(m) >= 60 and -(s @ g) < (1.0 - 1e-6) * np.linalg.norm(s) * np.linalg.norm(g), (k, np.sum(m), s @ g)
 
 
 # ---- the design map ---------------------------------------------------------------------------------------------------------
