@@ -906,6 +906,33 @@ enum {
 };
 vbmc_status vbmc_ctx_last_launch(vbmc_ctx* ctx, int* ent_form, int* lj_form);
 
+/* Reporting hook (an addition, backward compatible: VBMC_ABI_VERSION is unchanged): the launch form one call of vbmc_gp_pred /
+ * vbmc_gp_quad (quad != 0) on Nstar points would take on this context's device, want_ks != 0 for the callers that read the cross-kernel
+ * matrix themselves (the IQR acquisition functions).  It launches nothing and allocates nothing on the device: it evaluates the functions
+ * the launch itself reads (vbmc_amd/csrc/gp_pred.h: pred_needs_slab, pred_row_groups, pred_forms), so what it reports is what runs.
+ * The form depends on N, D, S, Nstar, on gp.post(s).Lchol, on the number of compute units and on the VBMC_PRED_FUSED switch; a sweep
+ * beyond the chunk size (1 GiB of cross-kernel values) repeats the launch per chunk and is not described here.  Refuses what
+ * vbmc_gp_pred / vbmc_gp_quad refuse.  Tests that mean to exercise a form assert it here. */
+typedef struct vbmc_pred_plan_info {
+  uint32_t struct_size;  /* sizeof(vbmc_pred_plan_info) of the caller */
+  int32_t num_cu;        /* compute units of the device */
+  int32_t slab;          /* 1: the variance comes from slab solves (k_pred_slab), N beyond the resident-tile range */
+  int32_t cw;            /* columns per slab of the triangular solves at this N (16 in the resident-tile range) */
+  int32_t fused;         /* 1: k_pred_fused / k_quad_fused; 0: k_pred_ks + k_gp_pred (or k_pred_slab) */
+  int32_t QS;            /* ceil(D / 4): steps of the MFMA distance blocks */
+  int32_t PT;            /* fused: resident 16-point tiles per workgroup (1..3); else 0 */
+  int32_t RS;            /* fused: workgroups sharing the row tiles of one unit (1..4); else 1 */
+  int32_t npass;         /* fused: passes of PT tiles over the points; else 0 */
+  int32_t units;         /* fused: npass * S (hyper-sample, pass) units; a workgroup walks several when units * RS > grid; else 0 */
+  int32_t grid;          /* workgroups of the variance kernel: k_pred_fused's x, k_gp_pred's x * y * z, k_pred_slab's x * y */
+  int32_t PZ;            /* two-kernel form: slices of the point tiles over gridDim.z; else 1 */
+  int32_t maxg;          /* row groups per hyper-sample, the largest over the samples (fused: RS; slab: 1) */
+  int32_t nblk;          /* 16-row tiles of the training set, ceil(N / 16) */
+  int32_t Rmax, Rmin;    /* resident row tiles of a group of the row-group table (what k_gp_pred holds in LDS), largest and
+                            smallest over all groups and samples; 0 for the slab form */
+} vbmc_pred_plan_info;
+vbmc_status vbmc_pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, int want_ks, int quad, vbmc_pred_plan_info* out);
+
 /* Device-memory helpers for callers without their own allocator (MEX). */
 vbmc_status vbmc_device_alloc(vbmc_ctx* ctx, size_t bytes, void** dptr);
 vbmc_status vbmc_device_free(vbmc_ctx* ctx, void* dptr);

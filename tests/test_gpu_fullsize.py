@@ -9,6 +9,7 @@ import pytest
 from oracle import c_oracle
 from oracle import vbmc_ref as R
 from tests._cases import block_relerr, synth_problem
+from tests._pred_ref import POWER_M, POWER_V, near_data_points, power
 from tests.test_gpu_elbo import relerr
 
 pytestmark = pytest.mark.gpu
@@ -81,8 +82,13 @@ def test_c5_noisy_path_prediction_and_iqr_acquisition(va):
         assert relerr(a["alpha"], b["alpha"]) < 1e-8 and a["Lchol"] == b["Lchol"] and a["sn2_mult"] == b["sn2_mult"]
     rng = np.random.default_rng(1)
     D = 20
-    Xs = 1.3 * rng.standard_normal((150, D))
-    Xa = 1.3 * rng.standard_normal((100, D))
+    # points that see the data (tests/_pred_ref.py): 1.3 N(0, I) around the inputs has a cross-kernel of 1e-9 sf2 at D = 20, and the
+    # comparisons below were then of the mean function and of sf2
+    Xs = near_data_points(gp_o, 150, rng)
+    Xa = near_data_points(gp_o, 100, rng)
+    for pts in (Xs, Xa):
+        pv, pm = power(gp_o, pts)
+        assert pv >= POWER_V and pm >= POWER_M, (pv, pm)
     r_o = R.gplite_pred(gp_o, Xs, None, None, True)
     r_d = va.gplite_pred(gp, Xs, None, None, True)
     sf2 = np.exp(2 * gp_o["post"][0]["hyp"][D])

@@ -303,7 +303,11 @@ def test_pred_and_acq_chunking_over_many_points(va):
 
 @pytest.mark.parametrize("cfg", [(4, 60, 3, 3000), (7, 130, 1, 2500), (3, 17, 2, 1111)])
 def test_pred_many_points_few_samples(va, cfg):
-    """Few hyper-samples and many test points: the point tiles are sliced over gridDim.z so that the chip is covered."""
+    """Few hyper-samples and many test points through the fused form (k_pred_fused): up to 63 passes of three point tiles per
+    hyper-sample, one workgroup per (hyper-sample, pass) unit.  On a 256-CU device none of the three shapes has more units than
+    workgroups (189 at most), so no workgroup walks a second unit here, and k_gp_pred, which slices the point tiles over gridDim.z, is
+    not launched at all: the walk and the slicing are the cases "walk" and "twok_pz" of tests/test_gpu_pred_forms.py, which assert
+    the form they ran through vbmc_pred_plan."""
     from tests.test_gpu_elbo import problem
     D, N, S, nstar = cfg
     p, gp, vp, _ = problem(71, D, N, 3, S)

@@ -15,6 +15,7 @@ import pytest
 from oracle import vbmc_ref as R
 from tests import _quad_ref as Q
 from tests._cases import relerr
+from tests._pred_ref import near_data_points
 from tests.test_gpu_elbo import problem
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,12 @@ def _case(D, N, Nstar, S, meanfun, seed=31):
     if Nstar >= 3:
         mu[-2:] = gp["X"][:2] + 1e-3                # two points beside the data: varF cancels to a small fraction of nf_kk
     sg = _sigma(D, seed)
+    if D >= 13:
+        # 1.3 N(0, I) around the inputs has a cross term of zero from D = 13 upwards: every second point sits near a training input on the
+        # quadrature's scale tau (the smallest over the hyper-samples, so that each of them sees it), z / nf between 1e-2 and 1
+        tau = np.min(np.sqrt(sg[None, :] ** 2 + np.stack([np.exp(q["hyp"][:D]) for q in gp["post"]]) ** 2), axis=0)
+        near = mu[:(Nstar - 2 if Nstar >= 3 else Nstar):2]        # (the last two rows are planted from Nstar = 3)
+        near[:] = near_data_points(gp, near.shape[0], np.random.default_rng(seed + 2), lo=1e-2, scale=tau)
     assert _conditioned(gp, mu, sg) < 1e-10
     return gp, mu, sg
 

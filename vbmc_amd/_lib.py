@@ -229,6 +229,12 @@ class GsArgs(C.Structure):
     ]
 
 
+class PredPlanInfo(C.Structure):
+    """vbmc_pred_plan_info (include/vbmc_hip.h)"""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in (
+        "num_cu", "slab", "cw", "fused", "QS", "PT", "RS", "npass", "units", "grid", "PZ", "maxg", "nblk", "Rmax", "Rmin")]
+
+
 _lib = None
 
 
@@ -270,6 +276,8 @@ def load():
     lib.vbmc_rng_dump.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp]
     lib.vbmc_entropy_plan.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
     lib.vbmc_entropy_plan.restype = C.c_int
+    lib.vbmc_pred_plan.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PredPlanInfo)]
+    lib.vbmc_pred_plan.restype = C.c_int
     lib.vbmc_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.vbmc_device_free.argtypes = [vp, vp]
     lib.vbmc_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]

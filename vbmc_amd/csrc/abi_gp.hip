@@ -291,6 +291,28 @@ extern "C" vbmc_status vbmc_gp_pred(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar,
   return pred_read_columns(ctx, pb, Nstar, gp->S, ssflag, false, {ymu, ys2, fmu, fs2});
 }
 
+// reporting hook: the launch form of one prediction / quadrature call, from the functions pred_plan and pred_launch read (no launch)
+extern "C" vbmc_status vbmc_pred_plan(vbmc_ctx* ctx, const vbmc_gp* gp, int Nstar, int want_ks, int quad, vbmc_pred_plan_info* out) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  if (!out || out->struct_size != sizeof(vbmc_pred_plan_info)) return set_err(ctx, VBMC_ERR_INVALID, "vbmc_pred_plan: bad arguments");
+  VB_TRY(pred_check(ctx, "vbmc_pred_plan", gp, Nstar, quad != 0));
+  const bool slab = pred_needs_slab(gp->N);
+  PredGroups grp = pred_row_groups(gp, slab);
+  const PredForms f = pred_forms(ctx, gp->N, gp->D, gp->S, Nstar, want_ks != 0, grp.maxg);
+  out->num_cu = ctx->num_cu; out->slab = f.slab_pred; out->cw = trsm_cw_for(gp->N); out->fused = f.fused; out->QS = f.QS;
+  out->PT = f.fused ? f.fused_pt : 0; out->RS = f.fused_rs; out->npass = f.npass; out->units = f.units; out->grid = f.grid;
+  out->PZ = (f.fused || f.slab_pred) ? 1 : f.PZ; out->maxg = f.fused ? f.fused_rs : grp.maxg; out->nblk = f.nblk;
+  int rmax = 0, rmin = 0;
+  for (int s = 0; s < gp->S && !slab; ++s)
+    for (int g = 0; g < grp.count(s); ++g) {
+      const int R = grp.edge(s, g, 1) - grp.edge(s, g, 0);
+      rmax = std::max(rmax, R);
+      rmin = rmin ? std::min(rmin, R) : R;
+    }
+  out->Rmax = rmax; out->Rmin = rmin;
+  return VBMC_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // gplite_quad (gplite/gplite_quad.m:1-119) with one sigma row shared by all points
 namespace {

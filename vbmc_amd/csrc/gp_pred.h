@@ -56,6 +56,13 @@ struct PredBufs {
 struct PredForms {
   bool slab_pred = false, fused = false;
   int PZ = 1, fused_pt = 0, fused_rs = 1;
+  // the grid arithmetic: what pred_launch launches with and what the reporting hook vbmc_pred_plan reports
+  int QS = 0, ntile = 0;       // ceil(D / 4) steps of the MFMA distance blocks; 16-point tiles
+  int nblk = 0;                // 16-row tiles of the training set
+  int npass = 0, units = 0;    // fused: passes of fused_pt tiles over the points, and the (hyper-sample, pass) units
+  int slab_cw = 0;             // slab: test points per wave of k_pred_slab (trsm_cw_for)
+  int grid = 0;                // workgroups of the variance kernel: k_pred_fused's x and k_pred_slab's x * y, which pred_launch reads;
+                               // for k_gp_pred the product of the dim3(maxg, S, PZ) it launches
 };
 struct PredPlan {
   PredArgs pa{};
@@ -159,16 +166,25 @@ PredForms pred_forms(const vbmc_ctx* ctx, int N, int D, int S, int Nstar, bool w
   f.slab_pred = pred_needs_slab(N);
   // one workgroup per CU (its LDS is full): slice the point tiles over gridDim.z until the chip is covered
   const int ntile_ = (Nstar + 15) / 16;
+  f.QS = (D + 3) / 4; f.ntile = ntile_; f.nblk = nblk;
   f.PZ = std::max(1, ctx->num_cu / std::max(1, maxg * S));
   f.PZ = std::min(f.PZ, std::max(1, ntile_ / (PRED_THREADS / 64)));
   static const bool fused_off = [] { const char* e = getenv("VBMC_PRED_FUSED"); return e && !strcmp(e, "0"); }();
   // point tiles resident per workgroup: as many N x 16 tiles as the 160 KB hold beside the 2 KB table (three at N = 400)
-  f.fused_pt = (int)std::min<size_t>(PREDF_PT_FOR_QS((D + 3) / 4), ((size_t)160 * 1024 - 2048 - (PREDF_THREADS / 64) * PREDF_MAXPT * 16 * 8 - 256) / ((size_t)Np * 16 * 8));
-  f.fused = !want_ks && !f.slab_pred && !fused_off && f.fused_pt >= 1 && (D + 3) / 4 <= 8;
+  f.fused_pt = (int)std::min<size_t>(PREDF_PT_FOR_QS(f.QS), ((size_t)160 * 1024 - 2048 - (PREDF_THREADS / 64) * PREDF_MAXPT * 16 * 8 - 256) / ((size_t)Np * 16 * 8));
+  f.fused = !want_ks && !f.slab_pred && !fused_off && f.fused_pt >= 1 && f.QS <= 8;
   // few points (the importance sampler's ~110 per call): RS workgroups per (hyper-sample, pass) unit share its row tiles (k_pred_fused)
   if (f.fused) {
-    const int units = ((ntile_ + f.fused_pt - 1) / f.fused_pt) * S;
-    f.fused_rs = std::max(1, std::min(std::min(4, nblk / 4), ctx->num_cu / std::max(1, units)));
+    f.npass = (ntile_ + f.fused_pt - 1) / f.fused_pt;
+    f.units = f.npass * S;
+    f.fused_rs = std::max(1, std::min(std::min(4, nblk / 4), ctx->num_cu / std::max(1, f.units)));
+    // one workgroup per compute unit (its LDS is full), each walking the (hyper-sample, pass, row share) units b, b + grid, ...
+    f.grid = std::max(1, std::min(f.units * f.fused_rs, ctx->num_cu));
+  } else if (f.slab_pred) {
+    f.slab_cw = std::max(1, trsm_cw_for(N));
+    f.grid = ((Nstar + f.slab_cw - 1) / f.slab_cw) * S;
+  } else {
+    f.grid = maxg * S * f.PZ;
   }
   return f;
 }
@@ -231,7 +247,6 @@ vbmc_status pred_launch(vbmc_ctx* ctx, PredBufs& pb, const PredPlan& pl) {
   const int N = pa.N, D = pa.D, S = pa.S, Nstar = pl.Nstar, Np = pl.Np, maxg = pl.maxg, fused_pt = pl.f.fused_pt;
   const bool quad = pl.quad;
   const size_t maxlds = pl.maxlds;
-  const int ntile_ = (Nstar + 15) / 16;
   hipStream_t st = ctx->stream;
   TmpBuf &dXc = pb.dXc, &daa = pb.daa, &dmuv = pb.dmuv;
   if (quad) hipLaunchKernelGGL(k_quad_prep, dim3(4, S), dim3(256), 0, st, pa, dXc.as<double>(), daa.as<double>(), dmuv.as<double>());
@@ -242,9 +257,7 @@ vbmc_status pred_launch(vbmc_ctx* ctx, PredBufs& pb, const PredPlan& pl) {
   };
   if (pl.f.fused) {
     const size_t fl = PREDF_LDS_BYTES(fused_pt, Np);   // the tiles, and no less than the per-wave sums that reuse the block
-    const int npass = (ntile_ + fused_pt - 1) / fused_pt;
-    // one workgroup per compute unit (its LDS is full), each walking the (hyper-sample, pass) units b, b + grid, ...
-    const int gxf = std::max(1, std::min(npass * S * pl.f.fused_rs, ctx->num_cu));
+    const int gxf = pl.f.grid;
     vbmc_status fs = VBMC_OK;
     DISPATCH_QS(D, fs = pred_launch_fused_pt<QS>(ctx, pb, pl, gxf, fl))
     VB_TRY(fs);
@@ -253,14 +266,14 @@ vbmc_status pred_launch(vbmc_ctx* ctx, PredBufs& pb, const PredPlan& pl) {
     return VBMC_OK;
   }
   // inner dimension of the MFMA distance blocks: QS = ceil(D / 4) steps
-  DISPATCH_QS(D, hipLaunchKernelGGL((quad ? k_quad_ks<QS> : k_pred_ks<QS>), dim3((Nstar + 15) / 16, S), dim3(64), 0, st, pa, dXc.as<double>(),
+  DISPATCH_QS(D, hipLaunchKernelGGL((quad ? k_quad_ks<QS> : k_pred_ks<QS>), dim3(pl.f.ntile, S), dim3(64), 0, st, pa, dXc.as<double>(),
                                     daa.as<double>(), dmuv.as<double>(), pb.dKs.as<double>(), pb.dpF.as<double>()))
   if (pl.f.slab_pred) {
-    TRSM_DISPATCH_CW(trsm_cw_for(N), {
+    TRSM_DISPATCH_CW(pl.f.slab_cw, {
       const size_t sl = TRSM_LDS_BYTES_CW(N, CW);
       if (sl > 64 * 1024)
         HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_pred_slab<CW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl));
-      hipLaunchKernelGGL((k_pred_slab<CW>), dim3((Nstar + CW - 1) / CW, S), dim3(64), sl, st, pa, pb.dKs.as<double>(), pb.dpV.as<double>());
+      hipLaunchKernelGGL((k_pred_slab<CW>), dim3(pl.f.grid / S, S), dim3(64), sl, st, pa, pb.dKs.as<double>(), pb.dpV.as<double>());
     });
   } else {
     if (maxlds > 64 * 1024)

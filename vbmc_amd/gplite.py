@@ -140,6 +140,21 @@ def gplite_pred(gp, Xstar, ystar=None, s2star=None, ssflag=False, nowarpflag=Fal
     return tuple(outs[: max(1, nargout)])
 
 
+def pred_plan(gp, Nstar, want_ks=False, quad=False, *, engine=None):
+    """The launch form one ``gplite_pred`` (``quad``: ``gplite_quad``) call on ``Nstar`` points takes on this device, as a dict of
+    the fields of vbmc_pred_plan_info (include/vbmc_hip.h); ``want_ks`` for the form behind the IQR acquisition functions.  Launches
+    nothing: the reporting hook vbmc_pred_plan evaluates the functions the launch itself reads."""
+    from ._lib import PredPlanInfo
+
+    engine = engine or default_engine()
+    ctx = engine.ctx
+    dgp = _device_gp_with_noise(engine, gp)
+    info = PredPlanInfo()
+    info.struct_size = C.sizeof(PredPlanInfo)
+    ctx.check(ctx.lib.vbmc_pred_plan(ctx.h, dgp.h, int(Nstar), 1 if want_ks else 0, 1 if quad else 0, C.byref(info)))
+    return {n: int(getattr(info, n)) for n, _ in PredPlanInfo._fields_[1:]}
+
+
 def gplite_quad(gp, mu, sigma, ssflag=False, nargout=2, *, engine=None):
     """[F,varF] = gplite_quad(gp,mu,sigma,ssflag)  (gplite/gplite_quad.m:1-119): Bayesian quadrature of the GP against
     N(mu_i, diag sigma^2) for every row of ``mu`` (Nstar x D).  ``sigma`` is a row of D values shared by all points, or an
