@@ -906,6 +906,33 @@ enum {
 };
 vbmc_status vbmc_ctx_last_launch(vbmc_ctx* ctx, int* ent_form, int* lj_form);
 
+/* Reporting hook (an addition, backward compatible: VBMC_ABI_VERSION is unchanged): what the variance stage of the last ELBO pass with
+ * compute_var != 0 enqueued on this context (vbmc_amd/csrc/elbo_pass.h: Pass::variance), recorded there from the expressions the
+ * launches themselves use.  compute_var = 0: no such pass has run on this context yet.  Tests that mean to exercise a form of the
+ * triangular step or a Gram kernel assert it here. */
+enum {
+  VBMC_VARSOLVE_TRSM2 = 1,      /* k_trsm2<solve_width>: a workgroup per 16 columns, solve_width = 4 or 8 row-block slots (N <= 512 / 1024) */
+  VBMC_VARSOLVE_SLAB = 2        /* k_trsm_fwd<solve_width> / k_trsm_bwd<solve_width>: a wave per slab of solve_width = 16, 8, 4, 2, 1 columns */
+};
+enum {
+  VBMC_VARGRAM_WAVE = 1,        /* k_var_gram: one wave per pair (the diagonal approximation)                                     */
+  VBMC_VARGRAM_MFMA = 2         /* k_var_gram_mfma: 16 x 16 tiles of the upper triangle on the matrix cores (the full matrix)     */
+};
+typedef struct vbmc_var_launch_info {
+  uint32_t struct_size;  /* sizeof(vbmc_var_launch_info) of the caller */
+  int32_t compute_var;   /* of that pass: 1 full matrix, 2 diagonal approximation; 0: none yet */
+  int32_t tri_gemm;      /* 1: V = inv(L') Z as a product with the explicit inverse (k_tri_gemm) for the Cholesky samples, no forward substitution */
+  int32_t symm;          /* 1: k_symm ran (a low-noise sample is present) */
+  int32_t fwd_solve;     /* VBMC_VARSOLVE_* of the forward substitution; 0 with tri_gemm */
+  int32_t bwd_solve;     /* VBMC_VARSOLVE_* of the backward substitution (the variance gradient alone); 0 without */
+  int32_t solve_width;   /* slots or slab columns of those substitutions; 0 where neither ran */
+  int32_t gram;          /* VBMC_VARGRAM_* */
+  int32_t vgrad;         /* 1: k_vargrad and k_var_sample ran */
+  int32_t sample_lds;    /* dynamic LDS of k_var_sample in bytes; 0 where it did not run */
+  int32_t final_lds;     /* dynamic LDS of k_var_final in bytes */
+} vbmc_var_launch_info;
+vbmc_status vbmc_ctx_last_variance(vbmc_ctx* ctx, vbmc_var_launch_info* out);
+
 /* Reporting hook (an addition, backward compatible: VBMC_ABI_VERSION is unchanged): the launch form one call of vbmc_gp_pred /
  * vbmc_gp_quad (quad != 0) on Nstar points would take on this context's device, want_ks != 0 for the callers that read the cross-kernel
  * matrix themselves (the IQR acquisition functions).  It launches nothing and allocates nothing on the device: it evaluates the functions

@@ -36,6 +36,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.vbmc_abi_version() == ver == _lib.ABI_VERSION
 
 
+def test_variance_launch_record_matches_the_header():
+    """vbmc_var_launch_info: the ctypes mirror has the header's fields in the header's order, and the enumerators the header's values"""
+    from vbmc_amd import _lib
+
+    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct vbmc_var_launch_info \{(.*?)\} vbmc_var_launch_info;", hdr, flags=re.S).group(1), flags=re.S)
+    fields = [(t, n) for t, n in re.findall(r"\b(uint32_t|int32_t)\s+(\w+);", body)]
+    assert fields[0] == ("uint32_t", "struct_size") and all(t == "int32_t" for t, _ in fields[1:])
+    assert [n for _, n in fields] == [n for n, _ in _lib.VarLaunchInfo._fields_]
+    assert ctypes.sizeof(_lib.VarLaunchInfo) == 4 * len(fields)
+    enum = dict((k, int(v)) for k, v in re.findall(r"\b(VBMC_VAR(?:SOLVE|GRAM)_\w+)\s*=\s*(\d+)", hdr))
+    assert enum == {"VBMC_VARSOLVE_TRSM2": _lib.VARSOLVE_TRSM2, "VBMC_VARSOLVE_SLAB": _lib.VARSOLVE_SLAB,
+                    "VBMC_VARGRAM_WAVE": _lib.VARGRAM_WAVE, "VBMC_VARGRAM_MFMA": _lib.VARGRAM_MFMA}
+    from tests import _var_cases as C
+
+    assert (C.TRSM2, C.SLAB, C.WAVE, C.MFMA) == (_lib.VARSOLVE_TRSM2, _lib.VARSOLVE_SLAB, _lib.VARGRAM_WAVE, _lib.VARGRAM_MFMA)
+
+
 def test_no_cpu_fallback_without_gpu():
     """Without a gfx950 device the product path must fail loudly, never compute on the CPU."""
     import torch

@@ -13,6 +13,7 @@ import pytest
 
 from oracle import vbmc_ref as R
 from tests._cases import (block_relerr, delta_golden_cases, load_delta_golden, relerr, synth_problem, theta_from_inputs)
+from tests.test_var_restatement import check_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -236,6 +237,7 @@ def test_full_variance_and_separate_K(va, meanfun, low_noise):
     assert np.max(np.abs(out[10] - ref["J_sjk"])) < RT_VAR * scale
     assert abs(out[7] - ref["varG"]) < RT_VAR * max(1.0, abs(ref["varG"]), scale)
     assert abs(out[6] - ref["varGss"]) < RT_VAR * max(1.0, abs(ref["varGss"]), scale)
+    check_entries(gp, vp, 1, what="delta, full", J=out[10], varG=out[7], varGss=out[6])     # per entry (tests/_var_ref.py)
 
 
 @pytest.mark.parametrize("meanfun", [0, 1, 4])
@@ -268,6 +270,7 @@ def test_diag_variance_and_its_gradient(va, meanfun, low_noise):
             grad_ok(dF[:, s], rdF[:, s], D, K)
         assert relerr(varF, ref["varF"], vsc) < RT_VAR
         assert relerr(dvarF, np.asarray(ref["dvarF"]).reshape(np.shape(dvarF)), dsc) < RT_DVAR
+        check_entries(gp, vp, 2, (1, 1, 1, 1), what="delta, diagonal", **(dict(varG=varF, dvarF=dvarF) if avg else dict(varF_s=varF, dvarF_s=dvarF)))
 
 
 # ---------------------------------------------------------------- call paths
@@ -371,6 +374,8 @@ def test_golden_delta_family_on_the_device(va, path):
     assert relerr(np.atleast_1d(out[2]), exp["varG_s_full"], jsc) < RT_VAR
     assert relerr(np.asarray(out[5]).reshape(S, K), exp["I_sk"]) < RT_VAL
     assert np.max(np.abs(np.asarray(out[6]).reshape(S, K, K) - exp["J_sjk"])) < RT_VAR * jsc
+    check_entries(gp, vp, 2, (1, 1, 1, 1), what="golden, diagonal", varF_s=varF, dvarF_s=dvarF)
+    check_entries(gp, vp, 1, what="golden, full", J=np.asarray(out[6]).reshape(S, K, K), varF_s=out[2])
     # the same family through the objective: negelcbo's G is gplogjoint's F averaged over the hyper-samples
     theta = theta_from_inputs(inp)
     r = va.negelcbo_batch(theta, 0, vp, gp, 0, True, 0)

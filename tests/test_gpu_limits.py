@@ -119,6 +119,10 @@ def test_variance_paths_and_nlz_beyond_the_wide_slab(va, N, S):
     assert abs(got["G"][0] - ref["G"]) < 1e-10 * max(1.0, abs(ref["G"]))
     assert abs(got["varG"][0] - ref["varG"]) < 1e-6 * max(abs(ref["varG"]), 1e-12) + 1e-9
     assert np.max(np.abs(got["J_sjk"][:, :, :, 0] - ref["J_sjk"])) < 1e-7 * max(1.0, np.max(np.abs(ref["J_sjk"])))
+    if N == 1300:    # per entry (tests/_var_ref.py); at N = 4500 the extended-precision substitution alone would take this test's time over
+        from tests.test_var_restatement import check_entries
+
+        check_entries(gp, vp, 1, what="N = 1300", J=got["J_sjk"][:, :, :, 0], varG=got["varG"][0], varGss=got["varGss"][0])
     refd = R.negelcbo_vbmc(theta, 0.5, vp, gp, 0, True, 2)
     gotd = va.negelcbo_batch(theta, 0.5, vp, gp, 0, True, 2)
     assert abs(gotd["F"][0] - refd["F"]) < 1e-8 * max(1.0, abs(refd["F"]))

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 from tests._cases import relerr  # noqa: E402  (relative to the largest reference entry; no floor)
+from tests.test_var_restatement import check_entries  # noqa: E402  (per entry, in units of what is added up: tests/_var_ref.py)
 
 
 @pytest.fixture(scope="module")
@@ -159,10 +160,15 @@ def test_gplogjoint_per_hyper_sample_outputs(va, cfg):
     assert out[4] == 0.0 or S == 1                      # varss is only formed when averaging (:398-404)
     assert relerr(out[5], ref["I_sk"]) < 1e-10
     assert np.max(np.abs(out[6] - ref["J_sjk"])) < 1e-7 * max(1.0, np.max(np.abs(ref["J_sjk"])))
+    # per entry, in units of what is added up (tests/_var_ref.py), where the inputs have power: the twenty components of the third
+    # shape sit on distinct training inputs far apart, and one of its three tiles has no off-diagonal pair that sees the data
+    if cfg != (10, 120, 20, 8):
+        check_entries(gp, vp, 1, what=str(cfg), J=np.asarray(out[6]).reshape(S, K, K), varF_s=varF)
     # diagonal approximation and value only
     refd = R.gplogjoint(vp, gp, grad_flags=0, avg_flag=False, compute_var=2)
     Fd, _, varFd = va.gplogjoint(vp, gp, 0, 0, 0, 2, nargout=3)
     assert relerr(Fd, refd["F"]) < 1e-10 and np.max(np.abs(np.asarray(varFd) - refd["varF"])) < 1e-7 * max(1.0, np.max(np.abs(refd["varF"])))
+    check_entries(gp, vp, 2, what=str(cfg), varF_s=varFd)
     F0 = va.gplogjoint(vp, gp, 0, 0, nargout=1)
     assert relerr(F0, ref["F"]) < 1e-10
     # averaging the per-sample outputs on the host reproduces the averaged call (:399-411)
@@ -193,6 +199,7 @@ def test_gplogjoint_per_hyper_sample_gradients(va, flags, jac):
     F2, dF2, varF2 = va.gplogjoint(vp, gp, flags, False, jac, 2, nargout=3)
     ref2 = R.gplogjoint(vp, gp, flags, False, jac, 2)
     assert relerr(dF2, ref2["dF"]) < 1e-9 and np.max(np.abs(np.asarray(varF2) - ref2["varF"])) < 1e-7 * max(1.0, np.max(np.abs(ref2["varF"])))
+    check_entries(gp, vp, 2, what="per-sample variance beside gradients", varF_s=varF2)
 
 
 @pytest.mark.parametrize("flags", FLAGS)
@@ -209,6 +216,7 @@ def test_gplogjoint_variance_gradient_every_form(va, flags, jac, avg):
     assert relerr(F, ref["F"]) < 1e-10 and relerr(dF, np.asarray(ref["dF"])) < 1e-9
     assert np.max(np.abs(np.asarray(varF) - ref["varF"])) < 1e-7 * max(1.0, np.max(np.abs(ref["varF"])))
     assert np.shape(dvarF) == np.shape(ref["dvarF"])
+    check_entries(gp, vp, 2, flags, jac, what="dvarF %r" % (flags,), **(dict(varG=varF, dvarF=dvarF) if avg else dict(varF_s=varF, dvarF_s=dvarF)))
     assert relerr(dvarF, ref["dvarF"], scale=max(np.max(np.abs(ref["dvarF"])), 1e-6 * np.max(np.abs(ref["varF"])))) < 1e-6     # z' K^-1 z cancels against nf_kk
     if not avg:
         Fa, dFa, varFa, dvarFa = va.gplogjoint(vp, gp, flags, True, jac, 2, nargout=4)
@@ -234,6 +242,7 @@ def test_gplogjoint_components_together_with_gradients(va, cv):
     if cv:
         assert relerr(out[2], o["varF"]) < 1e-8
         assert np.max(np.abs(out[6] - o["J_sjk"])) < 1e-7 * max(1.0, np.max(np.abs(o["J_sjk"])))
+        check_entries(gp, vp, cv, what="components with gradients", J=out[6], varG=out[2])
 
 
 def test_gplogjoint_per_hyper_sample_outputs_against_mpmath_vectors(va):

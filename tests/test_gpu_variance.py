@@ -9,6 +9,7 @@ import pytest
 from oracle import vbmc_ref as R
 from tests._cases import golden_cases, load_golden, theta_from_inputs, vp_from_inputs
 from tests.test_gpu_elbo import problem, relerr
+from tests.test_var_restatement import check_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +58,10 @@ def test_full_variance_eval_fullelcbo_form(va, cfg):
     assert abs(varG - ref["varG"]) < 1e-7 * max(1.0, abs(ref["varG"]), scale)
     assert abs(varGss - ref["varGss"]) < 1e-7 * max(1.0, abs(ref["varGss"]), scale)
     assert varH == 0.0 and varF == varG
+    # per entry, in units of what is added up (tests/_var_ref.py), where the inputs have power: the components of the third shape sit on
+    # distinct training inputs far apart, and one of its three tiles has no off-diagonal pair that sees the data
+    if cfg != (10, 150, 20, 4):
+        check_entries(gp, vp, 1, what=str(cfg), J=J_sjk, varG=varG, varGss=varGss)
 
 
 def test_diag_variance_gradient_with_beta(va):
@@ -92,6 +97,7 @@ def test_low_noise_branch_Lchol_false(va):
     scale = max(1.0, np.max(np.abs(ref["J_sjk"])))
     assert np.max(np.abs(out[10] - ref["J_sjk"])) < 1e-7 * scale
     assert abs(out[7] - ref["varG"]) < 1e-7 * max(1.0, scale)
+    check_entries(gp, vp, 1, what="low noise", J=out[10], varG=out[7], varGss=out[6])
     beta = 0.8
     F, dF = va.negelcbo_vbmc(theta, beta, vp, gp, 0, 1, 2)
     ref2 = R.negelcbo_vbmc(theta, beta, vp, gp, 0, True, 2)

@@ -235,6 +235,15 @@ class PredPlanInfo(C.Structure):
         "num_cu", "slab", "cw", "fused", "QS", "PT", "RS", "npass", "units", "grid", "PZ", "maxg", "nblk", "Rmax", "Rmin")]
 
 
+class VarLaunchInfo(C.Structure):
+    """vbmc_var_launch_info (include/vbmc_hip.h)"""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in (
+        "compute_var", "tri_gemm", "symm", "fwd_solve", "bwd_solve", "solve_width", "gram", "vgrad", "sample_lds", "final_lds")]
+
+
+VARSOLVE_TRSM2, VARSOLVE_SLAB = 1, 2     # VBMC_VARSOLVE_*
+VARGRAM_WAVE, VARGRAM_MFMA = 1, 2        # VBMC_VARGRAM_*
+
 _lib = None
 
 
@@ -260,6 +269,7 @@ def load():
     lib.vbmc_ctx_set_profiling.argtypes = [vp, C.c_int]
     lib.vbmc_ctx_last_kernel_ms.argtypes = [vp, _dp, _dp]
     lib.vbmc_ctx_last_launch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.vbmc_ctx_last_variance.argtypes = [vp, C.POINTER(VarLaunchInfo)]
     lib.vbmc_gp_upload.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.POINTER(vp)]
     lib.vbmc_gp_free.argtypes = [vp, vp]
@@ -404,6 +414,14 @@ class Context:
         a, b = C.c_int(), C.c_int()
         self.check(self.lib.vbmc_ctx_last_launch(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_variance(self):
+        """dict of the fields of vbmc_var_launch_info: what the variance stage of the last pass with compute_var != 0 enqueued on
+        this context (test hook: VARSOLVE_* / VARGRAM_*; compute_var 0 where none ran)"""
+        info = VarLaunchInfo()
+        info.struct_size = C.sizeof(VarLaunchInfo)
+        self.check(self.lib.vbmc_ctx_last_variance(self.h, C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in VarLaunchInfo._fields_[1:]}
 
     def rng_dump(self, D, K, R, Ns, seed):
         """eps (R, K, Ns/2, D) that eps_mode 0 consumes for `seed` (test hook)."""

@@ -74,6 +74,15 @@ extern "C" vbmc_status vbmc_ctx_last_launch(vbmc_ctx* ctx, int* ent_form, int* l
   return VBMC_OK;
 }
 
+extern "C" vbmc_status vbmc_ctx_last_variance(vbmc_ctx* ctx, vbmc_var_launch_info* out) {
+  if (!ctx || !out) return VBMC_ERR_INVALID;
+  if (out->struct_size != sizeof(vbmc_var_launch_info))
+    return set_err(ctx, VBMC_ERR_INVALID, "vbmc_var_launch_info.struct_size %u != %zu (ABI mismatch)", out->struct_size, sizeof(vbmc_var_launch_info));
+  *out = ctx->last_var;
+  out->struct_size = sizeof(vbmc_var_launch_info);
+  return VBMC_OK;
+}
+
 extern "C" vbmc_status vbmc_device_alloc(vbmc_ctx* ctx, size_t bytes, void** dptr) {
   if (!ctx || !dptr) return VBMC_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

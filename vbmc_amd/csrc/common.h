@@ -54,6 +54,7 @@ struct vbmc_ctx {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double last_ent_ms = 0.0, last_lj_ms = 0.0;
   int last_ent_form = 0, last_lj_form = 0;     // the kernels of the last ELBO pass enqueued here (VBMC_ENTFORM_* / VBMC_LJFORM_*, vbmc_ctx_last_launch)
+  vbmc_var_launch_info last_var = {};          // what Pass::variance enqueued last on this context (vbmc_ctx_last_variance); compute_var 0: nothing yet
   std::vector<PoolBlk> pool;
   size_t pool_bytes = 0;
   // pipelined evaluations (vbmc_elbo_submit / vbmc_elbo_collect, abi_elbo_slots.hip): each of the two slots has its own pinned

@@ -628,6 +628,9 @@ inline vbmc_status Pass::entropy_bound() const {
 // variance of the expected log joint (gplogjoint.m:273-337,375-413)
 inline vbmc_status Pass::variance() const {
   const int K = dm.K, R = dm.R, S = dm.S, T = dm.T, N = dm.N;
+  vbmc_var_launch_info& rec = ctx->last_var;   // vbmc_ctx_last_variance: filled as the kernels are enqueued, from what each launch reads
+  rec = vbmc_var_launch_info{};
+  rec.compute_var = P.compute_var; rec.symm = P.any_nochol ? 1 : 0; rec.tri_gemm = P.tri_gemm ? 1 : 0; rec.vgrad = P.vgrad ? 1 : 0;
   DISPATCH_DT(P.dt, {
     hipLaunchKernelGGL((k_var_z<DT>), dim3(K, S, R), dim3(WAVE), 0, st, dm, P.d_vpd, gp->X, gp->gpc, P.d_delta2, P.d_Z);
     LAUNCH_CHECK(ctx, "k_var_z");
@@ -639,7 +642,9 @@ inline vbmc_status Pass::variance() const {
     LAUNCH_CHECK(ctx, "k_tri_gemm");
   } else {
     HIP_TRY(ctx, trsm_fwd_launch(st, N, K, S, R, gp->L, gp->d_finv, gp->d_lchol, P.d_Z));
+    trsm_form_for(N, &rec.fwd_solve, &rec.solve_width);
   }
+  rec.gram = P.compute_var == 1 ? VBMC_VARGRAM_MFMA : VBMC_VARGRAM_WAVE;
   if (P.compute_var == 1)   // full K x K matrix: Gram products on the matrix cores, one workgroup per (s, r)
     hipLaunchKernelGGL(k_var_gram_mfma, dim3(S, R), dim3(1024), 0, st, dm, P.d_vpd, gp->gpc, P.d_delta2, gp->d_sn2, gp->d_lchol, P.d_Z, P.d_X, P.d_J, P.tri_gemm ? 1 : 0);
   else
@@ -647,6 +652,7 @@ inline vbmc_status Pass::variance() const {
   LAUNCH_CHECK(ctx, "k_var_gram");
   if (P.vgrad) {
     HIP_TRY(ctx, trsm_bwd_launch(st, N, K, S, R, gp->L, gp->d_finv, gp->d_lchol, P.d_Z, P.d_X));
+    trsm_form_for(N, &rec.bwd_solve, &rec.solve_width);
     DISPATCH_DT(P.dt, {
       hipLaunchKernelGGL((k_vargrad<DT>), dim3(K, S, R), dim3(WAVE), 0, st, dm, P.d_vpd, gp->X, gp->gpc, P.d_delta2, gp->d_sn2, gp->d_lchol, P.d_X, P.d_vg);
       LAUNCH_CHECK(ctx, "k_vargrad");
@@ -662,12 +668,14 @@ inline vbmc_status Pass::variance() const {
     if (slds > 64 * 1024)
       HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_var_sample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
     hipLaunchKernelGGL(k_var_sample, dim3(S, R), dim3(VARSMP_THREADS), slds, st, va);
+    rec.sample_lds = (int32_t)slds;
     LAUNCH_CHECK(ctx, "k_var_sample");
   }
   const size_t vlds = VAR_FINAL_LDS(S, K, P.compute_grad ? T : 0);
   if (vlds > 64 * 1024)
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_var_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds));
   hipLaunchKernelGGL(k_var_final, dim3(R), dim3(VARFIN_THREADS), vlds, st, va);
+  rec.final_lds = (int32_t)vlds;
   LAUNCH_CHECK(ctx, "k_var_final");
   return VBMC_OK;
 }

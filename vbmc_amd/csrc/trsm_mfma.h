@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
+#include "../../include/vbmc_hip.h"   // VBMC_VARSOLVE_* (trsm_form_for)
+
 typedef double tmf4 __attribute__((ext_vector_type(4)));
 #define TR_VS 17  // LDS row stride of the 16-column right-hand-side slab and of the panel buffer (16 columns + 1 pad)
 // Narrow slabs for large N: the slab of a wave holds CW = 16, 8 or 4 right-hand sides (row stride CW + 1), the MFMAs still
@@ -576,11 +578,18 @@ __global__ void __launch_bounds__(64 * TRI2_W, 2) k_trsm2(int N, int K, int S, c
 }
 // the workgroup-per-slab solves when the row blocks fit the accumulator registers (N <= 1024)
 static inline bool trsm2_wanted(int N) { return TRSM_NBLK(N) <= TRI2_W * 8; }
+// its row-block slots per wave: k_trsm2<4> up to N = 512, k_trsm2<8> beyond
+static inline int trsm2_slots(int N) { return TRSM_NBLK(N) <= TRI2_W * 4 ? 4 : 8; }
+// what trsm_fwd_launch / trsm_bwd_launch run at N, for the reporting hooks: (VBMC_VARSOLVE_TRSM2, slots) or (VBMC_VARSOLVE_SLAB, CW)
+static inline void trsm_form_for(int N, int* kind, int* width) {
+  if (trsm2_wanted(N)) { *kind = VBMC_VARSOLVE_TRSM2; *width = trsm2_slots(N); }
+  else { *kind = VBMC_VARSOLVE_SLAB; *width = trsm_cw_for(N); }
+}
 template <bool BWD>
 static inline hipError_t trsm2_launch(hipStream_t st, int N, int K, int S, int R, const double* Lall, const double* Finv,
                                       const unsigned char* lchol, const double* Zin, double* Zout) {
   const dim3 grid((K + 15) / 16, S, R);
-  if (TRSM_NBLK(N) <= TRI2_W * 4) hipLaunchKernelGGL((k_trsm2<4, BWD>), grid, dim3(64 * TRI2_W), 0, st, N, K, S, Lall, Finv, lchol, Zin, Zout);
+  if (trsm2_slots(N) == 4) hipLaunchKernelGGL((k_trsm2<4, BWD>), grid, dim3(64 * TRI2_W), 0, st, N, K, S, Lall, Finv, lchol, Zin, Zout);
   else hipLaunchKernelGGL((k_trsm2<8, BWD>), grid, dim3(64 * TRI2_W), 0, st, N, K, S, Lall, Finv, lchol, Zin, Zout);
   return hipGetLastError();
 }
