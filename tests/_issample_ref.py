@@ -139,7 +139,7 @@ def sample(logp, x0, LB, UB, Nm, U, *, thin=1, burnin=None, spec=1, max_steps=20
                         else:
                             Rq = ts[q]
                     shr += ns
-            for j in range(H):                     # the record rule of ensemble_slice_sample (vbmc_amd/acq.py)
+            for j in range(H):                     # the record rule of ensemble_slice_sample (vbmc_amd/ensemble.py)
                 moved += 1
                 if moved > burnin and (moved - burnin) % thin == 0 and nrec < Nm:
                     out["Xa"][nrec, :, e] = x[e, mine[j]]

@@ -5,6 +5,8 @@ import re
 
 import pytest
 
+from tests import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -31,27 +33,57 @@ def test_library_exports_every_declared_symbol():
     assert len(syms) >= 10
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
-    ver = int(re.search(r"#define\s+VBMC_ABI_VERSION\s+(\d+)", hdr).group(1))
-    assert lib.vbmc_abi_version() == ver == _lib.ABI_VERSION
+    assert lib.vbmc_abi_version() == _abi.header_enums()["VBMC_ABI_VERSION"] == _lib.ABI_VERSION
 
 
 def test_variance_launch_record_matches_the_header():
     """vbmc_var_launch_info: the ctypes mirror has the header's fields in the header's order, and the enumerators the header's values"""
     from vbmc_amd import _lib
 
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct vbmc_var_launch_info \{(.*?)\} vbmc_var_launch_info;", hdr, flags=re.S).group(1), flags=re.S)
-    fields = [(t, n) for t, n in re.findall(r"\b(uint32_t|int32_t)\s+(\w+);", body)]
-    assert fields[0] == ("uint32_t", "struct_size") and all(t == "int32_t" for t, _ in fields[1:])
-    assert [n for _, n in fields] == [n for n, _ in _lib.VarLaunchInfo._fields_]
+    fields = _abi.header_fields()["vbmc_var_launch_info"]
+    assert fields[0] == ("struct_size", ctypes.c_uint32) and all(t is ctypes.c_int32 for _, t in fields[1:])
+    assert [n for n, _ in fields] == [n for n, _ in _lib.VarLaunchInfo._fields_]
     assert ctypes.sizeof(_lib.VarLaunchInfo) == 4 * len(fields)
-    enum = dict((k, int(v)) for k, v in re.findall(r"\b(VBMC_VAR(?:SOLVE|GRAM)_\w+)\s*=\s*(\d+)", hdr))
+    enum = {k: v for k, v in _abi.header_enums().items() if k.startswith(("VBMC_VARSOLVE_", "VBMC_VARGRAM_"))}
     assert enum == {"VBMC_VARSOLVE_TRSM2": _lib.VARSOLVE_TRSM2, "VBMC_VARSOLVE_SLAB": _lib.VARSOLVE_SLAB,
                     "VBMC_VARGRAM_WAVE": _lib.VARGRAM_WAVE, "VBMC_VARGRAM_MFMA": _lib.VARGRAM_MFMA}
     from tests import _var_cases as C
 
     assert (C.TRSM2, C.SLAB, C.WAVE, C.MFMA) == (_lib.VARSOLVE_TRSM2, _lib.VARSOLVE_SLAB, _lib.VARGRAM_WAVE, _lib.VARGRAM_MFMA)
+
+
+def test_every_mirror_has_the_headers_layout(tmp_path):
+    """Every struct of include/vbmc_hip.h has exactly one ctypes mirror in _lib (named in the mirror's docstring), with the header's field
+    names in the header's order and, field by field, the type the declaration stands for and the offset and size the host C compiler
+    gives the header's struct.  (A field of the wrong type and the right size passes a comparison of names and the library's
+    struct_size check, and then hands the library a wrong pointer.)  The enumerators and status codes _lib restates have the header's values."""
+    from vbmc_amd import _lib, acq
+
+    structs = _abi.header_fields()
+    sizes, layout = _abi.header_layout(tmp_path)
+    assert len(structs) >= 13 and set(sizes) == set(structs)
+    mirrors = {}
+    for cls in vars(_lib).values():
+        if isinstance(cls, type) and issubclass(cls, ctypes.Structure) and cls is not ctypes.Structure:
+            mirrors.setdefault((cls.__doc__ or cls.__name__).split()[0], []).append(cls)
+    assert sorted(mirrors) == sorted(structs), sorted(set(mirrors) ^ set(structs))       # a mirror each, none beside them
+    for s, (cls, *more) in mirrors.items():
+        assert not more, (s, cls, more)
+        assert [n for n, _ in cls._fields_] == [n for n, _ in structs[s]], (s, cls._fields_)
+        for (n, t), (_, want) in zip(cls._fields_, structs[s]):
+            assert t is want, (s, n, t, want)                                            # the header's type, not merely its size
+            assert (getattr(cls, n).offset, getattr(cls, n).size) == layout["%s.%s" % (s, n)], (s, n)
+        assert ctypes.sizeof(cls) == sizes[s], (s, ctypes.sizeof(cls), sizes[s])
+    enums = _abi.header_enums()
+    restated = {k: v for k, v in enums.items() if re.match(r"VBMC_(ENTFORM|LJFORM|VARSOLVE|VARGRAM)_|VBMC_(OK|ERR_\w+)$", k)}
+    assert len(restated) == 4 + 6 + 2 + 2 + 6, sorted(restated)
+    for k, v in restated.items():
+        assert getattr(_lib, k if k.startswith(("VBMC_OK", "VBMC_ERR")) else k[5:]) == v, k
+        if k.startswith(("VBMC_OK", "VBMC_ERR")):
+            assert _lib._STATUS_NAMES[v] == k[5:].replace("ERR_", ""), k
+    assert enums["VBMC_ABI_VERSION"] == _lib.ABI_VERSION
+    assert {v: k for k, v in enums.items() if k.startswith("VBMC_SEARCH_STOP_")} == \
+        {i: "VBMC_SEARCH_STOP_" + n.upper() for i, n in acq.SEARCH_STOP.items()}
 
 
 def test_no_cpu_fallback_without_gpu():
@@ -98,23 +130,15 @@ def test_limits_are_the_librarys_and_the_shims_ask_for_them():
     device (K = 400 of 512, N = 4500 of 9696) -- and the MATLAB side takes them from there: no shim restates a limit."""
     import ctypes as C
     import glob
-    import re
 
     from vbmc_amd import _lib
 
-    class Lim(C.Structure):
-        _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in ("max_D", "max_K", "max_N", "max_Na", "max_T_vargrad", "delta_ok", "meanfun_mask")]
-
     lib = _lib.load()
-    lib.vbmc_get_limits.argtypes = [C.POINTER(Lim)]
-    lib.vbmc_get_limits.restype = C.c_int
-    lim = Lim()
-    lim.struct_size = C.sizeof(Lim)
+    lim = _lib.new_args(_lib.Limits)
     assert lib.vbmc_get_limits(C.byref(lim)) == 0
     assert (lim.max_D, lim.max_K, lim.max_N, lim.max_Na, lim.delta_ok, lim.meanfun_mask) == (32, 512, 9696, 256, 1, 0b10011)
     assert 3800 <= lim.max_T_vargrad <= 4100          # ("about 4000": five T-vectors beside the reduction scratch in 160 KB)
-    bad = Lim()
-    bad.struct_size = 4
+    bad = _lib.Limits(struct_size=4)
     assert lib.vbmc_get_limits(C.byref(bad)) != 0
     # the device tests reach into the upper half of each range
     txt = open(os.path.join(ROOT, "tests", "test_gpu_limits.py")).read()

@@ -6,38 +6,23 @@ exports vbmc_gp_surrogate_sample and vbmc_gp_surrogate_sample_rng_dump with ctyp
 the header; a NULL args pointer is refused without a device."""
 import os
 import re
-import subprocess
 
-from tests.test_vptools_build import _struct_names
+from tests import _abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROOT, CSRC = _abi.ROOT, _abi.CSRC
 PLAIN = ("k_gs_target", "k_gs_start", "k_gs_sum", "k_gs_thresh")
 DTS = (4, 8, 12, 16, 24, 32)
 
 
 def test_surrogate_kernels_use_no_scratch(tmp_path):
-    src = os.path.join(str(tmp_path), "gs.hip")
-    with open(src, "w") as f:
-        f.write('#include "%s/gp_surrogate_kernels.h"\n' % CSRC)
-        for qs in range(1, 9):
-            f.write("template __global__ void k_gs_pred<%d>(IsPredArgs);\n" % qs)
-        for dt in DTS:
-            f.write("template __global__ void k_gs_finish<%d>(GsFinishArgs);\n" % dt)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "gs.o")], capture_output=True, text=True, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(os.path.join(str(tmp_path), "gs-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    inst = ["template __global__ void k_gs_pred<%d>(IsPredArgs);" % qs for qs in range(1, 9)]
+    inst += ["template __global__ void k_gs_finish<%d>(GsFinishArgs);" % dt for dt in DTS]
+    kernels, asm = _abi.kernel_meta("gp_surrogate_kernels.h", inst, r"k_gs_", tmp_path)
     seen = set()
-    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_gs_\S*)\n(.*?)\.wavefront_size", asm, re.S):
-        name, rest, meta = m.group(2)[: int(m.group(1))], m.group(2)[int(m.group(1)):], m.group(3)
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
-        priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        print(name, rest[:8], "spill", spill, "private", priv)
-        assert spill == 0 and priv == 0, (name, rest, spill, priv)
-        t = re.match(r"ILi(\d+)E", rest)
-        seen.add(name + (t.group(1) if t else ""))
+    for k in kernels:
+        print(k["name"], k["targs"], "spill", k["vgpr_spill_count"], "private", k["private_segment_fixed_size"])
+        assert _abi.no_scratch(k), k
+        seen.add(k["name"] + "".join(str(t) for t in k["targs"][:1]))
     want = set(PLAIN) | {"k_gs_pred%d" % q for q in range(1, 9)} | {"k_gs_finish%d" % d for d in DTS}
     assert seen == want, seen ^ want
     names = set(re.findall(r"__global__[^\n]*\b(k_gs_\w+)\(", open(os.path.join(CSRC, "gp_surrogate_kernels.h")).read()))
@@ -63,7 +48,7 @@ def test_library_exports_the_surrogate_sampler():
     from vbmc_amd import _lib, gplite, vptools
 
     lib = _lib.load()
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
+    hdr = _abi.header_text()
     assert hasattr(lib, "vbmc_gp_surrogate_sample") and hasattr(lib, "vbmc_gp_surrogate_sample_rng_dump")
     assert hasattr(gplite, "gplite_sample") and hasattr(gplite, "gplite_sample_device") and hasattr(vptools, "gpsample_vbmc")
     proto = re.search(r"vbmc_status vbmc_gp_surrogate_sample\((.*?)\);", hdr, re.S).group(1)
@@ -71,20 +56,9 @@ def test_library_exports_the_surrogate_sampler():
     assert lib.vbmc_gp_surrogate_sample.argtypes[2] == C.POINTER(_lib.VpDesc) and lib.vbmc_gp_surrogate_sample.argtypes[3] == C.POINTER(_lib.GsArgs)
     assert re.search(r"vbmc_status vbmc_gp_surrogate_sample_rng_dump\(uint64_t seed, int E, int H, int M, double\* U\);", hdr)
     assert len(lib.vbmc_gp_surrogate_sample_rng_dump.argtypes) == 5
-    assert _struct_names(hdr, "vbmc_gs_args") == [f[0] for f in _lib.GsArgs._fields_]
-    # the field types, in the header's order -> the same layout on both sides
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct vbmc_gs_args \{(.*?)\} vbmc_gs_args;", hdr, re.S).group(1), flags=re.S)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double}
-    want = []
-    for decl in (d.strip() for d in body.split(";")):
-        if decl:
-            base = ctype[re.sub(r"^const\s+", "", decl).split()[0].rstrip("*")]
-            want += [C.POINTER(base) if "*" in decl else base] * len(decl.split(","))
-    assert want == [f[1] for f in _lib.GsArgs._fields_]
     assert lib.vbmc_abi_version() == 8 and int(re.search(r"#define VBMC_ABI_VERSION (\d+)", hdr).group(1)) == 8
     # a null context is refused first, a NULL args pointer and a wrong struct_size before anything is read (no device needed)
-    a = _lib.GsArgs()
-    a.struct_size = C.sizeof(_lib.GsArgs)
+    a = _lib.new_args(_lib.GsArgs)
     assert lib.vbmc_gp_surrogate_sample(None, None, None, C.byref(a)) == _lib.VBMC_ERR_INVALID
     assert lib.vbmc_gp_surrogate_sample(None, None, None, None) == _lib.VBMC_ERR_INVALID
     # the dump is a pure host function: the block of the importance sampler's generator with E in the place of S

@@ -195,8 +195,7 @@ def test_errors_leave_the_context_usable(va):
     # the library checks the layout and the noise estimate's arrays itself
     eng = va.default_engine()
     dgp = _device_gp_with_noise(eng, c["gp"])
-    a = _lib.GsArgs()
-    a.struct_size = C.sizeof(_lib.GsArgs)
+    a = _lib.new_args(_lib.GsArgs)
     a.D, a.S, a.E, a.Ns, a.thin, a.burnin, a.VarThresh = D, 1, 1, 8, 1, -1, np.inf
     keep = (f64(np.transpose(c["x0"], (1, 2, 0))), f64(c["LB"]), f64(c["UB"]), f64(np.ones(c["N"])))
     a.x0, a.LB, a.UB, a.W = ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), W

@@ -164,13 +164,12 @@ def test_errors_leave_the_context_usable(va):
     # a GP handle without vbmc_gp_set_noise
     import ctypes as C
 
-    from vbmc_amd._lib import IsSampleArgs
+    from vbmc_amd._lib import IsSampleArgs, new_args
     from vbmc_amd.acq import f64, ptr
 
     eng = va.default_engine()
     bare = eng.device_gp(dict(c["gp"], post=list(c["gp"]["post"])), need_L=True)      # a handle of its own, its noise model not set
-    a = IsSampleArgs()
-    a.struct_size = C.sizeof(IsSampleArgs)
+    a = new_args(IsSampleArgs)
     a.W, a.D, a.S, a.Nm, a.thin, a.burnin = W, D, S, c["Nm"], 1, -1
     keep = (f64(np.transpose(c["x0"], (1, 2, 0))), f64(c["LB"]), f64(c["UB"]))
     a.x0, a.LB, a.UB = ptr(keep[0]), ptr(keep[1]), ptr(keep[2])

@@ -167,7 +167,7 @@ def test_step_one_alone(va):
 def test_errors_leave_the_context_usable(va):
     import ctypes as C
 
-    from vbmc_amd._lib import IsSetupArgs
+    from vbmc_amd._lib import IsSetupArgs, new_args
     from vbmc_amd.acq import f64, ptr
 
     c, _ = T.run_case("A")
@@ -208,8 +208,7 @@ def test_errors_leave_the_context_usable(va):
     # a GP handle without vbmc_gp_set_noise, and a layout that is not the GP's
     eng = va.default_engine()
     bare = eng.device_gp(dict(c["gp"], post=list(c["gp"]["post"])), need_L=True)
-    a = IsSetupArgs()
-    a.struct_size = C.sizeof(IsSetupArgs)
+    a = new_args(IsSetupArgs)
     a.D, a.S, a.K, a.Nvp, a.Nbox, a.W, a.Nm, a.thin, a.burnin = D, S, K, c["Nvp"], c["Nbox"], W, c["Nm"], 1, -1
     keep = [f64(np.asarray(c["vp"][k], dtype=np.float64)) for k in ("mu", "sigma", "lambda", "w")]
     a.vp_mu, a.vp_sigma, a.vp_lambda, a.vp_w = (ptr(k) for k in keep)

@@ -4,30 +4,16 @@ compiler's own resource-usage metadata -- and call no device-library transcenden
 library exports vbmc_vp_mtv with a ctypes declaration and an argument structure that follow the header."""
 import os
 import re
-import subprocess
 
-from tests.test_vptools_build import _struct_names
+from tests import _abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROOT, CSRC = _abi.ROOT, _abi.CSRC
 KERNELS = ("k_mtv_mesh", "k_mtv_bin", "k_mtv_init", "k_mtv_dct", "k_mtv_root", "k_mtv_integral")
 
 
 def test_mtv_kernels_use_no_scratch(tmp_path):
-    src = os.path.join(str(tmp_path), "mtv.hip")
-    with open(src, "w") as f:
-        f.write('#include "%s/mtv_kernels.h"\n' % CSRC)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "mtv.o")], capture_output=True, text=True, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(os.path.join(str(tmp_path), "mtv-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    seen = {}
-    for rec in asm.split("  - .agpr_count:")[1:]:                                                  # one record per kernel
-        name = re.search(r"\n    \.name:\s+(\S+)", rec).group(1)
-        if "k_mtv_" in name:
-            seen[name] = tuple(int(re.search(r"\.%s:\s+(\d+)" % k, rec).group(1))
-                               for k in ("vgpr_spill_count", "private_segment_fixed_size", "max_flat_workgroup_size", "wavefront_size"))
+    kernels, asm = _abi.kernel_meta("mtv_kernels.h", (), r"k_mtv_", tmp_path)
+    seen = {k["mangled"]: (k["vgpr_spill_count"], k["private_segment_fixed_size"], k["max_flat_workgroup_size"], k["wavefront_size"]) for k in kernels}
     print(seen)
     names = set(re.findall(r"__global__[^\n]*\b(k_mtv_\w+)\(", open(os.path.join(CSRC, "mtv_kernels.h")).read()))
     assert names == set(KERNELS), names                                                           # every kernel of the header
@@ -56,29 +42,15 @@ def test_library_exports_vbmc_vp_mtv():
     from vbmc_amd import _lib, vptools
 
     lib = _lib.load()
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
+    hdr = _abi.header_text()
     assert hasattr(lib, "vbmc_vp_mtv") and hasattr(vptools, "vbmc_mtv")
     proto = re.search(r"vbmc_status vbmc_vp_mtv\((.*?)\);", hdr, re.S).group(1)
     assert len(proto.split(",")) == len(lib.vbmc_vp_mtv.argtypes) == 4, proto
     assert lib.vbmc_vp_mtv.argtypes[3] == C.POINTER(_lib.MtvArgs)
-    assert _struct_names(hdr, "vbmc_mtv_args") == [f[0] for f in _lib.MtvArgs._fields_]
-    # the field types: every pointer 8 bytes, Ns and seed 64 bits, in the header's order -> the same layout on both sides
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct vbmc_mtv_args \{(.*?)\} vbmc_mtv_args;", hdr, re.S).group(1), flags=re.S)
-    ctype = {"uint32_t": C.c_uint32, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
-    want = []
-    for decl in (d.strip() for d in body.split(";")):
-        if decl:
-            t = re.sub(r"^const\s+", "", decl).split()[0].rstrip("*")
-            base = C.c_double if t == "double" else ctype[t]
-            want.append(C.POINTER(base) if "*" in decl else base)
-    assert want == [f[1] for f in _lib.MtvArgs._fields_]
     assert lib.vbmc_abi_version() == 8 and int(re.search(r"#define VBMC_ABI_VERSION (\d+)", hdr).group(1)) == 8
     # a null context is refused first, a wrong struct_size before anything is read (no device needed)
-    d = _lib.VpDesc()
-    d.struct_size = C.sizeof(_lib.VpDesc)
-    a = _lib.MtvArgs()
-    a.struct_size = C.sizeof(_lib.MtvArgs)
+    d, a = _lib.new_args(_lib.VpDesc), _lib.new_args(_lib.MtvArgs)
     assert lib.vbmc_vp_mtv(None, C.byref(d), C.byref(d), C.byref(a)) == _lib.VBMC_ERR_INVALID
-    a.struct_size = C.sizeof(_lib.MtvArgs) + 8
+    a.struct_size += 8
     assert lib.vbmc_vp_mtv(None, C.byref(d), C.byref(d), C.byref(a)) == _lib.VBMC_ERR_INVALID
     assert lib.vbmc_vp_mtv(None, C.byref(d), C.byref(d), None) == _lib.VBMC_ERR_INVALID

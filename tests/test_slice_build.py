@@ -4,30 +4,19 @@ the chain's scalars in registers across its whole body; a spill there would put 
 memory)."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests import _abi
+
+CSRC = _abi.CSRC
 KERNELS = ("k_slice_propose", "k_gpobj_retry", "k_slice_decide")
 
 
 def test_slice_kernels_do_not_spill(tmp_path):
-    src = os.path.join(str(tmp_path), "sl.hip")
-    with open(src, "w") as f:
-        f.write('#include "%s/slice_kernels.h"\n' % CSRC)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "sl.o")], capture_output=True, text=True, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(os.path.join(str(tmp_path), "sl-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    kernels, _ = _abi.kernel_meta("slice_kernels.h", (), r"k_(slice|gpobj)_", tmp_path)
     seen = set()
-    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_(?:slice|gpobj)_\S*)\n(.*?)\.wavefront_size", asm, re.S):
-        name, meta = m.group(2)[: int(m.group(1))], m.group(3)
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
-        sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", meta).group(1))
-        priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        assert spill == 0 and sspill == 0 and priv == 0, (name, spill, sspill, priv)
-        seen.add(name)
+    for k in kernels:
+        assert _abi.no_scratch(k) and k["sgpr_spill_count"] == 0, k
+        seen.add(k["name"])
     assert seen == set(KERNELS), seen
 
 

@@ -4,18 +4,16 @@ fill stage's bookkeeping, the ABI plumbing of vbmc_gp_train_optimize and a cross
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 from scipy.optimize import minimize
 
+from tests import _abi
 from tests import _trainopt_ref as T
 from tests._trainopt_cases import PARITY_CASES, WIDE_CASES, gp_case, parity_case, parity_sizes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROOT, CSRC = _abi.ROOT, _abi.CSRC
 
 
 # ---- the optimiser ----------------------------------------------------------------------------------------------------------
@@ -230,43 +228,24 @@ def test_sort_starts_low_noise_pick_and_widths():
 def test_symbol_in_header_library_and_ctypes():
     from vbmc_amd import _lib
 
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
+    hdr = _abi.header_text()
     assert re.search(r"vbmc_status\s+vbmc_gp_train_optimize\s*\(\s*vbmc_ctx\s*\*\s*ctx\s*,\s*const\s+vbmc_gptrain_args\s*\*", hdr)
     assert int(re.search(r"#define\s+VBMC_ABI_VERSION\s+(\d+)", hdr).group(1)) == 8 == _lib.ABI_VERSION
     lib = _lib.load()
     assert lib.vbmc_gp_train_optimize.argtypes[1]._type_ is _lib.GpTrainArgs
-    # every field of the C struct, in order, in the ctypes mirror
-    body = re.search(r"typedef struct vbmc_gptrain_args \{(.*?)\} vbmc_gptrain_args;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        first, *rest = decl.split(",")
-        names.append(re.sub(r"\[\d+\]", "", first.split()[-1].lstrip("*")))
-        names += [r.strip().lstrip("*") for r in rest]
-    assert names == [n for n, _ in _lib.GpTrainArgs._fields_], names
+    # (the mirror's layout against the header's: tests/test_abi_symbols.py)
     # struct_size is checked before anything else is read (no device needed: a null context is refused first, a wrong size next)
-    a = _lib.GpTrainArgs()
-    a.struct_size = C.sizeof(_lib.GpTrainArgs) - 8
+    a = _lib.new_args(_lib.GpTrainArgs)
+    a.struct_size -= 8
     assert lib.vbmc_gp_train_optimize(None, C.byref(a)) == _lib.VBMC_ERR_INVALID
     src = open(os.path.join(CSRC, "abi_gp_train.hip")).read()
     assert "args->struct_size != sizeof(vbmc_gptrain_args)" in src
 
 
 def test_trainopt_kernels_compile_for_gfx950_without_scratch(tmp_path):
-    src = os.path.join(str(tmp_path), "topt.hip")
-    with open(src, "w") as f:
-        f.write('#include "%s/trainopt_kernels.h"\n' % CSRC)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-I" + os.path.join(ROOT, "include"),
-                        "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "topt.o")], capture_output=True, text=True, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(os.path.join(str(tmp_path), "topt-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    kernels, _ = _abi.kernel_meta("trainopt_kernels.h", (), r"k_(topt|gpobj)_", tmp_path, flags=("-Wno-pass-failed",))
     seen = set()
-    for m in re.finditer(r"\.name:\s+_Z(\d+)(k_(?:topt|gpobj)_\w+)\n(.*?)\.wavefront_size", asm, re.S):
-        meta = m.group(3)
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) == 0, m.group(2)
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0, m.group(2)
-        seen.add(m.group(2)[:int(m.group(1))])
+    for k in kernels:
+        assert _abi.no_scratch(k), k
+        seen.add(k["name"])
     assert seen == {"k_topt_propose", "k_gpobj_retry", "k_topt_fill_collect", "k_topt_fill_sort", "k_topt_decide", "k_topt_close"}, seen

@@ -4,33 +4,22 @@ compiler's own resource-usage metadata, for every instantiation of k_vp_pdf, k_v
 part of the build, and the library exports the five entry points with ctypes declarations that follow the header."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vbmc_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests import _abi
+
+ROOT, CSRC = _abi.ROOT, _abi.CSRC
 KERNELS = ("k_vp_pdf", "k_vp_draw", "k_vp_moments", "k_vp_kldiv")
 ENTRY_POINTS = {"vbmc_vp_pdf": 10, "vbmc_vp_rnd": 10, "vbmc_vp_moments": 7, "vbmc_vp_kldiv": 10, "vbmc_vp_rnd_rng_dump": 8}
 
 
 def test_vp_tools_kernels_use_no_scratch(tmp_path):
-    src = os.path.join(str(tmp_path), "vpt.hip")
-    with open(src, "w") as f:        # every instantiation the dispatch of abi_vp_tools.hip names
-        f.write('#include "%s/vp_tools_kernels.h"\n' % CSRC)
-        for dt in (4, 8, 12, 16, 24, 32):
-            f.write("template __global__ void k_vp_pdf<%d, true>(VptPdfArgs);\ntemplate __global__ void k_vp_pdf<%d, false>(VptPdfArgs);\n" % (dt, dt))
-            f.write("template __global__ void k_vp_draw<%d>(VptDrawArgs);\ntemplate __global__ void k_vp_moments<%d>(VptMomArgs);\n" % (dt, dt))
-            f.write("template __global__ void k_vp_kldiv<%d>(VptKlArgs);\n" % dt)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "--save-temps=obj", "-c", src, "-o", os.path.join(str(tmp_path), "vpt.o")], capture_output=True, text=True, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(os.path.join(str(tmp_path), "vpt-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    seen = {}
-    for m in re.finditer(r"\.name:\s+(_Z\d+k_vp_\S*)\n(.*?)\.wavefront_size", asm, re.S):
-        meta = m.group(2)
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
-        priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        seen[m.group(1)] = (spill, priv)
+    inst = []                        # every instantiation the dispatch of abi_vp_tools.hip names
+    for dt in (4, 8, 12, 16, 24, 32):
+        inst += ["template __global__ void k_vp_pdf<%d, true>(VptPdfArgs);" % dt, "template __global__ void k_vp_pdf<%d, false>(VptPdfArgs);" % dt,
+                 "template __global__ void k_vp_draw<%d>(VptDrawArgs);" % dt, "template __global__ void k_vp_moments<%d>(VptMomArgs);" % dt,
+                 "template __global__ void k_vp_kldiv<%d>(VptKlArgs);" % dt]
+    kernels, asm = _abi.kernel_meta("vp_tools_kernels.h", inst, r"k_vp_", tmp_path)
+    seen = {k["mangled"]: (k["vgpr_spill_count"], k["private_segment_fixed_size"]) for k in kernels}
     print(seen)
     for k in KERNELS:
         inst = [n for n in seen if re.match(r"_Z\d+%s(I|P|$)" % k, n)]
@@ -48,19 +37,6 @@ def test_the_translation_unit_is_part_of_the_build():
     assert unit.index("abi_is_setup.hip") < unit.index("abi_vp_tools.hip")
 
 
-def _struct_names(hdr, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            first, *rest = decl.split(",")
-            names.append(re.sub(r"[\s*]", "", first.split()[-1]))
-            names += [re.sub(r"[\s*]", "", t) for t in rest]
-    return names
-
-
 def test_library_exports_the_vp_tools():
     import ctypes as C
 
@@ -70,17 +46,16 @@ def test_library_exports_the_vp_tools():
     from vbmc_amd import _lib
 
     lib = _lib.load()
-    hdr = open(os.path.join(ROOT, "include", "vbmc_hip.h")).read()
+    hdr = _abi.header_text()
     for name, nargs in ENTRY_POINTS.items():
         assert hasattr(lib, name), name
         assert len(getattr(lib, name).argtypes) == nargs, name
         proto = re.search(r"vbmc_status %s\((.*?)\);" % name, hdr, re.S).group(1)
         assert len(proto.split(",")) == nargs, (name, proto)
-    assert _struct_names(hdr, "vbmc_vp_desc") == [f[0] for f in _lib.VpDesc._fields_]
     assert lib.vbmc_abi_version() == 8
     # a wrong struct_size is refused before anything is read; a null context is refused first (no device needed)
-    d = _lib.VpDesc()
-    d.struct_size = C.sizeof(_lib.VpDesc) + 8
+    d = _lib.new_args(_lib.VpDesc)
+    d.struct_size += 8
     y = (C.c_double * 2)()
     assert lib.vbmc_vp_pdf(None, C.byref(d), 1, y, 1, 1, 0, float("inf"), y, None) == _lib.VBMC_ERR_INVALID
     assert lib.vbmc_vp_rnd(None, C.byref(d), 1, 1, 0, float("inf"), 0, None, y, None) == _lib.VBMC_ERR_INVALID

@@ -14,9 +14,11 @@ from .elbo import (Engine, PreparedObjective, default_engine, entlb_vbmc, entmc_
 from .gplite import (fminfill_design, gp_surrogate_sample_rng_dump, gplite_hypprior, gplite_nlZ, gplite_post, gplite_post_rank1, gplite_pred,  # noqa: F401,E402
                      gplite_quad, gplite_sample, gplite_sample_device, gplite_train, gplite_train_optimize, gplite_train_sample, slice_rng_dump,
                      slicesamplebnd_gp, sq_dist)
-from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, active_search, activeimportancesampling_vbmc,  # noqa: F401,E402
-                  ensemble_slice_sample, importance_sample_device, importance_sample_rng_dump, vbmc_moments, vbmc_rnd)
-from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
-                       vpsieve_vbmc)
+from .ensemble import ensemble_slice_sample  # noqa: F401,E402
+from .mixture import vbmc_moments, vbmc_rnd  # noqa: F401,E402  (the HOST forms; the device forms are vptools.vbmc_rnd / vbmc_moments)
 from . import vptools  # noqa: F401,E402
 from .vptools import gpsample_vbmc, vbmc_diagnostics, vp_rnd_rng_dump, warpvars  # noqa: F401,E402
+from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
+                       vpsieve_vbmc)
+from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, active_search, activeimportancesampling_vbmc,  # noqa: F401,E402
+                  importance_sample_device, importance_sample_rng_dump)

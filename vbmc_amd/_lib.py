@@ -40,7 +40,19 @@ class VbmcUnsupported(VbmcHipError):
 _dp = C.POINTER(C.c_double)
 
 
+def new_args(Struct):
+    """An instance of one of the mirrors below with ``struct_size`` set, as every entry point that takes one checks first."""
+    return Struct(struct_size=C.sizeof(Struct))
+
+
+class Limits(C.Structure):
+    """vbmc_limits (include/vbmc_hip.h)"""
+    _fields_ = [("struct_size", C.c_uint32)] + [(n, C.c_int32) for n in (
+        "max_D", "max_K", "max_N", "max_Na", "max_T_vargrad", "delta_ok", "meanfun_mask")]
+
+
 class ElboArgs(C.Structure):
+    """vbmc_elbo_args (include/vbmc_hip.h)"""
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("D", C.c_int32), ("K", C.c_int32), ("R", C.c_int32),
@@ -49,7 +61,7 @@ class ElboArgs(C.Structure):
         ("vp_mu", _dp), ("vp_sigma", _dp), ("vp_lambda", _dp), ("vp_w", _dp), ("vp_delta", _dp),
         ("Ns", C.c_int32),
         ("eps_mode", C.c_int32),
-        ("eps", C.c_void_p),
+        ("eps", _dp),
         ("eps_shared", C.c_int32),
         ("seed", C.c_uint64),
         ("compute_grad", C.c_int32), ("compute_var", C.c_int32), ("separate_K", C.c_int32),
@@ -244,6 +256,16 @@ class VarLaunchInfo(C.Structure):
 VARSOLVE_TRSM2, VARSOLVE_SLAB = 1, 2     # VBMC_VARSOLVE_*
 VARGRAM_WAVE, VARGRAM_MFMA = 1, 2        # VBMC_VARGRAM_*
 
+# the host-only generator dumps (no device, no context): the argument types behind the leading uint64 seed
+_HOST_DUMPS = {
+    "vbmc_slice_rng_dump": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp],
+    "vbmc_acq_search_rng_dump": [C.c_int, C.c_int, C.c_int, _dp],
+    "vbmc_acq_is_sample_rng_dump": [C.c_int, C.c_int, C.c_int, _dp],
+    "vbmc_acq_is_setup_rng_dump": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp],
+    "vbmc_vp_rnd_rng_dump": [C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)],
+    "vbmc_gp_surrogate_sample_rng_dump": [C.c_int, C.c_int, C.c_int, _dp],
+}
+
 _lib = None
 
 
@@ -260,6 +282,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     vp = C.c_void_p
     lib.vbmc_abi_version.restype = C.c_int
+    lib.vbmc_get_limits.argtypes = [C.POINTER(Limits)]
     lib.vbmc_ctx_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
     lib.vbmc_ctx_destroy.argtypes = [vp]
     lib.vbmc_ctx_destroy.restype = None
@@ -311,14 +334,10 @@ def load():
     lib.vbmc_gp_nlz.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]
     lib.vbmc_gp_slice_sample.argtypes = [vp, C.POINTER(SliceArgs)]
     lib.vbmc_gp_train_optimize.argtypes = [vp, C.POINTER(GpTrainArgs)]
-    lib.vbmc_slice_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), _dp]
     lib.vbmc_acq_search.argtypes = [vp, vp, C.POINTER(AcqSearchArgs)]
     lib.vbmc_acq_search_iqr.argtypes = [vp, vp, vp, C.POINTER(AcqSearchArgs)]
-    lib.vbmc_acq_search_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_acq_is_sample.argtypes = [vp, vp, C.POINTER(IsSampleArgs)]
-    lib.vbmc_acq_is_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_acq_is_setup.argtypes = [vp, vp, C.POINTER(IsSetupArgs)]
-    lib.vbmc_acq_is_setup_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     vpd = C.POINTER(VpDesc)
     lib.vbmc_vp_pdf.argtypes = [vp, vpd, C.c_int64, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp]
     lib.vbmc_vp_rnd.argtypes = [vp, vpd, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, _dp, _dp, C.POINTER(C.c_int32)]
@@ -327,9 +346,7 @@ def load():
     lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
     lib.vbmc_vp_diagnostics.argtypes = [vp, C.c_int32, C.POINTER(vpd), C.POINTER(DiagArgs)]
     lib.vbmc_test_dct.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
-    lib.vbmc_vp_rnd_rng_dump.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int64)]
     lib.vbmc_gp_surrogate_sample.argtypes = [vp, vp, vpd, C.POINTER(GsArgs)]
-    lib.vbmc_gp_surrogate_sample_rng_dump.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
     lib.vbmc_test_exp.argtypes =[vp, C.c_int, C.c_int, _dp, _dp]
     lib.vbmc_sq_dist.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     # the communicator inside the library (abi_comm.hip)
@@ -355,16 +372,12 @@ def load():
     lib.vbmc_elbo_batch_multi.argtypes = [vp, vpp, C.POINTER(ElboArgs)]
     lib.vbmc_elbo_multi_submit.argtypes = [vp, vpp, C.POINTER(ElboArgs), C.c_int]
     lib.vbmc_elbo_multi_collect.argtypes = [vp, C.POINTER(ElboArgs), C.c_int]
-    for name in DECLARED_OPTIONAL:
-        if hasattr(lib, name):
-            pass
+    for name, types in _HOST_DUMPS.items():
+        getattr(lib, name).argtypes = [C.c_uint64] + types
     if lib.vbmc_abi_version() != ABI_VERSION:
         raise ImportError("libvbmc_hip.so ABI version mismatch")
     _lib = lib
     return lib
-
-
-DECLARED_OPTIONAL = ()
 
 
 def f64(a, order="F"):
@@ -374,6 +387,16 @@ def f64(a, order="F"):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def host_dump(name, seed, *args, hip_error=None):
+    """Call the host-only dump ``name`` of _HOST_DUMPS with ``seed`` and ``args`` (integers, and the NumPy arrays it fills) and raise on
+    a non-zero status: ValueError, or VbmcHipError with the message ``hip_error`` where one is given."""
+    fn = getattr(load(), name)
+    assert len(args) == len(_HOST_DUMPS[name]), name
+    st = fn(C.c_uint64(int(seed)), *[a.ctypes.data_as(t) if isinstance(a, np.ndarray) else int(a) for a, t in zip(args, _HOST_DUMPS[name])])
+    if st != VBMC_OK:
+        raise VbmcHipError(st, hip_error) if hip_error else ValueError("%s: bad arguments" % name)
 
 
 class Context:
@@ -418,8 +441,7 @@ class Context:
     def last_variance(self):
         """dict of the fields of vbmc_var_launch_info: what the variance stage of the last pass with compute_var != 0 enqueued on
         this context (test hook: VARSOLVE_* / VARGRAM_*; compute_var 0 where none ran)"""
-        info = VarLaunchInfo()
-        info.struct_size = C.sizeof(VarLaunchInfo)
+        info = new_args(VarLaunchInfo)
         self.check(self.lib.vbmc_ctx_last_variance(self.h, C.byref(info)))
         return {n: int(getattr(info, n)) for n, _ in VarLaunchInfo._fields_[1:]}
 

@@ -9,11 +9,17 @@ caller's: pass the boolean mask of out-of-bounds points as ``outside``.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
-from ._lib import VbmcUnsupported, f64, ptr
+from . import _pack
+from ._lib import AcqSearchArgs, IsSampleArgs, IsSetupArgs, VbmcUnsupported, f64, host_dump, new_args, ptr
 from .elbo import default_engine
-from .gplite import _device_gp_with_noise
+from .ensemble import ensemble_slice_sample
+from .gplite import _device_gp_with_noise, gplite_pred_device
+from .mixture import vbmc_lnpdf as _vbmc_lnpdf, vbmc_moments, vbmc_rnd
+from .optimize import gethpd_vbmc
 
 ACQ_IDS = {"acqf_vbmc": 0, "acqflog_vbmc": 1, "acqus_vbmc": 2, "acqfsn2_vbmc": 3, "acqviqr_vbmc": 10, "acqimiqr_vbmc": 11}
 
@@ -30,8 +36,6 @@ class ImportanceState:
         return self
 
     def __init__(self, engine, dgp, ais):
-        import ctypes as C
-
         self.ctx = engine.ctx
         Xa = np.asarray(ais["Xa"], dtype=np.float64)
         per_s = Xa.ndim == 3
@@ -133,15 +137,11 @@ def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpo
     Nstar, D = Xs.shape
     K = int(vp["K"])
     dgp = _device_gp_with_noise(engine, gp)
-    mu = f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K))
-    sigma = f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K))
-    lam = f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D))
-    w = f64(np.asarray(vp["w"], dtype=np.float64).reshape(K))
+    mu, sigma, lam, w = _pack.mixture(vp, D=D)
     gl = xr = sn = None
+    if acq_id == 3 or acq_id >= 10:
+        gl, xr, sn = _pack.nn_noise(None, optimState["gplengthscale"], gp["X_rescaled"], gp["sn2new"], dgp.N, D)
     if acq_id >= 10:
-        gl = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
-        xr = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
-        sn = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
         ist = _importance_state(engine, dgp, optimState["ActiveImportanceSampling"])
         acq = np.zeros(Nstar)
         fbar = np.zeros(Nstar)
@@ -154,10 +154,6 @@ def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpo
         if transpose_flag:
             acq = acq.reshape(1, -1)
         return (acq, fbar, vtot) if nargout >= 3 else acq
-    if acq_id == 3:
-        gl = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
-        xr = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
-        sn = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
     acq = np.zeros(Nstar)
     fbar = np.zeros(Nstar)
     vtot = np.zeros(Nstar)
@@ -165,9 +161,7 @@ def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpo
             float(optimState.get("ymax", 0.0)), int(bool(optimState.get("VarianceRegularizedAcqFcn", False))),
             float(optimState.get("TolGPVar", 0.0)), ptr(gl), ptr(xr), ptr(sn), ptr(acq), ptr(fbar), ptr(vtot))
     if use_quad:
-        dl = np.asarray(delta, dtype=np.float64).reshape(-1)
-        dl = f64(np.full(D, dl[0]) if dl.size == 1 else dl.reshape(D))     # gplite_quad's bsxfun admits a scalar (:70)
-        ctx.check(ctx.lib.vbmc_acq_eval_delta(*args, ptr(dl)))
+        ctx.check(ctx.lib.vbmc_acq_eval_delta(*args, ptr(_pack.delta_row(vp, D))))
     else:
         ctx.check(ctx.lib.vbmc_acq_eval(*args))
     if outside is not None:
@@ -175,40 +169,6 @@ def _acq_local(Xs, vp, gp, optimState, acqFun, outside, nargout, engine, transpo
     if transpose_flag:
         acq = acq.reshape(1, -1)
     return (acq, fbar, vtot) if nargout >= 3 else acq
-
-
-def vbmc_rnd(vp, N, origflag=False, balanceflag=False, *, rng=None):
-    """[X,I] = vbmc_rnd(vp,N,0,balanceflag)  (vbmc_rnd.m:50-109): N draws from the Gaussian-mixture variational
-    posterior in the TRANSFORMED space (origflag must be false here: the inverse variable transform is VBMC's
-    warpvars_vbmc).  Host-side; used to place the importance points of the IQR acquisition functions."""
-    if origflag:
-        raise VbmcUnsupported(-1, "vbmc_rnd: origflag = 1 needs warpvars_vbmc (caller's side)")
-    rng = np.random.default_rng() if rng is None else rng
-    D, K = int(vp["D"]), int(vp["K"])
-    N = int(N)
-    if N < 1:
-        return np.zeros((0, D)), np.zeros(0, dtype=int)
-    w = np.asarray(vp["w"], dtype=np.float64).reshape(K)
-    mu_t = np.asarray(vp["mu"], dtype=np.float64).reshape(D, K).T
-    sigma = np.asarray(vp["sigma"], dtype=np.float64).reshape(K)
-    lam = np.asarray(vp["lambda"], dtype=np.float64).reshape(D)
-    if K > 1:
-        if balanceflag:                                       # exact split by weight + weighted remainder (:69-88)
-            n_floor = np.floor(w * N).astype(int)
-            I = np.repeat(np.arange(K), n_floor)
-            if N > I.size:
-                w_extra = w * N - n_floor
-                n_extra = int(np.ceil(np.sum(w_extra)))
-                w_extra = w_extra + w * (n_extra - np.sum(w_extra))
-                I = np.concatenate([I, rng.choice(K, size=n_extra, p=w_extra / np.sum(w_extra))])
-            I = I[rng.permutation(I.size)[:N]]
-        else:
-            I = rng.choice(K, size=N, p=w / np.sum(w))        # catrnd(w,N) (:90)
-        X = mu_t[I] + lam[None, :] * (rng.standard_normal((N, D)) * sigma[I][:, None])      # :95
-    else:
-        I = np.zeros(N, dtype=int)
-        X = mu_t + lam[None, :] * (rng.standard_normal((N, D)) * sigma[0])                   # :103
-    return X, I
 
 
 _U_IQR = 0.6745   # norminv(0.75), acq/acqviqr_vbmc.m:4, acq/acqimiqr_vbmc.m:4
@@ -224,22 +184,6 @@ def _islogf(name, which, vlnpdf, fmu, fs2):
         return added
     fixed = fmu if name == "acqimiqr_vbmc" else (np.zeros_like(fs2) if which == "islogf1" else np.asarray(vlnpdf).reshape(-1, 1))
     return fixed if which == "islogf1" else fixed + added
-
-
-def _vbmc_lnpdf(vp, X):
-    """log vbmc_pdf(vp,X,0,1) in the transformed space (vbmc_pdf.m:38-71 with logflag): Gaussian mixture, host side (Na x K)."""
-    X = np.asarray(X, dtype=np.float64)
-    D, K = int(vp["D"]), int(vp["K"])
-    mu = np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)
-    sigma = np.asarray(vp["sigma"], dtype=np.float64).reshape(K)
-    lam = np.asarray(vp["lambda"], dtype=np.float64).reshape(D)
-    w = np.asarray(vp["w"], dtype=np.float64).reshape(K)
-    z = (X[:, None, :] - mu.T[None, :, :]) / (lam[None, None, :] * sigma[None, :, None])
-    lp = np.log(w)[None, :] - 0.5 * np.sum(z * z, axis=2) - D * np.log(sigma)[None, :] - np.sum(np.log(lam)) - 0.5 * D * np.log(2 * np.pi)
-    m = np.max(lp, axis=1, keepdims=True)
-    out = (m + np.log(np.sum(np.exp(lp - m), axis=1, keepdims=True))).reshape(-1)
-    # the reference forms the density and then takes its log (vbmc_pdf.m:71,117): below the smallest double it is log(0) = -Inf
-    return np.where(out < np.log(5e-324), -np.inf, out)
 
 
 def _proposal_lnw(Xa, gp, vp_is, w_vp, rect_delta, name, vp, isamplevp, engine):
@@ -266,161 +210,10 @@ def _proposal_lnw(Xa, gp, vp_is, w_vp, rect_delta, name, vp, isamplevp, engine):
     return lny - lpdf, fs2                                                                           # Na x S each
 
 
-def gplite_pred_device(gp, Xs, engine):
-    """[ymu,ys2,fmu,fs2] = gplite_pred(gp,Xs,[],[],1,0) per hyper-sample (Nstar x S) on the device."""
-    from .gplite import gplite_pred
-
-    out = gplite_pred(gp, Xs, None, None, True, False, 4, engine=engine)
-    S = len(gp["post"])
-    return tuple(np.asarray(o).reshape(np.asarray(Xs).shape[0], S) for o in out)
-
-
-def ensemble_slice_sample(logp, x0, N, LB, UB, *, thin=1, burnin=None, sigma_factor=1.0, rng=None, max_steps=20, max_shrink=60,
-                          spec=3, return_info=False):
-    """Ensemble slice sampling for E independent targets at once, every log-density evaluation ONE batched call.
-
-    Stands where the reference calls utils/eissample_lite.m (third-party, 1329 lines, not restated) with its default
-    transition operator (transSliceSampleRD with an ensemble, eissample_lite.m:212,956-962): a walker moves by one-dimensional
-    slice sampling (stepping out, shrinkage) along the difference of two other walkers of its ensemble.  The reference moves one
-    walker per iteration; here the two halves of every ensemble take turns and all walkers of a half -- of ALL E ensembles -- move
-    together, each along the difference of two walkers of the complementary half, so that a move costs a handful of batched
-    evaluations of E W / 2 points instead of that many sequential ones.
-
-    logp(X, e): X (M x D) points, e (M,) the ensemble each belongs to -> (M,) log densities (-inf outside the support).
-    x0: E x W x D starting walkers.  Returns (samples E x N x D, logp E x N): after ``burnin`` recorded moves per ensemble have
-    been discarded every thin-th moved walker is recorded, as eissample_lite counts them (:386, one sample per walker move).
-    ``spec``: steps of the stepping-out / proposals of the shrinkage evaluated per batched call (1: the textbook one at a time).
-    return_info=True adds a dict with ``funccount``, the evaluations of the target (proposals outside the bounds cost none)."""
-    rng = np.random.default_rng(0) if rng is None else rng
-    x = np.array(x0, dtype=np.float64, copy=True)
-    E, W, D = x.shape
-    assert W >= 4 and W % 2 == 0, "two halves of at least two walkers"
-    LB = np.broadcast_to(np.asarray(LB, dtype=np.float64), (D,))
-    UB = np.broadcast_to(np.asarray(UB, dtype=np.float64), (D,))
-    burnin = int(np.ceil(thin * N / 2)) if burnin is None else int(burnin)     # get_mcmcopts, activeimportancesampling_vbmc.m:372-376
-    ens = np.repeat(np.arange(E), W)
-    count = [0]          # evaluations of the target (proposals outside the bounds cost none)
-
-    def lp_of(P, e):
-        ok = np.all((P >= LB) & (P <= UB), axis=1)
-        out = np.full(P.shape[0], -np.inf)
-        if np.any(ok):
-            out[ok] = logp(P[ok], e[ok])
-            count[0] += int(np.sum(ok))
-        return out
-
-    lp = lp_of(x.reshape(E * W, D), ens).reshape(E, W)
-    if not np.all(np.isfinite(lp)):
-        raise ValueError("ensemble_slice_sample: a starting point has zero density")
-    H = W // 2
-    halves = (np.arange(0, H), np.arange(H, W))
-    total = burnin + N * thin
-    out_x = np.empty((E, N, D))
-    out_lp = np.empty((E, N))
-    moved = 0            # walker moves per ensemble so far
-    nrec = 0
-    while nrec < N:
-        for h in (0, 1):
-            mine, other = halves[h], halves[1 - h]
-            M = E * H
-            xc = x[:, mine, :].reshape(M, D)
-            lc = lp[:, mine].reshape(M)
-            ee = np.repeat(np.arange(E), H)
-            # direction: difference of two distinct walkers of the complementary half (eissample_lite.m:956-960)
-            a = rng.integers(0, H, size=M)
-            b = (a + 1 + rng.integers(0, H - 1, size=M)) % H
-            xo = x[:, other, :]
-            V = (xo[ee, b] - xo[ee, a]) * sigma_factor
-            y = lc + np.log(rng.random(M))                       # slice level
-            L = -rng.random(M)
-            Rr = L + 1.0
-            # Stepping out, both ends in lock-step.  The ends are tested `spec` steps at a time in ONE batched evaluation (an end
-            # stops at the first step that falls below the slice level; the steps behind it were evaluated for nothing, which is
-            # cheap, while a call is not: each is a device round trip): same interval as the one-step-at-a-time procedure.
-            growL = np.ones(M, dtype=bool)
-            growR = np.ones(M, dtype=bool)
-            steps = 0
-            while steps < max_steps and (np.any(growL) or np.any(growR)):
-                ns = min(spec, max_steps - steps)
-                il, ir = np.nonzero(growL)[0], np.nonzero(growR)[0]
-                off = np.arange(ns, dtype=np.float64)
-                tL = (L[il][:, None] - off[None, :]).reshape(-1)          # L, L - 1, ... of every growing left end
-                tR = (Rr[ir][:, None] + off[None, :]).reshape(-1)
-                idx = np.concatenate([np.repeat(il, ns), np.repeat(ir, ns)])
-                t = np.concatenate([tL, tR])
-                val = lp_of(xc[idx] + t[:, None] * V[idx], ee[idx])
-                okL = (val[: il.size * ns] > np.repeat(y[il], ns)).reshape(il.size, ns)
-                okR = (val[il.size * ns:] > np.repeat(y[ir], ns)).reshape(ir.size, ns)
-                nL = np.where(np.all(okL, axis=1), ns, np.argmin(okL, axis=1))     # leading steps inside the slice
-                nR = np.where(np.all(okR, axis=1), ns, np.argmin(okR, axis=1))
-                L[il] -= nL
-                Rr[ir] += nR
-                growL[il[nL < ns]] = False
-                growR[ir[nR < ns]] = False
-                steps += ns
-            # Shrinkage, `spec` proposals per batched evaluation: proposal q + 1 is drawn from the interval as it would be after the
-            # rejection of proposal q, which depends on where proposal q fell, not on its density -- so the chain of proposals can be
-            # laid out before any of them is evaluated; the first one inside the slice is accepted, the interval shrinks by the
-            # rejected ones in front of it.
-            todo = np.ones(M, dtype=bool)
-            xn = xc.copy()
-            ln = lc.copy()
-            shr = 0
-            while shr < max_shrink and np.any(todo):
-                ns = min(spec, max_shrink - shr)
-                idx = np.nonzero(todo)[0]
-                n = idx.size
-                Lq, Rq = L[idx].copy(), Rr[idx].copy()
-                T = np.empty((n, ns))
-                Ls, Rs = np.empty((n, ns)), np.empty((n, ns))             # the interval AFTER rejecting proposals 0..q
-                for q in range(ns):
-                    tq = Lq + rng.random(n) * (Rq - Lq)
-                    T[:, q] = tq
-                    neg = tq < 0
-                    Lq = np.where(neg, tq, Lq)
-                    Rq = np.where(neg, Rq, tq)
-                    Ls[:, q], Rs[:, q] = Lq, Rq
-                rep = np.repeat(idx, ns)
-                P = xc[rep] + T.reshape(-1)[:, None] * V[rep]
-                val = lp_of(P, ee[rep]).reshape(n, ns)
-                ok = val > y[idx][:, None]
-                anyok = np.any(ok, axis=1)
-                first = np.argmax(ok, axis=1)                               # first accepted proposal (0 if none: masked below)
-                acc = idx[anyok]
-                fa = first[anyok]
-                Pm = P.reshape(n, ns, D)
-                xn[acc] = Pm[anyok, fa]
-                ln[acc] = val[anyok, fa]
-                todo[acc] = False
-                # intervals: all ns proposals rejected -> after the last; (accepted ones no longer matter)
-                rej = idx[~anyok]
-                L[rej] = Ls[~anyok, ns - 1]
-                Rr[rej] = Rs[~anyok, ns - 1]
-                shr += ns
-            # (a walker whose slice collapsed stays where it is: eissample_lite's exitflag -5 case)
-            x[:, mine, :] = xn.reshape(E, H, D)
-            lp[:, mine] = ln.reshape(E, H)
-            for j in range(H):
-                moved += 1
-                if moved > burnin and (moved - burnin) % thin == 0 and nrec < N:
-                    out_x[:, nrec, :] = x[:, mine[j], :]
-                    out_lp[:, nrec] = lp[:, mine[j]]
-                    nrec += 1
-            if moved >= total and nrec >= N:
-                break
-    return (out_x, out_lp, {"funccount": count[0]}) if return_info else (out_x, out_lp)
-
-
 def importance_sample_rng_dump(seed, S, H, M):
     """U (64 x H x S x M) that ``importance_sample_device(..., seed=seed)`` consumes (vbmc_acq_is_sample_rng_dump: a pure host function)."""
-    import ctypes as C
-
-    from ._lib import load
-
     U = np.zeros((64, H, S, M), order="F")
-    st = load().vbmc_acq_is_sample_rng_dump(C.c_uint64(seed), int(S), int(H), int(M), ptr(U))
-    if st != 0:
-        raise ValueError("vbmc_acq_is_sample_rng_dump: bad arguments")
+    host_dump("vbmc_acq_is_sample_rng_dump", seed, S, H, M, U)
     return U
 
 
@@ -431,10 +224,6 @@ def importance_sample_device(gp, x0, LB, UB, Nm, *, thin=1, burnin=None, spec=0,
     takes them).  ``uniforms`` (64 x H x S x Mmax): parity mode, the library's own generator keyed by ``seed`` otherwise.
     Returns a dict: Xa (Nm x D x S), lnw (S x Nm), fs2a (Nm x S), logp (S x Nm), funccount, performed, rounds, behind and ``state``,
     the ``ImportanceState`` of those device buffers (None without ``want_state``)."""
-    import ctypes as C
-
-    from ._lib import IsSampleArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     dgp = _device_gp_with_noise(engine, gp)
@@ -446,48 +235,32 @@ def importance_sample_device(gp, x0, LB, UB, Nm, *, thin=1, burnin=None, spec=0,
         raise ValueError("importance_sample_device: x0 is S x W x D = %d x %d x %d, the GP has S = %d hyper-samples and D = %d"
                          % (S, W, D, len(gp["post"]), np.asarray(gp["X"]).shape[1]))
     Nm = int(Nm)
-    keep = {"x0": f64(np.transpose(x0, (1, 2, 0))),      # W x D x S
-            "LB": f64(np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (D,)).copy()),
-            "UB": f64(np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (D,)).copy())}
-    a = IsSampleArgs()
-    a.struct_size = C.sizeof(IsSampleArgs)
-    a.W, a.D, a.S, a.Nm, a.thin, a.burnin, a.spec = int(W), int(D), int(S), Nm, int(thin), -1 if burnin is None else int(burnin), int(spec)
-    a.max_steps, a.max_shrink, a.chunk = int(max_steps), int(max_shrink), int(chunk)
-    a.x0, a.LB, a.UB = ptr(keep["x0"]), ptr(keep["LB"]), ptr(keep["UB"])
+    keep = [f64(np.transpose(x0, (1, 2, 0))), *_pack.box(LB, UB, D)]      # x0: W x D x S
+    a = new_args(IsSampleArgs)
+    a.D, a.S = int(D), int(S)
+    _pack.sampler_opts(a, W, Nm, thin, burnin, spec, max_steps, max_shrink, chunk, seed)
+    a.x0, a.LB, a.UB = (ptr(k) for k in keep)
     if uniforms is not None:
-        keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
-        if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, W // 2, S):
-            raise ValueError("importance_sample_device: uniforms must be 64 x H x S x Mmax = 64 x %d x %d x Mmax" % (W // 2, S))
-        a.rng_mode, a.Mmax, a.U = 1, keep["U"].shape[3], ptr(keep["U"])
-    else:
-        a.rng_mode, a.seed = 0, int(seed)
+        keep.append(_pack.sampler_uniforms(a, uniforms, W // 2, S, "importance_sample_device"))
+        a.rng_mode = 1
     n = max(Nm, 1)
     out = {"Xa": np.zeros((n, D, S), order="F"), "lnw": np.zeros((S, n), order="F"), "fs2a": np.zeros((n, S), order="F"),
            "logp": np.zeros((S, n), order="F")}
-    fc, pf, rounds = C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
     handle = C.c_void_p()
     a.Xa, a.lnw, a.fs2a, a.logp = ptr(out["Xa"]), ptr(out["lnw"]), ptr(out["fs2a"]), ptr(out["logp"])
-    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
-    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    counts = _pack.counters(a)
     if want_state:
         a.state = C.pointer(handle)
     ctx.check(ctx.lib.vbmc_acq_is_sample(ctx.h, dgp.h, C.byref(a)))
-    out.update(funccount=int(fc.value), performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]),
-               state=ImportanceState.from_handle(engine, handle) if want_state else None, _dgp=dgp)
+    out.update(counts(), state=ImportanceState.from_handle(engine, handle) if want_state else None, _dgp=dgp)
     return out
 
 
 def importance_setup_rng_dump(seed, D, S, W, Nvp, Nbox):
     """The block B ((D + 1) (Nvp + Nbox) + W S doubles) that ``importance_setup_device(..., seed=seed)`` consumes in Step 1 and in the
     resampling (vbmc_acq_is_setup_rng_dump: a pure host function)."""
-    import ctypes as C
-
-    from ._lib import load
-
     B = np.zeros((D + 1) * (Nvp + Nbox) + W * S)
-    st = load().vbmc_acq_is_setup_rng_dump(C.c_uint64(seed), int(D), int(S), int(W), int(Nvp), int(Nbox), ptr(B))
-    if st != 0:
-        raise ValueError("vbmc_acq_is_setup_rng_dump: bad arguments")
+    host_dump("vbmc_acq_is_setup_rng_dump", seed, D, S, W, Nvp, Nbox, B)
     return B
 
 
@@ -499,10 +272,6 @@ def importance_setup_device(vp, gp, Nvp, Nbox, Nm, *, W=None, thin=1, burnin=Non
     otherwise.  ``Nm = 0``: Step 1 alone.  Returns a dict: Xa1 (Na1 x D), lnw1 (S x Na1), fs2a1 (Na1 x S), lpdf1 (Na1), rect_delta, LB,
     UB, and with Nm > 0 x0 (S x W x D, as ``importance_sample_device`` takes them), idx0 (W x S), n_bad, bad (W x S) and -- unless
     n_bad > 0 -- what ``importance_sample_device`` returns."""
-    import ctypes as C
-
-    from ._lib import IsSetupArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     dgp = _device_gp_with_noise(engine, gp)
@@ -510,24 +279,18 @@ def importance_setup_device(vp, gp, Nvp, Nbox, Nm, *, W=None, thin=1, burnin=Non
     Nvp, Nbox, Nm = int(Nvp), int(Nbox), int(Nm)
     W = 2 * (D + 1) if W is None else int(W)
     Na1 = max(Nvp + Nbox, 1)
-    keep = {"mu": f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)), "sigma": f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K)),
-            "lambda": f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D)), "w": f64(np.asarray(vp["w"], dtype=np.float64).reshape(K))}
-    a = IsSetupArgs()
-    a.struct_size = C.sizeof(IsSetupArgs)
+    a = new_args(IsSetupArgs)
     a.D, a.S, a.K, a.Nvp, a.Nbox = D, S, K, Nvp, Nbox
-    a.vp_mu, a.vp_sigma, a.vp_lambda, a.vp_w = ptr(keep["mu"]), ptr(keep["sigma"]), ptr(keep["lambda"]), ptr(keep["w"])
-    a.W, a.Nm, a.thin, a.burnin, a.spec = W, Nm, int(thin), -1 if burnin is None else int(burnin), int(spec)
-    a.max_steps, a.max_shrink, a.chunk, a.seed = int(max_steps), int(max_shrink), int(chunk), int(seed)
+    keep = list(_pack.mixture(vp, a))
+    _pack.sampler_opts(a, W, Nm, thin, burnin, spec, max_steps, max_shrink, chunk, seed)
     if block is not None:
-        keep["B"] = f64(np.asarray(block, dtype=np.float64).reshape(-1))
-        if keep["B"].size != (D + 1) * (Nvp + Nbox) + (W * S if Nm > 0 else 0):
+        B = f64(np.asarray(block, dtype=np.float64).reshape(-1))
+        if B.size != (D + 1) * (Nvp + Nbox) + (W * S if Nm > 0 else 0):
             raise ValueError("importance_setup_device: the block must hold (D + 1) (Nvp + Nbox) + W S values")
-        a.rng_mode, a.B = 1, ptr(keep["B"])
+        a.rng_mode, a.B = 1, ptr(B)
+        keep.append(B)
         if uniforms is not None:
-            keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
-            if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, W // 2, S):
-                raise ValueError("importance_setup_device: uniforms must be 64 x H x S x Mmax = 64 x %d x %d x Mmax" % (W // 2, S))
-            a.Mmax, a.U = keep["U"].shape[3], ptr(keep["U"])
+            keep.append(_pack.sampler_uniforms(a, uniforms, W // 2, S, "importance_setup_device"))
     elif uniforms is not None:
         raise ValueError("importance_setup_device: uniforms (Step 2's block) go with a Step 1 block")
     n, w = max(Nm, 1), max(W, 1)
@@ -538,20 +301,19 @@ def importance_setup_device(vp, gp, Nvp, Nbox, Nm, *, W=None, thin=1, burnin=Non
     bad = np.zeros((w, S), dtype=np.uint8, order="F")
     run = {"Xa": np.zeros((n, D, S), order="F"), "lnw": np.zeros((S, n), order="F"), "fs2a": np.zeros((n, S), order="F"),
            "logp": np.zeros((S, n), order="F")}
-    nb, fc, pf, rounds = C.c_int32(), C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
+    nb = C.c_int32()
     handle = C.c_void_p()
     a.Xa1, a.lnw1, a.fs2a1, a.lpdf1 = ptr(out["Xa1"]), ptr(out["lnw1"]), ptr(out["fs2a1"]), ptr(out["lpdf1"])
     a.rect_delta, a.LB, a.UB, a.x0 = ptr(out["rect_delta"]), ptr(out["LB"]), ptr(out["UB"]), ptr(x0)
-    a.idx0 = idx0.ctypes.data_as(C.POINTER(C.c_int32))
+    a.idx0 = idx0.ctypes.data_as(_pack.i32p)
     a.bad = bad.ctypes.data_as(C.POINTER(C.c_uint8))
     a.n_bad = C.pointer(nb)
     a.Xa, a.lnw, a.fs2a, a.logp = ptr(run["Xa"]), ptr(run["lnw"]), ptr(run["fs2a"]), ptr(run["logp"])
-    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
-    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    counts = _pack.counters(a)
     if want_state:
         a.state = C.pointer(handle)
     ctx.check(ctx.lib.vbmc_acq_is_setup(ctx.h, dgp.h, C.byref(a)))
-    out.update(n_bad=int(nb.value), funccount=int(fc.value), performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]), _dgp=dgp,
+    out.update(counts(), n_bad=int(nb.value), _dgp=dgp,
                state=ImportanceState.from_handle(engine, handle) if want_state and handle.value else None)
     if Nm > 0:
         out.update(x0=np.ascontiguousarray(np.transpose(x0, (2, 0, 1))), idx0=idx0, bad=bad.astype(bool))
@@ -738,14 +500,8 @@ SEARCH_STOP = {1: "TolX", 2: "TolFun", 3: "TolHistFun", 4: "MaxFunEvals", 5: "Ma
 
 def acq_search_rng_dump(seed, D, lam, G):
     """Z (D x lam x G) that ``acq_search(..., seed=seed)`` consumes (vbmc_acq_search_rng_dump: a pure host function)."""
-    import ctypes as C
-
-    from ._lib import load
-
     Z = np.zeros((D, lam, G), order="F")
-    st = load().vbmc_acq_search_rng_dump(C.c_uint64(seed), int(D), int(lam), int(G), ptr(Z))
-    if st != 0:
-        raise ValueError("vbmc_acq_search_rng_dump: bad arguments")
+    host_dump("vbmc_acq_search_rng_dump", seed, D, lam, G, Z)
     return Z
 
 
@@ -761,56 +517,36 @@ def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, T
     rank order, the sorted values, xmean and sigma of the first n generations.  Returns a dict: xmin / fmin (the last generation's
     best), xbest / fbest (the best ever seen), xmean, sigma, C, evals, generations, stop (name), behind (launches enqueued behind
     the end) and, with ``trace``, tr_order / tr_F / tr_xmean / tr_sigma."""
-    import ctypes as C
-
-    from ._lib import AcqSearchArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     acq_id = int(acqFun) if isinstance(acqFun, (int, np.integer)) else ACQ_IDS[acq_info(acqFun)["name"]]   # a name, or the library's id
     D = gp["X"].shape[1]
     K = int(vp["K"])
     dgp = _device_gp_with_noise(engine, gp)
-    keep = {
-        "mu": f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)), "sigma": f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K)),
-        "lam": f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D)), "w": f64(np.asarray(vp["w"], dtype=np.float64).reshape(K)),
-        "x0": f64(np.asarray(x0, dtype=np.float64).reshape(D)),
-        "insigma": f64(np.broadcast_to(np.asarray(insigma, dtype=np.float64).reshape(-1), (D,)).copy()),
-        "LB": f64(np.asarray(LB, dtype=np.float64).reshape(D)), "UB": f64(np.asarray(UB, dtype=np.float64).reshape(D)),
-    }
-    a = AcqSearchArgs()
-    a.struct_size = C.sizeof(AcqSearchArgs)
+    a = new_args(AcqSearchArgs)
     a.acq_id, a.K = acq_id, K
-    a.vp_mu, a.vp_sigma, a.vp_lambda, a.vp_w = ptr(keep["mu"]), ptr(keep["sigma"]), ptr(keep["lam"]), ptr(keep["w"])
-    delta = vp.get("delta")
-    if delta is not None and np.size(delta) > 0:
-        dl = np.asarray(delta, dtype=np.float64).reshape(-1)
-        keep["delta"] = f64(np.full(D, dl[0]) if dl.size == 1 else dl.reshape(D))
-        a.vp_delta = ptr(keep["delta"])
+    keep = [*_pack.mixture(vp, a, D=D), _pack.delta_row(vp, D), f64(np.asarray(x0, dtype=np.float64).reshape(D)), _pack.row(insigma, D),
+            *_pack.box(LB, UB, D)]
+    a.vp_delta, a.x0, a.insigma, a.LB, a.UB = (ptr(k) for k in keep[4:])
     a.ymax = float(optimState.get("ymax", 0.0))
     a.var_regularized = int(bool(optimState.get("VarianceRegularizedAcqFcn", False)))
     a.TolGPVar = float(optimState.get("TolGPVar", 0.0))
     ais = optimState.get("ActiveImportanceSampling")
     if iqr is None:
         iqr = acq_id in (10, 11) and ais is not None
-    if acq_id == 3 or iqr:
-        if optimState.get("gplengthscale") is not None:
-            keep["gl"] = f64(np.asarray(optimState["gplengthscale"], dtype=np.float64).reshape(D))
-            a.gplengthscale = ptr(keep["gl"])
-        if gp.get("X_rescaled") is not None and gp.get("sn2new") is not None:
-            keep["xr"] = f64(np.asarray(gp["X_rescaled"], dtype=np.float64))
-            keep["sn"] = f64(np.asarray(gp["sn2new"], dtype=np.float64).reshape(-1))
-            a.X_rescaled, a.sn2new = ptr(keep["xr"]), ptr(keep["sn"])
-    a.x0, a.insigma, a.LB, a.UB = ptr(keep["x0"]), ptr(keep["insigma"]), ptr(keep["LB"]), ptr(keep["UB"])
+    if acq_id == 3 or iqr:                                  # (what is missing stays NULL: the library names it in its refusal)
+        both = gp.get("X_rescaled") is not None and gp.get("sn2new") is not None
+        keep += _pack.nn_noise(a, optimState.get("gplengthscale"), gp["X_rescaled"] if both else None, gp["sn2new"] if both else None,
+                               dgp.N, D)
     a.TolX, a.TolFun, a.TolHistFun = float(TolX), float(TolFun), float(TolHistFun)
     a.MaxFunEvals = 0 if (MaxFunEvals is None or not np.isfinite(MaxFunEvals)) else int(MaxFunEvals)
     a.MaxIter, a.popsize, a.chunk = int(MaxIter or 0), int(popsize or 0), int(chunk or 0)
     lam = int(popsize) if popsize else 4 + int(np.floor(3 * np.log(D)))
     if Z is not None:
-        keep["Z"] = f64(np.asarray(Z, dtype=np.float64))
-        if keep["Z"].ndim != 3 or keep["Z"].shape[:2] != (D, lam):
+        Z = f64(np.asarray(Z, dtype=np.float64))
+        if Z.ndim != 3 or Z.shape[:2] != (D, lam):
             raise ValueError("acq_search: Z must be D x lam x Gmax = %d x %d x Gmax" % (D, lam))
-        a.rng_mode, a.Gmax, a.Z = 1, keep["Z"].shape[2], ptr(keep["Z"])
+        a.rng_mode, a.Gmax, a.Z = 1, Z.shape[2], ptr(Z)
     else:
         a.rng_mode, a.seed = 0, int(seed)
     out = {"xmin": np.zeros(D), "xbest": np.zeros(D), "xmean": np.zeros(D), "C": np.zeros((D, D), order="F")}
@@ -820,13 +556,13 @@ def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, T
     a.xmin, a.xbest, a.xmean, a.C = ptr(out["xmin"]), ptr(out["xbest"]), ptr(out["xmean"]), ptr(out["C"])
     a.fmin, a.fbest, a.sigma = C.pointer(sc["fmin"]), C.pointer(sc["fbest"]), C.pointer(sc["sigma"])
     a.evals, a.generations, a.stop = C.pointer(evals), C.pointer(gens), C.pointer(stop)
-    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    a.rounds = C.cast(rounds, _pack.i64p)
     n = int(trace or 0)
     if n > 0:
         out.update(tr_order=np.zeros((lam, n), dtype=np.int32, order="F"), tr_F=np.zeros((lam, n), order="F"),
                    tr_xmean=np.zeros((D, n), order="F"), tr_sigma=np.zeros(n))
         a.trace_cap = n
-        a.tr_order = out["tr_order"].ctypes.data_as(C.POINTER(C.c_int32))
+        a.tr_order = out["tr_order"].ctypes.data_as(_pack.i32p)
         a.tr_F, a.tr_xmean, a.tr_sigma = ptr(out["tr_F"]), ptr(out["tr_xmean"]), ptr(out["tr_sigma"])
     if iqr:
         ist = _importance_state(engine, dgp, ais)
@@ -836,24 +572,6 @@ def acq_search(x0, insigma, LB, UB, vp, gp, optimState, acqFun="acqf_vbmc", *, T
     out.update(fmin=sc["fmin"].value, fbest=sc["fbest"].value, sigma=sc["sigma"].value, evals=int(evals.value),
                generations=int(gens.value), stop=SEARCH_STOP.get(int(stop.value), "MaxIter"), behind=int(rounds[1]), popsize=lam)
     return out
-
-
-def vbmc_moments(vp, origflag=False):
-    """[mubar,Sigma] = vbmc_moments(vp,0)  (vbmc_moments.m:30-43): mean and covariance of the Gaussian-mixture variational posterior
-    in the TRANSFORMED space, analytically (origflag = 1 samples through warpvars_vbmc, the caller's side)."""
-    if origflag:
-        raise VbmcUnsupported(-1, "vbmc_moments: origflag = 1 needs warpvars_vbmc (caller's side)")
-    D, K = int(vp["D"]), int(vp["K"])
-    w = np.asarray(vp["w"], dtype=np.float64).reshape(1, K)
-    mu = np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)
-    sigma = np.asarray(vp["sigma"], dtype=np.float64).reshape(1, K)
-    lam = np.asarray(vp["lambda"], dtype=np.float64).reshape(D)
-    mubar = np.sum(w * mu, axis=1)
-    Sigma = np.sum(w * sigma ** 2) * np.diag(lam ** 2)
-    for k in range(K):
-        dk = (mu[:, k] - mubar).reshape(D, 1)
-        Sigma = Sigma + w[0, k] * (dk @ dk.T)
-    return mubar, Sigma
 
 
 SEARCH_DEFAULT_OPTIONS = {
@@ -872,8 +590,6 @@ def active_search(Xsearch, vp, gp, optimState, options=None, acqFun="acqf_vbmc",
     Returns (Xacq (D,), fval, info) with info = {"x0", "fval_old", "accepted", "search": acq_search's dict or None, "idx"}.  Integer
     variables (real2int_vbmc, :219,248,325) and the hard-bound mask in the original space are the caller's: ``outside`` marks sweep
     points outside the hard bounds, optimState.integervars must be empty."""
-    from .optimize import gethpd_vbmc
-
     opts = dict(SEARCH_DEFAULT_OPTIONS, **(options or {}))
     iv = optimState.get("integervars")
     if iv is not None and np.any(np.asarray(iv)):

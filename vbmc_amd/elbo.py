@@ -12,9 +12,12 @@ from __future__ import annotations
 
 import ctypes as C
 
+import os
+
 import numpy as np
 
-from ._lib import Context, DeviceGP, ElboArgs, VbmcUnsupported, f64, ptr
+from . import _pack
+from ._lib import Context, DeviceGP, ElboArgs, f64, new_args, ptr
 from .vp import get_vptheta
 
 _engines = {}
@@ -94,13 +97,10 @@ def _build_args(thetas, beta, vp, gp, Ns, compute_grad, compute_var, thetabnd, s
     if compute_var is None:
         compute_var = 1 if beta != 0 else 0  # :16 (first clause; nargout clause handled by callers)
     compute_var = int(compute_var)
-    a = ElboArgs()
-    a.struct_size = C.sizeof(ElboArgs)
+    a = new_args(ElboArgs)
     a.D, a.K, a.R = D, K, R
-    fl = _flags(vp)
-    for i in range(4):
-        a.optimize[i] = fl[i]
-    keep = [thetas]
+    a.optimize[:] = _flags(vp)
+    keep = [thetas, *_pack.mixture(vp, a)]
     a.theta = ptr(thetas)
 
     def hold(x):
@@ -108,20 +108,16 @@ def _build_args(thetas, beta, vp, gp, Ns, compute_grad, compute_var, thetabnd, s
         keep.append(x)
         return ptr(x)
 
-    a.vp_mu = hold(vp["mu"])
-    a.vp_sigma = hold(vp["sigma"])
-    a.vp_lambda = hold(vp["lambda"])
-    a.vp_w = hold(vp["w"])
-    delta = vp.get("delta")
-    if delta is not None and np.size(delta) > 0 and np.any(np.asarray(delta) != 0):
-        a.vp_delta = hold(np.broadcast_to(np.asarray(delta, dtype=np.float64).reshape(-1), (D,)).copy())
+    delta = _pack.delta_row(vp, D)
+    if delta is not None and np.any(delta != 0):          # (an all-zero delta stays NULL: the pass then takes the forms without it)
+        a.vp_delta = hold(delta)
     Ns = int(Ns)
     a.Ns = Ns
     a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     a.eps_shared = 1 if eps_shared else 0
     if Ns > 0 and eps_device_ptr is not None:
         a.eps_mode = 2
-        a.eps = C.c_void_p(int(eps_device_ptr))
+        a.eps = C.cast(C.c_void_p(int(eps_device_ptr)), C.POINTER(C.c_double))      # a device address
     elif Ns > 0 and eps is not None:
         Mh = (Ns + 1) // 2
         e = np.ascontiguousarray(np.asarray(eps, dtype=np.float64))
@@ -130,7 +126,7 @@ def _build_args(thetas, beta, vp, gp, Ns, compute_grad, compute_var, thetabnd, s
             raise ValueError("eps has shape %r, expected %r" % (e.shape, want_shape))
         keep.append(e)
         a.eps_mode = 1
-        a.eps = C.c_void_p(e.ctypes.data)
+        a.eps = ptr(e)
     else:
         a.eps_mode = 0
     a.compute_grad = 1 if compute_grad else 0
@@ -447,8 +443,6 @@ class PreparedObjective:
         """Generator over an iterable of theta batches (T x R each): yields (F, dF) copies in order, four batches in flight (two per
         stream; two in all for the variance forms, which stay on the context's own stream)."""
         pending = []
-        import os
-
         depth = 4 if int(self.args.compute_var) == 0 and os.environ.get("VBMC_SLOT_STREAMS") != "0" else 2
         try:
             for i, th in enumerate(batches):

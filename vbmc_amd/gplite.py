@@ -10,11 +10,15 @@ dict with the reference's field names; its ``post`` list holds the per-hyper-sam
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
-from ._lib import DeviceGP, f64, ptr
+from . import _pack
+from ._lib import (VBMC_ERR_UNSUPPORTED, DeviceGP, GpTrainArgs, GsArgs, PredPlanInfo, SliceArgs, VbmcUnsupported, f64, host_dump, new_args,
+                   ptr)
 from .elbo import default_engine
+from .ensemble import ensemble_slice_sample
 
 
 def _nnoise(noisefun):
@@ -67,8 +71,6 @@ def gplite_post(hyp, X, y, covfun=1, meanfun=1, noisefun=None, s2=None, *, need_
     if np.ndim(covfun) and len(covfun):
         covfun = covfun[0]
     if int(covfun) != 1:
-        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-
         raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "only the SE-ARD covariance (covfun 1) is accelerated")
     if meanfun is None:
         meanfun = 1  # gplite_post.m:103
@@ -140,17 +142,21 @@ def gplite_pred(gp, Xstar, ystar=None, s2star=None, ssflag=False, nowarpflag=Fal
     return tuple(outs[: max(1, nargout)])
 
 
+def gplite_pred_device(gp, Xs, engine):
+    """[ymu,ys2,fmu,fs2] = gplite_pred(gp,Xs,[],[],1,0) per hyper-sample (Nstar x S) on the device."""
+    out = gplite_pred(gp, Xs, None, None, True, False, 4, engine=engine)
+    S = len(gp["post"])
+    return tuple(np.asarray(o).reshape(np.asarray(Xs).shape[0], S) for o in out)
+
+
 def pred_plan(gp, Nstar, want_ks=False, quad=False, *, engine=None):
     """The launch form one ``gplite_pred`` (``quad``: ``gplite_quad``) call on ``Nstar`` points takes on this device, as a dict of
     the fields of vbmc_pred_plan_info (include/vbmc_hip.h); ``want_ks`` for the form behind the IQR acquisition functions.  Launches
     nothing: the reporting hook vbmc_pred_plan evaluates the functions the launch itself reads."""
-    from ._lib import PredPlanInfo
-
     engine = engine or default_engine()
     ctx = engine.ctx
     dgp = _device_gp_with_noise(engine, gp)
-    info = PredPlanInfo()
-    info.struct_size = C.sizeof(PredPlanInfo)
+    info = new_args(PredPlanInfo)
     ctx.check(ctx.lib.vbmc_pred_plan(ctx.h, dgp.h, int(Nstar), 1 if want_ks else 0, 1 if quad else 0, C.byref(info)))
     return {n: int(getattr(info, n)) for n, _ in PredPlanInfo._fields_[1:]}
 
@@ -160,8 +166,6 @@ def gplite_quad(gp, mu, sigma, ssflag=False, nargout=2, *, engine=None):
     N(mu_i, diag sigma^2) for every row of ``mu`` (Nstar x D).  ``sigma`` is a row of D values shared by all points, or an
     Nstar x D matrix whose rows are all equal (collapsed to that row); distinct rows raise VbmcUnsupported.  Averaged over the
     hyper-samples unless ``ssflag`` (:112-119); ``nargout=1`` skips the variance's readback."""
-    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-
     engine = engine or default_engine()
     ctx = engine.ctx
     D = gp["X"].shape[1]
@@ -194,8 +198,6 @@ def gplite_post_rank1(gp, xstar, ystar, s2star=None, *, need_L=True, engine=None
     (gplite/gplite_post.m:173-251).  Falls back to the full update when ``s2`` is present, as the
     reference does (:76-79).  need_L=False leaves post[s]["L"] = None on the host: the updated factors stay on the
     device, where this package's own consumers (gplite_pred, acqwrapper_vbmc, negelcbo_vbmc, the next append) read them."""
-    import math
-
     engine = engine or default_engine()
     ctx = engine.ctx
     xstar = np.asarray(xstar, dtype=np.float64).reshape(1, -1)
@@ -246,8 +248,7 @@ def gplite_post_rank1(gp, xstar, ystar, s2star=None, *, need_L=True, engine=None
 def gplite_hypprior(hyp, hprior, nargout=2):
     """[lp,dlp] = gplite_hypprior(hyp,hprior)  (gplite/gplite_hypprior.m:17-65): independent flat / Gaussian /
     Student-t log-priors per hyper-parameter.  O(Nhyp) host arithmetic, no device work."""
-    from math import lgamma, pi
-
+    lgamma, pi = math.lgamma, math.pi
     hyp = np.asarray(hyp, dtype=np.float64)
     if hyp.ndim == 2 and hyp.shape[1] > 1:
         raise ValueError("gplite_hypprior:nosampling Hyperparameter log priors are available only for one-sample hyperparameter inputs.")
@@ -298,7 +299,6 @@ def gplite_nlZ(hyp, gp, hprior=None, nargout=2, *, engine=None):
     if Nhyp != gp["Ncov"] + gp["Nnoise"] + gp["Nmean"]:
         raise ValueError("gplite_nlZ:dimmismatch Number of hyperparameters mismatched with dimension of training inputs.")
     if gp.get("intmeanfun", 0) or gp.get("outwarpfun") is not None or int(np.atleast_1d(gp.get("covfun", 1))[0]) != 1:
-        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
         raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_nlZ: integrated mean / output warping / non-SE covariance are not accelerated")
     nf = (C.c_int32 * 3)(*[int(v) for v in (list(noisefun) + [0, 0, 0])[:3]])
     grad = nargout > 1
@@ -321,14 +321,9 @@ def slice_rng_dump(seed, sweeps, Nhyp, Kmax):
     """(perms, U): the 0-based permutations (sweeps x Nhyp, int32) and the indexed uniform block U[sweep, idd, slot]
     (sweeps x Nhyp x (2 + Kmax)) that ``seed`` stands for in the device-RNG mode of slicesamplebnd_gp (vbmc_slice_rng_dump: a
     host function).  Feeding them back as ``perms=`` / ``uniforms=`` replays the chain bit for bit."""
-    from ._lib import load
-
     perms = np.zeros((int(sweeps), int(Nhyp)), dtype=np.int32)
     U = np.zeros((int(sweeps), int(Nhyp), 2 + int(Kmax)))
-    st = load().vbmc_slice_rng_dump(C.c_uint64(int(seed)), int(sweeps), int(Nhyp), int(Kmax), perms.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    U.ctypes.data_as(C.POINTER(C.c_double)))
-    if st != 0:
-        raise ValueError("vbmc_slice_rng_dump: bad arguments")
+    host_dump("vbmc_slice_rng_dump", seed, sweeps, Nhyp, Kmax, perms, U)
     return perms, U
 
 
@@ -348,54 +343,28 @@ def slicesamplebnd_gp(gp, hprior, x0, N, widths=None, LB=None, UB=None, options=
     include/vbmc_hip.h).  ``W``: speculation width (None: the library's default); every W returns the same bits.
     ``output``: widths, funccount (evaluations of the sequential algorithm), performed (evaluations launched), maxshrink,
     rounds_done / rounds_enqueued (rounds of the device chain that did work / that the host enqueued)."""
-    from ._lib import SliceArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     options = dict(options or {})
     if options.get("StepOut"):
-        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
         raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "slicesamplebnd_gp: the step-out procedure is not accelerated")
-    X = f64(gp["X"])
-    Np, D = X.shape
-    y = f64(np.asarray(gp["y"], dtype=np.float64).reshape(-1))
-    s2 = gp.get("s2")
-    s2 = None if s2 is None or np.size(s2) == 0 else f64(np.asarray(s2, dtype=np.float64).reshape(-1))
+    a = new_args(SliceArgs)
+    keep = [_pack.training_block(a, gp, "slicesamplebnd_gp")]
     x0 = f64(np.asarray(x0, dtype=np.float64).reshape(-1))
-    Nhyp = x0.size
-    if gp.get("intmeanfun", 0) or gp.get("outwarpfun") is not None or int(np.atleast_1d(gp.get("covfun", 1))[0]) != 1:
-        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "slicesamplebnd_gp: integrated mean / output warping / non-SE covariance are not accelerated")
-    lb = f64(np.broadcast_to(np.asarray(-np.inf if LB is None or np.size(LB) == 0 else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
-    ub = f64(np.broadcast_to(np.asarray(np.inf if UB is None or np.size(UB) == 0 else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    Nhyp = a.Nhyp = x0.size
+    lb, ub = _pack.box(LB, UB, Nhyp, open_ended=True)
     base = None
     if widths is None or np.size(widths) == 0:
         wd = (ub - lb) / 2                                                       # :173-174
         wd[np.isinf(wd)] = 10.0
     else:
-        wd = np.broadcast_to(np.asarray(widths, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+        wd = _pack.row(widths, Nhyp)
         base = f64(wd.copy())                                                    # :166
     wd = f64(wd)
     N = int(N)
     thin = int(np.floor(options.get("Thin", 1)))
     burn = int(np.floor(options.get("Burnin", round(N / 3))))
-    a = SliceArgs()
-    a.struct_size = C.sizeof(SliceArgs)
-    a.N, a.D, a.Nhyp, a.meanfun = Np, D, Nhyp, int(gp["meanfun"])
-    nf = [int(v) for v in (list(gp["noisefun"]) + [0, 0, 0])[:3]]
-    for i in range(3):
-        a.noisefun[i] = nf[i]
-    a.X, a.y, a.s2 = ptr(X), ptr(y), ptr(s2)
-    keep = []
-    if hprior is not None:
-        mu = f64(np.asarray(hprior["mu"], dtype=np.float64).reshape(-1))
-        sg = f64(np.asarray(hprior["sigma"], dtype=np.float64).reshape(-1))
-        df = hprior.get("df")
-        df = None if df is None or np.size(df) == 0 else f64(np.asarray(df, dtype=np.float64).reshape(-1))
-        if mu.size != Nhyp or sg.size != Nhyp or (df is not None and df.size != Nhyp):
-            raise ValueError("slicesamplebnd_gp: hprior.mu / sigma / df need one entry per hyper-parameter")
-        keep += [mu, sg, df]
-        a.prior_mu, a.prior_sigma, a.prior_df = ptr(mu), ptr(sg), ptr(df)
+    keep.append(_pack.hyper_prior(a, hprior, Nhyp, "slicesamplebnd_gp"))
     a.LB, a.UB, a.hyp_start, a.widths, a.basewidths = ptr(lb), ptr(ub), ptr(x0), ptr(wd), ptr(base)
     a.Ns, a.Thin, a.Burnin, a.Adaptive = N, thin, burn, int(bool(options.get("Adaptive", True)))
     a.W = 0 if W is None else int(W)
@@ -409,20 +378,19 @@ def slicesamplebnd_gp(gp, hprior, x0, N, widths=None, LB=None, UB=None, options=
             raise ValueError("slicesamplebnd_gp: uniforms must be sweeps x Nhyp x (2 + Kmax) and perms sweeps x Nhyp for %d sweeps" % sweeps)
         keep += [U, P]
         a.rng_mode, a.Kmax = 1, U.shape[2] - 2
-        a.perms, a.uniforms = P.ctypes.data_as(C.POINTER(C.c_int32)), U.ctypes.data_as(C.POINTER(C.c_double))
+        a.perms, a.uniforms = P.ctypes.data_as(_pack.i32p), ptr(U)
     else:
         a.rng_mode, a.seed = 0, int(seed)
     samples = np.zeros((N, Nhyp), order="F")
     logp = np.zeros(N)
     wout = np.zeros(Nhyp)
-    fc, pf, ms = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-    a.samples, a.logp, a.widths_out = ptr(samples), ptr(logp), ptr(wout)
-    a.funccount, a.performed, a.max_shrink = C.pointer(fc), C.pointer(pf), C.pointer(ms)
-    rd = (C.c_int64 * 2)()
-    a.rounds = C.cast(rd, C.POINTER(C.c_int64))
+    ms = C.c_int32(0)
+    a.samples, a.logp, a.widths_out, a.max_shrink = ptr(samples), ptr(logp), ptr(wout), C.pointer(ms)
+    counts = _pack.counters(a)
     ctx.check(ctx.lib.vbmc_gp_slice_sample(ctx.h, C.byref(a)))
-    out = SliceOutput(widths=wout, funccount=int(fc.value), performed=int(pf.value), maxshrink=int(ms.value), logpriors=None, rounds_done=int(rd[0]),
-                      rounds_enqueued=int(rd[1]))
+    c = counts()                                         # (the second slot of rounds[] counts the rounds enqueued here)
+    out = SliceOutput(widths=wout, funccount=c["funccount"], performed=c["performed"], maxshrink=int(ms.value), logpriors=None,
+                      rounds_done=c["rounds"], rounds_enqueued=c["behind"])
     return samples, logp, 0, out
 
 
@@ -439,8 +407,7 @@ def gplite_train_sample(gp, hyp_start, Ns, hprior=None, LB=None, UB=None, widths
     if Ns < 1 or Thin < 1:
         raise ValueError("gplite_train_sample: Ns and Thin must be positive")
     Burnin = Thin * Ns if Burnin is None else int(Burnin)
-    lb = np.broadcast_to(np.asarray(-np.inf if LB is None else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
-    ub = np.broadcast_to(np.asarray(np.inf if UB is None else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
+    lb, ub = _pack.box(LB, UB, Nhyp, open_ended=True)
     # the starting point inside the bounds, fixed coordinates at their value (:304-306)
     with np.errstate(invalid="ignore"):
         elb = np.where(np.isfinite(lb), np.spacing(np.abs(lb)), 0.0)
@@ -493,9 +460,8 @@ def fminfill_design(hyp0, LB, UB, PLB, PUB, hprior, Ninit, S=None, *, seed=0):
     Returns Ninit x Nhyp (max(Ninit, N0) rows when hyp0 holds more than Ninit)."""
     x0 = np.atleast_2d(np.asarray(hyp0, dtype=np.float64))
     nvars = x0.shape[1]
-    bc = lambda v, dflt: np.broadcast_to(np.asarray(dflt if v is None or np.size(v) == 0 else v, dtype=np.float64).reshape(-1), (nvars,)).copy()
-    LB, UB = bc(LB, -np.inf), bc(UB, np.inf)
-    PLB, PUB = bc(PLB, LB), bc(PUB, UB)
+    LB, UB = _pack.box(LB, UB, nvars, open_ended=True)
+    PLB, PUB = _pack.row(PLB, nvars, LB), _pack.row(PUB, nvars, UB)
     x0 = np.maximum(np.minimum(x0, UB), LB)                                      # :44
     N0, Ninit = x0.shape[0], int(Ninit)
     if Ninit <= N0:
@@ -537,24 +503,15 @@ def gplite_train_optimize(gp, hyp0, LB, UB, PLB=None, PUB=None, hprior=None, opt
     Design (the finished Ninit x Nhyp design, instead of S), History (iterations per start to record, 0).
     Returns a dict: hyp (Nhyp x Nopts), nll, best, hyp_start, widths_default, fill_fvals, fill_order, design, iterations,
     funccount, exitflag, performed and, with History, hist_x (Nopts x History x Nhyp), hist_f, hist_k."""
-    from ._lib import GpTrainArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     options = dict(options or {})
-    if gp.get("intmeanfun", 0) or gp.get("outwarpfun") is not None or int(np.atleast_1d(gp.get("covfun", 1))[0]) != 1:
-        from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-        raise VbmcUnsupported(VBMC_ERR_UNSUPPORTED, "gplite_train_optimize: integrated mean / output warping / non-SE covariance are not accelerated")
-    X = f64(gp["X"])
-    Np, D = X.shape
-    y = f64(np.asarray(gp["y"], dtype=np.float64).reshape(-1))
-    s2 = gp.get("s2")
-    s2 = None if s2 is None or np.size(s2) == 0 else f64(np.asarray(s2, dtype=np.float64).reshape(-1))
+    a = new_args(GpTrainArgs)
+    keep = [_pack.training_block(a, gp, "gplite_train_optimize")]
     H0 = np.asarray(hyp0, dtype=np.float64)
     H0 = H0.reshape(H0.shape[0], -1)
     Nhyp, N0 = H0.shape
-    lb = f64(np.broadcast_to(np.asarray(-np.inf if LB is None or np.size(LB) == 0 else LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
-    ub = f64(np.broadcast_to(np.asarray(np.inf if UB is None or np.size(UB) == 0 else UB, dtype=np.float64).reshape(-1), (Nhyp,)).copy())
+    lb, ub = _pack.box(LB, UB, Nhyp, open_ended=True)
     Ninit, Nopts = int(options.get("Ninit", 1024)), int(options.get("Nopts", 3))
     if options.get("Design") is not None:
         design = np.atleast_2d(np.asarray(options["Design"], dtype=np.float64))
@@ -567,25 +524,10 @@ def gplite_train_optimize(gp, hyp0, LB, UB, PLB=None, PUB=None, hprior=None, opt
     rows = design.shape[0]
     if design.ndim != 2 or design.shape[1] != Nhyp or (Ninit > 0 and rows != Ninit):
         raise ValueError("gplite_train_optimize: the design must be Ninit x Nhyp")
-    a = GpTrainArgs()
-    a.struct_size = C.sizeof(GpTrainArgs)
-    a.N, a.D, a.Nhyp, a.meanfun = Np, D, Nhyp, int(gp["meanfun"])
-    nf = [int(v) for v in (list(gp["noisefun"]) + [0, 0, 0])[:3]]
-    for i in range(3):
-        a.noisefun[i] = nf[i]
-    a.X, a.y, a.s2 = ptr(X), ptr(y), ptr(s2)
-    keep = []
-    if hprior is not None and hprior.get("mu") is not None and np.size(hprior.get("mu")) > 0:
-        mu = f64(np.asarray(hprior["mu"], dtype=np.float64).reshape(-1))
-        sg = f64(np.asarray(hprior["sigma"], dtype=np.float64).reshape(-1))
-        df = hprior.get("df")
-        df = None if df is None or np.size(df) == 0 else f64(np.asarray(df, dtype=np.float64).reshape(-1))
-        if mu.size != Nhyp or sg.size != Nhyp or (df is not None and df.size != Nhyp):
-            raise ValueError("gplite_train_optimize: hprior.mu / sigma / df need one entry per hyper-parameter")
-        keep += [mu, sg, df]
-        a.prior_mu, a.prior_sigma, a.prior_df = ptr(mu), ptr(sg), ptr(df)
+    a.Nhyp = Nhyp
+    keep.append(_pack.hyper_prior(a, hprior, Nhyp, "gplite_train_optimize", needs_mu=True))
     a.LB, a.UB, a.design = ptr(lb), ptr(ub), ptr(design)
-    a.Ninit, a.N0, a.Nopts, a.Ncov = (rows if Ninit > 0 else 0), rows, Nopts, D + 1
+    a.Ninit, a.N0, a.Nopts, a.Ncov = (rows if Ninit > 0 else 0), rows, Nopts, a.D + 1
     a.TolFun = float(options.get("TolFun", 1e-5))
     a.MaxIter, a.MaxFunEvals = int(options.get("MaxIter", 1000)), int(options.get("MaxFunEvals", 3000))
     W = options.get("W")
@@ -596,18 +538,17 @@ def gplite_train_optimize(gp, hyp0, LB, UB, PLB=None, PUB=None, hprior=None, opt
     hyp, nll, hs = np.zeros((Nhyp, n_o), order="F"), np.zeros(n_o), np.zeros(Nhyp)
     its, fcs, efs = np.zeros(n_o, dtype=np.int32), np.zeros(n_o, dtype=np.int64), np.zeros(n_o, dtype=np.int32)
     best, perf = C.c_int32(0), C.c_int64(0)
-    i32p = C.POINTER(C.c_int32)
+    i32p = _pack.i32p
     a.fill_fvals, a.fill_order, a.widths_default = ptr(fs), fo.ctypes.data_as(i32p), ptr(wd)
     a.hyp, a.nll, a.best, a.hyp_start = ptr(hyp), ptr(nll), C.pointer(best), ptr(hs)
-    a.iterations, a.funccount, a.exitflag = its.ctypes.data_as(i32p), fcs.ctypes.data_as(C.POINTER(C.c_int64)), efs.ctypes.data_as(i32p)
+    a.iterations, a.funccount, a.exitflag = its.ctypes.data_as(i32p), fcs.ctypes.data_as(_pack.i64p), efs.ctypes.data_as(i32p)
     a.performed = C.pointer(perf)
     if cap > 0:
         hx, hf, hk = np.zeros((n_o, cap, Nhyp)), np.zeros((n_o, cap)), np.zeros((n_o, cap), dtype=np.int32)
         a.hist_cap, a.hist_x, a.hist_f, a.hist_k = cap, ptr(hx), ptr(hf), hk.ctypes.data_as(i32p)
     ctx.check(ctx.lib.vbmc_gp_train_optimize(ctx.h, C.byref(a)))
     if Ninit <= 0:   # :255, the zero widths repaired as in :258-267
-        bc = lambda v, dflt: np.broadcast_to(np.asarray(dflt if v is None or np.size(v) == 0 else v, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
-        wd = bc(PUB, ub) - bc(PLB, lb)
+        wd = _pack.row(PUB, Nhyp, ub) - _pack.row(PLB, Nhyp, lb)
         z = wd == 0
         if np.any(z) and rows > 1:
             wd[z] = np.std(design[fo], axis=0, ddof=1)[z]
@@ -628,8 +569,6 @@ def gplite_train(hyp0, Ns, X, y, covfun=1, meanfun=None, noisefun=None, s2=None,
     gplite_post (:474).  Out of scope and refused: options.LogP (the ESS short-cut of :179-198), a Sampler other than
     'slicesample', and the covariance / mean / noise-function bound defaults of :95-158 -- the caller passes LB, UB (hprior.LB /
     hprior.UB are read too) and PLB, PUB.  options beyond the reference's: W, seed, S, MaxIter, MaxFunEvals."""
-    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-
     options = dict(options or {})
     hprior = dict(hprior or {})
     if options.get("LogP") is not None and np.size(options["LogP"]) > 0:
@@ -663,8 +602,8 @@ def gplite_train(hyp0, Ns, X, y, covfun=1, meanfun=None, noisefun=None, s2=None,
         df = pad(hprior.get("df"))
         df[np.isnan(df)] = float(options.get("DfBase", 7))                       # :113-117
         prior = {"mu": pad(hprior.get("mu")), "sigma": pad(hprior.get("sigma")), "df": df}
-    LBv = np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (Nhyp,)).copy()
-    UBv = np.maximum(LBv, np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (Nhyp,)))   # :142
+    LBv, UBv = _pack.box(LB, UB, Nhyp)
+    UBv = np.maximum(LBv, UBv)                                                   # :142
     Thin = int(options.get("Thin", 5))
     tol = float(options.get("TolOptMCMC", 1e-3)) if Ns > 0 else float(options.get("TolOpt", 1e-5))     # :163-167
     oo = {"Ninit": int(options.get("Ninit", 2 ** 10)), "Nopts": int(options.get("Nopts", 3)), "TolFun": tol}
@@ -691,12 +630,8 @@ def gplite_train(hyp0, Ns, X, y, covfun=1, meanfun=None, noisefun=None, s2=None,
 
 def gp_surrogate_sample_rng_dump(seed, E, H, M):
     """U (64 x H x E x M) that ``gplite_sample_device(..., seed=seed)`` consumes (vbmc_gp_surrogate_sample_rng_dump: a pure host function)."""
-    from ._lib import load
-
     U = np.zeros((64, int(H), int(E), int(M)), order="F")
-    st = load().vbmc_gp_surrogate_sample_rng_dump(C.c_uint64(int(seed)), int(E), int(H), int(M), ptr(U))
-    if st != 0:
-        raise ValueError("vbmc_gp_surrogate_sample_rng_dump: bad arguments")
+    host_dump("vbmc_gp_surrogate_sample_rng_dump", seed, E, H, M, U)
     return U
 
 
@@ -711,23 +646,18 @@ def gplite_sample_device(gp, Ns, LB, UB, *, vp=None, x0=None, E=1, W=0, thin=1, 
     ``uniforms`` (64 x H x E x Mmax): parity mode; the library's own generator keyed by ``seed`` otherwise.
     Returns a dict: X (Ns x D), Xt (Nm x D x E), logp (E x Nm), x0 (E x W x D, the clipped start), VarThresh, sn2_avg, sn2_nn (with
     ``noise``), funccount, performed, rounds, behind."""
-    from ._lib import GsArgs
-
     engine = engine or default_engine()
     ctx = engine.ctx
     dgp = _device_gp_with_noise(engine, gp)
     D, S = int(np.asarray(gp["X"]).shape[1]), len(gp["post"])
     Ns, E = int(Ns), int(E)
     Wn = int(W) if W else 2 * (D + 1)
-    keep = {"LB": f64(np.broadcast_to(np.asarray(LB, dtype=np.float64).reshape(-1), (D,)).copy()),
-            "UB": f64(np.broadcast_to(np.asarray(UB, dtype=np.float64).reshape(-1), (D,)).copy())}
-    a = GsArgs()
-    a.struct_size = C.sizeof(GsArgs)
-    a.D, a.S, a.E, a.W, a.Ns = D, S, E, int(W), Ns
-    a.thin, a.burnin, a.spec, a.chunk = int(thin), -1 if burnin is None else int(burnin), int(spec), int(chunk)
-    a.max_steps, a.max_shrink, a.origflag = int(max_steps), int(max_shrink), int(bool(origflag))
+    keep = list(_pack.box(LB, UB, D))
+    a = new_args(GsArgs)
+    a.D, a.S, a.E, a.origflag = D, S, E, int(bool(origflag))
+    _pack.sampler_opts(a, W, Ns, thin, burnin, spec, max_steps, max_shrink, chunk, seed)
     a.beta, a.VarThresh = float(beta), float(VarThresh)
-    a.LB, a.UB = ptr(keep["LB"]), ptr(keep["UB"])
+    a.LB, a.UB = ptr(keep[0]), ptr(keep[1])
     if x0 is not None:
         x0 = np.asarray(x0, dtype=np.float64)
         if x0.ndim == 2:
@@ -736,28 +666,17 @@ def gplite_sample_device(gp, Ns, LB, UB, *, vp=None, x0=None, E=1, W=0, thin=1, 
             raise ValueError("gplite_sample_device: x0 must be E x W x D = %d x W x %d" % (E, D))
         Wn = x0.shape[1]
         a.W = Wn
-        keep["x0"] = f64(np.transpose(x0, (1, 2, 0)))       # W x D x E
-        a.x0 = ptr(keep["x0"])
+        keep.append(f64(np.transpose(x0, (1, 2, 0))))       # W x D x E
+        a.x0 = ptr(keep[-1])
     if uniforms is not None:
-        keep["U"] = f64(np.asarray(uniforms, dtype=np.float64))
-        if keep["U"].ndim != 4 or keep["U"].shape[:3] != (64, Wn // 2, E):
-            raise ValueError("gplite_sample_device: uniforms must be 64 x H x E x Mmax = 64 x %d x %d x Mmax" % (Wn // 2, E))
-        a.rng_mode, a.Mmax, a.U = 1, keep["U"].shape[3], ptr(keep["U"])
-    a.seed = int(seed) & (2 ** 64 - 1)
+        keep.append(_pack.sampler_uniforms(a, uniforms, Wn // 2, E, "gplite_sample_device", axis="E"))
+        a.rng_mode = 1
     Nnn = 0
     if noise is not None:
-        N = np.asarray(gp["X"]).shape[0]
-        keep["xr"] = f64(np.asarray(noise["X_rescaled"], dtype=np.float64).reshape(N, D))
-        keep["gl"] = f64(np.asarray(noise["gplengthscale"], dtype=np.float64).reshape(D))
-        keep["sn"] = f64(np.asarray(noise["sn2new"], dtype=np.float64).reshape(N))
-        a.X_rescaled, a.gplengthscale, a.sn2new = ptr(keep["xr"]), ptr(keep["gl"]), ptr(keep["sn"])
+        keep += _pack.nn_noise(a, noise["gplengthscale"], noise["X_rescaled"], noise["sn2new"], np.asarray(gp["X"]).shape[0], D)
         a.Nnn = int(noise.get("Nnn", 0) or 0)
         Nnn = a.Nnn if a.Nnn > 0 else 20000
-    desc = None
-    if vp is not None:
-        from .vptools import _Desc
-
-        desc = _Desc(vp)
+    desc = None if vp is None else _pack.Desc(vp)
     Nm = max(-(-max(Ns, 1) // max(E, 1)), 1)
     n, Wp, Ep = max(Ns, 1), max(Wn, 1), max(E, 1)
     out = {}
@@ -777,12 +696,9 @@ def gplite_sample_device(gp, Ns, LB, UB, *, vp=None, x0=None, E=1, W=0, thin=1, 
     if noise is not None:
         out["sn2_nn"] = np.zeros(Nnn)
         a.sn2_nn = ptr(out["sn2_nn"])
-    fc, pf, rounds = C.c_int64(), C.c_int64(), (C.c_int64 * 2)()
-    a.funccount, a.performed = C.pointer(fc), C.pointer(pf)
-    a.rounds = C.cast(rounds, C.POINTER(C.c_int64))
+    counts = _pack.counters(a)
     ctx.check(ctx.lib.vbmc_gp_surrogate_sample(ctx.h, dgp.h, desc.ref() if desc is not None else None, C.byref(a)))
-    out.update(x0=np.ascontiguousarray(np.transpose(x0o, (2, 0, 1))), VarThresh=float(vt[0]), sn2_avg=float(sa[0]), funccount=int(fc.value),
-               performed=int(pf.value), rounds=int(rounds[0]), behind=int(rounds[1]))
+    out.update(counts(), x0=np.ascontiguousarray(np.transpose(x0o, (2, 0, 1))), VarThresh=float(vt[0]), sn2_avg=float(sa[0]))
     return out
 
 
@@ -809,8 +725,6 @@ def gplite_sample(gp, Ns, x0=None, method="parallel", logprior=None, beta=0, Var
     'slicesample', a ``logprior`` and proposal functions raise VbmcUnsupported.  A GP beyond the range in which the prediction keeps
     inv(L') resident is sampled by the host-driven ``ensemble_slice_sample`` over device ``gplite_pred`` calls.
     nargout=2 adds the dict of ``gplite_sample_device`` (None on the host-driven path)."""
-    from ._lib import VBMC_ERR_UNSUPPORTED, VbmcUnsupported
-
     if method is None or method == "":
         method = "slicesample"                                                   # :5
     if str(method).lower() != "parallel":
@@ -845,8 +759,6 @@ def gplite_sample(gp, Ns, x0=None, method="parallel", logprior=None, beta=0, Var
     except VbmcUnsupported as err:
         if "resident" not in str(err):
             raise
-        from .acq import ensemble_slice_sample
-
         engine = engine or default_engine()
         Nm = -(-Ns // E)
         xs, _ = ensemble_slice_sample(_log_gpfun_host(gp, float(beta), float(VarThresh), engine), x0, Nm, LB, UB, thin=int(thin),

@@ -15,35 +15,11 @@ import warnings
 
 import numpy as np
 
-from . import _lib
-from ._lib import VbmcUnsupported, f64, ptr
-
-
-def _trinfo(vp):
-    tr = vp.get("trinfo") if isinstance(vp, dict) else None
-    if tr is None or len(tr) == 0:
-        return None
-    return tr
-
-
-def _row(tr, name, D):
-    return np.asarray(tr[name], dtype=np.float64).reshape(D)
-
-
-def _scale(tr, D):
-    """warpvars_vbmc.m:66-69: the scale row counts only where it differs from one"""
-    sc = tr.get("scale")
-    if sc is None or np.size(sc) == 0:
-        return None
-    sc = np.asarray(sc, dtype=np.float64).reshape(D)
-    return sc if np.any(sc != 1) else None
-
-
-def _rot(tr, D):
-    R = tr.get("R_mat")
-    if R is None or np.size(R) == 0:
-        return None
-    return np.asarray(R, dtype=np.float64).reshape(D, D)
+from . import _lib, mixture
+from ._lib import VbmcUnsupported, f64, host_dump, new_args, ptr
+from ._pack import U64, Desc as _Desc, i32p, i64p, trinfo_rot as _rot, trinfo_row as _row, trinfo_scale as _scale
+from .elbo import default_engine
+from .gplite import gplite_sample_device
 
 
 def warpvars(x, action, trinfo):
@@ -99,46 +75,8 @@ def warpvars(x, action, trinfo):
         return p if act == "l" else np.exp(p)
 
 
-class _Desc:
-    """A vbmc_vp_desc and the arrays it points at"""
-
-    def __init__(self, vp):
-        D, K = int(vp["D"]), int(vp["K"])
-        self.D, self.K = D, K
-        self.keep = [f64(np.asarray(vp["mu"], dtype=np.float64).reshape(D, K)), f64(np.asarray(vp["sigma"], dtype=np.float64).reshape(K)),
-                     f64(np.asarray(vp["lambda"], dtype=np.float64).reshape(D)), f64(np.asarray(vp["w"], dtype=np.float64).reshape(K))]
-        d = _lib.VpDesc()
-        d.struct_size = C.sizeof(_lib.VpDesc)
-        d.D, d.K = D, K
-        d.mu, d.sigma, d.w = ptr(self.keep[0]), ptr(self.keep[1]), ptr(self.keep[3])
-        setattr(d, "lambda", ptr(self.keep[2]))
-        tr = _trinfo(vp)
-        if tr is not None:
-            typ = np.ascontiguousarray(np.asarray(tr["type"]).reshape(D).astype(np.int32))
-            rows = [f64(_row(tr, n, D)) for n in ("lb_orig", "ub_orig", "mu", "delta")]
-            sc, R = _scale(tr, D), _rot(tr, D)
-            self.keep += [typ] + rows
-            d.type = typ.ctypes.data_as(C.POINTER(C.c_int32))
-            d.lb, d.ub, d.tmu, d.tdelta = (ptr(r) for r in rows)
-            if sc is not None:
-                sc = f64(sc)
-                self.keep.append(sc)
-                d.scale = ptr(sc)
-            if R is not None:
-                R = f64(R)
-                self.keep.append(R)
-                d.R = ptr(R)
-        self.d = d
-
-    def ref(self):
-        return C.byref(self.d)
-
-
 def _engine(engine):
-    if engine is None:
-        from .elbo import default_engine
-        engine = default_engine()
-    return engine
+    return default_engine() if engine is None else engine
 
 
 def _block(block):
@@ -161,14 +99,12 @@ def split_size(w, N, balanceflag):
 def vp_rnd_rng_dump(seed, N, D, w, balanceflag=False):
     """(B, perm): the block ``seed`` stands for -- B (M, D + 1), row i the slots of sample i (a uniform, then D standard normals) --
     and the permutation perm (N,): output row r is sample perm[r]."""
-    lib = _lib.load()
     w = f64(np.asarray(w, dtype=np.float64).reshape(-1))
     N, D, K = int(N), int(D), w.size
     B = np.zeros((N + K, D + 1), dtype=np.float64)
     perm = np.zeros(N, dtype=np.int64)
-    st = lib.vbmc_vp_rnd_rng_dump(C.c_uint64(int(seed)), N, D, K, 1 if balanceflag else 0, ptr(w), ptr(B), perm.ctypes.data_as(C.POINTER(C.c_int64)))
-    if st != _lib.VBMC_OK:
-        raise _lib.VbmcHipError(st, "vbmc_vp_rnd_rng_dump(N=%d, D=%d, K=%d)" % (N, D, K))
+    host_dump("vbmc_vp_rnd_rng_dump", seed, N, D, K, 1 if balanceflag else 0, w, B, perm,
+              hip_error="vbmc_vp_rnd_rng_dump(N=%d, D=%d, K=%d)" % (N, D, K))
     return B[: split_size(w, N, balanceflag)].copy(), perm
 
 
@@ -188,7 +124,8 @@ def vbmc_pdf(vp, X, origflag=True, logflag=False, transflag=False, df=np.inf, *,
 
 
 def vbmc_rnd(vp, N, origflag=True, balanceflag=False, df=np.inf, *, seed=0, block=None, nargout=2, engine=None):
-    """[X,I] = vbmc_rnd(vp,N,origflag,balanceflag,df) on the device (Gaussian components; 'gp' and a finite df: VbmcUnsupported)"""
+    """[X,I] = vbmc_rnd(vp,N,origflag,balanceflag,df), the DEVICE form (mixture.vbmc_rnd is the host draw with a NumPy rng).  Gaussian
+    components; 'gp' and a finite df: VbmcUnsupported."""
     engine = _engine(engine)
     ctx = engine.ctx
     d = _Desc(vp)
@@ -200,16 +137,15 @@ def vbmc_rnd(vp, N, origflag=True, balanceflag=False, df=np.inf, *, seed=0, bloc
     I = np.zeros(N, dtype=np.int32)
     B = _block(block)
     ctx.check(ctx.lib.vbmc_vp_rnd(ctx.h, d.ref(), N, int(bool(origflag)), bal, float(df), C.c_uint64(int(seed)), ptr(B), ptr(X),
-                                  I.ctypes.data_as(C.POINTER(C.c_int32))))
+                                  I.ctypes.data_as(i32p)))
     return (X, I.astype(int)) if nargout > 1 else X
 
 
 def vbmc_moments(vp, origflag=True, Ns=1e6, *, seed=0, block=None, engine=None):
-    """[mubar,Sigma] = vbmc_moments(vp,origflag,Ns): the original space by Ns balanced draws on the device (the samples never reach
-    memory); the transformed space (origflag = 0) is the analytic host form."""
+    """[mubar,Sigma] = vbmc_moments(vp,origflag,Ns), the DEVICE form: the original space by Ns balanced draws on the device (the samples
+    never reach memory); the transformed space (origflag = 0) is the analytic host form, mixture.vbmc_moments."""
     if not origflag:
-        from .acq import vbmc_moments as _analytic
-        return _analytic(vp, False)
+        return mixture.vbmc_moments(vp, False)
     engine = _engine(engine)
     ctx = engine.ctx
     d = _Desc(vp)
@@ -273,9 +209,8 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
     d1, d2 = _Desc(vp1), _Desc(vp2)
     Ns, D = int(Ns), d1.D
     n = 8192 if not nkde else int(nkde)
-    a = _lib.MtvArgs()
-    a.struct_size = C.sizeof(_lib.MtvArgs)
-    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & (2 ** 64 - 1)
+    a = new_args(_lib.MtvArgs)
+    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & U64
     B1, B2 = _block(block1), _block(block2)
     a.block1, a.block2 = ptr(B1), ptr(B2)
     mtv = np.zeros(D, dtype=np.float64)
@@ -289,8 +224,8 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
         st = {"mesh": np.zeros((2, D, 2)), "counts": np.zeros((2, D, n), dtype=np.int32), "nuniq": np.zeros((2, D), dtype=np.int64),
               "tstar": np.zeros((2, D)), "density": np.zeros((2, D, n))}
         a.mesh, a.tstar, a.density = ptr(st["mesh"]), ptr(st["tstar"]), ptr(st["density"])
-        a.counts = st["counts"].ctypes.data_as(C.POINTER(C.c_int32))
-        a.nuniq = st["nuniq"].ctypes.data_as(C.POINTER(C.c_int64))
+        a.counts = st["counts"].ctypes.data_as(i32p)
+        a.nuniq = st["nuniq"].ctypes.data_as(i64p)
     ctx.check(ctx.lib.vbmc_vp_mtv(ctx.h, d1.ref(), d2.ref(), C.byref(a)))
     out = (mtv, xx1, xx2)[: max(1, min(int(nargout), 3))]
     if stages:
@@ -310,9 +245,8 @@ def vp_diagnostics(vp_array, Ns=1e5, *, seed=0, nkde=None, nquad=None, stages=Fa
     descs = [_Desc(v) for v in vp_array]
     R, D, Ns = len(descs), descs[0].D if descs else 0, int(Ns)
     n = 8192 if not nkde else int(nkde)
-    a = _lib.DiagArgs()
-    a.struct_size = C.sizeof(_lib.DiagArgs)
-    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & (2 ** 64 - 1)
+    a = new_args(_lib.DiagArgs)
+    a.nkde, a.nquad, a.Ns, a.seed = int(nkde or 0), int(nquad or 0), Ns, int(seed) & U64
     out = {"kl_mat": np.zeros((R, R), order="F"), "mtv": np.zeros((R, R, D)), "maxmtv_mat": np.zeros((R, R), order="F")}
     for k in ("kl_mat", "mtv", "maxmtv_mat"):
         if k in outputs:
@@ -323,8 +257,8 @@ def vp_diagnostics(vp_array, Ns=1e5, *, seed=0, nkde=None, nquad=None, stages=Fa
         out.update(mesh=np.zeros((R, D, 2)), counts=np.zeros((R, D, n), dtype=np.int32), nuniq=np.zeros((R, D), dtype=np.int64),
                    tstar=np.zeros((R, D)), density=np.zeros((R, D, n)))
         a.mesh, a.tstar, a.density = ptr(out["mesh"]), ptr(out["tstar"]), ptr(out["density"])
-        a.counts = out["counts"].ctypes.data_as(C.POINTER(C.c_int32))
-        a.nuniq = out["nuniq"].ctypes.data_as(C.POINTER(C.c_int64))
+        a.counts = out["counts"].ctypes.data_as(i32p)
+        a.nuniq = out["nuniq"].ctypes.data_as(i64p)
     if draws:
         xx = np.zeros((R, D, max(Ns, 0)))                       # run i, column d, row r: the ABI's Ns x D x R column-major
         a.xx = ptr(xx)
@@ -503,8 +437,6 @@ def gpsample_vbmc(vp, gp, Ns, origflag=True, *, E=1, seed=0, Nnn=0, bounds=None,
     GP carries s2 (VarThresh = max(1, sn2_avg), :30-38), W = 2 (D + 1) starting walkers per ensemble drawn from ``vp`` (:41), the
     'parallel' chain of gplite_sample on its default box, and the way back to the original space (:43-45).  E > 1 runs that many
     independent ensembles, each with its own burn-in.  nargout=2 adds the dict of ``gplite.gplite_sample_device``."""
-    from .gplite import gplite_sample_device
-
     X = np.asarray(gp["X"], dtype=np.float64)
     D = X.shape[1]
     if bounds is None or np.size(bounds) == 0:                                   # gplite_sample.m:16-20
