@@ -1102,6 +1102,64 @@ typedef struct vbmc_diag_args {
 } vbmc_diag_args;
 vbmc_status vbmc_vp_diagnostics(vbmc_ctx* ctx, int32_t R, const vbmc_vp_desc* const* vps, const vbmc_diag_args* args);
 
+/*
+ * vbmc_vp_mode: the mode of the variational posterior, vbmc_mode.m, in one call (an addition, backward compatible: VBMC_ABI_VERSION is
+ * unchanged).  One launch optimises from every start; the optimiser is the library's own, not fmincon.
+ *
+ * THE OBJECTIVE.  origflag = 0: log q(u), the mixture in the transformed space.  origflag != 0: the log density in the original space,
+ * log q(T(x)) - logJ, which the library maximises over u as g(u) = log q(u) - logprob(u), logprob what warpvars_vbmc(u, 'logprob',
+ * trinfo) returns (vbmc_pdf.m:115): T is a bijection, so the maximiser over x is the inverse transform of the maximiser over u.  The
+ * objective stays in the log domain: a start whose density underflows still has a finite objective and a gradient, and is optimised
+ * (the reference hands fmincon -Inf there).
+ *
+ * THE STARTS are the means of S = min(nmax, K) components.  nmax >= K: all of them in index order.  nmax < K: the objective is
+ * evaluated at all K means and the first nmax of a stable ascending sort of its negative are kept (vbmc_mode.m:23-28).  With origflag
+ * the reference ranks by the original-space density evaluated AT the transformed-space means (vbmc_mode.m:24); the library ranks by
+ * the objective at the starts themselves.
+ *
+ * THE OPTIMISER, per start: BFGS on an inverse-Hessian approximation that starts from diag((sigma_c lambda_d)^2) of the start's own
+ * component c, direction d = -H grad F for F = -g, backtracking candidates u + 2^-k d, k = 0 .. 31, the first with
+ * F(u + t d) <= F(u) + 1e-4 t grad F' d taken; the update is skipped unless y's > 1e-10 |y| |s|.  It stops with
+ *   VBMC_MODE_STOP_GRAD     max_d |grad_d| <= tol_grad (tested before every iteration, the start included),
+ *   VBMC_MODE_STOP_STEP     no candidate was acceptable,
+ *   VBMC_MODE_STOP_MAXITER  max_iter iterations were made (0: 200; at most 1000).
+ * The objective never decreases along an optimisation: fs[s] >= f0[s].
+ *
+ * THE ANSWER is the start with the largest fs, the first of equal ones: idx, fval = fs[idx], and x (D) = xs(idx, :).  us is the
+ * maximiser in the transformed space; xs is us for origflag = 0 and otherwise its inverse transform with vbmc_vp_rnd's clamp to
+ * [lb + eps(lb), ub - eps(ub)] (the reference keeps sqrt(eps) from the bounds).  Per start s < S (the arrays are S long, us and xs
+ * S x D column-major; each may be NULL): start_comp the component (from 0), f0 the objective at the start, iters, nfev the objective
+ * evaluations (the line search evaluates four candidates at a time) and stop.  S_out receives S.
+ *
+ * Posteriors and transforms as vbmc_vp_pdf takes them (D <= 32, K <= 512, types 0 .. 3, scale, rotation, no trinfo); types 4 .. 13:
+ * VBMC_ERR_UNSUPPORTED.  A NULL context, a wrong struct_size, tol_grad that is not positive, max_iter outside 0 .. 1000, a missing x,
+ * fval or idx and a posterior that is not finite are refused, in this order, with VBMC_ERR_INVALID before anything runs.  Results are
+ * identical from call to call.
+ */
+#define VBMC_MODE_STOP_GRAD 1
+#define VBMC_MODE_STOP_STEP 2
+#define VBMC_MODE_STOP_MAXITER 3
+typedef struct vbmc_mode_args {
+  uint32_t struct_size;
+  int32_t nmax;           /* <= 0: 20 */
+  int32_t origflag;
+  int32_t max_iter;       /* 0: 200; else 1 .. 1000 */
+  double tol_grad;        /* > 0; the shims pass 1e-6 */
+  double* x;              /* D */
+  double* fval;           /* 1 */
+  int32_t* idx;           /* 1: the start that won, from 0 */
+  int32_t* S_out;         /* 1 */
+  int32_t* start_comp;    /* S */
+  double* f0;             /* S */
+  double* us;             /* S x D column-major */
+  double* xs;             /* S x D column-major */
+  double* fs;             /* S */
+  int32_t* iters;         /* S */
+  int32_t* nfev;          /* S */
+  int32_t* stop;          /* S: VBMC_MODE_STOP_* */
+} vbmc_mode_args;
+vbmc_status vbmc_vp_mode(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_mode_args* args);
+
 /* Test hook: one cosine transform of kde1d (forward: dct1d with a2 = (a_k / 2)^2, a2 may be NULL; inverse: idct1d) of C columns of n
  * values (n a power of two in 256 .. 16384, column c at [c n ..]) by the kernel of vbmc_vp_mtv (kernel 0) or of vbmc_vp_diagnostics
  * (kernel 1), launched reps times; out / a2 are the last launch's, ms[reps] (may be NULL) each launch's HIP-event duration. */

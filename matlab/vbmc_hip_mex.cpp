@@ -853,6 +853,24 @@ static int cmd_vp_diag(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
   return done(vbmc_vp_diagnostics(g_ctx, R, p.data(), &a));
 }
 
+// -> [x,fval,idx] of vbmc_mode(vp,nmax,origflag): the mode (1 x D), its log density and the winning start (from 0): vbmc_vp_mode, matlab/vbmc_hip_mode.m
+static int cmd_vp_mode(int nlhs, mxArray* plhs[], int, const mxArray* prhs[]) {
+  vbmc_vp_desc d;
+  std::vector<int32_t> ty;
+  if (fill_vp_desc(d, prhs[1], ty)) return 1;
+  plhs[0] = mxCreateDoubleMatrix(1, d.D, mxREAL);
+  mxArray* fval = mxCreateDoubleMatrix(1, 1, mxREAL);
+  mxArray* idx = mxCreateDoubleMatrix(1, 1, mxREAL);
+  int32_t won = 0;
+  vbmc_mode_args a = zeroed<vbmc_mode_args>();
+  a.nmax = (int32_t)mxGetScalar(prhs[2]); a.origflag = mxGetScalar(prhs[3]) != 0; a.tol_grad = mxGetScalar(prhs[4]);
+  a.x = mxGetDoubles(plhs[0]); a.fval = mxGetDoubles(fval); a.idx = &won;
+  const vbmc_status st = vbmc_vp_mode(g_ctx, &d, &a);
+  mxGetDoubles(idx)[0] = (double)won;
+  give(nlhs, plhs, 1, {fval, idx});
+  return done(st);
+}
+
 // -> [acq,fbar,vtot], Nstar x 1 each: the IQR acquisition functions at the rows of Xs; his: the state of 'is_create'
 static int cmd_acq_iqr(int nlhs, mxArray* plhs[], int, const mxArray* prhs[]) {
   vbmc_acq_is* is = handle_in<vbmc_acq_is>(prhs[2]);
@@ -1092,6 +1110,7 @@ static const Command commands[] = {
     {"vp_kldiv", 5, 0, "vp1, vp2, Ns, seed", cmd_vp_kldiv, 0},
     {"vp_mtv", 5, 0, "vp1, vp2, Ns, seed", cmd_vp_mtv, 0},
     {"vp_diag", 4, 0, "Ns, seed, vp1 [, vp2, ...]", cmd_vp_diag, 0},
+    {"vp_mode", 5, 0, "vp, nmax, origflag, tol_grad", cmd_vp_mode, 0},
     {"acq_iqr", 9, 2, "h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar", cmd_acq_iqr, 0},
     {"gp_surrogate_sample", 9, 1, "h, vp, Ns, origflag, LB, UB, noise, opts", cmd_gp_surrogate_sample, 0},
     {"gp_nlz", 7, 0, "Hyp, X, y, s2, meanfun, noisefun", cmd_gp_nlz, 0},

@@ -223,6 +223,22 @@ class DiagArgs(C.Structure):
     ]
 
 
+class ModeArgs(C.Structure):
+    """vbmc_mode_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nmax", C.c_int32), ("origflag", C.c_int32), ("max_iter", C.c_int32),
+        ("tol_grad", C.c_double),
+        ("x", _dp), ("fval", _dp),
+        ("idx", C.POINTER(C.c_int32)), ("S_out", C.POINTER(C.c_int32)), ("start_comp", C.POINTER(C.c_int32)),
+        ("f0", _dp), ("us", _dp), ("xs", _dp), ("fs", _dp),
+        ("iters", C.POINTER(C.c_int32)), ("nfev", C.POINTER(C.c_int32)), ("stop", C.POINTER(C.c_int32)),
+    ]
+
+
+MODE_STOP = {1: "grad", 2: "step", 3: "maxiter"}     # VBMC_MODE_STOP_*
+
+
 class GsArgs(C.Structure):
     """vbmc_gs_args (include/vbmc_hip.h)"""
     _fields_ = [
@@ -345,6 +361,7 @@ def load():
     lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
     lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
     lib.vbmc_vp_diagnostics.argtypes = [vp, C.c_int32, C.POINTER(vpd), C.POINTER(DiagArgs)]
+    lib.vbmc_vp_mode.argtypes = [vp, vpd, C.POINTER(ModeArgs)]
     lib.vbmc_test_dct.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     lib.vbmc_gp_surrogate_sample.argtypes = [vp, vp, vpd, C.POINTER(GsArgs)]
     lib.vbmc_test_exp.argtypes =[vp, C.c_int, C.c_int, _dp, _dp]

@@ -1,6 +1,8 @@
 // C-ABI entry points of the variational-posterior tools: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments, vbmc_vp_kldiv and
 // vbmc_vp_rnd_rng_dump (include/vbmc_hip.h).  The kernels are vp_tools_kernels.h; validation, the constants of a call and the upload of
-// a posterior are vp_tools_host.h.  Here: the launches, and the O(D^2) tail of the moments.
+// a posterior are vp_tools_host.h.  Here: the launches, and the O(D^2) tail of the moments.  vbmc_vp_mode: its refusals here, the kernel
+// mode_kernels.h, the launches and the winner rule mode_host.h.
+#include "mode_host.h"
 #include "parity_rng.h"
 #include "vp_tools_host.h"
 
@@ -200,4 +202,16 @@ extern "C" vbmc_status vbmc_vp_kldiv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, con
   HIP_TRY(ctx, hipStreamSynchronize(st));
   for (int s = 0; s < 2; ++s) { const double v = -(ho[s] / (double)Ns); kls[s] = v > 0.0 ? v : 0.0; }   // vbmc_kldiv.m:77, :84, :88 (max ignores a NaN)
   return VBMC_OK;
+}
+
+extern "C" vbmc_status vbmc_vp_mode(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_mode_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  const char* who = "vbmc_vp_mode";
+  if (!args || args->struct_size != sizeof(vbmc_mode_args)) return set_err(ctx, VBMC_ERR_INVALID, "%s: struct_size mismatch", who);
+  if (!(args->tol_grad > 0.0)) return set_err(ctx, VBMC_ERR_INVALID, "%s: tol_grad must be positive", who);
+  if (args->max_iter < 0 || args->max_iter > MODE_ITER_CAP) return set_err(ctx, VBMC_ERR_INVALID, "%s: max_iter = %d outside 0 .. %d", who, args->max_iter, MODE_ITER_CAP);
+  if (!args->x || !args->fval || !args->idx) return set_err(ctx, VBMC_ERR_INVALID, "%s: x, fval and idx are required", who);
+  VptPack pk;
+  VB_TRY(vpt_pack(ctx, who, vp, 0.0, pk));
+  return mode_run(ctx, vp, args, pk);
 }

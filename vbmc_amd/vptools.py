@@ -233,6 +233,55 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
     return out if len(out) > 1 else out[0]
 
 
+def vbmc_mode(vp, nmax=20, origflag=True, *, nargout=1, details=False, max_iter=0, tol_grad=1e-6, engine=None):
+    """[x,vp] = vbmc_mode(vp,nmax,origflag) on the device in one call (vbmc_vp_mode): the mode of the variational posterior, in the
+    original space (origflag, the default) or the transformed one.  With origflag a stored ``vp["mode"]`` is returned without a device
+    (vbmc_mode.m:18-19) and nargout=2 returns a copy of ``vp`` with ``mode`` stored (:53-55).  details=True appends a dict with fval,
+    idx and per start start_comp, f0, us, xs, fs, iters, nfev and stop (the names of _lib.MODE_STOP).
+
+    Intentional divergences from the reference (include/vbmc_hip.h has the whole statement): the optimiser is the library's BFGS on
+    the smooth objective in the transformed space, not fmincon in the box; with origflag the starts are ranked by the objective at
+    the starts themselves (:24 evaluates the original-space density at transformed-space coordinates); the answer is kept eps, not
+    sqrt(eps), from the bounds; a start whose density underflows is still optimised."""
+    origflag = bool(origflag)
+    stored = vp.get("mode") if origflag else None
+    if stored is not None and np.size(stored) > 0 and not details:
+        x = np.array(stored, dtype=np.float64).reshape(-1)
+        return (x, vp) if nargout > 1 else x
+    engine = _engine(engine)
+    ctx = engine.ctx
+    d = _Desc(vp)
+    nmax = _mode_nmax(nmax)
+    S = min(nmax, d.K)
+    a = new_args(_lib.ModeArgs)
+    a.nmax, a.origflag, a.max_iter, a.tol_grad = nmax, int(origflag), int(max_iter), float(tol_grad)
+    x, fval, idx, S_out = np.zeros(d.D), C.c_double(), C.c_int32(), C.c_int32()
+    a.x, a.fval, a.idx, a.S_out = ptr(x), C.pointer(fval), C.pointer(idx), C.pointer(S_out)
+    out = None
+    if details:
+        out = {"start_comp": np.zeros(S, dtype=np.int32), "f0": np.zeros(S), "us": np.zeros((S, d.D), order="F"), "xs": np.zeros((S, d.D), order="F"),
+               "fs": np.zeros(S), "iters": np.zeros(S, dtype=np.int32), "nfev": np.zeros(S, dtype=np.int32), "stop": np.zeros(S, dtype=np.int32)}
+        for k, v in out.items():
+            setattr(a, k, v.ctypes.data_as(i32p) if v.dtype == np.int32 else ptr(v))
+    ctx.check(ctx.lib.vbmc_vp_mode(ctx.h, d.ref(), C.byref(a)))
+    res = (x,)
+    if nargout > 1:
+        vp2 = dict(vp)
+        if origflag:
+            vp2["mode"] = x.copy()
+        res = res + (vp2,)
+    if details:
+        out = {k: np.ascontiguousarray(v) for k, v in out.items()}
+        out.update(fval=float(fval.value), idx=int(idx.value), S=int(S_out.value))
+        res = res + (out,)
+    return res if len(res) > 1 else res[0]
+
+
+def _mode_nmax(nmax):
+    nmax = 20 if nmax is None else int(nmax)
+    return 20 if nmax <= 0 else nmax
+
+
 def vp_diagnostics(vp_array, Ns=1e5, *, seed=0, nkde=None, nquad=None, stages=False, draws=False, outputs=("kl_mat", "mtv", "maxmtv_mat"),
                    engine=None):
     """The pair loop of vbmc_diagnostics.m:116-127 on the device in one call (vbmc_vp_diagnostics).  Run i draws once, with seed + i.
