@@ -10,7 +10,8 @@ import re
 from tests import _abi
 
 ROOT, CSRC = _abi.ROOT, _abi.CSRC
-KERNELS = {"k_diag_cross_kl": (6, 128), "k_diag_dct": (1, 256), "k_diag_integral": (1, 256)}      # instantiations, threads per workgroup
+KERNELS = {"k_diag_cross_kl": (6, 128), "k_diag_dct": (1, 256)}      # instantiations, threads per workgroup (the integral of every pair
+# is k_mtv_integral: tests/test_mtv_build.py)
 
 
 def test_diag_kernels_use_no_scratch(tmp_path):
@@ -81,7 +82,14 @@ def test_refusals_before_anything_is_read():
     order = [body.index(s) for s in ("if (!ctx)", "struct_size != sizeof(vbmc_diag_args)", "if (R < 2)", "if (R > DIAG_MAXR)", "vpt_pack(")]
     assert order == sorted(order), order                                                          # the order of the refusals
     assert "VBMC_ERR_UNSUPPORTED" in body[order[3]:order[3] + 120] and "VBMC_ERR_INVALID" in body[order[2]:order[2] + 120]
-    assert re.search(r'"run %d, dimension %d: [^"]*fminbnd', body)                                # the message names run and dimension
+    # the fminbnd message lives once, in mtv_host.h's pipeline, and names the unit the entry point gives it and the dimension:
+    # "run" here, "posterior" in vbmc_vp_mtv
+    host = open(os.path.join(CSRC, "mtv_host.h")).read()
+    assert len(re.findall(r"fminbnd", host)) == 1 and re.search(r'"%s %d, dimension %d: [^"]*fminbnd[^"]*",\s*unit, c / D \+ 1, c % D \+ 1\)', host)
+    assert re.search(r'kde\.begin\(ctx, who, "run", \*args\)', body) and "fminbnd" not in src
+    mtv = open(os.path.join(CSRC, "abi_vp_mtv.hip")).read()
+    assert re.search(r'kde\.begin\(ctx, who, "posterior", \*args\)', mtv) and "fminbnd" not in mtv
+    assert re.search(r'unit = unit_;', host) and len(re.findall(r"\bunit = ", host)) == 2         # set in begin alone (and its default)
     assert "#define DIAG_MAXR 32" in open(os.path.join(CSRC, "diag_kernels.h")).read()
     lib = _lib.load()
     a = _lib.new_args(_lib.DiagArgs)

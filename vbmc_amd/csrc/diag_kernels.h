@@ -1,7 +1,7 @@
 // The multi-run diagnostics on the device: the pair loop of vbmc_diagnostics.m:116-127 -- vbmc_kldiv.m:72-77 and vbmc_mtv.m on sample
 // matrices (infinite mesh bounds, :35-38, :44-47) for every pair of R runs -- with what is per run done once per run.  Run i's draws
 // are k_vp_draw's (vp_tools_kernels.h); its mesh, counts, cosine coefficients, bandwidth and inverse transform are mtv_kernels.h's
-// kernels over the R D columns, column c = i D + d.  New here:
+// kernels over the R D columns, column c = i D + d, and so is the integral of every pair and dimension (k_mtv_integral).  New here:
 //   k_diag_cross_kl  the draws of run i against the densities of the runs.  Phase 0 (grid nb x 1): the run's own log density at each
 //                    of its points with the rule of vbmc_kldiv.m:75 into own[r].  Phase 1 (grid nb x R): workgroup row j evaluates
 //                    posterior j at the same points, applies the rule of :76 and sums log q_j - log q_i: lane in row order, wave
@@ -17,8 +17,6 @@
 //                    and used for 32 columns; B is 4 inputs x 16 columns.  A wave owns 16 outputs of 32 columns and walks all n inputs
 //                    in index order through one accumulator chain per output, so a column's result depends neither on C nor on the
 //                    grid nor on its neighbours (columns beyond C enter as zeros and are not stored).
-//   k_diag_integral  vbmc_mtv.m:73-78 for every pair and dimension in one launch: k_mtv_integral's sums with the two columns and
-//                    the four sorted mesh ends looked up per pair; grid (partial, dimension, pair), MTV_NBLK partials per entry.
 // Every floating-point sum has a fixed order; nothing depends on the grid, on R or on which other runs are in the call.
 #pragma once
 #include "mtv_kernels.h"
@@ -117,18 +115,9 @@ __global__ void __launch_bounds__(VPT_T) k_diag_cross_kl(DiagKlArgs a) {
       else acc = acc + ((bad ? VPT_LOG_REALMIN : vpt_log(q)) - a.own[r]);
     }
   }
-  if (!a.phase) return;
-  {
-#pragma clang fp contract(off)
-    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
-    if ((tid & 63) == 0) s_w[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-      double s = 0.0;
-      for (int w = 0; w < VPT_T / 64; ++w) s = s + s_w[w];
-      a.partial[(size_t)blockIdx.x * a.R + j] = s;
-    }
-  }
+  if (!a.phase) return;                                     // (the whole workgroup: the phase is the launch's)
+  acc = vpt_block_sum<VPT_T>(acc, s_w, tid);
+  if (tid == 0) a.partial[(size_t)blockIdx.x * a.R + j] = acc;
 }
 
 #define DIAG_DCT_T 256            // threads per workgroup: four waves, 64 outputs
@@ -198,38 +187,5 @@ __global__ void __launch_bounds__(DIAG_DCT_T) k_diag_dct(MtvDctArgs a, int C) {
       a.out[base + row] = s;
       if (a.a2) { const double h = 0.5 * s; a.a2[base + row] = h * h; }
     }
-  }
-}
-
-struct DiagIntArgs {
-  MtvIntArgs m;                   // n, nquad, ntile, msh, yy, mm over the R D columns; D; geo is npair x D x 4; partial MTV_NBLK x 3 D npair
-  const int* pairs;               // npair x 2: the runs i < j of a pair
-  int npair;
-};
-
-__global__ void __launch_bounds__(MTV_T) k_diag_integral(DiagIntArgs A) {
-#pragma clang fp contract(off)
-  __shared__ double s_w[MTV_T / 64];
-  const MtvIntArgs& a = A.m;
-  const int tid = threadIdx.x, d = blockIdx.y, p = blockIdx.z;
-  const int c1 = A.pairs[2 * p] * a.D + d, c2 = A.pairs[2 * p + 1] * a.D + d;
-  const size_t e = (size_t)p * a.D + d, nent = 3 * (size_t)a.D * A.npair;
-  const bool bad = a.msh[4 * c1 + 3] != 0.0 || a.msh[4 * c2 + 3] != 0.0;
-  for (int j = 0; j < 3; ++j) {
-    const double b0 = a.geo[4 * e + j], b1 = a.geo[4 * e + j + 1];
-    const double step = (b1 - b0) / (double)(a.nquad - 1);                               // linspace
-    double acc = 0.0;
-    if (!bad && b1 > b0) {
-      for (int t = blockIdx.x; t < a.ntile; t += gridDim.x) {
-        const int i = t * MTV_T + tid;
-        if (i < a.nquad) {
-          const double x = i == a.nquad - 1 ? b1 : b0 + (double)i * step;
-          const double v = fabs(mtv_spline(a, c1, x) - mtv_spline(a, c2, x));
-          acc = acc + ((i == 0 || i == a.nquad - 1) ? 0.5 * v : v);                      // qtrapz
-        }
-      }
-    }
-    acc = mtv_block_sum(acc, s_w, tid);
-    if (tid == 0) a.partial[(size_t)blockIdx.x * nent + 3 * e + j] = acc;
   }
 }

@@ -1,18 +1,21 @@
-// The marginal total variation between two posteriors on the device: vbmc_mtv.m:24-79 with shared/kde1d.m:35-140 (Botev's diffusion
-// estimator) and shared/qtrapz.m.  The draws are k_vp_draw's (vp_tools_kernels.h); a column is one (posterior, dimension) pair,
-// col = p D + d.
-//   k_mtv_mesh      one workgroup per column: min and max of the draws, the counts on the two clamp ends -> MIN, MAX, N
+// The marginal total variation between posteriors on the device: vbmc_mtv.m:24-79 with shared/kde1d.m:35-140 (Botev's diffusion
+// estimator) and shared/qtrapz.m, for vbmc_vp_mtv's two posteriors and vbmc_vp_diagnostics' R runs alike.  The draws are k_vp_draw's
+// (vp_tools_kernels.h), one run at a time; a column is one (run, dimension) pair, col = i D + d.
+//   k_mtv_mesh      one run's D columns, one workgroup each: min and max of the draws, the counts on the two clamp ends -> MIN, MAX, N
 //                   (vbmc_mtv.m:55-63, kde1d.m:46)
-//   k_mtv_bin       histc on the uniform mesh (kde1d.m:48): integer atomics on global memory (integer addition is order-free)
+//   k_mtv_bin       one run's D columns: histc on the uniform mesh (kde1d.m:48), integer atomics on global memory (integer addition
+//                   is order-free)
 //   k_mtv_init      initial_data = counts / N, divided by its sum (kde1d.m:48)
 //   k_mtv_dct       dct1d (kde1d.m:113-122) resp. idct1d (:94-110) as the direct sums they stand for,
 //                     a_0 = sum_j x_j, a_k = 2 sum_j x_j cos(pi k (2 j + 1) / (2 n)),   out_j = sum_k a_k cos(pi k (2 j + 1) / (2 n)),
 //                   one output per thread, the cosine from a host-made quarter-wave table of n + 1 doubles in LDS
 //   k_mtv_root      one workgroup per column: the bracket of root() (kde1d.m:124-140) and a bisection-safeguarded secant iteration on
 //                   fixed_point (:79-89) down to a bracket a few ulps wide; then a_t = a exp(-k^2 pi^2 t / 2) (:55)
-//   k_mtv_integral  vbmc_mtv.m:73-78: both not-a-knot splines at nquad points of each of the three segments, the trapezoid sums as
-//                   per-workgroup partials that k_vp_reduce adds in index order
-// Every floating-point sum has a fixed order (thread in index order, wave shuffle, waves in order); nothing depends on the grid.
+//   k_mtv_integral  vbmc_mtv.m:73-78 for every pair of runs and dimension in one launch: both not-a-knot splines at nquad points of
+//                   each of the three segments, the trapezoid sums as MTV_NBLK per-workgroup partials per entry that k_vp_reduce
+//                   adds in index order
+// Every floating-point sum has a fixed order (thread in index order, vpt_block_sum); nothing depends on the grid, on R or on which
+// other runs are in the call.
 #pragma once
 #include "vp_tools_kernels.h"
 
@@ -26,32 +29,20 @@ struct MtvCol {                   // one column's mesh (written by k_mtv_mesh)
   int bad, pad;                   // the draws' range is zero or not finite: NaN for this dimension
 };
 
-// the same value in every thread: lane sums by wave shuffle, the waves in order
-__device__ __forceinline__ double mtv_block_sum(double v, double* s_w, int tid) {
-#pragma clang fp contract(off)
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) s_w[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < MTV_T / 64; ++w) s = s + s_w[w];
-  return s;
-}
-
 struct MtvMeshArgs {
-  int Ns, D;
-  const double* xx[2];            // Ns x D column-major
-  const double* ends;             // 2 D x 4: lb_orig, ub_orig, the clamp ends lb + eps(lb), ub - eps(ub) (+-Inf: none)
-  MtvCol* col;
-  long long* nuniq;               // 2 D
+  int Ns;
+  const double* x;                // Ns x D column-major: one run's draws; one workgroup per column
+  const double* ends;             // D x 4: lb_orig, ub_orig, the clamp ends lb + eps(lb), ub - eps(ub) (+-Inf: none)
+  MtvCol* col;                    // D
+  long long* nuniq;               // D
 };
 
 __global__ void __launch_bounds__(MTV_T) k_mtv_mesh(MtvMeshArgs a) {
 #pragma clang fp contract(off)
   __shared__ double s_lo[MTV_T / 64], s_hi[MTV_T / 64];
   __shared__ int s_cl[MTV_T / 64], s_ch[MTV_T / 64];
-  const int tid = threadIdx.x, c = blockIdx.x, p = c / a.D, d = c - p * a.D;
-  const double* x = a.xx[p] + (size_t)a.Ns * d;
+  const int tid = threadIdx.x, c = blockIdx.x;
+  const double* x = a.x + (size_t)a.Ns * c;
   const double lb = a.ends[4 * c], ub = a.ends[4 * c + 1], el = a.ends[4 * c + 2], eh = a.ends[4 * c + 3];
   double lo = __builtin_inf(), hi = -__builtin_inf();
   int cl = 0, ch = 0;
@@ -95,19 +86,19 @@ __device__ __forceinline__ int mtv_locate(double x, double MIN, double dx, int l
 }
 
 struct MtvBinArgs {
-  int Ns, D, n;
-  const double* xx[2];
-  const MtvCol* col;
-  int* counts;                    // 2 D x n, zeroed
+  int Ns, n;
+  const double* x;                // Ns x D column-major: one run's draws; blockIdx.y is the column
+  const MtvCol* col;              // D
+  int* counts;                    // D x n, zeroed
 };
 
 __global__ void __launch_bounds__(MTV_T) k_mtv_bin(MtvBinArgs a) {
 #pragma clang fp contract(off)
-  const int c = blockIdx.y, p = c / a.D, d = c - p * a.D;
+  const int c = blockIdx.y;
   const MtvCol q = a.col[c];
   if (q.bad) return;
   const double dx = (q.MAX - q.MIN) / (double)(a.n - 1);                                // kde1d.m:46
-  const double* x = a.xx[p] + (size_t)a.Ns * d;
+  const double* x = a.x + (size_t)a.Ns * c;
   int* cnt = a.counts + (size_t)c * a.n;
   for (long long i = (long long)blockIdx.x * MTV_T + threadIdx.x; i < a.Ns; i += (long long)gridDim.x * MTV_T) {
     const double v = x[i];
@@ -136,7 +127,7 @@ __global__ void __launch_bounds__(MTV_T) k_mtv_init(MtvInitArgs a) {
   }
   double s = 0.0;
   for (int j = tid; j < a.n; j += MTV_T) s = s + (double)cnt[j] / q.N;
-  s = mtv_block_sum(s, s_w, tid);
+  s = vpt_block_sum<MTV_T>(s, s_w, tid);
   for (int j = tid; j < a.n; j += MTV_T) x[j] = ((double)cnt[j] / q.N) / s;               // kde1d.m:48
 }
 
@@ -206,7 +197,7 @@ __device__ __forceinline__ double mtv_gamma_sum(const double* a2, int n, double 
     const double e = arg != arg ? arg : vb_exp_tab<0>(arg, tab);   // (the table exponential's clamp would drop a NaN)
     s = s + (p * a2[k]) * e;
   }
-  return mtv_block_sum(s, s_w, tid);
+  return vpt_block_sum<MTV_T>(s, s_w, tid);
 }
 
 __device__ __forceinline__ double mtv_powexp(double x, double y, const double* tab) {
@@ -248,7 +239,7 @@ __global__ void __launch_bounds__(MTV_T) k_mtv_root(MtvRootArgs A) {
     if (tid == 0) { A.tstar[c] = __builtin_nan(""); A.status[c] = 2; }
     return;
   }
-  // every thread carries the same scalars: the sums are broadcast by mtv_block_sum
+  // every thread carries the same scalars: the sums are broadcast by vpt_block_sum
   const double Nc = fmin(fmax(q.N, 50.0), 1050.0);                                        // kde1d.m:126
   double tol = 1e-12 + 0.01 * (Nc - 50.0) / 1000.0;                                       // :127
   const double f0 = mtv_fixed_point(0.0, A, a2, q.N, tab, s_w, tid);
@@ -302,12 +293,13 @@ __global__ void __launch_bounds__(MTV_T) k_mtv_root(MtvRootArgs A) {
 
 // ---- the integral (vbmc_mtv.m:73-78)
 struct MtvIntArgs {
-  int n, D, nquad, ntile;
-  const double* geo;              // D x 4: bb, the four mesh ends sorted (vbmc_mtv.m:74)
-  const double* msh;              // 2 D x 4: MIN, dx, the last mesh point, bad
-  const double* yy;               // 2 D x n: the normalised densities
-  const double* mm;               // 2 D x n: the splines' second derivatives times dx^2 / 6
-  double* partial;                // MTV_NBLK x 3 D
+  int n, D, nquad, ntile, npair;
+  const int* pairs;               // npair x 2: the runs i < j of a pair; its columns are i D + d and j D + d
+  const double* geo;              // npair x D x 4: bb, the four mesh ends sorted (vbmc_mtv.m:74)
+  const double* msh;              // R D x 4: MIN, dx, the last mesh point, bad
+  const double* yy;               // R D x n: the normalised densities
+  const double* mm;               // R D x n: the splines' second derivatives times dx^2 / 6
+  double* partial;                // MTV_NBLK x 3 D npair
 };
 
 // the not-a-knot spline of column c at x; 0 outside its mesh (interp1(..., 'spline', 0))
@@ -322,13 +314,16 @@ __device__ __forceinline__ double mtv_spline(const MtvIntArgs& a, int c, double 
   return (y[i] * r + y[i + 1] * s) + (m[i] * (r * r * r - r) + m[i + 1] * (s * s * s - s));
 }
 
+// grid (partial, dimension, pair)
 __global__ void __launch_bounds__(MTV_T) k_mtv_integral(MtvIntArgs a) {
 #pragma clang fp contract(off)
   __shared__ double s_w[MTV_T / 64];
-  const int tid = threadIdx.x, d = blockIdx.y, c1 = d, c2 = a.D + d;
+  const int tid = threadIdx.x, d = blockIdx.y, p = blockIdx.z;
+  const int c1 = a.pairs[2 * p] * a.D + d, c2 = a.pairs[2 * p + 1] * a.D + d;
+  const size_t e = (size_t)p * a.D + d, nent = 3 * (size_t)a.D * a.npair;
   const bool bad = a.msh[4 * c1 + 3] != 0.0 || a.msh[4 * c2 + 3] != 0.0;
   for (int j = 0; j < 3; ++j) {
-    const double b0 = a.geo[4 * d + j], b1 = a.geo[4 * d + j + 1];
+    const double b0 = a.geo[4 * e + j], b1 = a.geo[4 * e + j + 1];
     const double step = (b1 - b0) / (double)(a.nquad - 1);                               // linspace
     double acc = 0.0;
     if (!bad && b1 > b0) {
@@ -341,7 +336,7 @@ __global__ void __launch_bounds__(MTV_T) k_mtv_integral(MtvIntArgs a) {
         }
       }
     }
-    acc = mtv_block_sum(acc, s_w, tid);
-    if (tid == 0) a.partial[(size_t)blockIdx.x * (3 * a.D) + 3 * d + j] = acc;
+    acc = vpt_block_sum<MTV_T>(acc, s_w, tid);
+    if (tid == 0) a.partial[(size_t)blockIdx.x * nent + 3 * e + j] = acc;
   }
 }

@@ -412,6 +412,19 @@ __global__ void __launch_bounds__(VPT_T) k_vp_moments(VptMomArgs a) {
   }
 }
 
+// The family's one workgroup sum of T threads, the same value in every thread: lane sums by wave shuffle, the waves in index order
+template <int T>
+__device__ __forceinline__ double vpt_block_sum(double v, double* s_w, int tid) {
+#pragma clang fp contract(off)
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((tid & 63) == 0) s_w[tid >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < T / 64; ++w) s = s + s_w[w];
+  return s;
+}
+
 // out[e] = sum_b partial[b nent + e], b in index order
 __global__ void __launch_bounds__(VPT_T) k_vp_reduce(const double* partial, int nb, int nent, double* out) {
 #pragma clang fp contract(off)
@@ -476,15 +489,6 @@ __global__ void __launch_bounds__(VPT_T) k_vp_kldiv(VptKlArgs a) {
       acc = acc + (to - tg);
     }
   }
-  {
-#pragma clang fp contract(off)
-    for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
-    if ((tid & 63) == 0) s_w[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-      double s = 0.0;
-      for (int w = 0; w < VPT_T / 64; ++w) s = s + s_w[w];
-      a.partial[blockIdx.x] = s;
-    }
-  }
+  acc = vpt_block_sum<VPT_T>(acc, s_w, tid);
+  if (tid == 0) a.partial[blockIdx.x] = acc;
 }
