@@ -1062,6 +1062,70 @@ typedef struct vbmc_mtv_args {
 vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const vbmc_vp_desc* vp2, const vbmc_mtv_args* args);
 
 /*
+ * vbmc_vp_corner: the data of a corner plot -- what vbmc_plot.m:12-15 and private/vbmc_iterplot.m:21, :47 hand to utils/cornerplot.m --
+ * in one call (an addition, backward compatible: VBMC_ABI_VERSION is unchanged).
+ *
+ * THE SAMPLES.  With a posterior: the Ns rows of vbmc_vp_rnd(vp, Ns, origflag, balanceflag, Inf, seed, block), exactly (vbmc_plot
+ * draws with balanceflag 0, vbmc_iterplot with 1).  With vp == NULL: the caller's matrix X_in (Ns x D column-major) and D, what
+ * cornerplot(Xs, ...) of vbmc_examples.m takes; an entry that is not finite answers VBMC_ERR_INVALID.  2 <= Ns <= 2^28 and
+ * Ns x D doubles <= 1 GiB (else VBMC_ERR_UNSUPPORTED); D <= 32, K <= 512, transform types 0 .. 3 through the posterior; D = 1 has no
+ * pairs.
+ *
+ * THE BOUNDS.  bounds == NULL: each column's min and max (cornerplot.m:93-96, :116).  Given bounds (2 x D, finite, lo < hi, else
+ * VBMC_ERR_INVALID) are vbmc_iterplot's case: a sample outside them is dropped from every count and is still counted in N (kde2d.m:79,
+ * :193).  bounds_out receives the ones used.
+ *
+ * hist      nbins x D counts on nbins equal bins between the column's bounds: bin k is the largest k with lo + k (hi - lo) / nbins <= x,
+ *           a sample on hi goes to the last bin, a sample outside the bounds is not counted; the probability is count / Ns.  A
+ *           DEPARTURE: cornerplot.m:129 calls histogram(x, 40), whose "nice" bin edges are toolbox code outside the reference tree.
+ * quant     nq x D: utils/quantile1.m:37-72 of every column over all Ns rows at the probabilities p (at most 16, in [0, 1]): the
+ *           median's own branch (:40-45) for p = {0.5}, the caps of :53-54 and the "exact" and "same" copies of :59-70.  The device
+ *           selects exact order statistics (no sort of the matrix); the ranks and the interpolation of :57 are the host's.
+ * Per pair pp of dimensions d1 < d2 in cornerplot.m:154-155's order (d1 = 0 .. D-2 outer, d2 = d1+1 .. D-1 inner), P = D (D - 1) / 2,
+ * kde2d.m:74-212 on res x res (Botev's diffusion estimator: ndhist on 0:1/res:1 of the rescaled samples, dct2d, the root of
+ * t - evolve(t) with N = Ns inside the bracket of root(), t_x / t_y, idct2d):
+ *   density    res x res x P column-major, row the d2 mesh, column the d1 mesh, as kde2d.m:103 returns it (idct2d has one
+ *              transpose); negative values are eps (:104).  The mesh MIN : scaling / (res - 1) : MAX (:105) is the caller's to build
+ *              from bounds_out.
+ *   bandwidth  2 x P (:107).
+ *   tstar      P: the root; counts2 res x res x P int32: ndhist's counts, row the d1 bin, column the d2 bin.
+ * The cosine transforms are the direct sums dct2d / idct2d stand for (the reference goes through fft), the root comes from a
+ * bisection-safeguarded secant iteration down to a few ulps (the reference's fzero stops at its own tolerance).
+ *
+ * DEGENERATE AND REFUSED.  A column of zero range without given bounds: its histogram is zero, every pair that contains it is NaN in
+ * density, bandwidth and tstar, the other outputs are unaffected.  A pair whose equation has no bracket below 0.1 is the fminbnd
+ * branch of kde2d.m:208-210: VBMC_ERR_UNSUPPORTED, the message names the pair.  res: 0 is 64 (cornerplot.m:104), else 16, 32 or 64;
+ * anything else VBMC_ERR_UNSUPPORTED (kde2d's own default of 256 does not fit one workgroup's LDS tile).  nbins: 0 is 40 (:102), else
+ * 1 .. 1024.  Refused in this order: a NULL context, a wrong struct_size, the arguments, the posterior.  Every output pointer may be
+ * NULL.  Results are identical from run to run.
+ */
+typedef struct vbmc_corner_args {
+  uint32_t struct_size;
+  int32_t D;              /* with X_in; ignored with a posterior */
+  int32_t res;            /* 0: 64; else 16, 32 or 64 */
+  int32_t nbins;          /* 0: 40; else 1 .. 1024 */
+  int32_t nq;             /* 0 .. 16 */
+  int32_t origflag;       /* the draws' space (vbmc_plot: 1) */
+  int32_t balanceflag;    /* 0 or 1 */
+  int32_t reserved_;
+  int64_t Ns;             /* >= 2 */
+  uint64_t seed;
+  const double* block;    /* NULL, or vbmc_vp_rnd_rng_dump's block for (seed, vp) */
+  const double* X_in;     /* Ns x D column-major with vp == NULL, else NULL */
+  const double* bounds;   /* NULL, or 2 x D: lo, hi of dimension d at [2 d], [2 d + 1] */
+  const double* p;        /* nq */
+  double* xx;             /* Ns x D column-major: the samples used */
+  double* bounds_out;     /* 2 x D */
+  int32_t* hist;          /* nbins x D */
+  double* quant;          /* nq x D */
+  double* density;        /* res x res x P */
+  double* bandwidth;      /* 2 x P */
+  double* tstar;          /* P */
+  int32_t* counts2;       /* res x res x P */
+} vbmc_corner_args;
+vbmc_status vbmc_vp_corner(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_corner_args* args);
+
+/*
  * vbmc_vp_diagnostics: the pair loop of vbmc_diagnostics.m:116-127 over R runs in one call (an addition, backward compatible:
  * VBMC_ABI_VERSION is unchanged).  Run i draws ONCE: the rows of vbmc_vp_rnd(vps[i], Ns, 1, 1, seed + i).  (The reference draws afresh
  * for every pair; here every pair's estimate is the reference's estimator on Ns balanced draws of each posterior, and only the

@@ -252,7 +252,7 @@ static void read_gp(const mxArray* gp, GpArrays& g) {
 }
 
 // vp struct with its trinfo (shared/warpvars_vbmc.m: lb_orig, ub_orig, type, mu, delta, scale, R_mat; empty: the identity) -> vbmc_vp_desc
-// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv', 'vp_mtv', 'vp_diag').  The arrays stay MATLAB's; only the types are converted to int32.
+// (shared by 'vp_pdf', 'vp_rnd', 'vp_moments', 'vp_kldiv', 'vp_mtv', 'vp_diag', 'vp_corner').  The arrays stay MATLAB's; only the types are converted to int32.
 static int fill_vp_desc(vbmc_vp_desc& d, const mxArray* vp, std::vector<int32_t>& types) {
   d = zeroed<vbmc_vp_desc>();
   if (!vp || !mxIsStruct(vp)) return raise("vbmc_hip:usage", "vp must be a variational-posterior struct");
@@ -871,6 +871,54 @@ static int cmd_vp_mode(int nlhs, mxArray* plhs[], int, const mxArray* prhs[]) {
   return done(st);
 }
 
+// -> [xx,bounds,hist,quant,density,bandwidth,tstar,counts2]: the data of cornerplot (utils/cornerplot.m:113-156) for Ns draws of vp with the library's draws for
+// seed, or, with vp = [], for the rows of the sample matrix X (else X = []): vbmc_vp_corner, matlab/vbmc_hip_cornerdata.m.  bounds: [] or 2 x D as cornerplot takes
+// them; res, nbins: 0 for cornerplot's own 64 and 40; p: the probabilities of quant (nq x D).  hist (nbins x D) and counts2 (res x res x P) are counts as doubles;
+// density is res x res x P, page pp what kde2d returns for pair pp; bandwidth 2 x P; tstar 1 x P
+static int cmd_vp_corner(int nlhs, mxArray* plhs[], int, const mxArray* prhs[]) {
+  vbmc_vp_desc d;
+  std::vector<int32_t> ty;
+  const bool given = mxIsEmpty(prhs[1]);
+  vbmc_corner_args a = zeroed<vbmc_corner_args>();
+  if (given) {
+    if (mxIsEmpty(prhs[2]) || !mxIsDouble(prhs[2])) return raise("vbmc_hip:usage", "vp_corner: a variational posterior or a matrix of samples");
+    a.X_in = mxGetDoubles(prhs[2]); a.D = (int32_t)mxGetN(prhs[2]); a.Ns = (int64_t)mxGetM(prhs[2]);
+  } else {
+    if (fill_vp_desc(d, prhs[1], ty)) return 1;
+    if (!mxIsEmpty(prhs[2])) return raise("vbmc_hip:usage", "vp_corner: a variational posterior or a matrix of samples, not both");
+    const double n = mxGetScalar(prhs[3]);
+    if (!(n >= 1)) return raise("vbmc_hip:usage", "vp_corner: Ns must be positive");
+    a.D = d.D; a.Ns = (int64_t)n;
+  }
+  const mwSize D = (mwSize)a.D, Ns = (mwSize)a.Ns, P = D * (D - 1) / 2;
+  if (D < 1 || D > 32) return raise("vbmc_hip:unsupported", "vp_corner: D = %d outside 1 .. 32 not accelerated", (int)D);
+  a.seed = (uint64_t)mxGetScalar(prhs[4]); a.origflag = 1; a.balanceflag = mxGetScalar(prhs[5]) != 0;
+  if (!mxIsEmpty(prhs[6])) {
+    if (mxGetNumberOfElements(prhs[6]) != 2 * D) return raise("vbmc_hip:usage", "vp_corner: bounds must be 2 x D");
+    a.bounds = mxGetDoubles(prhs[6]);
+  }
+  a.res = (int32_t)mxGetScalar(prhs[7]); a.nbins = (int32_t)mxGetScalar(prhs[8]);
+  a.nq = (int32_t)mxGetNumberOfElements(prhs[9]); a.p = dbl(prhs[9]);
+  const mwSize n = a.res == 0 ? 64 : (mwSize)a.res, nb = a.nbins == 0 ? 40 : (mwSize)a.nbins;
+  if ((n != 16 && n != 32 && n != 64) || nb < 1 || nb > 1024 || a.nq > 16) {   // the library words the refusal; nothing is sized from these
+    const vbmc_status st = vbmc_vp_corner(g_ctx, given ? nullptr : &d, &a);
+    return st == VBMC_OK ? raise("vbmc_hip:error", "vp_corner: the library accepted res = %d, nbins = %d", a.res, a.nbins) : fail(st);
+  }
+  const mwSize d3[3] = {n, n, P};
+  std::vector<int32_t> hist((size_t)nb * D), cnt(nlhs > 7 ? (size_t)n * n * P : 0);
+  plhs[0] = mxCreateDoubleMatrix(Ns, D, mxREAL);
+  mxArray *bo = mxCreateDoubleMatrix(2, D, mxREAL), *hi = mxCreateDoubleMatrix(nb, D, mxREAL), *qu = mxCreateDoubleMatrix(a.nq, D, mxREAL);
+  mxArray *de = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *bw = mxCreateDoubleMatrix(2, P, mxREAL), *ts = mxCreateDoubleMatrix(1, P, mxREAL);
+  mxArray* c2 = nlhs > 7 ? mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL) : nullptr;
+  a.xx = mxGetDoubles(plhs[0]); a.bounds_out = mxGetDoubles(bo); a.hist = hist.data(); a.quant = mxGetDoubles(qu);
+  a.density = mxGetDoubles(de); a.bandwidth = mxGetDoubles(bw); a.tstar = mxGetDoubles(ts); a.counts2 = c2 ? cnt.data() : nullptr;
+  const vbmc_status st = vbmc_vp_corner(g_ctx, given ? nullptr : &d, &a);
+  for (size_t i = 0; i < hist.size(); ++i) mxGetDoubles(hi)[i] = (double)hist[i];
+  for (size_t i = 0; i < cnt.size(); ++i) mxGetDoubles(c2)[i] = (double)cnt[i];
+  give(nlhs, plhs, 1, {bo, hi, qu, de, bw, ts, c2});
+  return done(st);
+}
+
 // -> [acq,fbar,vtot], Nstar x 1 each: the IQR acquisition functions at the rows of Xs; his: the state of 'is_create'
 static int cmd_acq_iqr(int nlhs, mxArray* plhs[], int, const mxArray* prhs[]) {
   vbmc_acq_is* is = handle_in<vbmc_acq_is>(prhs[2]);
@@ -1111,6 +1159,7 @@ static const Command commands[] = {
     {"vp_mtv", 5, 0, "vp1, vp2, Ns, seed", cmd_vp_mtv, 0},
     {"vp_diag", 4, 0, "Ns, seed, vp1 [, vp2, ...]", cmd_vp_diag, 0},
     {"vp_mode", 5, 0, "vp, nmax, origflag, tol_grad", cmd_vp_mode, 0},
+    {"vp_corner", 10, 0, "vp, X, Ns, seed, balanceflag, bounds, res, nbins, p", cmd_vp_corner, 0},
     {"acq_iqr", 9, 2, "h, his, Xs, gplengthscale, X_rescaled, sn2new, var_regularized, TolGPVar", cmd_acq_iqr, 0},
     {"gp_surrogate_sample", 9, 1, "h, vp, Ns, origflag, LB, UB, noise, opts", cmd_gp_surrogate_sample, 0},
     {"gp_nlz", 7, 0, "Hyp, X, y, s2, meanfun, noisefun", cmd_gp_nlz, 0},

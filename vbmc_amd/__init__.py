@@ -17,7 +17,7 @@ from .gplite import (fminfill_design, gp_surrogate_sample_rng_dump, gplite_hyppr
 from .ensemble import ensemble_slice_sample  # noqa: F401,E402
 from .mixture import vbmc_moments, vbmc_rnd  # noqa: F401,E402  (the HOST forms; the device forms are vptools.vbmc_rnd / vbmc_moments)
 from . import vptools  # noqa: F401,E402
-from .vptools import gpsample_vbmc, vbmc_diagnostics, vbmc_mode, vp_rnd_rng_dump, warpvars  # noqa: F401,E402
+from .vptools import cornerplot_data, gpsample_vbmc, vbmc_plot_data, vbmc_diagnostics, vbmc_mode, vp_rnd_rng_dump, warpvars  # noqa: F401,E402
 from .optimize import (eval_fullelcbo, fminadam, gethpd_vbmc, sieve_evaluate, vbinit_vbmc, vpoptimize_vbmc,  # noqa: F401,E402
                        vpsieve_vbmc)
 from .acq import (acq_info, acq_search, acq_search_rng_dump, acqwrapper_vbmc, active_search, activeimportancesampling_vbmc,  # noqa: F401,E402

@@ -209,6 +209,22 @@ class MtvArgs(C.Structure):
     ]
 
 
+class CornerArgs(C.Structure):
+    """vbmc_corner_args (include/vbmc_hip.h)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("D", C.c_int32), ("res", C.c_int32), ("nbins", C.c_int32), ("nq", C.c_int32), ("origflag", C.c_int32), ("balanceflag", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("Ns", C.c_int64),
+        ("seed", C.c_uint64),
+        ("block", _dp), ("X_in", _dp), ("bounds", _dp), ("p", _dp),
+        ("xx", _dp), ("bounds_out", _dp),
+        ("hist", C.POINTER(C.c_int32)),
+        ("quant", _dp), ("density", _dp), ("bandwidth", _dp), ("tstar", _dp),
+        ("counts2", C.POINTER(C.c_int32)),
+    ]
+
+
 class DiagArgs(C.Structure):
     """vbmc_diag_args (include/vbmc_hip.h)"""
     _fields_ = [
@@ -360,6 +376,7 @@ def load():
     lib.vbmc_vp_moments.argtypes = [vp, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp]
     lib.vbmc_vp_kldiv.argtypes = [vp, vpd, vpd, C.c_int64, C.c_uint64, _dp, _dp, _dp, _dp, _dp]
     lib.vbmc_vp_mtv.argtypes = [vp, vpd, vpd, C.POINTER(MtvArgs)]
+    lib.vbmc_vp_corner.argtypes = [vp, vpd, C.POINTER(CornerArgs)]
     lib.vbmc_vp_diagnostics.argtypes = [vp, C.c_int32, C.POINTER(vpd), C.POINTER(DiagArgs)]
     lib.vbmc_vp_mode.argtypes = [vp, vpd, C.POINTER(ModeArgs)]
     lib.vbmc_test_dct.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]

@@ -3,6 +3,9 @@
 // here over two runs whose draws are held together, with the mesh cut at each posterior's bounds, the caller's random blocks, and
 // k_mtv_dct as the cosine transform.
 // Here: validation, the two posteriors' uploads and the one pair (0, 1).
+// vbmc_vp_corner, the data of a corner plot (cornerplot.m's histograms and kde2d densities, quantile1's quantiles), is corner_host.h's
+// CornerPipeline over corner_kernels.h; here its refusal order and the choice between a posterior's draws and a caller's matrix.
+#include "corner_host.h"
 #include "mtv_host.h"
 #include "vp_tools_host.h"
 
@@ -35,4 +38,27 @@ extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const
   VB_TRY(kde.integrals({0, 1}, v));
   std::copy(v.begin(), v.end(), args->mtv);
   return VBMC_OK;
+}
+
+extern "C" vbmc_status vbmc_vp_corner(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_corner_args* args) {
+  if (!ctx) return VBMC_ERR_INVALID;
+  const char* who = "vbmc_vp_corner";
+  if (!args || args->struct_size != sizeof(vbmc_corner_args)) return set_err(ctx, VBMC_ERR_INVALID, "%s: struct_size mismatch", who);
+  CornerPipeline cp;
+  VB_TRY(cp.begin(ctx, who, vp != nullptr, *args));
+  if (!vp) {
+    VB_TRY(cp.alloc(args->D, *args));
+    VB_TRY(cp.upload(args->X_in));
+    return cp.finish(*args);
+  }
+  VptPack pk;
+  VB_TRY(vpt_pack(ctx, who, vp, 0.0, pk));
+  VB_TRY(cp.alloc(vp->D, *args));
+  VptGenHost g;
+  VB_TRY(vpt_gen_host(ctx, who, vp->D, vp->K, vp->w, args->Ns, args->balanceflag, args->seed, g));
+  g.G.origflag = args->origflag ? 1 : 0;
+  VB_TRY(vpt_upload(ctx, pk));
+  VB_TRY(vpt_gen_upload(ctx, who, vp->D, args->block, g));
+  VB_TRY(cp.draw(pk, g));
+  return cp.finish(*args);
 }

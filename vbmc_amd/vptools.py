@@ -1,6 +1,7 @@
 """The variational posterior in the caller's own parameter space: vbmc_pdf, vbmc_rnd, vbmc_moments, vbmc_kldiv and vbmc_mtv with the
 variable transform of shared/warpvars_vbmc.m on the device (include/vbmc_hip.h: vbmc_vp_pdf, vbmc_vp_rnd, vbmc_vp_moments,
-vbmc_vp_kldiv, vbmc_vp_mtv), and vbmc_diagnostics over several runs (vbmc_vp_diagnostics: every pair's divergences in one call).
+vbmc_vp_kldiv, vbmc_vp_mtv), vbmc_diagnostics over several runs (vbmc_vp_diagnostics: every pair's divergences in one call) and the
+data of vbmc_plot's corner plot (vbmc_vp_corner: histograms, pair densities and quantiles of the draws in one call).
 
 ``vp["trinfo"]`` is a dict with the reference's field names (lb_orig, ub_orig, type, mu, delta and, optionally, scale and R_mat), or
 None / empty for the identity.  Transform types 0 .. 3 are accelerated; anything else raises VbmcUnsupported, on which a caller falls
@@ -231,6 +232,68 @@ def vbmc_mtv(vp1, vp2, Ns=1e5, *, seed=0, block1=None, block2=None, nkde=None, n
     if stages:
         out = out + (st,)
     return out if len(out) > 1 else out[0]
+
+
+def _corner(ctx, desc, X, Ns, D, seed, block, origflag, balanceflag, bounds, res, nbins, p, stages):
+    """One vbmc_vp_corner call; the arrays come back in NumPy's order (see vbmc_plot_data)"""
+    n = 64 if not res else int(res)
+    nb = 40 if not nbins else int(nbins)
+    p = f64(np.asarray(() if p is None else p, dtype=np.float64).reshape(-1))
+    P = D * (D - 1) // 2
+    a = new_args(_lib.CornerArgs)
+    a.D, a.res, a.nbins, a.nq, a.origflag, a.balanceflag = D, int(res or 0), int(nbins or 0), p.size, int(bool(origflag)), int(balanceflag)
+    a.Ns, a.seed = Ns, int(seed) & U64
+    B = _block(block)
+    Xin = None if X is None else f64(X)
+    b = None if bounds is None else np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(D, 2))
+    a.block, a.X_in, a.bounds, a.p = ptr(B), ptr(Xin), ptr(b), ptr(p) if p.size else None
+    rows, sq = max(Ns, 0), (n if n in (16, 32, 64) else 0)
+    out = {"xx": np.zeros((rows, D), order="F"), "bounds": np.zeros((D, 2)), "hist": np.zeros((D, max(min(nb, 1024), 0)), dtype=np.int32),
+           "quant": np.zeros((D, min(p.size, 16))), "density": np.zeros((P, sq, sq)), "bandwidth": np.zeros((P, 2))}
+    a.xx, a.bounds_out, a.quant, a.density, a.bandwidth = (ptr(out[k]) for k in ("xx", "bounds", "quant", "density", "bandwidth"))
+    a.hist = out["hist"].ctypes.data_as(i32p)
+    if stages:
+        out.update(tstar=np.zeros(P), counts2=np.zeros((P, sq, sq), dtype=np.int32))
+        a.tstar, a.counts2 = ptr(out["tstar"]), out["counts2"].ctypes.data_as(i32p)
+    ctx.check(ctx.lib.vbmc_vp_corner(ctx.h, None if desc is None else desc.ref(), C.byref(a)))
+    # the library's res x res x P is column-major: [pp][column][row] in NumPy's order
+    out["density"] = np.ascontiguousarray(out["density"].transpose(0, 2, 1))
+    if stages:
+        out["counts2"] = np.ascontiguousarray(out["counts2"].transpose(0, 2, 1))
+    out["pairs"] = [(d1, d2) for d1 in range(D - 1) for d2 in range(d1 + 1, D)]
+    out["p"], out["res"], out["Ns"] = p.copy(), n, Ns
+    return out
+
+
+def vbmc_plot_data(vp, Ns=1e5, *, seed=0, block=None, origflag=True, balanceflag=0, bounds=None, res=64, nbins=40, p=(0.5,), stages=False,
+                   engine=None):
+    """What vbmc_plot(vp) (vbmc_plot.m:12-15; balanceflag=1: private/vbmc_iterplot.m:21, :47) hands to utils/cornerplot.m and what that
+    computes from it, on the device in one call (vbmc_vp_corner): Ns draws of the posterior -- vbmc_rnd's rows for ``seed`` --, a
+    histogram of nbins equal bins per dimension between its bounds, kde2d on res x res (16, 32 or 64) for every pair of dimensions,
+    and the quantiles of utils/quantile1.m at the probabilities ``p``.
+
+    Returns a dict: xx (Ns, D), bounds (D, 2: given, or each column's min and max), hist (D, nbins) counts (the probability is
+    hist / Ns), quant (D, len(p)), pairs (the (d1, d2) of each pair in cornerplot's order), density (P, res, res: density[pp][i, j] at
+    (d2 mesh point i, d1 mesh point j), as kde2d returns it and contour(X, Y, density) takes it), bandwidth (P, 2); stages=True adds
+    tstar (P) and counts2 (P, res, res: [pp][d1 bin, d2 bin]).  The mesh of dimension d is
+    ``np.linspace(bounds[d, 0], bounds[d, 1], res)``.  A sample outside given bounds is dropped from the counts and still counts in N,
+    as in kde2d.  Raises VbmcUnsupported where a pair reaches kde2d's fminbnd branch, for res above 64 and for what vbmc_rnd refuses:
+    there a caller falls through to the reference's plot.  A departure: MATLAB's histogram(x, 40) picks its own "nice" edges."""
+    if not isinstance(vp, dict):
+        raise ValueError("vbmc_plot_data: vp needs to be a variational posterior (cornerplot_data takes a sample matrix)")
+    engine = _engine(engine)
+    d = _Desc(vp)
+    return _corner(engine.ctx, d, None, int(Ns), d.D, seed, block, origflag, balanceflag, bounds, res, nbins, p, stages)
+
+
+def cornerplot_data(X, bounds=None, *, res=64, nbins=40, p=(0.5,), stages=False, engine=None):
+    """vbmc_plot_data for a given sample matrix X (Ns, D): the numbers of cornerplot(X, names, truths, bounds).  An entry that is not
+    finite is a ValueError (VBMC_ERR_INVALID)."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("cornerplot_data: X must be a matrix of samples, one per row")
+    engine = _engine(engine)
+    return _corner(engine.ctx, None, X, X.shape[0], X.shape[1], 0, None, True, 0, bounds, res, nbins, p, stages)
 
 
 def vbmc_mode(vp, nmax=20, origflag=True, *, nargout=1, details=False, max_iter=0, tol_grad=1e-6, engine=None):
