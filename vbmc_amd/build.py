@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
-MAIN_DEPS = ["vbmc_hip.hip", "abi_ctx.hip", "ctx_core.h", "elbo_pass.h", "abi_elbo.hip", "abi_elbo_slots.hip", "elbo_slots.h", "gp_factor.h", "gp_pred.h", "abi_gp.hip", "abi_acq.hip", "abi_gp_train.hip", "round_driver.h", "abi_acq_search.hip", "abi_is_sample.hip", "imiqr_target.h", "abi_is_setup.hip", "abi_vp_tools.hip", "vp_tools_host.h", "mode_host.h", "abi_gp_surrogate.hip", "abi_vp_mtv.hip", "mtv_host.h", "abi_vp_diag.hip", "abi_comm.hip", "common.h", "device_math.h", "exp2_tab1k.h", "elbo_types.h", "elbo_kernels.h", "logjoint_body.h", "trsm_mfma.h",
+MAIN_DEPS = ["vbmc_hip.hip", "abi_ctx.hip", "ctx_core.h", "dev_layout.h", "elbo_pass.h", "abi_elbo.hip", "abi_elbo_slots.hip", "elbo_slots.h", "gp_factor.h", "gp_pred.h", "abi_gp.hip", "abi_acq.hip", "abi_gp_train.hip", "round_driver.h", "abi_acq_search.hip", "abi_is_sample.hip", "imiqr_target.h", "abi_is_setup.hip", "abi_vp_tools.hip", "vp_tools_host.h", "mode_host.h", "abi_gp_surrogate.hip", "abi_vp_mtv.hip", "mtv_host.h", "abi_vp_diag.hip", "abi_comm.hip", "common.h", "device_math.h", "exp2_tab1k.h", "elbo_types.h", "elbo_kernels.h", "logjoint_body.h", "trsm_mfma.h",
              "elbo_launch_plan.h", "var_kernels.h", "gp_factor_kernels.h", "gp_pred_kernels.h", "gp_nlz_kernels.h", "gp_acq_kernels.h", "chol_mfma.h", "parity_rng.h", "gpobj_kernels.h", "slice_kernels.h", "trainopt_kernels.h", "search_kernels.h", "iqr_tile_kernels.h", "is_sample_kernels.h", "is_core.h", "is_setup_kernels.h", "vp_tools_kernels.h", "mode_kernels.h", "gp_surrogate_kernels.h", "mtv_kernels.h", "diag_kernels.h", "corner_kernels.h", "corner_host.h", os.path.join("..", "..", "include", "vbmc_hip.h")]
 MFMA_DEPS = ["ent_mfma_inst.hip", "entropy_mfma.h", "device_math.h", "exp2_tab1k.h", "elbo_types.h", "logjoint_body.h"]
 LANE_DEPS = ["ent_lane_inst.hip", "entropy_lane.h", "device_math.h", "exp2_tab1k.h", "elbo_types.h", "logjoint_body.h"]

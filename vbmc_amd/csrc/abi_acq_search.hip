@@ -139,42 +139,27 @@ vbmc_status search_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, const
     const AcqInputs in{g.acq_id, g.K, g.vp_mu, g.vp_sigma, g.vp_lambda, g.vp_w, g.ymax, g.var_regularized, g.TolGPVar, g.gplengthscale, g.X_rescaled, g.sn2new};
     VB_TRY(ac.upload(ctx, who, gp, lam, in));
   }
-  // one block of fp64 state:  wts | LB | UB | xmean ps pc xbest xlast | C | A | Y | hist | F fbar vtot | Z
   const size_t nZ = g.rng_mode == 1 ? (size_t)D * lam * g.Gmax : 0;
-  const size_t n_fixed = (size_t)mu + 7 * (size_t)D + 2 * (size_t)D * D + (size_t)D * lam + a.nh + 3 * (size_t)lam;
   const size_t tcap = a.trace_cap;
+  const SearchBlocks L(D, lam, mu, a.nh, nZ, tcap);                       // one block of fp64 state, one of the trace's
   TmpBuf dW, dState, dTrI, dTrD;
-  HIP_TRY(ctx, dW.alloc(ctx, (n_fixed + nZ) * 8));
+  HIP_TRY(ctx, dW.alloc(ctx, L.w.bytes()));
   HIP_TRY(ctx, dState.alloc(ctx, sizeof(SearchState)));
   if (tcap) {
     HIP_TRY(ctx, dTrI.alloc(ctx, tcap * lam * sizeof(int)));
-    HIP_TRY(ctx, dTrD.alloc(ctx, tcap * ((size_t)lam + D + 1) * 8));
+    HIP_TRY(ctx, dTrD.alloc(ctx, L.trd.bytes()));
     HIP_TRY(ctx, hipMemsetAsync(dTrI.p, 0, tcap * lam * sizeof(int), st));
-    HIP_TRY(ctx, hipMemsetAsync(dTrD.p, 0, tcap * ((size_t)lam + D + 1) * 8, st));
+    HIP_TRY(ctx, hipMemsetAsync(dTrD.p, 0, L.trd.bytes(), st));
   }
   VB_TRY(ensure_pin(ctx, 2 * sizeof(SearchState) + 64));                  // two landing slots of the progress word
-  std::vector<double> hw(n_fixed, 0.0);
-  double* q = dW.as<double>();
-  {
-    double* h = hw.data();
-    memcpy(h, wts.data(), (size_t)mu * 8); a.wts = q; h += mu; q += mu;
-    memcpy(h, g.LB, (size_t)D * 8); a.LB = q; h += D; q += D;
-    memcpy(h, g.UB, (size_t)D * 8); a.UB = q; h += D; q += D;
-    memcpy(h, g.x0, (size_t)D * 8); a.xmean = q; h += D; q += D;
-    a.ps = q; h += D; q += D;
-    a.pc = q; h += D; q += D;
-    memcpy(h, g.x0, (size_t)D * 8); a.xbest = q; h += D; q += D;
-    memcpy(h, g.x0, (size_t)D * 8); a.xlast = q; h += D; q += D;
-    for (int d = 0; d < D; ++d) { const double sc = g.insigma[d] / sigma0; h[d + (size_t)D * d] = sc * sc; }   // the initial C: diagonal
-    a.C = q; h += (size_t)D * D; q += (size_t)D * D;
-    a.A = q; h += (size_t)D * D; q += (size_t)D * D;
-    a.Y = q; h += (size_t)D * lam; q += (size_t)D * lam;
-    a.hist = q; h += a.nh; q += a.nh;
-    a.F = q; ac.a.acq = iq.a.acq = q; ac.a.fbar = iq.a.fbar = q + lam; ac.a.vtot = iq.a.vtot = q + 2 * lam; q += 3 * (size_t)lam;
-    a.Z = nZ ? q : nullptr;
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(dW.p, hw.data(), n_fixed * 8, hipMemcpyHostToDevice, st));
-  if (nZ) HIP_TRY(ctx, hipMemcpyAsync(dW.as<double>() + n_fixed, g.Z, nZ * 8, hipMemcpyHostToDevice, st));
+  std::vector<double> hw(L.fixed / 8, 0.0);
+  L.wts.put(hw.data(), wts.data()); L.LB.put(hw.data(), g.LB); L.UB.put(hw.data(), g.UB);
+  L.xmean.put(hw.data(), g.x0); L.xbest.put(hw.data(), g.x0); L.xlast.put(hw.data(), g.x0);
+  for (int d = 0; d < D; ++d) { const double sc = g.insigma[d] / sigma0; L.C.at(hw.data())[d + (size_t)D * d] = sc * sc; }   // the initial C: diagonal
+  L.bind(a, dW.p, dTrD.p);
+  ac.a.acq = iq.a.acq = L.F.at(dW.p); ac.a.fbar = iq.a.fbar = L.fbar.at(dW.p); ac.a.vtot = iq.a.vtot = L.vtot.at(dW.p);
+  HIP_TRY(ctx, hipMemcpyAsync(dW.p, hw.data(), L.fixed, hipMemcpyHostToDevice, st));
+  if (nZ) HIP_TRY(ctx, hipMemcpyAsync(L.Z.at(dW.p), g.Z, L.Z.size(), hipMemcpyHostToDevice, st));
   SearchState s0{};
   s0.sigma = sigma0; s0.fbest = INFINITY; s0.flast = INFINITY;
   HIP_TRY(ctx, hipMemcpyAsync(dState.p, &s0, sizeof(SearchState), hipMemcpyHostToDevice, st));
@@ -182,10 +167,7 @@ vbmc_status search_impl(vbmc_ctx* ctx, const char* who, const vbmc_gp* gp, const
   a.Xs = pb.dXs.as<double>(); a.mb = pb.dmb.as<double>();
   ac.a.Xs = pb.dXs.as<double>(); ac.a.fmu = pb.fmu; ac.a.fs2 = pb.fs2;
   iq.a.Xs = pb.dXs.as<double>(); iq.a.fmu = pb.fmu; iq.a.fs2 = pb.fs2; iq.a.muv = pb.dmuv.as<double>(); iq.a.KsW = pb.dKs.as<double>();
-  if (tcap) {
-    a.tr_order = dTrI.as<int>();
-    a.tr_F = dTrD.as<double>(); a.tr_xmean = a.tr_F + tcap * lam; a.tr_sigma = a.tr_xmean + tcap * D;
-  }
+  if (tcap) a.tr_order = dTrI.as<int>();
   // a generation: the optimiser's step, then the objective at the points it wrote.  A step that finds the search finished does
   // nothing; the prediction and the acquisition kernels behind it still run on the last points (their results are never read).
   auto round = [&](int) -> vbmc_status {

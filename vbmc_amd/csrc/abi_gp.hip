@@ -69,19 +69,20 @@ static vbmc_status gp_post_impl(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, in
   const bool resident = gp_out != nullptr && optimistic && D <= 32 && D > 0 && S > 0 && N > 0;
   const size_t nG = resident ? (size_t)S * GPC_STRIDE(D) : 0;
   std::vector<double> sW1(S > 0 ? S : 0), mult(S > 0 ? S : 0, 1.0);
+  const GpPostExtra xl(resident ? D : 0, resident ? S : 0, nG);
   if (resident) {
-    o.extra_in = nG + (size_t)S + (size_t)D + (size_t)S;            // gpc | sn2_eff | meanX | mult
+    o.extra_in = xl.L.count();
     o.fill_extra = [&](double* e) {
-      gp_constants(D, S, Nhyp, D + 1, noise_nhyp(noisefun), meanfun, hyp, e);
+      gp_constants(D, S, Nhyp, D + 1, noise_nhyp(noisefun), meanfun, hyp, xl.gpc.at(e));
       for (int s = 0; s < S; ++s) {
         const double w = 1.0 / std::sqrt(f.sn2min[s]);               // post.sW(1) with sn2_mult = 1  (:281)
-        e[nG + s] = 1.0 / (w * w);                                   // gplogjoint.m:160
-        e[nG + S + D + s] = 1.0;
+        xl.sn2_eff.at(e)[s] = 1.0 / (w * w);                         // gplogjoint.m:160
+        xl.mult.at(e)[s] = 1.0;
       }
       for (int d = 0; d < D; ++d) {
         double acc = 0.0;
         for (int n = 0; n < N; ++n) acc += X[n + (size_t)N * d];
-        e[nG + S + d] = acc / N;
+        xl.meanX.at(e)[d] = acc / N;
       }
     };
   }
@@ -151,7 +152,7 @@ static vbmc_status gp_post_impl(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, in
     gp->blk_in = f.dIn.release();
     gp->X = f.dX.as<double>(); gp->hyp = f.dhyp.as<double>(); gp->d_lchol = f.dlch.as<unsigned char>();
     double* e = f.dExtra.as<double>();
-    gp->gpc = e; gp->d_sn2 = e + nG; gp->d_meanX = e + nG + S; gp->d_mult = e + nG + S + D;
+    gp->gpc = xl.gpc.at(e); gp->d_sn2 = xl.sn2_eff.at(e); gp->d_meanX = xl.meanX.at(e); gp->d_mult = xl.mult.at(e);
     gp->alpha = (double*)dal.release();
     gp->L = (double*)dA.release();
     gp->d_finv = (double*)dfinv.release();
@@ -212,8 +213,8 @@ static vbmc_status gp_nlz_impl(vbmc_ctx* ctx, int N, int D, int B, int Nhyp, int
         noise_grad(noisefun, hyp + (size_t)b * Nhyp + D + 1, N, y, s2, NnoiseH, e + (size_t)b * NnoiseH * N);
     };
   }
-  // results: [nlZ B | failure indices B | dnlZ B x Nhyp], one block on the device, one copy back
-  const size_t nout = (size_t)B * (2 + (compute_grad ? Nhyp : 0));
+  const GpNlzOut ol(B > 0 ? B : 0, Nhyp, compute_grad != 0);   // the results: one block on the device, one copy back
+  const size_t nout = ol.L.count();
   o.pin_out = nout;
   // few matrices of moderate order with a gradient: the factor's inverse and alpha's backward solve share one launch (gp_launch_grad);
   // otherwise, for few matrices, alpha's solve runs on the second stream beside the inverse and the streams join in front of k_nlz_grad
@@ -241,11 +242,11 @@ static vbmc_status gp_nlz_impl(vbmc_ctx* ctx, int N, int D, int B, int Nhyp, int
                       (const double*)f.w.pfd, dnlz);
   HIP_TRY(ctx, hipGetLastError());
   if (!out_direct) HIP_TRY(ctx, hipMemcpyAsync(f.pin_out, dnlz, nout * 8, hipMemcpyDeviceToHost, st));   // pinned: asynchronous
-  f.h_pfd = f.pin_out + B;
+  f.h_pfd = ol.pfd.at(f.pin_out);
   HIP_TRY(ctx, stream_wait_latency(st, N > 1024));
   if (!(*ok = gp_factor_ok(f, B))) return VBMC_OK;
-  memcpy(nlZ, f.pin_out, (size_t)B * 8);
-  if (compute_grad) memcpy(dnlZ, f.pin_out + 2 * (size_t)B, (size_t)B * Nhyp * 8);
+  memcpy(nlZ, ol.nlZ.at(f.pin_out), ol.nlZ.size());
+  if (compute_grad) memcpy(dnlZ, ol.dnlZ.at(f.pin_out), ol.dnlZ.size());
   // a matrix still not positive definite after the retries: MATLAB errors downstream and the caller maps it to NaN
   // (gplite_train.m:542-546)
   const double qnan = std::numeric_limits<double>::quiet_NaN();
@@ -444,29 +445,28 @@ extern "C" vbmc_status vbmc_gp_rank1_update(vbmc_ctx* ctx, const vbmc_gp* gp, co
   // block [X_new | meanX | hyp | gpc | sn2_eff | mult | lchol]: X_new and its column means come up through the pinned block, the
   // per-sample constants -- unchanged by an append -- are copied from the surrogate it extends in one launch.
   const int Nhyp = gp->Nhyp;
-  const size_t nXn = (size_t)N1 * D, nG = (size_t)S * GPC_STRIDE(D), nH = (size_t)Nhyp * S;
-  const size_t nsmall = nXn + D + nH + nG + 2 * (size_t)S + ((size_t)S + 7) / 8;
-  VB_TRY(ensure_pin(ctx, ((nXn + D) + (size_t)S * N1) * 8 + 8));
+  const size_t nG = (size_t)S * GPC_STRIDE(D), nH = (size_t)Nhyp * S;
+  const GpRank1Block bl(N1, D, S, Nhyp, nG);
+  VB_TRY(ensure_pin(ctx, (bl.upload + (size_t)S * N1) * 8 + 8));
   double* hin = (double*)ctx->pin;
-  memcpy(hin, X_new, nXn * 8);
+  bl.X.put(hin, X_new);
   for (int d = 0; d < D; ++d) {
     double acc = 0.0;
     for (int n = 0; n < N1; ++n) acc += X_new[n + (size_t)N1 * d];
-    hin[nXn + d] = acc / N1;
+    bl.meanX.at(hin)[d] = acc / N1;
   }
-  double* ah = hin + nXn + D;              // alpha comes back here
+  double* ah = hin + bl.upload;            // alpha comes back here
   GpGuard ng(ctx, new vbmc_gp());
   ng->N = N1; ng->D = D; ng->S = S; ng->Nhyp = Nhyp; ng->Ncov = gp->Ncov; ng->Nnoise = gp->Nnoise; ng->meanfun = gp->meanfun;
   ng->hyp_host = gp->hyp_host; ng->sn2_eff = gp->sn2_eff; ng->Lchol = gp->Lchol;     // post.sW(1) is unchanged by the append (:239)
   ng->pooled = true; ng->in_views = true; ng->hasL = true;
-  HIP_TRY(ctx, pool_get(ctx, nsmall * 8, &ng->blk_in));
+  HIP_TRY(ctx, pool_get(ctx, bl.L.bytes(), &ng->blk_in));
   HIP_TRY(ctx, pool_get(ctx, (size_t)S * TRSM_NBLK(N1) * 256 * sizeof(double), (void**)&ng->d_finv));
   double* blk = (double*)ng->blk_in;
-  ng->X = blk; ng->d_meanX = blk + nXn; ng->hyp = blk + nXn + D; ng->gpc = ng->hyp + nH; ng->d_sn2 = ng->gpc + nG; ng->d_mult = ng->d_sn2 + S;
-  ng->d_lchol = (unsigned char*)(ng->d_mult + S);
+  bl.bind(*ng.h, blk);
   ng->L = (double*)dLn.release();
   ng->alpha = (double*)dan.release();
-  HIP_TRY(ctx, copy_f64_small(ctx, st, blk, hin, nXn + D, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, copy_f64_small(ctx, st, blk, hin, bl.upload, hipMemcpyHostToDevice));
   {
     CopySegs cs{};
     cs.src[0] = gp->hyp; cs.dst[0] = ng->hyp; cs.n[0] = (int)nH;

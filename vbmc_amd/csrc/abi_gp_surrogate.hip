@@ -19,7 +19,7 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample_rng_dump(uint64_t seed, int E, i
 namespace {
 // N unbalanced transformed-space draws of the posterior into X (N x D column-major, on the device): vbmc_vp_rnd(vp, N, 0, 0, seed)
 vbmc_status gs_draw(vbmc_ctx* ctx, const char* who, const vbmc_vp_desc* vp, const VptPack& pk, long long N, unsigned long long seed, VptGenHost& g, double* X) {
-  VB_TRY(vpt_gen_host(ctx, who, vp->D, vp->K, vp->w, N, 0, seed, g));
+  VB_TRY(vpt_gen_host(ctx, who, vp->K, vp->w, N, 0, seed, g));
   g.G.origflag = 0;
   VB_TRY(vpt_gen_upload(ctx, who, vp->D, nullptr, g));
   VptDrawArgs a{};
@@ -78,35 +78,32 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
       if (!std::isfinite(g.x0[i])) return set_err(ctx, VBMC_ERR_INVALID, "%s: a starting point is not finite", who);
 
   hipStream_t st = ctx->stream;
-  // vt: VarThresh | sn2_avg | the sum | the partials of k_gs_sum
   const int nb = noise ? std::min((Nnn + GS_SUM_T - 1) / GS_SUM_T, VPT_MAXBLK) : 0;
   TmpBuf dV, dX0, dNn;
   NnNoise nn;
-  HIP_TRY(ctx, dV.alloc(ctx, (3 + (size_t)VPT_MAXBLK) * 8));
-  double* d_vt = dV.as<double>();
-  // behind the E x C values:  ymu | ys2, S x E x C each
+  const GsBlocks L(D, S, E, is_round_candidates(p), n0, noise ? Nnn : 0);
+  HIP_TRY(ctx, dV.alloc(ctx, L.v.bytes()));
+  double *d_vt = L.vt.at(dV.p), *d_sum = L.sum.at(dV.p), *d_part = L.part.at(dV.p);
   IsCore c;
-  const size_t nsv = (size_t)S * E * is_round_candidates(p);
-  VB_TRY(is_core_begin(ctx, gp, who, p, E, 2 * nsv, c));
-  c.pg.fmu = c.d_extra; c.pg.ys2 = c.d_extra + nsv;
+  VB_TRY(is_core_begin(ctx, gp, who, p, E, L.extra, c));
   IsPredKernel pred;
   void (*gs_pred)(IsPredArgs) = nullptr;
   DISPATCH_QS(D, gs_pred = k_gs_pred<QS>)
   VB_TRY(pred.set(ctx, N, D, gs_pred));
   GsTargetArgs tg{};
-  tg.S = S; tg.E = E; tg.C = c.C; tg.nstride = c.pg.nstride; tg.ncand = c.pg.ncand; tg.mask = c.a.mask; tg.ymu = c.pg.fmu; tg.ys2 = c.pg.ys2;
-  tg.vt = d_vt; tg.beta = g.beta; tg.val = c.d_val;
-  std::vector<double> hb(2 * (size_t)D), h0;
-  memcpy(hb.data(), g.LB, (size_t)D * 8);
-  memcpy(hb.data() + D, g.UB, (size_t)D * 8);
-  HIP_TRY(ctx, hipMemcpyAsync(c.dW.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, st));
+  L.bind(tg, c.pg, c.d_extra, dV.p);
+  tg.S = S; tg.E = E; tg.C = c.C; tg.nstride = c.pg.nstride; tg.ncand = c.pg.ncand; tg.mask = c.a.mask;
+  tg.beta = g.beta; tg.val = c.d_val;
+  std::vector<double> hb(c.L.UB.end() / 8), h0;            // the head of the sampler's block: LB | UB
+  c.L.LB.put(hb.data(), g.LB); c.L.UB.put(hb.data(), g.UB);
+  HIP_TRY(ctx, hipMemcpyAsync(c.dW.p, hb.data(), c.L.UB.end(), hipMemcpyHostToDevice, st));
   const double hvt[2] = {g.VarThresh, 0.0};
   HIP_TRY(ctx, hipMemcpyAsync(d_vt, hvt, sizeof hvt, hipMemcpyHostToDevice, st));
   if (vp) VB_TRY(vpt_upload(ctx, pk));
 
   // ---- the start: rows r = w + W e of a (W E) x D column-major buffer, clipped into the walker buffer and into x0_out's layout
-  HIP_TRY(ctx, dX0.alloc(ctx, 2 * n0 * 8));
-  double *d_x0 = dX0.as<double>(), *d_x0c = d_x0 + n0;
+  HIP_TRY(ctx, dX0.alloc(ctx, L.x0.bytes()));
+  double *d_x0 = L.start.at(dX0.p), *d_x0c = L.clipped.at(dX0.p);
   VptGenHost gen0, genn;
   if (g.x0) {
     h0.resize(n0);
@@ -120,18 +117,18 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   }
   hipLaunchKernelGGL(k_gs_start, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, W, D, E, d_x0, c.a.LB, c.a.UB, c.a.x, d_x0c);
 
-  // ---- the noise estimate: the draws | sn2new at each draw's nearest row
+  // ---- the noise estimate
   double* d_nn = nullptr;
   if (noise) {
-    HIP_TRY(ctx, dNn.alloc(ctx, ((size_t)Nnn * D + Nnn) * 8));
-    double* d_xx = dNn.as<double>();
-    d_nn = d_xx + (size_t)Nnn * D;
+    HIP_TRY(ctx, dNn.alloc(ctx, L.nn.bytes()));
+    double* d_xx = L.draws.at(dNn.p);
+    d_nn = L.sn2.at(dNn.p);
     VB_TRY(nn.upload(ctx, gp, g.gplengthscale, g.X_rescaled, g.sn2new));
     VB_TRY(gs_draw(ctx, who, vp, pk, Nnn, g.seed + 1, genn, d_xx));
     nn.launch(st, Nnn, d_xx, d_nn);
-    hipLaunchKernelGGL(k_gs_sum, dim3(nb), dim3(GS_SUM_T), 0, st, Nnn, d_nn, d_vt + 3);
-    hipLaunchKernelGGL(k_vp_reduce, dim3(1), dim3(VPT_T), 0, st, d_vt + 3, nb, 1, d_vt + 2);
-    hipLaunchKernelGGL(k_gs_thresh, dim3(1), dim3(64), 0, st, d_vt + 2, Nnn, d_vt);
+    hipLaunchKernelGGL(k_gs_sum, dim3(nb), dim3(GS_SUM_T), 0, st, Nnn, d_nn, d_part);
+    hipLaunchKernelGGL(k_vp_reduce, dim3(1), dim3(VPT_T), 0, st, d_part, nb, 1, d_sum);
+    hipLaunchKernelGGL(k_gs_thresh, dim3(1), dim3(64), 0, st, d_sum, Nnn, d_vt);
   }
   HIP_TRY(ctx, hipGetLastError());
 
@@ -160,7 +157,7 @@ extern "C" vbmc_status vbmc_gp_surrogate_sample(vbmc_ctx* ctx, const vbmc_gp* gp
   }
   std::vector<double> hr;
   double hv[2] = {0.0, 0.0};
-  if (g.Xt) HIP_TRY(ctx, hipMemcpyAsync(g.Xt, c.a.Xa, c.nXa * 8, hipMemcpyDeviceToHost, st));
+  if (g.Xt) HIP_TRY(ctx, hipMemcpyAsync(g.Xt, c.a.Xa, c.L.Xa.size(), hipMemcpyDeviceToHost, st));
   if (g.logp) { hr.resize(nr); HIP_TRY(ctx, hipMemcpyAsync(hr.data(), c.a.rlp, nr * 8, hipMemcpyDeviceToHost, st)); }
   if (g.x0_out) HIP_TRY(ctx, hipMemcpyAsync(g.x0_out, d_x0c, n0 * 8, hipMemcpyDeviceToHost, st));
   if (g.sn2_nn && noise) HIP_TRY(ctx, hipMemcpyAsync(g.sn2_nn, d_nn, (size_t)Nnn * 8, hipMemcpyDeviceToHost, st));

@@ -146,45 +146,33 @@ extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t nU = g.rng_mode == 1 ? (size_t)total * Nhyp * (size_t)(2 + g.Kmax) : 0;
-  // one block of fp64 inputs / chain vectors, one of work space
-  //   X | y | s2 | LB UB LBo UBo | pmu psig pdf pc | basew | xx widths xsum xsq | U
-  const size_t nX = (size_t)N * D;
-  const size_t in_doubles = nX + 2 * (size_t)N + 13 * (size_t)Nhyp + nU;
+  const SliceBlocks L(N, D, Nhyp, g.s2 != nullptr, total, nU, g.Ns);   // one block of fp64 inputs / chain vectors, one of work space
   TmpBuf dIn, dInt, dState, dHyp, dSn2, dScal, dLp, dFlags, dOut, dSmp;
   GpObjWork wk;
-  HIP_TRY(ctx, dIn.alloc(ctx, in_doubles * 8));
-  HIP_TRY(ctx, dInt.alloc(ctx, ((size_t)total * Nhyp + Nhyp) * sizeof(int)));
+  HIP_TRY(ctx, dIn.alloc(ctx, L.in.bytes()));
+  HIP_TRY(ctx, dInt.alloc(ctx, L.ints.bytes()));
   HIP_TRY(ctx, dState.alloc(ctx, sizeof(SliceChainState)));
   HIP_TRY(ctx, dHyp.alloc(ctx, (size_t)W * Nhyp * 8));
   HIP_TRY(ctx, dSn2.alloc(ctx, (size_t)W * N * 8));
   HIP_TRY(ctx, dScal.alloc(ctx, (size_t)W * 4 * 8));
   HIP_TRY(ctx, dLp.alloc(ctx, (size_t)W * 8));
-  HIP_TRY(ctx, dFlags.alloc(ctx, 2 * (size_t)SLICE_MAXW));
+  HIP_TRY(ctx, dFlags.alloc(ctx, L.flags.bytes()));
   VB_TRY(wk.alloc(ctx, N, D, W));
   HIP_TRY(ctx, dOut.alloc(ctx, (size_t)W * 2 * 8));
-  HIP_TRY(ctx, dSmp.alloc(ctx, ((size_t)g.Ns * Nhyp + g.Ns) * 8));
+  HIP_TRY(ctx, dSmp.alloc(ctx, L.smp.bytes()));
   VB_TRY(ensure_pin(ctx, 2 * sizeof(SliceChainState) + 64));              // two landing slots of the progress word
 
-  std::vector<double> hin(in_doubles, 0.0);
-  {
-    double* q = hin.data();
-    memcpy(q, g.X, nX * 8); q += nX;
-    memcpy(q, g.y, (size_t)N * 8); q += N;
-    if (g.s2) memcpy(q, g.s2, (size_t)N * 8);
-    q += N;
-    const double* blocks[9] = {g.LB, g.UB, LBo.data(), UBo.data(), pr.pmu.data(), pr.psig.data(), pr.pdf.data(), pr.pc.data(), g.basewidths};
-    for (int b = 0; b < 9; ++b, q += Nhyp) if (blocks[b]) memcpy(q, blocks[b], (size_t)Nhyp * 8);
-    memcpy(q, xx0.data(), (size_t)Nhyp * 8); q += Nhyp;
-    memcpy(q, wd.data(), (size_t)Nhyp * 8); q += 3 * (size_t)Nhyp;      // xsum, xsq start at zero
-    if (nU) memcpy(q, g.uniforms, nU * 8);
-  }
-  std::vector<int> hint((size_t)total * Nhyp + Nhyp);
-  for (size_t e = 0; e < (size_t)total * Nhyp; ++e) hint[e] = perms[e];
-  for (int i = 0; i < Nhyp; ++i) hint[(size_t)total * Nhyp + i] = pr.ptype[i];
-  HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin.data(), in_doubles * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dInt.p, hint.data(), hint.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  std::vector<double> hin(L.in.count(), 0.0);                            // (basew without the caller's; xsum, xsq start at zero)
+  L.head.pack(hin.data(), g.X, g.y, g.s2);
+  L.LB.put(hin.data(), g.LB); L.UB.put(hin.data(), g.UB); L.LBo.put(hin.data(), LBo.data()); L.UBo.put(hin.data(), UBo.data());
+  L.prior.pack(hin.data(), pr.pmu.data(), pr.psig.data(), pr.pdf.data(), pr.pc.data());
+  L.basew.put(hin.data(), g.basewidths); L.xx.put(hin.data(), xx0.data()); L.widths.put(hin.data(), wd.data()); L.U.put(hin.data(), g.uniforms);
+  std::vector<int> hint(L.ints.count<int>());
+  L.perms.put(hint.data(), perms); L.ptype.put(hint.data(), pr.ptype.data());
+  HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin.data(), L.in.bytes(), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(dInt.p, hint.data(), L.ints.bytes(), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(dState.p, 0, sizeof(SliceChainState), st));
-  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, 2 * (size_t)SLICE_MAXW, st));
+  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, L.flags.bytes(), st));
   HIP_TRY(ctx, hipMemsetAsync(dHyp.p, 0, (size_t)W * Nhyp * 8, st));     // k_gp_scale / k_nlz_final are not gated: they read every row
   HIP_TRY(ctx, hipMemsetAsync(dScal.p, 0, (size_t)W * 4 * 8, st));
 
@@ -193,18 +181,10 @@ extern "C" vbmc_status vbmc_gp_slice_sample(vbmc_ctx* ctx, const vbmc_slice_args
   a.adaptive = g.Adaptive ? 1 : 0; a.total = total; a.parity = g.rng_mode; a.nf0 = g.noisefun[0]; a.nf1 = g.noisefun[1]; a.nf2 = g.noisefun[2];
   a.has_base = g.basewidths ? 1 : 0; a.has_prior = g.prior_mu ? 1 : 0; a.seed = g.seed;
   {
-    double* q = dIn.as<double>();
-    double* dX = q; q += nX;
-    a.y = q; q += N;
-    a.s2 = g.s2 ? q : nullptr; q += N;
-    a.LB = q; a.UB = q + Nhyp; a.LBo = q + 2 * Nhyp; a.UBo = q + 3 * Nhyp; a.pmu = q + 4 * Nhyp; a.psig = q + 5 * Nhyp; a.pdf = q + 6 * Nhyp;
-    a.pc = q + 7 * Nhyp; a.basew = q + 8 * Nhyp; a.xx = q + 9 * Nhyp; a.widths = q + 10 * Nhyp; a.xsum = q + 11 * Nhyp; a.xsq = q + 12 * Nhyp;
-    a.U = nU ? q + 13 * Nhyp : nullptr;
-    a.perms = dInt.as<int>(); a.ptype = dInt.as<int>() + (size_t)total * Nhyp;
+    double* dX = L.bind(a, dIn.p, dInt.p, dFlags.p, dSmp.p);
     a.st = dState.as<SliceChainState>();
     a.hyp = dHyp.as<double>(); a.sn2 = dSn2.as<double>(); a.scal = dScal.as<double>(); a.lp = dLp.as<double>();
-    a.act = dFlags.as<unsigned char>(); a.on = a.act + SLICE_MAXW; a.out = dOut.as<double>();
-    a.samples = dSmp.as<double>(); a.logp = a.samples + (size_t)g.Ns * Nhyp;
+    a.out = dOut.as<double>();
     wk.Nhyp = Nhyp; wk.moff = Ncov + Nnoise; wk.meanfun = meanfun; wk.X = dX; wk.y = a.y; wk.hyp = a.hyp; wk.sn2 = a.sn2; wk.scal = a.scal;
     wk.act = a.act; wk.on = a.on;
     long long enqueued = 0;
@@ -304,76 +284,60 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t nX = (size_t)N * D, nDes = (size_t)Nrows * Nhyp;
-  //   X | y | s2 | LB UB | pmu psig pdf pc | design
-  const size_t in_doubles = nX + 2 * (size_t)N + 6 * (size_t)Nhyp + nDes;
+  const ToptBlocks L(N, D, Nhyp, g.s2 != nullptr, Nrows, Nopts, BB, hist_cap);
   const int nt1 = (N + NLZ_T - 1) / NLZ_T, ntile = nt1 * nt1, P = D + 1 + Nnoise;
   TmpBuf dIn, dInt, dState, dVec, dH, dHyp, dSn2, dDs, dScal, dLp, dFlags, dCode, dOut, dKi, dTT, dPart, dFill, dRes, dHist;
   GpObjWork wk;
-  HIP_TRY(ctx, dIn.alloc(ctx, in_doubles * 8));
-  HIP_TRY(ctx, dInt.alloc(ctx, ((size_t)Nhyp + Nrows + 1 + (size_t)Nopts * hist_cap + 1) * sizeof(int)));
+  HIP_TRY(ctx, dIn.alloc(ctx, L.in.bytes()));
+  HIP_TRY(ctx, dInt.alloc(ctx, L.ints.bytes()));
   HIP_TRY(ctx, dState.alloc(ctx, (size_t)Nopts * sizeof(ToptStart)));
-  HIP_TRY(ctx, dVec.alloc(ctx, 3 * (size_t)Nopts * Nhyp * 8));
+  HIP_TRY(ctx, dVec.alloc(ctx, L.vec.bytes()));
   HIP_TRY(ctx, dH.alloc(ctx, (size_t)Nopts * Nhyp * Nhyp * 8));
   HIP_TRY(ctx, dHyp.alloc(ctx, (size_t)BB * Nhyp * 8));
   HIP_TRY(ctx, dSn2.alloc(ctx, (size_t)BB * N * 8));
   HIP_TRY(ctx, dDs.alloc(ctx, (size_t)BB * std::max(Nnoise, 1) * N * 8));
   HIP_TRY(ctx, dScal.alloc(ctx, (size_t)BB * 4 * 8));
-  HIP_TRY(ctx, dLp.alloc(ctx, ((size_t)BB + (size_t)BB * Nhyp) * 8));
-  HIP_TRY(ctx, dFlags.alloc(ctx, 2 * (size_t)BB));
+  HIP_TRY(ctx, dLp.alloc(ctx, L.lp.bytes()));
+  HIP_TRY(ctx, dFlags.alloc(ctx, L.flags.bytes()));
   HIP_TRY(ctx, dCode.alloc(ctx, (size_t)BB * sizeof(int)));
   VB_TRY(wk.alloc(ctx, N, D, BB));
   HIP_TRY(ctx, dOut.alloc(ctx, (size_t)BB * (2 + Nhyp) * 8));
   HIP_TRY(ctx, dKi.alloc(ctx, (size_t)B * N * N * 8));
   HIP_TRY(ctx, dTT.alloc(ctx, (size_t)B * N * N * 8));
   HIP_TRY(ctx, dPart.alloc(ctx, (size_t)B * ntile * P * 8));
-  HIP_TRY(ctx, dFill.alloc(ctx, (2 * (size_t)Nrows + Nhyp) * 8));
-  HIP_TRY(ctx, dRes.alloc(ctx, ((size_t)Nopts + Nhyp) * 8));
-  HIP_TRY(ctx, dHist.alloc(ctx, std::max<size_t>(1, (size_t)Nopts * hist_cap * (Nhyp + 1)) * 8));
+  HIP_TRY(ctx, dFill.alloc(ctx, L.fill.bytes()));
+  HIP_TRY(ctx, dRes.alloc(ctx, L.res.bytes()));
+  HIP_TRY(ctx, dHist.alloc(ctx, L.hist.bytes()));
   VB_TRY(ensure_pin(ctx, 2 * (size_t)TOPT_MAXOPTS * sizeof(ToptStart) + 64));    // two landing slots of the progress words
 
-  std::vector<double> hin(in_doubles, 0.0);
-  {
-    double* q = hin.data();
-    memcpy(q, g.X, nX * 8); q += nX;
-    memcpy(q, g.y, (size_t)N * 8); q += N;
-    if (g.s2) memcpy(q, g.s2, (size_t)N * 8);
-    q += N;
-    const double* blocks[6] = {g.LB, g.UB, pr.pmu.data(), pr.psig.data(), pr.pdf.data(), pr.pc.data()};
-    for (int b = 0; b < 6; ++b, q += Nhyp) memcpy(q, blocks[b], (size_t)Nhyp * 8);
-    memcpy(q, g.design, nDes * 8);
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin.data(), in_doubles * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(dInt.p, pr.ptype.data(), (size_t)Nhyp * sizeof(int), hipMemcpyHostToDevice, st));
+  std::vector<double> hin(L.in.count(), 0.0);
+  L.head.pack(hin.data(), g.X, g.y, g.s2);
+  L.LB.put(hin.data(), g.LB); L.UB.put(hin.data(), g.UB);
+  L.prior.pack(hin.data(), pr.pmu.data(), pr.psig.data(), pr.pdf.data(), pr.pc.data());
+  L.design.put(hin.data(), g.design);
+  HIP_TRY(ctx, hipMemcpyAsync(dIn.p, hin.data(), L.in.bytes(), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(L.ptype.at(dInt.p), pr.ptype.data(), L.ptype.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(dState.p, 0, (size_t)Nopts * sizeof(ToptStart), st));
-  HIP_TRY(ctx, hipMemsetAsync(dVec.p, 0, 3 * (size_t)Nopts * Nhyp * 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, 2 * (size_t)BB, st));
+  HIP_TRY(ctx, hipMemsetAsync(dVec.p, 0, L.vec.bytes(), st));
+  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, L.flags.bytes(), st));
   HIP_TRY(ctx, hipMemsetAsync(dHyp.p, 0, (size_t)BB * Nhyp * 8, st));       // k_gp_scale / k_nlz_grad / k_nlz_final are not gated: they read every row
   HIP_TRY(ctx, hipMemsetAsync(dScal.p, 0, (size_t)BB * 4 * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dDs.p, 0, (size_t)BB * std::max(Nnoise, 1) * N * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(wk.w.dal.p, 0, ((size_t)BB * N + BB) * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(dKi.p, 0, (size_t)B * N * N * 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(dHist.p, 0, std::max<size_t>(1, (size_t)Nopts * hist_cap * (Nhyp + 1)) * 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(dInt.as<int>() + Nhyp, 0, ((size_t)Nrows + 1 + (size_t)Nopts * hist_cap + 1) * sizeof(int), st));
+  HIP_TRY(ctx, hipMemsetAsync(dHist.p, 0, L.hist.bytes(), st));
+  HIP_TRY(ctx, hipMemsetAsync(L.order.at(dInt.p), 0, L.ints.bytes() - L.order.off, st));   // everything behind ptype
 
   ToptArgs a{};
   a.N = N; a.D = D; a.Nhyp = Nhyp; a.Ncov = Ncov; a.Nnoise = Nnoise; a.Nopts = Nopts; a.W = W; a.Ninit = Nrows;
   a.nf0 = g.noisefun[0]; a.nf1 = g.noisefun[1]; a.nf2 = g.noisefun[2]; a.has_prior = g.prior_mu ? 1 : 0;
   a.max_iter = g.MaxIter > 0 ? g.MaxIter : 1000; a.max_evals = g.MaxFunEvals > 0 ? g.MaxFunEvals : 3000; a.hist_cap = hist_cap;
   a.lownoise = fill ? 1 : 0; a.tol = g.TolFun;
-  double* q = dIn.as<double>();
-  double* dX = q; q += nX;
-  a.y = q; q += N;
-  a.s2 = g.s2 ? q : nullptr; q += N;
-  a.LB = q; a.UB = q + Nhyp; a.pmu = q + 2 * Nhyp; a.psig = q + 3 * Nhyp; a.pdf = q + 4 * Nhyp; a.pc = q + 5 * Nhyp; a.design = q + 6 * Nhyp;
-  a.ptype = dInt.as<int>(); a.order = dInt.as<int>() + Nhyp; a.best = a.order + Nrows; a.hist_k = a.best + 1;
+  double* dX = L.bind(a, dIn.p, dInt.p, dVec.p, dLp.p, dFlags.p, dFill.p, dRes.p, dHist.p);
   a.st = dState.as<ToptStart>();
-  a.x = dVec.as<double>(); a.g = a.x + (size_t)Nopts * Nhyp; a.d = a.g + (size_t)Nopts * Nhyp; a.H = dH.as<double>();
-  a.hyp = dHyp.as<double>(); a.sn2 = dSn2.as<double>(); a.scal = dScal.as<double>(); a.lp = dLp.as<double>(); a.dlp = a.lp + BB;
-  a.dsn2 = dDs.as<double>(); a.act = dFlags.as<unsigned char>(); a.on = a.act + BB; a.code = dCode.as<int>(); a.out = dOut.as<double>();
-  a.fvals = dFill.as<double>(); a.fsorted = a.fvals + Nrows; a.widths = a.fsorted + Nrows;
-  a.res_nll = dRes.as<double>(); a.hyp_start = a.res_nll + Nopts;
-  if (hist_cap) { a.hist_f = dHist.as<double>(); a.hist_x = a.hist_f + (size_t)Nopts * hist_cap; }
+  a.H = dH.as<double>();
+  a.hyp = dHyp.as<double>(); a.sn2 = dSn2.as<double>(); a.scal = dScal.as<double>();
+  a.dsn2 = dDs.as<double>(); a.code = dCode.as<int>(); a.out = dOut.as<double>();
   wk.Nhyp = Nhyp; wk.moff = Ncov + Nnoise; wk.meanfun = meanfun; wk.X = dX; wk.y = a.y; wk.hyp = a.hyp; wk.sn2 = a.sn2; wk.scal = a.scal;
   wk.act = a.act; wk.on = a.on;
   // the tile form of the inverse's rank-k product is fixed by Nopts and N, not by W: every W computes the same bits
@@ -391,7 +355,7 @@ extern "C" vbmc_status vbmc_gp_train_optimize(vbmc_ctx* ctx, const vbmc_gptrain_
   }
   // 2. starts
   hipLaunchKernelGGL(k_topt_fill_sort, dim3(1), dim3(256), 0, st, a);
-  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, 2 * (size_t)BB, st));
+  HIP_TRY(ctx, hipMemsetAsync(dFlags.p, 0, L.flags.bytes(), st));
   HIP_TRY(ctx, hipGetLastError());
   // 3. optimiser
   // (a start that is done and a candidate that is never consumed launch nothing in propose / build / factorise / solve / inverse /

@@ -38,13 +38,13 @@ extern "C" vbmc_status vbmc_acq_is_sample(vbmc_ctx* ctx, const vbmc_gp* gp, cons
   IsCore c;
   ImiqrTarget t;
   VB_TRY(imiqr_begin(ctx, gp, who, p, c, t));
-  std::vector<double> hx(2 * (size_t)D + c.nx);
-  memcpy(hx.data(), g.LB, (size_t)D * 8);
-  memcpy(hx.data() + D, g.UB, (size_t)D * 8);
+  std::vector<double> hx(c.L.x.end() / 8);               // the head of the sampler's block: LB | UB | x
+  c.L.LB.put(hx.data(), g.LB); c.L.UB.put(hx.data(), g.UB);
+  double* hx0 = c.L.x.at(hx.data());
   for (int e = 0; e < S; ++e)
     for (int w = 0; w < W; ++w)
-      for (int d = 0; d < D; ++d) hx[2 * (size_t)D + ((size_t)e * W + w) * D + d] = g.x0[w + (size_t)W * (d + (size_t)D * e)];
-  HIP_TRY(ctx, hipMemcpyAsync(c.dW.p, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+      for (int d = 0; d < D; ++d) hx0[((size_t)e * W + w) * D + d] = g.x0[w + (size_t)W * (d + (size_t)D * e)];
+  HIP_TRY(ctx, hipMemcpyAsync(c.dW.p, hx.data(), c.L.x.end(), hipMemcpyHostToDevice, ctx->stream));
   IsCounters n;
   VB_TRY(imiqr_rounds(ctx, who, p, c, t, nullptr, n));
   return imiqr_close(ctx, gp, who, c, t, n, {g.Xa, g.lnw, g.fs2a, g.logp, g.funccount, g.performed, g.rounds, g.state});

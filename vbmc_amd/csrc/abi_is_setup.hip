@@ -8,10 +8,6 @@
 #include "is_setup_kernels.h"
 #include "parity_rng.h"
 
-namespace {
-inline size_t iss_block_len(int D, int S, int W, int Na1) { return (size_t)(D + 1) * Na1 + (size_t)W * S; }
-}  // namespace
-
 extern "C" vbmc_status vbmc_acq_is_setup_rng_dump(uint64_t seed, int D, int S, int W, int Nvp, int Nbox, double* B) {
   if (D <= 0 || S <= 0 || W < 0 || Nvp < 0 || Nbox < 0 || Nvp + Nbox < 1 || !B) return VBMC_ERR_INVALID;
   const int Na1 = Nvp + Nbox;
@@ -42,7 +38,7 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   if (g.Nvp < 0 || g.Nbox < 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nvp = %d and Nbox = %d must be non-negative", who, g.Nvp, g.Nbox);
   const long long na_ll = (long long)g.Nvp + g.Nbox;
   if (na_ll < 1 || na_ll > ISS_MAXNA) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nvp + Nbox = %lld outside 1 .. %d", who, na_ll, ISS_MAXNA);
-  const int Na1 = (int)na_ll, Nap1 = ((Na1 + 15) / 16) * 16, K4 = 4 * K;
+  const int Na1 = (int)na_ll, Nap1 = ((Na1 + 15) / 16) * 16;
   if (N < 2) return set_err(ctx, VBMC_ERR_INVALID, "%s: rect_delta = 2 std(X) needs at least two training inputs", who);
   if (g.rng_mode != 0 && g.rng_mode != 1) return set_err(ctx, VBMC_ERR_INVALID, "%s: rng_mode %d (0 device, 1 parity)", who, g.rng_mode);
   if (Nm < 0) return set_err(ctx, VBMC_ERR_INVALID, "%s: Nm = %d outside 0 .. %d", who, Nm, VBMC_LIM_NA);
@@ -62,7 +58,7 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   for (int d = 0; d < D; ++d) vp_ok = vp_ok && std::isfinite(g.vp_lambda[d]) && g.vp_lambda[d] > 0.0;
   if (!vp_ok || !(wsum > 0.0) || !std::isfinite(wsum))
     return set_err(ctx, VBMC_ERR_INVALID, "%s: the variational posterior must be finite with sigma, lambda > 0 and weights >= 0 of positive sum", who);
-  const size_t nB = g.rng_mode == 1 ? iss_block_len(D, S, W, Na1) : 0;
+  const size_t nB = g.rng_mode == 1 ? IsSetupBlock::block_len(D, S, W, Na1) : 0;
   if (g.rng_mode == 1) {
     if (!g.B) return set_err(ctx, VBMC_ERR_INVALID, "%s: parity mode needs the block B", who);
     for (size_t j = 0; j < nB; ++j) {
@@ -78,53 +74,31 @@ extern "C" vbmc_status vbmc_acq_is_setup(vbmc_ctx* ctx, const vbmc_gp* gp, const
   ImiqrTarget t;
   VB_TRY(imiqr_begin(ctx, gp, who, p, c, t));
   hipStream_t st = ctx->stream;
-  // one block of fp64:  mu | sigma | lambda | w | B | geo (D + 1) | comp (12 K) | Xa1 | P1 | logp fmu fs2 ys2 (S x Na1 each) | lpdf |
-  //                     lnw1 fs2a1 (S x Nap1) | lw (S x Na1) | x0
-  const size_t nvp = (size_t)D * K + K + D + K, nX1 = (size_t)Na1 * D, nP1 = (size_t)S * D * Na1, nv1 = (size_t)S * Na1, np1 = (size_t)S * Nap1;
-  const size_t nx0 = (size_t)std::max(W, 1) * D * S;
-  const size_t n1 = nvp + nB + (size_t)(D + 1) + 3 * (size_t)K4 + nX1 + nP1 + 4 * nv1 + Na1 + 2 * np1 + nv1 + nx0;
+  const IsSetupBlock L(D, S, K, W, Na1, g.rng_mode == 1);
+  const size_t nX1 = L.Xa1.n, np1 = L.lnw1.n;
   TmpBuf d1, dIdx, dNc1;
-  HIP_TRY(ctx, d1.alloc(ctx, n1 * 8));
+  HIP_TRY(ctx, d1.alloc(ctx, L.L.bytes()));
   HIP_TRY(ctx, dIdx.alloc(ctx, (size_t)std::max(W, 1) * S * sizeof(int)));
   HIP_TRY(ctx, dNc1.alloc(ctx, (size_t)S * sizeof(int)));
-  std::vector<double> hup(nvp + nB);
-  memcpy(hup.data(), g.vp_mu, (size_t)D * K * 8);
-  memcpy(hup.data() + (size_t)D * K, g.vp_sigma, (size_t)K * 8);
-  memcpy(hup.data() + (size_t)D * K + K, g.vp_lambda, (size_t)D * 8);
-  memcpy(hup.data() + (size_t)D * K + K + D, g.vp_w, (size_t)K * 8);
-  if (nB) memcpy(hup.data() + nvp, g.B, nB * 8);
+  std::vector<double> hup(L.upload / 8);
+  L.mu.put(hup.data(), g.vp_mu); L.sigma.put(hup.data(), g.vp_sigma); L.lambda.put(hup.data(), g.vp_lambda); L.w.put(hup.data(), g.vp_w);
+  L.B.put(hup.data(), g.B);
   const std::vector<int> hnc1(S, Na1);
-  HIP_TRY(ctx, hipMemcpyAsync(d1.p, hup.data(), hup.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d1.p, hup.data(), L.upload, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(dNc1.p, hnc1.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
 
   IsSetupKArgs k{};
   k.D = D; k.N = N; k.S = S; k.K = K; k.Nvp = g.Nvp; k.Nbox = g.Nbox; k.W = W; k.parity = g.rng_mode; k.seed = g.seed;
   k.w_vp = (double)g.Nvp / (double)Na1;                // :110
   k.X = gp->X;
-  double* q = d1.as<double>();
-  k.mu = q; q += (size_t)D * K;
-  k.sigma = q; q += K;
-  k.lambda = q; q += D;
-  k.w = q; q += K;
-  k.B = nB ? q : nullptr; q += nB;
-  k.geo = q; q += D + 1;
-  k.comp = q; q += 3 * (size_t)K4;
-  k.Xa1 = q; q += nX1;
-  k.P = q; q += nP1;
-  double* d_pv = q; q += 4 * nv1;
-  k.fmu = d_pv + nv1; k.fs2 = d_pv + 2 * nv1;
-  k.lpdf = q; q += Na1;
-  k.lnw1 = q; q += np1;
-  k.fs2a1 = q; q += np1;
-  k.lw = q; q += nv1;
-  k.x0 = q; q += nx0;
+  L.bind(k, d1.p);
   k.LB = const_cast<double*>(c.a.LB); k.UB = const_cast<double*>(c.a.UB);
   k.x = c.a.x; k.idx0 = dIdx.as<int>();
 
   hipLaunchKernelGGL(k_is_draw, dim3(1), dim3(ISS_DRAW_THREADS), 0, st, k);
   IsPredArgs pg1 = c.pg;
-  pg1.P = k.P; pg1.mask = nullptr; pg1.ncand = dNc1.as<int>(); pg1.nstride = 1; pg1.C = Na1;
-  pg1.logp = d_pv; pg1.fmu = d_pv + nv1; pg1.fs2 = d_pv + 2 * nv1; pg1.ys2 = d_pv + 3 * nv1;
+  L.bind(pg1, d1.p);
+  pg1.mask = nullptr; pg1.ncand = dNc1.as<int>(); pg1.nstride = 1; pg1.C = Na1;
   t.pk.launch(st, dim3((Na1 + 15) / 16, S), pg1);
   hipLaunchKernelGGL(k_is_proposal, dim3(Nap1), dim3(64), 0, st, k);
   if (step2) hipLaunchKernelGGL(k_is_resample, dim3(S), dim3(64), 0, st, k);

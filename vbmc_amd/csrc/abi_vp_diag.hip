@@ -31,12 +31,12 @@ extern "C" vbmc_status vbmc_vp_diagnostics(vbmc_ctx* ctx, int32_t R, const vbmc_
   std::vector<VptPost> hP(R);
   std::vector<double> hlc(R);
   for (int i = 0; i < R; ++i) {
-    VB_TRY(vpt_gen_host(ctx, who, D, vps[i]->K, vps[i]->w, Ns, 1, args->seed + (uint64_t)i, g[i]));
+    VB_TRY(vpt_gen_host(ctx, who, vps[i]->K, vps[i]->w, Ns, 1, args->seed + (uint64_t)i, g[i]));
     g[i].G.origflag = 1;
     VB_TRY(vpt_upload(ctx, pk[i]));
     VB_TRY(vpt_gen_upload(ctx, who, D, nullptr, g[i]));
     hP[i] = pk[i].P;
-    hlc[i] = *std::max_element(pk[i].h.begin() + pk[i].o_cst, pk[i].h.begin() + pk[i].o_cst + vps[i]->K) + pk[i].P.lognf;
+    hlc[i] = *std::max_element(pk[i].L.cst.at(pk[i].h.data()), pk[i].L.cst.at(pk[i].h.data()) + vps[i]->K) + pk[i].P.lognf;
   }
   const bool want_kl = args->kl_mat != nullptr;
   const int ntile_kl = (int)((Ns + VPT_T - 1) / VPT_T), nb_kl = std::min(ntile_kl, VPT_MAXBLK);

@@ -26,7 +26,7 @@ extern "C" vbmc_status vbmc_vp_mtv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, const
   double* xx[2] = {args->xx1, args->xx2};
   VptGenHost g[2];
   for (int s = 0; s < 2; ++s) {
-    VB_TRY(vpt_gen_host(ctx, who, D, vps[s]->K, vps[s]->w, args->Ns, 1, args->seed + (uint64_t)s, g[s]));
+    VB_TRY(vpt_gen_host(ctx, who, vps[s]->K, vps[s]->w, args->Ns, 1, args->seed + (uint64_t)s, g[s]));
     g[s].G.origflag = 1;
     VB_TRY(vpt_upload(ctx, pk[s]));
     VB_TRY(vpt_gen_upload(ctx, who, D, blocks[s], g[s]));
@@ -55,7 +55,7 @@ extern "C" vbmc_status vbmc_vp_corner(vbmc_ctx* ctx, const vbmc_vp_desc* vp, con
   VB_TRY(vpt_pack(ctx, who, vp, 0.0, pk));
   VB_TRY(cp.alloc(vp->D, *args));
   VptGenHost g;
-  VB_TRY(vpt_gen_host(ctx, who, vp->D, vp->K, vp->w, args->Ns, args->balanceflag, args->seed, g));
+  VB_TRY(vpt_gen_host(ctx, who, vp->K, vp->w, args->Ns, args->balanceflag, args->seed, g));
   g.G.origflag = args->origflag ? 1 : 0;
   VB_TRY(vpt_upload(ctx, pk));
   VB_TRY(vpt_gen_upload(ctx, who, vp->D, args->block, g));

@@ -12,7 +12,7 @@ extern "C" vbmc_status vbmc_vp_rnd_rng_dump(uint64_t seed, int64_t N, int D, int
   for (int k = 0; k < K; ++k) { if (!(std::isfinite(w[k]) && w[k] >= 0.0)) return VBMC_ERR_INVALID; ws += w[k]; }
   if (!(ws > 0.0)) return VBMC_ERR_INVALID;
   VptGenHost g;
-  VB_TRY(vpt_gen_host(nullptr, "vbmc_vp_rnd_rng_dump", D, K, w, N, balanceflag, seed, g));
+  VB_TRY(vpt_gen_host(nullptr, "vbmc_vp_rnd_rng_dump", K, w, N, balanceflag, seed, g));
   if (B)
     for (long long i = 0; i < g.G.M; ++i) {
       B[(size_t)(D + 1) * i] = slice_uniform(seed, VPT_CTR, (unsigned)i, 0u);
@@ -72,7 +72,7 @@ extern "C" vbmc_status vbmc_vp_rnd(vbmc_ctx* ctx, const vbmc_vp_desc* vp, int64_
   const int D = vp->D;
   hipStream_t st = ctx->stream;
   VptGenHost g;
-  VB_TRY(vpt_gen_host(ctx, who, D, vp->K, vp->w, N, balanceflag, seed, g));
+  VB_TRY(vpt_gen_host(ctx, who, vp->K, vp->w, N, balanceflag, seed, g));
   g.G.origflag = origflag ? 1 : 0;
   VB_TRY(vpt_upload(ctx, pk));
   VB_TRY(vpt_gen_upload(ctx, who, D, block, g));
@@ -101,7 +101,7 @@ extern "C" vbmc_status vbmc_vp_moments(vbmc_ctx* ctx, const vbmc_vp_desc* vp, in
   const int D = vp->D, K = vp->K, DT = pk.DT;
   hipStream_t st = ctx->stream;
   VptGenHost g;
-  VB_TRY(vpt_gen_host(ctx, who, D, K, vp->w, Ns, 1, seed, g));
+  VB_TRY(vpt_gen_host(ctx, who, K, vp->w, Ns, 1, seed, g));
   g.G.origflag = 1;
   // the centre of the shifted sums: the image of the mixture mean
   std::vector<double> hc(DT, 0.0), ym(D, 0.0);
@@ -114,26 +114,30 @@ extern "C" vbmc_status vbmc_vp_moments(vbmc_ctx* ctx, const vbmc_vp_desc* vp, in
   }
   vpt_host_inverse(vp, pk, ym.data(), hc.data());
   const int nent = D + D * (D + 1) / 2;
-  std::vector<unsigned char> he(2 * (size_t)nent);
+  const VptMomEntries el(nent);
+  std::vector<unsigned char> he(el.L.bytes());
   {
+    unsigned char *ei = el.ei.at(he.data()), *ej = el.ej.at(he.data());
     int e = 0;
-    for (int d = 0; d < D; ++d, ++e) { he[e] = (unsigned char)d; he[nent + e] = (unsigned char)DT; }
+    for (int d = 0; d < D; ++d, ++e) { ei[e] = (unsigned char)d; ej[e] = (unsigned char)DT; }
     for (int j = 0; j < D; ++j)
-      for (int i = 0; i <= j; ++i, ++e) { he[e] = (unsigned char)i; he[nent + e] = (unsigned char)j; }
+      for (int i = 0; i <= j; ++i, ++e) { ei[e] = (unsigned char)i; ej[e] = (unsigned char)j; }
   }
   const int ntile = (int)((Ns + VPT_T - 1) / VPT_T), nb = std::min(ntile, VPT_MAXBLK);
+  const VptReduceBlock rl((size_t)nb * nent, nent);
   VB_TRY(vpt_upload(ctx, pk));
   VB_TRY(vpt_gen_upload(ctx, who, D, block, g));
   TmpBuf dC, dE, dP;
   HIP_TRY(ctx, dC.alloc(ctx, (size_t)DT * 8));
   HIP_TRY(ctx, dE.alloc(ctx, he.size()));
-  HIP_TRY(ctx, dP.alloc(ctx, ((size_t)nb + 1) * nent * 8));
+  HIP_TRY(ctx, dP.alloc(ctx, rl.L.bytes()));
   HIP_TRY(ctx, hipMemcpyAsync(dC.p, hc.data(), (size_t)DT * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(dE.p, he.data(), he.size(), hipMemcpyHostToDevice, st));
   VptMomArgs a{};
-  a.P = pk.P; a.G = g.G; a.centre = dC.as<double>(); a.ei = dE.as<unsigned char>(); a.ej = a.ei + nent; a.nent = nent; a.ntile = ntile;
-  a.partial = dP.as<double>();
-  double* d_out = a.partial + (size_t)nb * nent;
+  el.bind(a, dE.p);
+  a.P = pk.P; a.G = g.G; a.centre = dC.as<double>(); a.nent = nent; a.ntile = ntile;
+  a.partial = rl.partial.at(dP.p);
+  double* d_out = rl.out.at(dP.p);
   VPT_FOR_DT(DT, hipLaunchKernelGGL((k_vp_moments<DT>), dim3(nb), dim3(VPT_T), 0, st, a))
   hipLaunchKernelGGL(k_vp_reduce, dim3((nent + VPT_T - 1) / VPT_T), dim3(VPT_T), 0, st, a.partial, nb, nent, d_out);
   HIP_TRY(ctx, hipGetLastError());
@@ -174,23 +178,24 @@ extern "C" vbmc_status vbmc_vp_kldiv(vbmc_ctx* ctx, const vbmc_vp_desc* vp1, con
   double* xx[2] = {xx1, xx2};
   VptGenHost g[2];
   for (int s = 0; s < 2; ++s) {
-    VB_TRY(vpt_gen_host(ctx, who, D, vps[s]->K, vps[s]->w, Ns, 1, seed + (uint64_t)s, g[s]));
+    VB_TRY(vpt_gen_host(ctx, who, vps[s]->K, vps[s]->w, Ns, 1, seed + (uint64_t)s, g[s]));
     g[s].G.origflag = 1;
   }
   const int ntile = (int)((Ns + VPT_T - 1) / VPT_T), nb = std::min(ntile, VPT_MAXBLK);
   const size_t nX = (size_t)Ns * D;
+  const VptReduceBlock rl(2 * (size_t)nb, 2);            // a row of nb partial sums and a total per direction
   TmpBuf dP, dXX[2];
-  HIP_TRY(ctx, dP.alloc(ctx, (2 * (size_t)nb + 2) * 8));
+  HIP_TRY(ctx, dP.alloc(ctx, rl.L.bytes()));
   for (int s = 0; s < 2; ++s) {
     VB_TRY(vpt_upload(ctx, pk[s]));
     VB_TRY(vpt_gen_upload(ctx, who, D, blocks[s], g[s]));
     if (xx[s]) HIP_TRY(ctx, dXX[s].alloc(ctx, nX * 8));
   }
-  double* d_out = dP.as<double>() + 2 * (size_t)nb;
+  double* d_out = rl.out.at(dP.p);
   for (int s = 0; s < 2; ++s) {
     VptKlArgs a{};
     a.Pg = pk[s].P; a.Po = pk[1 - s].P; a.G = g[s].G; a.ntile = ntile; a.xx = xx[s] ? dXX[s].as<double>() : nullptr;
-    a.partial = dP.as<double>() + (size_t)s * nb;
+    a.partial = rl.partial.part((size_t)s * nb, nb).at(dP.p);
     VPT_FOR_DT(DT, hipLaunchKernelGGL((k_vp_kldiv<DT>), dim3(nb), dim3(VPT_T), 0, st, a))
     hipLaunchKernelGGL(k_vp_reduce, dim3(1), dim3(VPT_T), 0, st, a.partial, nb, 1, d_out + s);
   }

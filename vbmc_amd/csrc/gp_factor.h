@@ -9,6 +9,7 @@
 #include <functional>
 #include <limits>
 
+#include "dev_layout.h"
 #include "elbo_pass.h"   // copy_f64_small
 #include "gp_factor_kernels.h"
 #include "gp_nlz_kernels.h"
@@ -201,16 +202,54 @@ struct GpFactor {
   TmpBuf dIn, dX, dy, dhyp, dsn2, dscal, dact, dones, dninv, dlch, dExtra;   // dIn: the packed inputs (the others are its windows)
 };
 
-// The packed upload, one pinned block and one copy: [X | y | hyp | sn2 | scal | flags | caller's extras], offsets in doubles.  flags: four
-// arrays of S bytes, ones | needinv | active | lchol.
+// The packed upload, one pinned block and one copy: [X | y | hyp | sn2 | scal | flags | caller's extras].  flags: four arrays of S
+// bytes, ones | needinv | active | lchol, rounded up together to whole doubles.  total: the block in doubles.
 struct GpPackLayout {
-  size_t X = 0, y, hyp, sn2, scal, flags, extra, total;
-  size_t S;
-  GpPackLayout(int N, int D, int S_, int Nhyp, size_t extra_in) : S(S_) {
-    y = (size_t)N * D; hyp = y + N; sn2 = hyp + (size_t)Nhyp * S; scal = sn2 + S * N; flags = scal + S * 4;
-    extra = flags + (4 * S + 7) / 8; total = extra + extra_in;
+  DevLayout L;
+  DevWin<double> X, y, hyp, sn2, scal, extra;
+  DevWin<unsigned char> ones, needinv, active, lchol;
+  size_t total;
+  GpPackLayout(int N, int D, int S, int Nhyp, size_t extra_in) {
+    X = L.add<double>((size_t)N * D); y = L.add<double>(N); hyp = L.add<double>((size_t)Nhyp * S); sn2 = L.add<double>((size_t)S * N);
+    scal = L.add<double>((size_t)S * 4);
+    ones = L.add<unsigned char>(S); needinv = L.add<unsigned char>(S); active = L.add<unsigned char>(S); lchol = L.add<unsigned char>(S);
+    L.round_up(sizeof(double));
+    extra = L.add<double>(extra_in);
+    total = L.count();
   }
-  unsigned char* flag(double* base, int k) const { return (unsigned char*)(base + flags) + k * S; }
+};
+
+// vbmc_gp_post's extras in that block, what a device-resident posterior needs beyond the factorisation:  gpc (nG) | sn2_eff (S) | meanX (D) | mult (S)
+struct GpPostExtra {
+  DevLayout L;
+  DevWin<double> gpc, sn2_eff, meanX, mult;
+  GpPostExtra(int D, int S, size_t nG) { gpc = L.add<double>(nG); sn2_eff = L.add<double>(S); meanX = L.add<double>(D); mult = L.add<double>(S); }
+};
+
+// gplite_nlZ's block of results, what k_nlz_final writes:  nlZ (B) | failure indices (B) | dnlZ (B x Nhyp, with a gradient only)
+struct GpNlzOut {
+  DevLayout L;
+  DevWin<double> nlZ, pfd, dnlZ;
+  GpNlzOut(int B, int Nhyp, bool grad) { nlZ = L.add<double>(B); pfd = L.add<double>(B); dnlZ = L.add_if<double>(grad, (size_t)B * Nhyp); }
+};
+// The small blocks of the surrogate a rank-one update makes, windows of one pooled block:
+//   X_new (N1 x D) | meanX (D) | hyp | gpc (nG) | sn2_eff | mult (S each) | lchol (S bytes, rounded up to whole doubles)
+// X_new and meanX come up from the host (upload: their doubles); the rest is copied from the surrogate it extends.
+struct GpRank1Block {
+  DevLayout L;
+  DevWin<double> X, meanX, hyp, gpc, sn2_eff, mult;
+  DevWin<unsigned char> lchol;
+  size_t upload;
+  GpRank1Block(int N1, int D, int S, int Nhyp, size_t nG) {
+    X = L.add<double>((size_t)N1 * D); meanX = L.add<double>(D);
+    upload = L.count();
+    hyp = L.add<double>((size_t)Nhyp * S); gpc = L.add<double>(nG); sn2_eff = L.add<double>(S); mult = L.add<double>(S);
+    lchol = L.add<unsigned char>(S);
+    L.round_up(sizeof(double));
+  }
+  void bind(vbmc_gp& g, void* b) const {
+    g.X = X.at(b); g.d_meanX = meanX.at(b); g.hyp = hyp.at(b); g.gpc = gpc.at(b); g.d_sn2 = sn2_eff.at(b); g.d_mult = mult.at(b); g.d_lchol = lchol.at(b);
+  }
 };
 
 // host: noise vectors, Lchol flags, the constants of the first try (gplite_core.m:33-40,67)
@@ -293,19 +332,15 @@ vbmc_status gp_factorize(vbmc_ctx* ctx, int N, int D, int S, int Nhyp, int meanf
   VB_TRY(ensure_pin(ctx, (lay.total + o.pin_out) * 8 + 8));
   double* hin = (double*)ctx->pin;
   f.pin_out = hin + lay.total;
-  memcpy(hin + lay.X, X, (size_t)N * D * 8);
-  memcpy(hin + lay.y, y, (size_t)N * 8);
-  memcpy(hin + lay.hyp, hyp, (size_t)Nhyp * S * 8);
-  memcpy(hin + lay.sn2, f.sn2all.data(), (size_t)S * N * 8);
-  memcpy(hin + lay.scal, f.scal.data(), (size_t)S * 4 * 8);
-  memcpy(lay.flag(hin, 0), ones.data(), S); memcpy(lay.flag(hin, 1), needinv.data(), S);
-  memcpy(lay.flag(hin, 2), ones.data(), S); memcpy(lay.flag(hin, 3), f.lch.data(), S);      // every vector starts active
-  if (o.extra_in && o.fill_extra) o.fill_extra(hin + lay.extra);
-  HIP_TRY(ctx, f.dIn.alloc(ctx, lay.total * 8));
+  lay.X.put(hin, X); lay.y.put(hin, y); lay.hyp.put(hin, hyp); lay.sn2.put(hin, f.sn2all.data()); lay.scal.put(hin, f.scal.data());
+  lay.ones.put(hin, ones.data()); lay.needinv.put(hin, needinv.data());
+  lay.active.put(hin, ones.data()); lay.lchol.put(hin, f.lch.data());                        // every vector starts active
+  if (o.extra_in && o.fill_extra) o.fill_extra(lay.extra.at(hin));
+  HIP_TRY(ctx, f.dIn.alloc(ctx, lay.L.bytes()));
   double* din = f.dIn.as<double>();
-  f.dX.view(din + lay.X); f.dy.view(din + lay.y); f.dhyp.view(din + lay.hyp); f.dsn2.view(din + lay.sn2); f.dscal.view(din + lay.scal);
-  f.dones.view(lay.flag(din, 0)); f.dninv.view(lay.flag(din, 1)); f.dact.view(lay.flag(din, 2)); f.dlch.view(lay.flag(din, 3));
-  f.dExtra.view(din + lay.extra);
+  f.dX.view(lay.X.at(din)); f.dy.view(lay.y.at(din)); f.dhyp.view(lay.hyp.at(din)); f.dsn2.view(lay.sn2.at(din)); f.dscal.view(lay.scal.at(din));
+  f.dones.view(lay.ones.at(din)); f.dninv.view(lay.needinv.at(din)); f.dact.view(lay.active.at(din)); f.dlch.view(lay.lchol.at(din));
+  f.dExtra.view(lay.extra.at(din));
   VB_TRY(f.w.alloc(ctx, N, D, S));
   // (small blocks by a kernel that reads the pinned block over the host link instead of the copy engine: the hand-over from a DMA
   // copy to the first kernel of the stream is 8-9 us on top of the copy's 6.5 -- elbo_pass.h: copy_by_kernel)

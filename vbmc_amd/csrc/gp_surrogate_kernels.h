@@ -35,6 +35,22 @@ struct GsTargetArgs {
   double* val;                  // E x C: what k_is_step consumes
 };
 
+// The packed blocks of vbmc_gp_surrogate_sample, from the shape alone (C candidates a round, n0 = W E D, Nnn: 0 without the noise estimate):
+//   extra (behind the sampler's E x C values, is_core.h): ymu | ys2, S x E x C each
+//   v:  VarThresh | sn2_avg | the sum | the partials of k_gs_sum (VPT_MAXBLK)
+//   x0: the start | the same clipped into the box           nn: the draws (Nnn x D) | sn2new at each draw's nearest row
+struct GsBlocks {
+  DevLayout extra, v, x0, nn;
+  DevWin<double> ymu, ys2, vt, sum, part, start, clipped, draws, sn2;
+  GsBlocks(int D, int S, int E, int C, size_t n0, int Nnn) {
+    ymu = extra.add<double>((size_t)S * E * C); ys2 = extra.add<double>((size_t)S * E * C);
+    vt = v.add<double>(2); sum = v.add<double>(1); part = v.add<double>(VPT_MAXBLK);
+    start = x0.add<double>(n0); clipped = x0.add<double>(n0);
+    draws = nn.add<double>((size_t)Nnn * D); sn2 = nn.add<double>(Nnn);
+  }
+  void bind(GsTargetArgs& t, IsPredArgs& g, void* dextra, void* dv) const { g.fmu = ymu.at(dextra); g.ys2 = ys2.at(dextra); t.ymu = g.fmu; t.ys2 = g.ys2; t.vt = vt.at(dv); }
+};
+
 __global__ void __launch_bounds__(64) k_gs_target(GsTargetArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x, C = a.C, S = a.S;

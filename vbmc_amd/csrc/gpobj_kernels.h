@@ -4,6 +4,7 @@
 // results bit for bit (W-invariance, parity with the NumPy restatements), so there is one copy of this arithmetic.
 #pragma once
 #include "common.h"
+#include "dev_layout.h"
 #include "device_math.h"
 
 // What gpobj_emit reads and writes.  SliceKernelArgs and ToptArgs derive from it.
@@ -14,6 +15,21 @@ struct GpObjArgs {
   const int* ptype;                           // Nhyp: 0 flat, 1 Gaussian, 2 Student-t
   double *hyp, *sn2, *scal, *lp;              // B x Nhyp, B x N, B x 4, B
   double *dsn2, *dlp;                         // GRAD only: B x Nnoise x N, B x Nhyp
+};
+
+// The windows of both callers' input block that GpObjArgs points into: the head X | y | s2 (s2 keeps its N doubles when the caller
+// has none, and is then null) and the hyper-prior's rows pmu | psig | pdf | pc.
+struct GpObjHead {
+  DevWin<double> X, y, s2;
+  void add(DevLayout& L, int N, int D, bool has_s2) { X = L.add<double>((size_t)N * D); y = L.add<double>(N); s2 = L.add<double>(N, has_s2); }
+  void pack(void* img, const double* X_, const double* y_, const double* s2_) const { X.put(img, X_); y.put(img, y_); s2.put(img, s2_); }
+  double* bind(GpObjArgs& a, void* base) const { a.y = y.at(base); a.s2 = s2.at(base); return X.at(base); }   // returns X
+};
+struct GpObjPrior {
+  DevWin<double> pmu, psig, pdf, pc;
+  void add(DevLayout& L, int Nhyp) { pmu = L.add<double>(Nhyp); psig = L.add<double>(Nhyp); pdf = L.add<double>(Nhyp); pc = L.add<double>(Nhyp); }
+  void pack(void* img, const double* mu, const double* sig, const double* df, const double* c) const { pmu.put(img, mu); psig.put(img, sig); pdf.put(img, df); pc.put(img, c); }
+  void bind(GpObjArgs& a, void* base) const { a.pmu = pmu.at(base); a.psig = psig.at(base); a.pdf = pdf.at(base); a.pc = pc.at(base); }
 };
 
 // MATLAB's eps(x) for a finite x

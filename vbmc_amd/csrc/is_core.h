@@ -51,8 +51,9 @@ struct IsCore {
   TmpBuf dW, dSt, dWk, dMask;
   IsStepArgs a{};
   IsPredArgs pg{};              // the set-up, the point buffer, its mask and counts, logp = the values; the outputs are the target's
-  double *d_val = nullptr, *d_extra = nullptr;   // E x C values, and the target's doubles behind them
-  size_t nx = 0, nXa = 0, nr = 0;
+  IsCoreBlock L;                // dW's layout
+  double* d_val = nullptr;      // E x C values
+  void* d_extra = nullptr;      // the base of the target's region behind them
   int C = 0;
 };
 
@@ -87,10 +88,10 @@ vbmc_status is_check_params(vbmc_ctx* ctx, const char* who, int D, int E, int nm
   return VBMC_OK;
 }
 
-// The prediction's per-hyper-sample set-up, the sampler's device state (zeroed, the target's `extra` doubles with it) and its uniforms.
+// The prediction's per-hyper-sample set-up, the sampler's device state (zeroed, the target's region with it) and its uniforms.
 // What is left to the caller before is_core_run: the outputs of c.pg and the kernel for it, the box c.a.LB / c.a.UB and the E x W x D
 // starting walkers c.a.x, on the device, in the context's stream.
-vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, const IsParams& g, int E, size_t extra, IsCore& c) {
+vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, const IsParams& g, int E, const DevLayout& target, IsCore& c) {
   VB_TRY(pred_check(ctx, who, gp, 16, false));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -117,34 +118,23 @@ vbmc_status is_core_begin(vbmc_ctx* ctx, const vbmc_gp* gp, const char* who, con
   const int C = is_round_candidates(g);
   a.C = C;
   c.C = C;
-  // one block of fp64 state:  LB | UB | x | lp | P | val | the target's | Xa | rlp | U
-  const size_t nU = g.parity ? (size_t)IS_SLOTS * H * E * g.Mmax : 0;
-  const size_t nx = (size_t)E * W * D, nP = (size_t)E * D * C, nv = (size_t)E * C, nXa = (size_t)Nm * D * E, nr = (size_t)E * Nm;
-  const size_t n_fixed = 2 * (size_t)D + nx + (size_t)E * W + nP + nv + extra + nXa + nr;
-  c.nx = nx; c.nXa = nXa; c.nr = nr;
-  HIP_TRY(ctx, c.dW.alloc(ctx, (n_fixed + nU) * 8));
+  const size_t nU = g.parity ? (size_t)IS_SLOTS * H * E * g.Mmax : 0, nv = (size_t)E * C;
+  c.L = IsCoreBlock(D, E, W, C, Nm, target, nU);
+  const IsCoreBlock& L = c.L;
+  HIP_TRY(ctx, c.dW.alloc(ctx, L.w.bytes()));
   HIP_TRY(ctx, c.dSt.alloc(ctx, (size_t)E * sizeof(IsEnsState)));
   HIP_TRY(ctx, c.dWk.alloc(ctx, (size_t)E * IS_MAXH * sizeof(IsWalker)));
   HIP_TRY(ctx, c.dMask.alloc(ctx, nv));
   VB_TRY(ensure_pin(ctx, 2 * (size_t)E * sizeof(IsEnsState) + 64));       // two landing slots of the progress words
-  HIP_TRY(ctx, hipMemsetAsync(c.dW.p, 0, n_fixed * 8, st));
+  HIP_TRY(ctx, hipMemsetAsync(c.dW.p, 0, L.fixed, st));
   HIP_TRY(ctx, hipMemsetAsync(c.dSt.p, 0, (size_t)E * sizeof(IsEnsState), st));
   HIP_TRY(ctx, hipMemsetAsync(c.dWk.p, 0, (size_t)E * IS_MAXH * sizeof(IsWalker), st));
   HIP_TRY(ctx, hipMemsetAsync(c.dMask.p, 0, nv, st));
-  double* q = c.dW.as<double>();
-  a.LB = q; q += D;
-  a.UB = q; q += D;
-  a.x = q; q += nx;
-  a.lp = q; q += (size_t)E * W;
-  a.P = q; q += nP;
-  c.d_val = q; q += nv;
-  a.val = c.d_val;
-  c.d_extra = q; q += extra;
-  a.Xa = q; q += nXa;
-  a.rlp = q; q += nr;
-  a.U = nU ? q : nullptr;
+  L.bind(a, c.dW.p);
+  c.d_val = L.val.at(c.dW.p);
+  c.d_extra = L.extra.at(c.dW.p);
   a.st = c.dSt.as<IsEnsState>(); a.wk = c.dWk.as<IsWalker>(); a.mask = c.dMask.as<unsigned char>();
-  if (nU) HIP_TRY(ctx, hipMemcpyAsync(c.dW.as<double>() + n_fixed, g.U, nU * 8, hipMemcpyHostToDevice, st));
+  if (nU) HIP_TRY(ctx, hipMemcpyAsync(L.U.at(c.dW.p), g.U, L.U.size(), hipMemcpyHostToDevice, st));
 
   IsPredArgs& pg = c.pg;
   pg.pa = pl.pa;

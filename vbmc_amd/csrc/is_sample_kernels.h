@@ -18,6 +18,7 @@
 // and column, every sum runs in a fixed order, nothing is atomic).
 #pragma once
 #include "common.h"
+#include "dev_layout.h"
 #include "device_math.h"
 #include "gp_factor_kernels.h"   // gp_meanfun
 #include "gp_pred_kernels.h"     // PredArgs
@@ -69,6 +70,28 @@ struct IsStepArgs {
   const double* val;            // S x C: the target at last round's candidates (k_is_pred)
   double* Xa;                   // Nm x D x S recorded walkers
   double* rlp;                  // S x Nm: the chain's own value at each
+};
+
+// The sampler's block of fp64 state, from the shape alone (E ensembles, C candidates a round; nU: the parity uniforms, 0 without):
+//   LB | UB | x | lp | P | val | the target's | Xa | rlp | U      (fixed: the bytes in front of U, zeroed at the start)
+// The target describes its own region behind the values as a layout; its windows resolve against extra.at(block).
+struct IsCoreBlock {
+  DevLayout w;
+  size_t fixed = 0;
+  DevWin<double> LB, UB, x, lp, P, val, Xa, rlp, U;
+  DevWin<unsigned char> extra;
+  IsCoreBlock() {}
+  IsCoreBlock(int D, int E, int W, int C, int Nm, const DevLayout& target, size_t nU) {
+    LB = w.add<double>(D); UB = w.add<double>(D); x = w.add<double>((size_t)E * W * D); lp = w.add<double>((size_t)E * W);
+    P = w.add<double>((size_t)E * D * C); val = w.add<double>((size_t)E * C); extra = w.add(target);
+    Xa = w.add<double>((size_t)Nm * D * E); rlp = w.add<double>((size_t)E * Nm);
+    fixed = w.bytes();
+    U = w.add_if<double>(nU != 0, nU);
+  }
+  void bind(IsStepArgs& a, void* dw) const {
+    a.LB = LB.at(dw); a.UB = UB.at(dw); a.x = x.at(dw); a.lp = lp.at(dw); a.P = P.at(dw); a.val = val.at(dw);
+    a.Xa = Xa.at(dw); a.rlp = rlp.at(dw); a.U = U.at(dw);
+  }
 };
 
 __device__ __forceinline__ double is_u(const IsStepArgs& a, int m, int e, int j, int slot) {

@@ -44,6 +44,33 @@ struct IsSetupKArgs {
   int* idx0;                               // W x S
 };
 
+// The set-up's block of fp64, from the shape alone (Na1 = Nvp + Nbox Step 1 points, Nap1 that rounded up to whole tiles of 16; W = 0
+// without Step 2, when x0 still has room for one walker; parity: the caller's block B of (D + 1) Na1 + W S values, else absent):
+//   mu | sigma | lambda | w | B | geo (D + 1) | comp (12 K) | Xa1 | P1 | logp fmu fs2 ys2 (S x Na1 each) | lpdf |
+//   lnw1 fs2a1 (S x Nap1) | lw (S x Na1) | x0                (upload: the bytes the caller fills, mu .. B)
+struct IsSetupBlock {
+  DevLayout L;
+  size_t upload;
+  DevWin<double> mu, sigma, lambda, w, B, geo, comp, Xa1, P, logp, fmu, fs2, ys2, lpdf, lnw1, fs2a1, lw, x0;
+  static size_t block_len(int D, int S, int W, int Na1) { return (size_t)(D + 1) * Na1 + (size_t)W * S; }
+  IsSetupBlock(int D, int S, int K, int W, int Na1, bool parity) {
+    const size_t nv1 = (size_t)S * Na1, np1 = (size_t)S * (((Na1 + 15) / 16) * 16);
+    mu = L.add<double>((size_t)D * K); sigma = L.add<double>(K); lambda = L.add<double>(D); w = L.add<double>(K);
+    B = L.add_if<double>(parity, block_len(D, S, W, Na1));
+    upload = L.bytes();
+    geo = L.add<double>(D + 1); comp = L.add<double>(12 * (size_t)K); Xa1 = L.add<double>((size_t)Na1 * D); P = L.add<double>((size_t)S * D * Na1);
+    logp = L.add<double>(nv1); fmu = L.add<double>(nv1); fs2 = L.add<double>(nv1); ys2 = L.add<double>(nv1);
+    lpdf = L.add<double>(Na1); lnw1 = L.add<double>(np1); fs2a1 = L.add<double>(np1); lw = L.add<double>(nv1);
+    x0 = L.add<double>((size_t)(W > 1 ? W : 1) * D * S);
+  }
+  void bind(IsSetupKArgs& k, void* d) const {
+    k.mu = mu.at(d); k.sigma = sigma.at(d); k.lambda = lambda.at(d); k.w = w.at(d); k.B = B.at(d); k.geo = geo.at(d); k.comp = comp.at(d);
+    k.Xa1 = Xa1.at(d); k.P = P.at(d); k.fmu = fmu.at(d); k.fs2 = fs2.at(d); k.lpdf = lpdf.at(d); k.lnw1 = lnw1.at(d); k.fs2a1 = fs2a1.at(d);
+    k.lw = lw.at(d); k.x0 = x0.at(d);
+  }
+  void bind(IsPredArgs& g, void* d) const { g.P = P.at(d); g.logp = logp.at(d); g.fmu = fmu.at(d); g.fs2 = fs2.at(d); g.ys2 = ys2.at(d); }   // Step 1's prediction
+};
+
 __device__ __forceinline__ double iss_u_point(const IsSetupKArgs& a, int i, int slot) {
   if (!a.parity) return slice_uniform(a.seed, ISS_CTR_POINT, (unsigned)i, (unsigned)slot);
   return a.B[(size_t)slot + (size_t)(a.D + 1) * i];

@@ -16,22 +16,20 @@ vbmc_status mode_run(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_mode_args
   VB_TRY(vpt_upload(ctx, pk));
   const int Kp = (K + 63) / 64 * 64;
   std::vector<double> muT((size_t)DT * Kp, 0.0);
+  const double* h_mus = pk.L.mus.at(pk.h.data());
   for (int k = 0; k < K; ++k)
-    for (int d = 0; d < D; ++d) muT[(size_t)d * Kp + k] = pk.h[pk.o_mus + (size_t)k * DT + d];
-  // device block: muT | f_all (K) | f0, fs (S each) | us, xs (S D each) | start_comp, iters, nfev, stop (S ints each)
-  const size_t nd = muT.size() + (size_t)K + 2 * (size_t)S + 2 * (size_t)S * D;
+    for (int d = 0; d < D; ++d) muT[(size_t)d * Kp + k] = h_mus[(size_t)k * DT + d];
+  const ModeBlocks L(D, DT, K, Kp, S);
   TmpBuf dB, dI;
-  HIP_TRY(ctx, dB.alloc(ctx, nd * 8));
-  HIP_TRY(ctx, dI.alloc(ctx, 4 * (size_t)S * sizeof(int)));
-  double* q = dB.as<double>();
-  HIP_TRY(ctx, hipMemcpyAsync(q, muT.data(), muT.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, dB.alloc(ctx, L.b.bytes()));
+  HIP_TRY(ctx, dI.alloc(ctx, L.i.bytes()));
+  HIP_TRY(ctx, hipMemcpyAsync(L.muT.at(dB.p), muT.data(), L.muT.size(), hipMemcpyHostToDevice, st));
   ModeArgs a{};
-  a.P = pk.P; a.muT = q; a.Kp = Kp; a.origflag = args->origflag ? 1 : 0;
+  L.bind(a, dB.p, dI.p);
+  a.P = pk.P; a.Kp = Kp; a.origflag = args->origflag ? 1 : 0;
   a.max_iter = args->max_iter == 0 ? MODE_DEFAULT_ITER : args->max_iter;
   a.tol_grad = args->tol_grad;
-  double* f_all = q + muT.size();
-  a.f0 = f_all + K; a.fs = a.f0 + S; a.us = a.fs + S; a.xs = a.us + (size_t)S * D;
-  a.start_comp = dI.as<int>(); a.iters = a.start_comp + S; a.nfev = a.iters + S; a.stop = a.nfev + S;
+  double* f_all = L.f_all.at(dB.p);
   if (ranked) {
     ModeArgs r = a;
     r.role = 1; r.ranked = 0; r.f_rank = f_all;
@@ -40,12 +38,13 @@ vbmc_status mode_run(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_mode_args
   }
   VPT_FOR_DT(DT, hipLaunchKernelGGL((k_vp_mode<DT>), dim3(S), dim3(MODE_T), 0, st, a))
   HIP_TRY(ctx, hipGetLastError());
-  std::vector<double> hd(2 * (size_t)S + 2 * (size_t)S * D);
-  std::vector<int> hi(4 * (size_t)S);
-  HIP_TRY(ctx, hipMemcpyAsync(hd.data(), a.f0, hd.size() * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(hi.data(), a.start_comp, hi.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  std::vector<double> hd(L.res.count());
+  std::vector<int> hi(L.i.count<int>());
+  HIP_TRY(ctx, hipMemcpyAsync(hd.data(), L.results.at(dB.p), L.res.bytes(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(hi.data(), dI.p, L.i.bytes(), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  const double *f0 = hd.data(), *fs = f0 + S, *us = fs + S, *xs = us + (size_t)S * D;
+  const double *f0 = L.f0.at(hd.data()), *fs = L.fs.at(hd.data()), *us = L.us.at(hd.data()), *xs = L.xs.at(hd.data());
+  const int *h_comp = L.start_comp.at(hi.data()), *h_iters = L.iters.at(hi.data()), *h_nfev = L.nfev.at(hi.data()), *h_stop = L.stop.at(hi.data());
   int best = 0;                                         // the largest fs, the first of equal ones (MATLAB's min of -fs)
   for (int s = 1; s < S; ++s)
     if (fs[s] > fs[best]) best = s;
@@ -56,10 +55,10 @@ vbmc_status mode_run(vbmc_ctx* ctx, const vbmc_vp_desc* vp, const vbmc_mode_args
   for (int s = 0; s < S; ++s) {
     if (args->f0) args->f0[s] = f0[s];
     if (args->fs) args->fs[s] = fs[s];
-    if (args->start_comp) args->start_comp[s] = hi[s];
-    if (args->iters) args->iters[s] = hi[S + s];
-    if (args->nfev) args->nfev[s] = hi[2 * (size_t)S + s];
-    if (args->stop) args->stop[s] = hi[3 * (size_t)S + s];
+    if (args->start_comp) args->start_comp[s] = h_comp[s];
+    if (args->iters) args->iters[s] = h_iters[s];
+    if (args->nfev) args->nfev[s] = h_nfev[s];
+    if (args->stop) args->stop[s] = h_stop[s];
     for (int d = 0; d < D; ++d) {
       if (args->us) args->us[s + (size_t)S * d] = us[(size_t)s * D + d];
       if (args->xs) args->xs[s + (size_t)S * d] = xs[(size_t)s * D + d];

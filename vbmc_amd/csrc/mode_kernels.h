@@ -14,6 +14,7 @@
 // a start far from every other component keeps a finite objective and a usable gradient.
 #pragma once
 #include "common.h"
+#include "dev_layout.h"
 #include "device_math.h"        // vb_exp_tab
 #include "parity_rng.h"         // srch_log
 #include "vp_tools_kernels.h"   // VptPost, VptTrS, vpt_log1p, vpt_inverse
@@ -36,6 +37,26 @@ struct ModeArgs {
   double* f_rank;            // role 1: K
   double *f0, *us, *xs, *fs; // S; S x D with start b at [b D ..] (us, xs)
   int *start_comp, *iters, *nfev, *stop;
+};
+
+// The two device blocks of vbmc_vp_mode, from the shape alone (S starts of K components, Kp = K rounded up to 64):
+//   b: muT (DT x Kp) | f_all (K) | res        res: f0, fs (S each) | us, xs (S D each)        i: start_comp, iters, nfev, stop (S ints each)
+// res and i are what the host reads back: its two vectors are images of those two layouts.
+struct ModeBlocks {
+  DevLayout b, res, i;
+  DevWin<double> muT, f_all, f0, fs, us, xs;
+  DevWin<unsigned char> results;
+  DevWin<int> start_comp, iters, nfev, stop;
+  ModeBlocks(int D, int DT, int K, int Kp, int S) {
+    f0 = res.add<double>(S); fs = res.add<double>(S); us = res.add<double>((size_t)S * D); xs = res.add<double>((size_t)S * D);
+    muT = b.add<double>((size_t)DT * Kp); f_all = b.add<double>(K); results = b.add(res);
+    start_comp = i.add<int>(S); iters = i.add<int>(S); nfev = i.add<int>(S); stop = i.add<int>(S);
+  }
+  void bind(ModeArgs& a, void* db, void* di) const {
+    void* r = results.at(db);
+    a.muT = muT.at(db); a.f0 = f0.at(r); a.fs = fs.at(r); a.us = us.at(r); a.xs = xs.at(r);
+    a.start_comp = start_comp.at(di); a.iters = iters.at(di); a.nfev = nfev.at(di); a.stop = stop.at(di);
+  }
 };
 
 __device__ __forceinline__ double mode_wave_sum(double v) {

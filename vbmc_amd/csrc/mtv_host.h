@@ -92,6 +92,7 @@ struct MtvPipeline {
   long long Ns = 0;
   int n = 0, nquad = 0, R = 0, D = 0, C = 0;
   size_t nX = 0, nC = 0;
+  MtvWork W;                                              // dW's layout
   TmpBuf dX, dEnds, dCol, dNu, dCnt, dW, dTab, dT, dStat;
   std::vector<double> ends, htab, yy, mm, msh;
   std::vector<MtvCol> hcol;
@@ -119,13 +120,13 @@ struct MtvPipeline {
     const double inf = std::numeric_limits<double>::infinity();
     ends.resize(4 * (size_t)C);
     for (int i = 0; i < R; ++i) {
-      const double* tr = pk[i].P.has_tr ? pk[i].h.data() + pk[i].o_tr : nullptr;
+      const double* tr = pk[i].L.tr.at(pk[i].h.data());
       for (int d = 0; d < D; ++d) {
         double* e = &ends[4 * ((size_t)i * D + d)];
         e[0] = bounded ? pk[i].lb[d] : -inf;
         e[1] = bounded ? pk[i].ub[d] : inf;
-        e[2] = tr ? tr[6 * pk[i].DT + d] : -inf;
-        e[3] = tr ? tr[7 * pk[i].DT + d] : inf;
+        e[2] = tr ? tr[VPT_ROW_LO * pk[i].DT + d] : -inf;
+        e[3] = tr ? tr[VPT_ROW_HI * pk[i].DT + d] : inf;
       }
     }
     mtv_cos_table(n, htab);
@@ -134,7 +135,8 @@ struct MtvPipeline {
     HIP_TRY(ctx, dCol.alloc(ctx, (size_t)C * sizeof(MtvCol)));
     HIP_TRY(ctx, dNu.alloc(ctx, (size_t)C * sizeof(long long)));
     HIP_TRY(ctx, dCnt.alloc(ctx, nC * sizeof(int)));
-    HIP_TRY(ctx, dW.alloc(ctx, 5 * nC * 8));              // initial data, a, a2, a_t, the inverse transform
+    W = MtvWork(nC);
+    HIP_TRY(ctx, dW.alloc(ctx, W.w.bytes()));
     HIP_TRY(ctx, dTab.alloc(ctx, htab.size() * 8));
     HIP_TRY(ctx, dT.alloc(ctx, (size_t)C * 8));
     HIP_TRY(ctx, dStat.alloc(ctx, (size_t)C * sizeof(int)));
@@ -175,7 +177,7 @@ struct MtvPipeline {
   // k_mtv_dct); the one synchronisation; the columns' host tail; the stage outputs the caller asked for
   template <class Args>
   vbmc_status finish(bool mfma_dct, const Args& args) {
-    double *d_x = dW.as<double>(), *d_a = d_x + nC, *d_a2 = d_a + nC, *d_at = d_a2 + nC, *d_raw = d_at + nC;
+    double *d_x = W.x.at(dW.p), *d_a = W.a.at(dW.p), *d_a2 = W.a2.at(dW.p), *d_at = W.at.at(dW.p), *d_raw = W.raw.at(dW.p);
     if (hold_all) mesh_and_bin(0, C, dX.as<double>());
     {
       MtvInitArgs c{};
@@ -245,20 +247,23 @@ struct MtvPipeline {
       }
     const int ntile = (nquad + MTV_T - 1) / MTV_T, nb = std::min(ntile, MTV_NBLK);
     const size_t nent = 3 * (size_t)D * npair;
+    const MtvIntBlocks L(nC, msh.size(), geo.size());
+    const VptReduceBlock rl((size_t)nb * nent, nent);
     TmpBuf dS, dG, dPr, dP;
-    HIP_TRY(ctx, dS.alloc(ctx, 2 * nC * 8));
-    HIP_TRY(ctx, dG.alloc(ctx, (msh.size() + geo.size()) * 8));
+    HIP_TRY(ctx, dS.alloc(ctx, L.s.bytes()));
+    HIP_TRY(ctx, dG.alloc(ctx, L.g.bytes()));
     HIP_TRY(ctx, dPr.alloc(ctx, pairs.size() * sizeof(int)));
-    HIP_TRY(ctx, dP.alloc(ctx, ((size_t)nb + 1) * nent * 8));
-    HIP_TRY(ctx, hipMemcpyAsync(dS.p, yy.data(), nC * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dS.as<double>() + nC, mm.data(), nC * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dG.p, msh.data(), msh.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dG.as<double>() + msh.size(), geo.data(), geo.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, dP.alloc(ctx, rl.L.bytes()));
+    HIP_TRY(ctx, hipMemcpyAsync(L.yy.at(dS.p), yy.data(), L.yy.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.mm.at(dS.p), mm.data(), L.mm.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.msh.at(dG.p), msh.data(), L.msh.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.geo.at(dG.p), geo.data(), L.geo.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dPr.p, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, st));
     MtvIntArgs ia{};
     ia.n = n; ia.D = D; ia.nquad = nquad; ia.ntile = ntile; ia.npair = npair; ia.pairs = dPr.as<int>();
-    ia.msh = dG.as<double>(); ia.geo = ia.msh + msh.size(); ia.yy = dS.as<double>(); ia.mm = ia.yy + nC; ia.partial = dP.as<double>();
-    double* d_out = ia.partial + (size_t)nb * nent;
+    L.bind(ia, dS.p, dG.p);
+    ia.partial = rl.partial.at(dP.p);
+    double* d_out = rl.out.at(dP.p);
     hipLaunchKernelGGL(k_mtv_integral, dim3(nb, D, npair), dim3(MTV_T), 0, st, ia);
     hipLaunchKernelGGL(k_vp_reduce, dim3((unsigned)((nent + VPT_T - 1) / VPT_T)), dim3(VPT_T), 0, st, ia.partial, nb, (int)nent, d_out);
     HIP_TRY(ctx, hipGetLastError());

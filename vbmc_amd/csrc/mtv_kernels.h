@@ -302,6 +302,21 @@ struct MtvIntArgs {
   double* partial;                // MTV_NBLK x 3 D npair
 };
 
+// The KDE pipeline's work block, from the shape alone (nC = R D x n mesh values):  initial data | a | a2 | a_t | the inverse transform
+struct MtvWork {
+  DevLayout w;
+  DevWin<double> x, a, a2, at, raw;
+  MtvWork() = default;
+  explicit MtvWork(size_t nC) { x = w.add<double>(nC); a = w.add<double>(nC); a2 = w.add<double>(nC); at = w.add<double>(nC); raw = w.add<double>(nC); }
+};
+// The two input blocks of k_mtv_integral:  s: yy | mm (nC each)        g: msh (4 R D) | geo (4 D npair)
+struct MtvIntBlocks {
+  DevLayout s, g;
+  DevWin<double> yy, mm, msh, geo;
+  MtvIntBlocks(size_t nC, size_t nmsh, size_t ngeo) { yy = s.add<double>(nC); mm = s.add<double>(nC); msh = g.add<double>(nmsh); geo = g.add<double>(ngeo); }
+  void bind(MtvIntArgs& ia, void* ds, void* dg) const { ia.yy = yy.at(ds); ia.mm = mm.at(ds); ia.msh = msh.at(dg); ia.geo = geo.at(dg); }
+};
+
 // the not-a-knot spline of column c at x; 0 outside its mesh (interp1(..., 'spline', 0))
 __device__ __forceinline__ double mtv_spline(const MtvIntArgs& a, int c, double x) {
 #pragma clang fp contract(off)

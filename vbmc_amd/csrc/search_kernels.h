@@ -10,6 +10,7 @@
 // the launch that happens to run it.
 #pragma once
 #include "common.h"
+#include "dev_layout.h"
 #include "parity_rng.h"
 
 #define SRCH_MAXD 32
@@ -45,6 +46,31 @@ struct SearchArgs {
   const double* F;                    // lam acquisition values of the pending generation (k_acq)
   int* tr_order;                      // trace_cap x lam   (all four may be null)
   double *tr_F, *tr_xmean, *tr_sigma; // trace_cap x lam sorted values, trace_cap x D, trace_cap
+};
+
+// The packed blocks of the search, from the shape alone (nZ: the parity normals, 0 without; tcap: trace_cap, 0 without a trace):
+//   w:   wts | LB | UB | xmean ps pc xbest xlast | C | A | Y | hist | F fbar vtot | Z      (fixed: the bytes in front of Z)
+//   trd: tr_F | tr_xmean | tr_sigma
+// F, fbar and vtot (lam each) are what the objective's kernels write: their argument structures point into the same windows.
+struct SearchBlocks {
+  DevLayout w, trd;
+  size_t fixed;
+  DevWin<double> wts, LB, UB, xmean, ps, pc, xbest, xlast, C, A, Y, hist, F, fbar, vtot, Z, tr_F, tr_xmean, tr_sigma;
+  SearchBlocks(int D, int lam, int mu, int nh, size_t nZ, size_t tcap) {
+    wts = w.add<double>(mu); LB = w.add<double>(D); UB = w.add<double>(D);
+    xmean = w.add<double>(D); ps = w.add<double>(D); pc = w.add<double>(D); xbest = w.add<double>(D); xlast = w.add<double>(D);
+    C = w.add<double>((size_t)D * D); A = w.add<double>((size_t)D * D); Y = w.add<double>((size_t)D * lam); hist = w.add<double>(nh);
+    F = w.add<double>(lam); fbar = w.add<double>(lam); vtot = w.add<double>(lam);
+    fixed = w.bytes();
+    Z = w.add_if<double>(nZ != 0, nZ);
+    tr_F = trd.add_if<double>(tcap != 0, tcap * lam); tr_xmean = trd.add_if<double>(tcap != 0, tcap * D); tr_sigma = trd.add_if<double>(tcap != 0, tcap);
+  }
+  void bind(SearchArgs& a, void* dw, void* dtrd) const {
+    a.wts = wts.at(dw); a.LB = LB.at(dw); a.UB = UB.at(dw); a.xmean = xmean.at(dw); a.ps = ps.at(dw); a.pc = pc.at(dw);
+    a.xbest = xbest.at(dw); a.xlast = xlast.at(dw); a.C = C.at(dw); a.A = A.at(dw); a.Y = Y.at(dw); a.hist = hist.at(dw);
+    a.F = F.at(dw); a.Z = Z.at(dw);
+    a.tr_F = tr_F.at(dtrd); a.tr_xmean = tr_xmean.at(dtrd); a.tr_sigma = tr_sigma.at(dtrd);
+  }
 };
 
 // lower Cholesky factor of the D x D matrix sC (leading dimension SRCH_MAXD + 1) into sA, column by column, lane i owning row i; every

@@ -41,6 +41,37 @@ struct SliceKernelArgs : GpObjArgs {           // (hyp, sn2, scal, lp: one row p
   double *samples, *logp;                     // Ns x Nhyp (column-major), Ns
 };
 
+// The packed blocks of vbmc_gp_slice_sample, from the shape alone (nU: the parity uniforms, 0 without):
+//   in:  X | y | s2 | LB UB LBo UBo | pmu psig pdf pc | basew | xx widths xsum xsq | U      ints: perms | ptype
+//   flags: act | on (SLICE_MAXW each)                                                        smp: samples | logp
+struct SliceBlocks {
+  DevLayout in, ints, flags, smp;
+  GpObjHead head;
+  GpObjPrior prior;
+  DevWin<double> LB, UB, LBo, UBo, basew, xx, widths, xsum, xsq, U, samples, logp;
+  DevWin<int> perms, ptype;
+  DevWin<unsigned char> act, on;
+  SliceBlocks(int N, int D, int Nhyp, bool has_s2, size_t total, size_t nU, int Ns) {
+    head.add(in, N, D, has_s2);
+    LB = in.add<double>(Nhyp); UB = in.add<double>(Nhyp); LBo = in.add<double>(Nhyp); UBo = in.add<double>(Nhyp);
+    prior.add(in, Nhyp);
+    basew = in.add<double>(Nhyp); xx = in.add<double>(Nhyp); widths = in.add<double>(Nhyp); xsum = in.add<double>(Nhyp); xsq = in.add<double>(Nhyp);
+    U = in.add_if<double>(nU != 0, nU);
+    perms = ints.add<int>(total * Nhyp); ptype = ints.add<int>(Nhyp);
+    act = flags.add<unsigned char>(SLICE_MAXW); on = flags.add<unsigned char>(SLICE_MAXW);
+    samples = smp.add<double>((size_t)Ns * Nhyp); logp = smp.add<double>(Ns);
+  }
+  double* bind(SliceKernelArgs& a, void* din, void* dints, void* dflags, void* dsmp) const {   // returns X
+    prior.bind(a, din);
+    a.LB = LB.at(din); a.UB = UB.at(din); a.LBo = LBo.at(din); a.UBo = UBo.at(din); a.basew = basew.at(din);
+    a.xx = xx.at(din); a.widths = widths.at(din); a.xsum = xsum.at(din); a.xsq = xsq.at(din); a.U = U.at(din);
+    a.perms = perms.at(dints); a.ptype = ptype.at(dints);
+    a.act = act.at(dflags); a.on = on.at(dflags);
+    a.samples = samples.at(dsmp); a.logp = logp.at(dsmp);
+    return head.bind(a, din);
+  }
+};
+
 // slot 0: slice level (:245), 1: interval placement (:252), 2 + k: k-th shrink proposal (:286).  NaN: the parity block has no such slot.
 __device__ __forceinline__ double slice_u(const SliceKernelArgs& a, int sweep, int idd, int slot) {
   if (!a.parity) return slice_uniform(a.seed, (unsigned)sweep, (unsigned)idd, (unsigned)slot);

@@ -57,6 +57,46 @@ struct ToptArgs : GpObjArgs {                  // (hyp .. dsn2: one row per cand
   int* best;
 };
 
+// The packed blocks of vbmc_gp_train_optimize, from the shape alone (Nrows: the design's rows, BB: candidate rows):
+//   in: X | y | s2 | LB UB | pmu psig pdf pc | design     ints: ptype | order | best | hist_k (one spare int behind it)
+//   vec: x | g | d     lp: lp | dlp     flags: act | on     fill: fvals | fsorted | widths     res: res_nll | hyp_start
+//   hist: hist_f | hist_x (absent with hist_cap = 0, when the block is one spare double)
+struct ToptBlocks {
+  DevLayout in, ints, vec, lp, flags, fill, res, hist;
+  GpObjHead head;
+  GpObjPrior prior;
+  DevWin<double> LB, UB, design, x, g, d, lpv, dlp, fvals, fsorted, widths, res_nll, hyp_start, hist_f, hist_x;
+  DevWin<int> ptype, order, best, hist_k;
+  DevWin<unsigned char> act, on;
+  ToptBlocks(int N, int D, int Nhyp, bool has_s2, int Nrows, int Nopts, int BB, int hist_cap) {
+    const size_t nv = (size_t)Nopts * Nhyp, nh = (size_t)Nopts * hist_cap;
+    head.add(in, N, D, has_s2);
+    LB = in.add<double>(Nhyp); UB = in.add<double>(Nhyp);
+    prior.add(in, Nhyp);
+    design = in.add<double>((size_t)Nrows * Nhyp);
+    ptype = ints.add<int>(Nhyp); order = ints.add<int>(Nrows); best = ints.add<int>(1); hist_k = ints.add<int>(nh + 1);
+    x = vec.add<double>(nv); g = vec.add<double>(nv); d = vec.add<double>(nv);
+    lpv = lp.add<double>(BB); dlp = lp.add<double>((size_t)BB * Nhyp);
+    act = flags.add<unsigned char>(BB); on = flags.add<unsigned char>(BB);
+    fvals = fill.add<double>(Nrows); fsorted = fill.add<double>(Nrows); widths = fill.add<double>(Nhyp);
+    res_nll = res.add<double>(Nopts); hyp_start = res.add<double>(Nhyp);
+    hist_f = hist.add_if<double>(hist_cap != 0, nh); hist_x = hist.add_if<double>(hist_cap != 0, nh * Nhyp);
+    if (!hist_cap) hist.add<double>(1);
+  }
+  double* bind(ToptArgs& a, void* din, void* dints, void* dvec, void* dlpb, void* dflags, void* dfill, void* dres, void* dhist) const {   // returns X
+    prior.bind(a, din);
+    a.LB = LB.at(din); a.UB = UB.at(din); a.design = design.at(din);
+    a.ptype = ptype.at(dints); a.order = order.at(dints); a.best = best.at(dints); a.hist_k = hist_k.at(dints);
+    a.x = x.at(dvec); a.g = g.at(dvec); a.d = d.at(dvec);
+    a.lp = lpv.at(dlpb); a.dlp = dlp.at(dlpb);
+    a.act = act.at(dflags); a.on = on.at(dflags);
+    a.fvals = fvals.at(dfill); a.fsorted = fsorted.at(dfill); a.widths = widths.at(dfill);
+    a.res_nll = res_nll.at(dres); a.hyp_start = hyp_start.at(dres);
+    a.hist_f = hist_f.at(dhist); a.hist_x = hist_x.at(dhist);
+    return head.bind(a, din);
+  }
+};
+
 __device__ __forceinline__ bool topt_finite(double v) { return v > -__builtin_inf() && v < __builtin_inf(); }
 // min(UB - eps(UB), max(LB + eps(LB), v))   (:272,304): MATLAB's min / max pass over the NaN that eps(Inf) produces
 __device__ __forceinline__ double topt_clamp_in(double v, double lb, double ub) {

@@ -38,7 +38,7 @@ inline double vpt_eps(double x) {   // eps(x): the spacing of the doubles at |x|
 struct VptPack {
   int DT = 0;
   std::vector<double> h, lb, ub;   // the packed block; the bounds (+-Inf without a trinfo) for vbmc_vp_kldiv's comparison
-  size_t o_mus = 0, o_cst = 0, o_is2 = 0, o_mu = 0, o_sig = 0, o_lam = 0, o_ilam = 0, o_tr = 0;
+  VptPackLayout L;                 // h's layout, and dev's
   VptPost P{};
   TmpBuf dev;
 };
@@ -111,41 +111,35 @@ vbmc_status vpt_pack(vbmc_ctx* ctx, const char* who, const vbmc_vp_desc* vp, dou
     P.fam = 2; P.dfa = a; P.ce = 0.5 * (a + 1.0);
     P.lognf = D * (std::lgamma(0.5 * (a + 1.0)) - std::lgamma(0.5 * a) - 0.5 * std::log(a * pi)) - sll;              // :93
   }
-  size_t o = 0;
-  pk.o_mus = o; o += (size_t)K * DT;
-  pk.o_cst = o; o += K;
-  pk.o_is2 = o; o += K;
-  pk.o_mu = o; o += (size_t)D * K;
-  pk.o_sig = o; o += K;
-  pk.o_lam = o; o += DT;
-  pk.o_ilam = o; o += DT;
-  pk.o_tr = o; o += has_tr ? (size_t)VPT_NROWS * DT + (size_t)DT * DT : 0;
-  pk.h.assign(o, 0.0);
+  pk.L = VptPackLayout(D, DT, K, has_tr);
+  const VptPackLayout& L = pk.L;
+  pk.h.assign(L.L.count(), 0.0);
   double* h = pk.h.data();
+  double *h_mus = L.mus.at(h), *h_cst = L.cst.at(h), *h_is2 = L.is2.at(h), *h_mu = L.mu.at(h), *h_sig = L.sig.at(h);
   for (int k = 0; k < K; ++k) {
     for (int d = 0; d < D; ++d) {
-      h[pk.o_mus + (size_t)k * DT + d] = vp->mu[d + (size_t)D * k] / vp->lambda[d];
-      h[pk.o_mu + d + (size_t)D * k] = vp->mu[d + (size_t)D * k];
+      h_mus[(size_t)k * DT + d] = vp->mu[d + (size_t)D * k] / vp->lambda[d];
+      h_mu[d + (size_t)D * k] = vp->mu[d + (size_t)D * k];
     }
-    h[pk.o_cst + k] = vp->w[k] > 0.0 ? std::log(vp->w[k]) - D * std::log(vp->sigma[k]) : -1e300;
-    h[pk.o_is2 + k] = 1.0 / (vp->sigma[k] * vp->sigma[k]);
-    h[pk.o_sig + k] = vp->sigma[k];
+    h_cst[k] = vp->w[k] > 0.0 ? std::log(vp->w[k]) - D * std::log(vp->sigma[k]) : -1e300;
+    h_is2[k] = 1.0 / (vp->sigma[k] * vp->sigma[k]);
+    h_sig[k] = vp->sigma[k];
   }
-  for (int d = 0; d < D; ++d) { h[pk.o_lam + d] = vp->lambda[d]; h[pk.o_ilam + d] = 1.0 / vp->lambda[d]; }
+  for (int d = 0; d < D; ++d) { L.lam.at(h)[d] = vp->lambda[d]; L.ilam.at(h)[d] = 1.0 / vp->lambda[d]; }
   if (has_tr) {
-    double* tr = h + pk.o_tr;
+    double* tr = L.tr.at(h);
     for (int d = 0; d < DT; ++d) {
       const bool in = d < D;
       const int t = in ? vp->type[d] : 0;
       const double a = in ? vp->lb[d] : -inf, b = in ? vp->ub[d] : inf;
-      tr[0 * DT + d] = t;
-      tr[1 * DT + d] = a;
-      tr[2 * DT + d] = b;
-      tr[3 * DT + d] = in && (t == 0 || t == 3) ? vp->tmu[d] : 0.0;
-      tr[4 * DT + d] = in && (t == 0 || t == 3) ? vp->tdelta[d] : 1.0;
-      tr[5 * DT + d] = in && has_sc ? vp->scale[d] : 1.0;
-      tr[6 * DT + d] = std::isfinite(a) ? a + vpt_eps(a) : a;                // :457
-      tr[7 * DT + d] = std::isfinite(b) ? b - vpt_eps(b) : b;                // :458
+      tr[VPT_ROW_TYPE * DT + d] = t;
+      tr[VPT_ROW_A * DT + d] = a;
+      tr[VPT_ROW_B * DT + d] = b;
+      tr[VPT_ROW_MU * DT + d] = in && (t == 0 || t == 3) ? vp->tmu[d] : 0.0;
+      tr[VPT_ROW_DELTA * DT + d] = in && (t == 0 || t == 3) ? vp->tdelta[d] : 1.0;
+      tr[VPT_ROW_SCALE * DT + d] = in && has_sc ? vp->scale[d] : 1.0;
+      tr[VPT_ROW_LO * DT + d] = std::isfinite(a) ? a + vpt_eps(a) : a;       // :457
+      tr[VPT_ROW_HI * DT + d] = std::isfinite(b) ? b - vpt_eps(b) : b;       // :458
     }
     if (P.has_rot)
       for (int i = 0; i < D; ++i)
@@ -155,12 +149,9 @@ vbmc_status vpt_pack(vbmc_ctx* ctx, const char* who, const vbmc_vp_desc* vp, dou
 }
 
 vbmc_status vpt_upload(vbmc_ctx* ctx, VptPack& pk) {
-  HIP_TRY(ctx, pk.dev.alloc(ctx, pk.h.size() * 8));
-  HIP_TRY(ctx, hipMemcpyAsync(pk.dev.p, pk.h.data(), pk.h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  const double* q = pk.dev.as<double>();
-  VptPost& P = pk.P;
-  P.mus = q + pk.o_mus; P.cst = q + pk.o_cst; P.is2 = q + pk.o_is2; P.mu = q + pk.o_mu; P.sig = q + pk.o_sig;
-  P.lam = q + pk.o_lam; P.ilam = q + pk.o_ilam; P.tr = P.has_tr ? q + pk.o_tr : nullptr;
+  HIP_TRY(ctx, pk.dev.alloc(ctx, pk.L.L.bytes()));
+  HIP_TRY(ctx, hipMemcpyAsync(pk.dev.p, pk.h.data(), pk.L.L.bytes(), hipMemcpyHostToDevice, ctx->stream));
+  pk.L.bind(pk.P, pk.dev.p);
   return VBMC_OK;
 }
 
@@ -172,7 +163,7 @@ struct VptGenHost {
   TmpBuf dcdf, dcum, dB;
 };
 
-vbmc_status vpt_gen_host(vbmc_ctx* ctx, const char* who, int D, int K, const double* w, long long N, int balanced, unsigned long long seed, VptGenHost& g) {
+vbmc_status vpt_gen_host(vbmc_ctx* ctx, const char* who, int K, const double* w, long long N, int balanced, unsigned long long seed, VptGenHost& g) {
   g.cdf.assign(K, 0.0);
   g.cum.assign(K + 1, 0);
   std::vector<double> nf(K);
@@ -204,7 +195,6 @@ vbmc_status vpt_gen_host(vbmc_ctx* ctx, const char* who, int D, int K, const dou
   VptGen& G = g.G;
   G.N = (int)N; G.M = (int)M; G.M0 = (int)M0; G.K = K; G.hb = hb; G.balanced = balanced ? 1 : 0; G.parity = 0; G.origflag = 0; G.seed = seed;
   vpt_keys(seed, G.key);
-  (void)D;
   return VBMC_OK;
 }
 
@@ -244,7 +234,7 @@ void vpt_host_inverse(const vbmc_vp_desc* vp, const VptPack& pk, const double* y
     for (int j = 0; j < D; ++j) s += v[j] * vp->R[i + (size_t)D * j];
     u[i] = s;
   }
-  const double* tr = pk.h.data() + pk.o_tr;
+  const double* tr = pk.L.tr.at(pk.h.data());
   for (int d = 0; d < D; ++d) {
     const int t = vp->type[d];
     const double a = vp->lb[d], b = vp->ub[d];
@@ -253,7 +243,7 @@ void vpt_host_inverse(const vbmc_vp_desc* vp, const VptPack& pk, const double* y
     else if (t == 1) z = std::exp(u[d]) + a;
     else if (t == 2) z = b - std::exp(u[d]);
     else z = a + (b - a) / (1.0 + std::exp(-(u[d] * vp->tdelta[d] + vp->tmu[d])));
-    x[d] = std::min(std::max(z, tr[6 * pk.DT + d]), tr[7 * pk.DT + d]);
+    x[d] = std::min(std::max(z, tr[VPT_ROW_LO * pk.DT + d]), tr[VPT_ROW_HI * pk.DT + d]);
   }
 }
 

@@ -15,6 +15,7 @@
 // Kernels are templated on the padded dimension DT (4, 8, 12, 16, 24, 32): every per-dimension loop over registers is unrolled.
 #pragma once
 #include "common.h"
+#include "dev_layout.h"
 #include "device_math.h"   // vb_exp_tab
 #include "parity_rng.h"    // srch_log, srch_normal, slice_uniform, slice_philox
 
@@ -26,6 +27,7 @@
 #define VPT_LOG_DENORM_MIN (-744.4400719213812)   // log(5e-324): the reference forms the density, which is zero below it
 #define VPT_LOG_REALMIN (-708.3964185322641)      // log(realmin), vbmc_kldiv.m:70
 #define VPT_NROWS 8               // transform rows: type, a, b, mu, delta, scale, lo, hi
+enum { VPT_ROW_TYPE, VPT_ROW_A, VPT_ROW_B, VPT_ROW_MU, VPT_ROW_DELTA, VPT_ROW_SCALE, VPT_ROW_LO, VPT_ROW_HI };   // (the host's names for them)
 
 struct VptPost {                  // one posterior; arrays padded to DT
   int D, K, fam, has_tr, has_rot, has_sc;   // fam 0: Gaussian, 1: multivariate t, 2: product of univariate t
@@ -34,6 +36,20 @@ struct VptPost {                  // one posterior; arrays padded to DT
   const double *mu, *sig;         // D x K, K (generation)
   const double *lam, *ilam;       // DT, DT
   const double* tr;               // VPT_NROWS x DT rows, then DT x DT rotation R(i, j) at [i DT + j]
+};
+
+// The packed block of one posterior, from the shape alone:  mus | cst | is2 | mu | sig | lam | ilam | tr   (tr with a trinfo only)
+struct VptPackLayout {
+  DevLayout L;
+  DevWin<double> mus, cst, is2, mu, sig, lam, ilam, tr;
+  VptPackLayout() {}
+  VptPackLayout(int D, int DT, int K, bool has_tr) {
+    mus = L.add<double>((size_t)K * DT); cst = L.add<double>(K); is2 = L.add<double>(K); mu = L.add<double>((size_t)D * K); sig = L.add<double>(K);
+    lam = L.add<double>(DT); ilam = L.add<double>(DT); tr = L.add_if<double>(has_tr, (size_t)VPT_NROWS * DT + (size_t)DT * DT);
+  }
+  void bind(VptPost& P, const void* b) const {
+    P.mus = mus.at(b); P.cst = cst.at(b); P.is2 = is2.at(b); P.mu = mu.at(b); P.sig = sig.at(b); P.lam = lam.at(b); P.ilam = ilam.at(b); P.tr = tr.at(b);
+  }
 };
 
 struct VptGen {
@@ -362,6 +378,20 @@ struct VptMomArgs {
   const unsigned char *ei, *ej;    // nent: the rows of the tile an entry multiplies (row DT holds ones)
   int nent, ntile;
   double* partial;                 // gridDim.x x nent
+};
+
+// What k_vp_reduce folds, one block:  partial (the launches' per-workgroup sums) | out (their totals)
+struct VptReduceBlock {
+  DevLayout L;
+  DevWin<double> partial, out;
+  VptReduceBlock(size_t npartial, size_t nout) { partial = L.add<double>(npartial); out = L.add<double>(nout); }
+};
+// vbmc_vp_moments' entry table:  ei | ej, nent bytes each
+struct VptMomEntries {
+  DevLayout L;
+  DevWin<unsigned char> ei, ej;
+  explicit VptMomEntries(int nent) { ei = L.add<unsigned char>(nent); ej = L.add<unsigned char>(nent); }
+  void bind(VptMomArgs& a, void* d) const { a.ei = ei.at(d); a.ej = ej.at(d); }
 };
 
 template <int DT>
